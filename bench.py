@@ -2,19 +2,25 @@
 """bench.py — mel frames/sec of Sequential(*Melspectrogram(128 mel, 2048/512), AmplitudeToDb())
 on N MI355X (BASELINE.json metric; workload = configs[1]: 256 x 1ch x 16 kHz x 10 s per GPU).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one pass of the fused hot path over one device-resident synthetic batch per rank
 (weak scaling: per-GPU work fixed; ranks shard the batch axis, no data-path collective).  Rank 0
-prints ONE JSON line.  The K-step timed region (barrier + synchronize on both sides, max over ranks) is
+prints ONE JSON line.  A plain run sets up, warms up, times K steps (barrier + synchronize on both sides,
+max over ranks) and prints the headline: `value` (mel frames/s) and `ms_per_step`.  `--dump-outputs DIR`
+writes what the last timed step returned as DIR/mel_db.npy (float32; inputs are seeded, so two builds
+can be compared output for output).
+
+Everything else is measured only with `--full`: there the K-step timed region is
 repeated `--repeats` times back to back and the MEDIAN region decides `value` / `ms_per_step`
 (`value_p10` / `value_p90` beside it), so the headline is not one 2 ms window.  `roofline` is measured
 live with HIP events on the launch stream around the dominant (only) kernel, names the kernel the
 library actually launched (tac_last_route), the shader clock that kernel ran at (tac_debug_clock_probe)
 and what binds it according to the committed counter passes; `cpu_baseline` times the CPU oracle
 (torch-CPU restatement of the reference's op sequence) on a bounded sample of the same workload on this
-box's host cores.
+box's host cores; `stages`, `single_buffer`, `with_allgather` and `cfg3` time the other kernels and
+configurations.
 """
 import argparse
 import ctypes
@@ -47,10 +53,17 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--repeats', type=int, default=25,
-                    help='back-to-back repetitions of the K-step timed region; the median region is reported')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-stages', action='store_true')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='back-to-back repetitions of the K-step timed region; the median region is reported '
+                         '(default: 1, with --full 25)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one returned as DIR/<name>.npy (float32, at most '
+                         '64 MB in all: a larger output is cut to a fixed seeded sample of its batch rows)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline measure everything else: roofline, shader clock, counters, single-buffer '
+                         'loop, stages, other BASELINE configs, all-gather legs, CPU baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip cpu_baseline')
+    ap.add_argument('--no-stages', action='store_true', help='(--full) skip stages')
     ap.add_argument('--no-live-counters', action='store_true',
                     help='do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic in this '
                          'run; the committed counter pass of the same kernel is quoted instead')
@@ -62,7 +75,30 @@ def parse():
     ap.add_argument('--dry-run-cpu', action='store_true',
                     help='control-flow check without a GPU: gloo backend, CPU tensors, a tiny batch (tests/ use it to '
                          'cover the --gpus N spawn / reduce / JSON path); the printed line is marked invalid')
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 25 if a.full else 1
+    return a
+
+
+DUMP_BYTES = 64 * 10 ** 6                           # --dump-outputs: cap over all files
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every (name, tensor) of `arrays` as <path>/<name>.npy in float32 / float64.  An output beyond its share of
+    DUMP_BYTES is cut to a fixed seeded sample of its leading (batch) rows, in row order, so two runs dump the same rows."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        if t.numel() * t.element_size() > share:
+            keep = max(1, share // (t[0].numel() * t.element_size()))
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
 
 
 def event_ms(fn, iters):
@@ -86,7 +122,8 @@ def cpu_baseline(x):
     The host may expose far more hardware threads than torch's CPU kernels scale to, so a few thread counts are tried
     briefly and the best one is reported (cores = threads actually used)."""
     from oracle import torch_ref
-    avail = os.cpu_count() or 1
+    # (a shared host may grant this process fewer cores than it has: OMP_NUM_THREADS, when set, is the allowance)
+    avail = min(os.cpu_count() or 1, int(os.environ.get('OMP_NUM_THREADS') or os.cpu_count() or 1))
     rows = x.shape[0]
 
     def run(t):
@@ -427,7 +464,7 @@ def run(a):
     rccl_log = None
     if distributed:
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
-        if 'NCCL_DEBUG' not in os.environ:
+        if a.full and 'NCCL_DEBUG' not in os.environ:
             # make the run self-explaining: RCCL's own account of the rings / channels it built and of the algorithm and protocol
             # it picks per message size goes to a per-process file; rank 0 quotes it in the JSON line (`rccl_debug`)
             rccl_log = '/tmp/tac_rccl_%d.log' % os.getpid()
@@ -452,7 +489,7 @@ def run(a):
     for _ in range(1, nbuf):
         xs.append(torch.rand(BATCH, CHANNELS, length, device=dev, generator=gen) * 2 - 1)
     x = xs[0]
-    if rank != 0 or a.no_cpu_baseline or a.config != 'cfg2':
+    if rank != 0 or not a.full or a.no_cpu_baseline or a.config != 'cfg2':
         x_host = None
 
     def pipeline(rate):
@@ -501,15 +538,42 @@ def run(a):
             evs.append(ms)
         return walls, evs, y
 
-    spin(step, 0.5)
+    # the warm-up has a rotation of its own (spin() makes a time-dependent number of calls): the timed steps start at buffer 0,
+    # so which batch the last timed step reads depends on the arguments alone
+    warm = rotating(model, xs)
+    spin(warm, 0.5)
     for _ in range(a.warmup):
-        y = step()
+        warm()
     walls, region_mss, y = repeated(step, a.steps, a.repeats)
     assert type(y) is torch.Tensor and tuple(y.shape) == (BATCH, CHANNELS, N_MELS, frames)
     frames_per_step = world * BATCH * CHANNELS * frames
     elapsed = quantile(walls, 0.5)                                       # the median region
     value = frames_per_step * a.steps / elapsed
     region_ms = quantile(region_mss, 0.5)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {'mel_db': y})
+    result = {
+        'metric': 'mel frames/sec', 'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': a.steps,
+        'warmup': a.warmup, 'ms_per_step': elapsed / a.steps * 1e3, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'repeats': len(walls), 'value_p10': frames_per_step * a.steps / quantile(walls, 0.9),
+        'value_p90': frames_per_step * a.steps / quantile(walls, 0.1),
+        'value_note': 'median of `repeats` back-to-back timed regions of `steps` steps each (barrier + synchronize on both '
+                      'sides of every region, max over ranks); p10 / p90 over the same regions',
+        'process_group': 'nccl' if distributed else None,
+        'config': {'workload': 'Melspectrogram+AmplitudeToDb batch=%d/GPU x %dch x %dHz x %ds, fft_len=%d hop=%d '
+                               '%d mel (%s)' % (BATCH, CHANNELS, sr, seconds, N_FFT, HOP, N_MELS, label),
+                   'global_batch': world * BATCH, 'frames_per_step': frames_per_step,
+                   'parallelism': 'batch-sharded x%d, no data-path collective' % world,
+                   'input_buffers': '%d distinct device-resident batches of %.1f MB visited round-robin (%.0f MB > the '
+                                    '256 MiB Infinity Cache)' % (nbuf, x.numel() * 4 / 1e6, nbuf * x.numel() * 4 / 1e6)},
+    }
+    if not a.full:                              # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(result))
+        if distributed:
+            dist.destroy_process_group()
+        return
     route = tac._native.lib().tac_last_route().decode()                  # the kernel instantiation the launches took
 
     # ---- the shader clock the kernel runs at, measured by the kernel itself: every workgroup's wave 0 records the shader
@@ -539,37 +603,21 @@ def run(a):
     mean_ms = region_ms
     alg_bytes = BATCH * CHANNELS * frames * (4 * HOP + 4 * N_MELS)      # 2560 B/frame
     achieved = alg_bytes / (mean_ms * 1e-3) / 1e9
-    result = {
-        'metric': 'mel frames/sec', 'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': a.steps,
-        'warmup': a.warmup, 'ms_per_step': elapsed / a.steps * 1e3, 'higher_is_better': True,
-        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-        'repeats': len(walls), 'value_p10': frames_per_step * a.steps / quantile(walls, 0.9),
-        'value_p90': frames_per_step * a.steps / quantile(walls, 0.1),
-        'value_note': 'median of `repeats` back-to-back timed regions of `steps` steps each (barrier + synchronize on both '
-                      'sides of every region, max over ranks); p10 / p90 over the same regions',
-        'process_group': 'nccl' if distributed else None,
-        'config': {'workload': 'Melspectrogram+AmplitudeToDb batch=%d/GPU x %dch x %dHz x %ds, fft_len=%d hop=%d '
-                               '%d mel (%s)' % (BATCH, CHANNELS, sr, seconds, N_FFT, HOP, N_MELS, label),
-                   'global_batch': world * BATCH, 'frames_per_step': frames_per_step,
-                   'parallelism': 'batch-sharded x%d, no data-path collective' % world,
-                   'input_buffers': '%d distinct device-resident batches of %.1f MB visited round-robin (%.0f MB > the '
-                                    '256 MiB Infinity Cache)' % (nbuf, x.numel() * 4 / 1e6, nbuf * x.numel() * 4 / 1e6)},
-        'roofline': {'kernel': '%s (fused STFT + power + band-sparse mel + dB, one launch per step)' % route,
-                     'kernel_route': route, 'bound': 'hbm',
-                     'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                     'traffic': None, 'alg_bytes_per_launch': alg_bytes, 'kernel_ms_mean': mean_ms,
-                     'kernel_ms_p10': quantile(region_mss, 0.1), 'kernel_ms_p90': quantile(region_mss, 0.9),
-                     'kernel_ms_median': med_ms, 'kernel_ms_per_launch_events': per_launch_mean_ms,
-                     'shader_clock_mhz': clock_mhz,
-                     'median_vs_mean_note': 'kernel_ms_mean is a K-launch region / K (launches back to back: no gap, no event '
-                                            'overhead); kernel_ms_median / kernel_ms_per_launch_events bracket EVERY launch with its '
-                                            'own event pair, which adds ~3 us of event processing per launch and lets the '
-                                            'queue drain between launches — it reads higher and is kept only as a cross-check',
-                     'timing': 'median over `repeats` regions of: one HIP event pair on the launch stream around the K timed '
-                               'steps (one launch per step) / K; kernel_ms_per_launch_events / kernel_ms_median: event '
-                               'pairs around single launches; shader_clock_mhz: shader cycles / 100 MHz ticks of every '
-                               'workgroup\'s frame loop, recorded by the kernel (tac_debug_clock_probe)'},
-    }
+    result['roofline'] = {'kernel': '%s (fused STFT + power + band-sparse mel + dB, one launch per step)' % route,
+                           'kernel_route': route, 'bound': 'hbm',
+                           'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                           'traffic': None, 'alg_bytes_per_launch': alg_bytes, 'kernel_ms_mean': mean_ms,
+                           'kernel_ms_p10': quantile(region_mss, 0.1), 'kernel_ms_p90': quantile(region_mss, 0.9),
+                           'kernel_ms_median': med_ms, 'kernel_ms_per_launch_events': per_launch_mean_ms,
+                           'shader_clock_mhz': clock_mhz,
+                           'median_vs_mean_note': 'kernel_ms_mean is a K-launch region / K (launches back to back: no gap, no event '
+                                                  'overhead); kernel_ms_median / kernel_ms_per_launch_events bracket EVERY launch with its '
+                                                  'own event pair, which adds ~3 us of event processing per launch and lets the '
+                                                  'queue drain between launches — it reads higher and is kept only as a cross-check',
+                           'timing': 'median over `repeats` regions of: one HIP event pair on the launch stream around the K timed '
+                                     'steps (one launch per step) / K; kernel_ms_per_launch_events / kernel_ms_median: event '
+                                     'pairs around single launches; shader_clock_mhz: shader cycles / 100 MHz ticks of every '
+                                     'workgroup\'s frame loop, recorded by the kernel (tac_debug_clock_probe)'}
     bound_from_counters(result['roofline'], route, clock_mhz)
     if nbuf > 1:
         # the same loop re-reading ONE batch (163.8 MB: it fits the Infinity Cache) — what rounds 1 and 2 reported
@@ -776,9 +824,12 @@ def dry_run_cpu(a, rank, world):
                 lb, le = g.local_rows(k)
                 g.add(k, model(x[lb:le]))
             assert torch.equal(g.finish(), gathered), method
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {'mel_db': y})
     if rank == 0:
         print(json.dumps({'metric': 'mel frames/sec', 'value': world * BATCH * CHANNELS * FRAMES * a.steps / float(t.item()),
                           'unit': 'frames/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
+                          'ms_per_step': float(t.item()) / a.steps * 1e3,
                           'valid': False, 'data': 'dry run on CPU tensors (control flow only)'}))
     if world > 1:
         dist.destroy_process_group()

@@ -102,7 +102,7 @@ def test_bench_under_torchrun_one_rank():
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr',
            '127.0.0.1', '--master-port', _port(), os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '5',
-           '--warmup', '2', '--repeats', '3', '--no-cpu-baseline', '--no-stages']
+           '--warmup', '2', '--repeats', '3', '--full', '--no-cpu-baseline', '--no-stages']
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]

@@ -520,6 +520,46 @@ def test_bench_gpus_flag_is_real():
     assert mismatch.returncode != 0 and 'WORLD_SIZE=1' in mismatch.stderr
 
 
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed step returned as float32 .npy files, from seeded inputs: two runs
+    with the same arguments dump the same arrays (control flow on CPU tensors; the GPU run shares dump_outputs)."""
+    import json
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    env.pop('WORLD_SIZE', None)
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ('run%d' % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run-cpu', '--steps', '3', '--warmup', '1',
+                              '--dump-outputs', str(d)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env,
+                             timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec['steps'] == 3 and rec['ms_per_step'] > 0
+        assert sorted(os.listdir(d)) == ['mel_db.npy']
+        dumps.append(np.load(d / 'mel_db.npy'))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (4, 1, 128, 17)
+    assert np.isfinite(dumps[0]).all() and np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_outputs_caps_the_size(tmp_path):
+    """An output beyond the 64 MB cap is cut to the same seeded sample of batch rows every time."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('tac_bench', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(600 * 128 * 256, dtype=torch.float32).reshape(600, 1, 128, 256)     # 78.6 MB
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {'mel_db': big, 'codes': torch.arange(10)})
+    a, b = np.load(tmp_path / '0' / 'mel_db.npy'), np.load(tmp_path / '1' / 'mel_db.npy')
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert a.nbytes <= bench.DUMP_BYTES // 2 and a.shape[1:] == (1, 128, 256) and a.shape[0] > 1
+    rows = a[:, 0, 0, 0] // (128 * 256)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, big.numpy()[rows.astype(np.int64)])
+    assert np.load(tmp_path / '0' / 'codes.npy').dtype == np.float32
+
+
 _MEDIAN_CHECK = r'''
 #include <cmath>
 #include <cstdio>

@@ -53,10 +53,10 @@ for label, sub, key, per_frame in (('fused STFT + power + band-sparse mel + dB',
 out = []
 out.append('# profiles/%s — MI355X (gfx950), ROCm 7.2, collected by `tools/collect_profiles.sh %s`, summarised by '
            '`tools/summarize_profiles.py` and this table by `tools/profiles_readme.py`\n' % (tag, tag))
-out.append('* `bench_N1.json` — the JSON line of `python bench.py` (N=1, cfg-2) on the same box: **%.0f M mel frames/s**, '
+out.append('* `bench_N1.json` — the JSON line of `python bench.py --full` (N=1, cfg-2) on the same box: **%.0f M mel frames/s**, '
            '%.4f ms per step; CPU baseline on that box %.0f K frames/s (%d threads).'
            % (bench['value'] / 1e6, bench['ms_per_step'], bench['cpu_baseline']['value'] / 1e3, bench['cpu_baseline']['cores']))
-out.append('* `kernel_stats.csv` — `rocprofv3 --kernel-trace --stats -- python bench.py --steps 50 --warmup 10 '
+out.append('* `kernel_stats.csv` — `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 50 --warmup 10 '
            '--no-cpu-baseline --no-stages` (the headline steps alone; long torch kernel names truncated); `kernel_stats_stages.csv` '
            '— the same command with its stages (the stage kernels\' rows below come from it).')
 out.append('* `pmc_mel.json`, `pmc_stft.json`, `pmc_spec.json` — per-launch means from separate `--pmc` passes '
