@@ -34,10 +34,19 @@ def tac():
     assert torch.cuda.is_available(), 'these tests need the MI355X'
     t._native.lib()
     t.set_strict(True)
-    t._hip.POISON_OUTPUTS = True          # gradient buffers start as NaN: a sample no kernel writes cannot pass by luck
+    t._hip.set_poison_outputs(True)       # every kernel output starts as a NaN pattern: a sample no kernel writes cannot pass by luck
     yield t
-    t._hip.POISON_OUTPUTS = False
+    t._hip.set_poison_outputs(False)
     t.set_strict(False)
+
+
+@pytest.fixture(autouse=True)
+def every_output_written(tac):
+    """After each test: no launch left a position of what it fills holding the poison pattern (named per entry point)."""
+    tac._hip.poison_report()
+    yield
+    left = tac._hip.poison_report()
+    assert not left, 'kernel outputs left unwritten (poisoned elements per entry point): %r' % left
 
 
 def dev(a):

@@ -23,8 +23,9 @@ _lock = threading.Lock()
 launches = {}
 
 
-def _count(name):
+def _count(name, *filled):
     launches[name] = launches.get(name, 0) + 1
+    check_written(name, *filled)
 
 
 # ----------------------------------------------------------------------------- constant-table caches
@@ -266,13 +267,13 @@ def _stft_dft(wave, window, g):
         x = torch.nn.functional.pad(x.unsqueeze(1), (pad, pad), mode=g.pad_mode).squeeze(1)
     x = x.contiguous()
     mat = _dft_matrix(window, g.n_fft, g.win_length, g.onesided, g.normalized)
-    out = torch.empty(g.stft_shape, dtype=torch.float32, device=x.device)
+    out = _empty(g.stft_shape, device=x.device)
     with _native.on_device(x.device):
         rc = _native.lib().tac_apply_filterbank_f32(
             _native.ptr(x), x.shape[0], g.n_fft, g.n_frames, x.stride(0), 1, g.hop,
             _native.ptr(mat), None, 2 * g.n_bins, _native.ptr(out), _native.stream_ptr(x.device))
     _native.check(rc, 'tac_apply_filterbank_f32 (DFT matrix)')
-    _count('tac_apply_filterbank_f32')
+    _count('tac_apply_filterbank_f32', out)
     return out.transpose(-3, -2)
 
 
@@ -281,12 +282,12 @@ def stft(wave, window, n_fft, hop, win_length, center, pad_mode, normalized, one
     if not (g.fft_kernel or (g.mixed_radix and g.onesided)):
         return _stft_dft(wave, window, g)
     src = _rows_of(wave, g)
-    out = torch.empty(g.stft_shape, dtype=torch.float32, device=wave.device)
+    out = _empty(g.stft_shape, device=wave.device)
     with _native.on_device(wave.device):
         rc = _native.lib().tac_stft_f32(_native.ptr(src), _native.ptr(window), g.desc, _native.ptr(out),
                                         _native.stream_ptr(wave.device))
     _native.check(rc, 'tac_stft_f32')
-    _count('tac_stft_f32')
+    _count('tac_stft_f32', out)
     return out.transpose(-3, -2)
 
 
@@ -296,18 +297,103 @@ def spectrogram(wave, window, n_fft, hop, win_length, center, pad_mode, normaliz
         mag = complex_norm(_stft_dft(wave, window, g), power)
         return amplitude_to_db(mag, ref, amin) if db else mag
     src = _rows_of(wave, g)
-    out = torch.empty(g.spec_shape, dtype=torch.float32, device=wave.device)
+    out = _empty(g.spec_shape, device=wave.device)
     with _native.on_device(wave.device):
         rc = _native.lib().tac_spectrogram_f32(
             _native.ptr(src), _native.ptr(window), g.desc, float(power), 1 if db else 0, float(ref), float(amin),
             _native.ptr(out), _native.stream_ptr(wave.device))
     _native.check(rc, 'tac_spectrogram_f32')
-    _count('tac_spectrogram_f32')
+    _count('tac_spectrogram_f32', out)
     return out.transpose(-2, -1)
 
 
-#: test hook: gradient outputs start as NaN, so that a position no kernel writes cannot pass a comparison by luck
-POISON_OUTPUTS = False
+# ----------------------------------------------------------------------------- poisoned outputs (test hook)
+# While ``set_poison_outputs(True)`` is on, every buffer a launcher here allocates for a kernel to fill starts as a fixed bit
+# pattern (a quiet NaN with a payload no arithmetic produces; a negative sentinel for int64 codes), and after each launch the
+# part of the buffer that launch fills is compared with the pattern on the launch stream.  Hits are added to a device counter
+# per entry point; ``poison_report()`` reads them (one host sync, outside any call).  A position no kernel writes can then
+# neither pass a comparison by holding an earlier identical result nor hide as zeros of a fresh allocation.
+# Constant tables built once per filterbank or window (packed banks, tile plans, adjoint tables) and the gradient copies torch
+# itself fills (``go``) are not per-call kernel outputs and are allocated plainly.
+POISON_OUTPUTS = False          # read-only mirror of the switch: change it with set_poison_outputs()
+
+#: the poison patterns, as the integers of the same width the buffer is viewed as
+POISON_BITS = {torch.float32: 0x7FC0DEAD, torch.float64: 0x7FF80000DEADBEEF, torch.int64: -0x21524111DEADBEEF,
+               torch.int32: -0x21524111}
+_BIT_VIEW = {torch.float32: torch.int32, torch.float64: torch.int64, torch.int64: torch.int64, torch.int32: torch.int32}
+_poison_hits = {}                # (entry point, device index) -> int64 device counter of poisoned elements left after a launch
+
+
+def set_poison_outputs(on):
+    """Switch poisoning and the write check on or off — for the ctypes launchers here and the compiled binding alike."""
+    global POISON_OUTPUTS
+    POISON_OUTPUTS = bool(on)
+    ext = _native.ext()
+    if ext is not None:
+        ext.set_poison(POISON_OUTPUTS)
+
+
+def poison_fill(t):
+    """Fill ``t`` (float32 / float64 / int32 / int64, any device) with its poison pattern; returns ``t``."""
+    if t.numel():
+        t.view(_BIT_VIEW[t.dtype]).fill_(POISON_BITS[t.dtype])
+    return t
+
+
+def poison_count(t):
+    """Number of elements of ``t`` that hold the poison pattern, as a 0-d int64 tensor on ``t``'s device (no host sync)."""
+    if not t.numel():
+        return torch.zeros((), dtype=torch.int64, device=t.device)
+    return (t.view(_BIT_VIEW[t.dtype]) == POISON_BITS[t.dtype]).sum()
+
+
+def _poisoning(t):
+    return POISON_OUTPUTS and not (t.is_cuda and torch.cuda.is_current_stream_capturing())
+
+
+def _empty(shape, dtype=torch.float32, device=None):
+    out = torch.empty(shape, dtype=dtype, device=device)
+    return poison_fill(out) if _poisoning(out) else out
+
+
+def _empty_strided(shape, stride, dtype=torch.float32, device=None):
+    out = torch.empty_strided(shape, stride, dtype=dtype, device=device)
+    return poison_fill(out) if _poisoning(out) else out
+
+
+def _empty_like(x):
+    out = torch.empty_like(x)
+    return poison_fill(out) if _poisoning(out) else out
+
+
+def check_written(name, *parts):
+    """After a launch of ``name``: count the poisoned elements left in ``parts`` (the tensors, or the slices of them, that
+    this launch fills) into the entry point's device counter.  Enqueued on the current stream; skipped while a graph is
+    being captured and while poisoning is off."""
+    if not POISON_OUTPUTS:
+        return
+    for t in parts:
+        if t is None or not t.numel() or not _poisoning(t):
+            continue
+        key = (name, t.device.index)
+        acc = _poison_hits.get(key)
+        if acc is None:
+            with torch.inference_mode(False):       # (an inference tensor could not be updated outside inference mode)
+                acc = _poison_hits[key] = torch.zeros((), dtype=torch.int64, device=t.device)
+        acc += poison_count(t)
+
+
+def poison_report(reset=True):
+    """{entry point: number of poisoned elements its launches left} for every entry point with at least one, since the last
+    reset.  Reads the device counters (a host synchronisation): call it between calls, not inside one."""
+    bad = {}
+    for (name, _), acc in list(_poison_hits.items()):
+        n = int(acc.item())
+        if n:
+            bad[name] = bad.get(name, 0) + n
+    if reset:
+        _poison_hits.clear()
+    return bad
 
 # A/B knob for the two fused Melspectrogram kernels: 'auto' (band-sparse when the bank allows it, else MFMA),
 # 'sparse', 'mfma'
@@ -402,13 +488,15 @@ class MelPlan(object):
             v = c.launch(wave)
             if v is not None:
                 launches['tac_melspec_sparse_f32'] = launches.get('tac_melspec_sparse_f32', 0) + 1
+                if POISON_OUTPUTS:                  # (the binding poisons its output while the switch is on)
+                    check_written('tac_melspec_sparse_f32', v)
             else:
                 self.last_rc = c.last_rc
             return v
         return self.launch(wave) if self.matches(wave) else None
 
     def launch(self, wave):
-        out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        out = _empty(self.shape, device=self.device)
         rc = self.fn(wave.data_ptr(), self.win_ptr, self.desc, self.power, self.wpack_ptr, self.dsc_ptr, self.info_ptr,
                      self.n_mels, self.db, self.ref, self.amin, out.data_ptr(),
                      torch._C._cuda_getCurrentRawStream(self.dev_index))
@@ -416,6 +504,8 @@ class MelPlan(object):
             self.last_rc = rc
             return None                     # (the general path reports it)
         launches['tac_melspec_sparse_f32'] = launches.get('tac_melspec_sparse_f32', 0) + 1
+        if POISON_OUTPUTS:
+            check_written('tac_melspec_sparse_f32', out)
         return out.transpose(-2, -1)
 
     def matches(self, wave):
@@ -482,7 +572,7 @@ def melspectrogram(wave, window, fb, n_fft, hop, win_length, center, pad_mode, n
         return apply_filterbank(spec, fb, db=(ref, amin) if db else None)    # the dB epilogue rides on the filterbank kernel
     n_mels = fb.shape[1]
     src = _rows_of(wave, g)
-    out = torch.empty(g.lead + (g.n_frames, n_mels), dtype=torch.float32, device=wave.device)
+    out = _empty(g.lead + (g.n_frames, n_mels), device=wave.device)
     if route == 'sparse':          # band-sparse contraction (the faster form for triangular banks)
         wpack, desc, info = _melbank_pack(fb, g.n_fft)
         with _native.on_device(wave.device):
@@ -495,7 +585,7 @@ def melspectrogram(wave, window, fb, n_fft, hop, win_length, center, pad_mode, n
                                False, 1.0, 1e-7)
             return apply_filterbank(spec, fb, db=(ref, amin) if db else None)
         _native.check(rc, 'tac_melspec_sparse_f32')
-        _count('tac_melspec_sparse_f32')
+        _count('tac_melspec_sparse_f32', out)
         return out.transpose(-2, -1)
     _, plan_host = _filterbank_plan(fb)
     with _native.on_device(wave.device):
@@ -504,7 +594,7 @@ def melspectrogram(wave, window, fb, n_fft, hop, win_length, center, pad_mode, n
             ctypes.cast(plan_host, ctypes.c_void_p), n_mels, 1 if db else 0, float(ref), float(amin),
             _native.ptr(out), _native.stream_ptr(wave.device))
     _native.check(rc, 'tac_melspec_f32')
-    _count('tac_melspec_f32')
+    _count('tac_melspec_f32', out)
     return out.transpose(-2, -1)
 
 
@@ -516,7 +606,7 @@ def apply_filterbank(spec, fb, allow_sparse=True, db=None):
     n_freqs, n_frames = spec.shape[-2], spec.shape[-1]
     lead = tuple(spec.shape[:-2])
     n_mels = fb.shape[1]
-    out = torch.empty(lead + (n_frames, n_mels), dtype=torch.float32, device=spec.device)
+    out = _empty(lead + (n_frames, n_mels), device=spec.device)
     if out.numel():
         rows = spec.reshape(-1, n_freqs, n_frames)
         # frame-major spectrogram (what the kernels here produce) + band-sparse bank: stream it through the fused
@@ -539,7 +629,7 @@ def apply_filterbank(spec, fb, allow_sparse=True, db=None):
                         1, float(db[0]), float(db[1]), _native.ptr(out), _native.stream_ptr(spec.device))
             if rc != _native.TAC_E_UNSUPPORTED:
                 _native.check(rc, name)
-                _count(name)
+                _count(name, out)
                 return out.transpose(-2, -1)
         plan, _ = _filterbank_plan(fb)
         with _native.on_device(spec.device):
@@ -548,7 +638,7 @@ def apply_filterbank(spec, fb, allow_sparse=True, db=None):
                 rows.stride(2), _native.ptr(fb), _native.ptr(plan), n_mels, _native.ptr(out),
                 _native.stream_ptr(spec.device))
         _native.check(rc, 'tac_apply_filterbank_f32')
-        _count('tac_apply_filterbank_f32')
+        _count('tac_apply_filterbank_f32', out)
     out = out.transpose(-2, -1)
     return out if db is None else amplitude_to_db(out, db[0], db[1])
 
@@ -575,8 +665,7 @@ def _pairs(z):
 
 
 def _pair_output(z):
-    return torch.empty_strided(z.shape[:-1], tuple(s // 2 for s in z.stride()[:-1]), dtype=torch.float32,
-                               device=z.device)
+    return _empty_strided(z.shape[:-1], tuple(s // 2 for s in z.stride()[:-1]), device=z.device)
 
 
 def complex_norm(z, power):
@@ -588,7 +677,7 @@ def complex_norm(z, power):
             rc = _native.lib().tac_complex_norm_f32(_native.ptr(z), n, float(power), _native.ptr(out),
                                                     _native.stream_ptr(z.device))
         _native.check(rc, 'tac_complex_norm_f32')
-        _count('tac_complex_norm_f32')
+        _count('tac_complex_norm_f32', out)
     return out
 
 
@@ -600,7 +689,7 @@ def angle(z):
             rc = _native.lib().tac_magphase_f32(_native.ptr(z), phase.numel(), 1.0, None, _native.ptr(phase),
                                                 _native.stream_ptr(z.device))
         _native.check(rc, 'tac_magphase_f32')
-        _count('tac_magphase_f32')
+        _count('tac_magphase_f32', phase)
     return phase
 
 
@@ -612,7 +701,7 @@ def magphase(z, power):
             rc = _native.lib().tac_magphase_f32(_native.ptr(z), phase.numel(), float(power), _native.ptr(mag),
                                                 _native.ptr(phase), _native.stream_ptr(z.device))
         _native.check(rc, 'tac_magphase_f32')
-        _count('tac_magphase_f32')
+        _count('tac_magphase_f32', mag, phase)
     return mag, phase
 
 
@@ -652,7 +741,7 @@ def phase_vocoder(spec, rate, phase_advance):
     rows = spec.reshape((-1,) + tuple(spec.shape[-3:]))          # a view whenever the leading dims collapse
     if any(st % 2 for st in rows.stride()[:-1]) or rows.data_ptr() % (2 * rows.element_size()):
         rows = rows.contiguous()                                 # (re, im) pairs are fetched as one aligned access
-    out = torch.empty(lead + (n_out, n_freqs, 2), dtype=dtype, device=spec.device)
+    out = _empty(lead + (n_out, n_freqs, 2), dtype=dtype, device=spec.device)
     if out.numel() and n_frames:
         name = 'tac_phase_vocoder_f64' if dtype == torch.float64 else 'tac_phase_vocoder_f32'
         with _native.on_device(spec.device):
@@ -661,7 +750,7 @@ def phase_vocoder(spec, rate, phase_advance):
                 rows.stride(1), rows.stride(2), _native.ptr(pa), _native.ptr(idx0), _native.ptr(idx1),
                 _native.ptr(alpha), n_out, _native.ptr(out), _native.stream_ptr(spec.device))
         _native.check(rc, name)
-        _count(name)
+        _count(name, out)
     return out.transpose(-3, -2)
 
 
@@ -694,12 +783,12 @@ def phase_vocoder_backward(spec, rate, grad_out):
 # ----------------------------------------------------------------------------- elementwise
 def _unary(x, name, launch):
     x = x if is_dense(x) else x.contiguous()
-    out = torch.empty_like(x)
+    out = _empty_like(x)
     if x.numel():
         with _native.on_device(x.device):
             rc = launch(_native.lib(), _native.ptr(x), x.numel(), _native.ptr(out), _native.stream_ptr(x.device))
         _native.check(rc, name)
-        _count(name)
+        _count(name, out)
     return out
 
 
@@ -730,7 +819,7 @@ def _mulaw_tables(device):
 
 def mu_law_encoding(x, n_quantize):
     x = x if x.is_contiguous() else x.contiguous()
-    out = torch.empty(x.shape, dtype=torch.int64, device=x.device)
+    out = _empty(x.shape, dtype=torch.int64, device=x.device)
     if x.numel():
         if n_quantize == 256:
             thr, n_pos, n_neg, zero, _ = _mulaw_tables(x.device)
@@ -741,21 +830,21 @@ def mu_law_encoding(x, n_quantize):
             rc = _native.lib().tac_mulaw_encode_f32_i64(_native.ptr(x), x.numel(), n_quantize, thr_ptr, n_pos, n_neg,
                                                         zero, _native.ptr(out), _native.stream_ptr(x.device))
         _native.check(rc, 'tac_mulaw_encode_f32_i64')
-        _count('tac_mulaw_encode_f32_i64')
+        _count('tac_mulaw_encode_f32_i64', out)
     return out
 
 
 def mu_law_decoding_int(codes, n_quantize):
     """int64 codes -> float32 (reference functional.py:348-354 with the default dtype)."""
     codes = codes.to(torch.int64).contiguous()
-    out = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
+    out = _empty(codes.shape, device=codes.device)
     if codes.numel():
         lut_ptr = _native.ptr(_mulaw_tables(codes.device)[4]) if n_quantize == 256 else None
         with _native.on_device(codes.device):
             rc = _native.lib().tac_mulaw_decode_i64_f32(_native.ptr(codes), codes.numel(), n_quantize, lut_ptr,
                                                         _native.ptr(out), _native.stream_ptr(codes.device))
         _native.check(rc, 'tac_mulaw_decode_i64_f32')
-        _count('tac_mulaw_decode_i64_f32')
+        _count('tac_mulaw_decode_i64_f32', out)
     return out
 
 
@@ -772,26 +861,26 @@ def mu_law_decoding_float(codes, n_quantize):
 def mu_law_encoding_f64(x, n_quantize):
     """float64 waveform -> int64 codes, the formula in double (reference functional.py:329-335 on double input)."""
     x = x if x.is_contiguous() else x.contiguous()
-    out = torch.empty(x.shape, dtype=torch.int64, device=x.device)
+    out = _empty(x.shape, dtype=torch.int64, device=x.device)
     if x.numel():
         with _native.on_device(x.device):
             rc = _native.lib().tac_mulaw_encode_f64_i64(_native.ptr(x), x.numel(), n_quantize, _native.ptr(out),
                                                         _native.stream_ptr(x.device))
         _native.check(rc, 'tac_mulaw_encode_f64_i64')
-        _count('tac_mulaw_encode_f64_i64')
+        _count('tac_mulaw_encode_f64_i64', out)
     return out
 
 
 def mu_law_decoding_f64(codes, n_quantize):
     """int64 or float64 codes -> float64 (reference functional.py:349-354 evaluated in double)."""
     codes = codes if codes.is_contiguous() else codes.contiguous()
-    out = torch.empty(codes.shape, dtype=torch.float64, device=codes.device)
+    out = _empty(codes.shape, dtype=torch.float64, device=codes.device)
     if codes.numel():
         with _native.on_device(codes.device):
             rc = _native.lib().tac_mulaw_decode_f64(_native.ptr(codes), 1 if codes.dtype == torch.int64 else 0, codes.numel(),
                                                     n_quantize, _native.ptr(out), _native.stream_ptr(codes.device))
         _native.check(rc, 'tac_mulaw_decode_f64')
-        _count('tac_mulaw_decode_f64')
+        _count('tac_mulaw_decode_f64', out)
     return out
 
 
@@ -847,14 +936,14 @@ def apply_filterbank_backward(grad_out, fb):
         gm = gm if gm.is_contiguous() else gm.contiguous()
         if gm.dtype != torch.float32:
             gm = gm.float()
-        out = torch.empty(tuple(gm.shape[:-1]) + (n_freqs,), dtype=torch.float32, device=gm.device)
+        out = _empty(tuple(gm.shape[:-1]) + (n_freqs,), device=gm.device)
         with _native.on_device(gm.device):
             rc = _native.lib().tac_apply_filterbank_adjoint_f32(_native.ptr(gm), gm.numel() // n_mels, n_mels,
                                                                 _native.ptr(table), n_freqs, _native.ptr(out),
                                                                 _native.stream_ptr(gm.device))
         if rc != _native.TAC_E_UNSUPPORTED:
             _native.check(rc, 'tac_apply_filterbank_adjoint_f32')
-            _count('tac_apply_filterbank_adjoint_f32')
+            _count('tac_apply_filterbank_adjoint_f32', out)
             return out.transpose(-2, -1)
     return apply_filterbank(grad_out, transposed_bank(fb), allow_sparse=False)
 
@@ -891,10 +980,8 @@ def _melspectrogram_backward_ola(grad_mel, wave, window, fb, n_fft, hop, win_len
     gm = gm if gm.is_contiguous() else gm.contiguous()
     if gm.dtype != torch.float32:
         gm = gm.float()
-    out = torch.empty(tuple(wave.shape), dtype=torch.float32, device=wave.device)
-    if POISON_OUTPUTS:
-        out.fill_(float('nan'))
-    work = torch.empty(max(int(need), 4) // 4, dtype=torch.float32, device=wave.device)
+    out = _empty(tuple(wave.shape), device=wave.device)
+    work = _empty(max(int(need), 4) // 4, device=wave.device)          # (scratch: poisoned, not checked)
     with _native.on_device(wave.device):
         rc = _native.lib().tac_melspectrogram_backward_ola_f32(
             _native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc, _native.ptr(gm), n_mels, _native.ptr(table),
@@ -903,7 +990,7 @@ def _melspectrogram_backward_ola(grad_mel, wave, window, fb, n_fft, hop, win_len
     if rc == _native.TAC_E_UNSUPPORTED:
         return None
     _native.check(rc, 'tac_melspectrogram_backward_ola_f32')
-    _count('tac_melspectrogram_backward_ola_f32')
+    _count('tac_melspectrogram_backward_ola_f32', out)
     return out
 
 
@@ -921,8 +1008,8 @@ def _melspectrogram_backward_fused_n400(grad_mel, wave, window, fb, hop, win_len
     gm = gm if gm.is_contiguous() else gm.contiguous()
     if gm.dtype != torch.float32:
         gm = gm.float()
-    frames = torch.empty((g.rows, g.n_frames, 400), dtype=torch.float32, device=wave.device)
-    out = torch.empty(tuple(wave.shape), dtype=torch.float32, device=wave.device)
+    frames = _empty((g.rows, g.n_frames, 400), device=wave.device)
+    out = _empty(tuple(wave.shape), device=wave.device)
     desc = _native.StftDesc(rows=g.rows, length=g.length, row_stride=g.length, n_fft=400, hop=hop, win_length=win_length,
                             center=1 if center else 0, pad_mode=_native.PAD_MODES[pad_mode],
                             normalized=1 if normalized else 0, onesided=1, reserved=0)
@@ -933,11 +1020,11 @@ def _melspectrogram_backward_fused_n400(grad_mel, wave, window, fb, hop, win_len
         if rc == _native.TAC_E_UNSUPPORTED:
             return None
         _native.check(rc, 'tac_melspectrogram_backward_f32')
-        _count('tac_melspectrogram_backward_f32')
+        _count('tac_melspectrogram_backward_f32', frames)
         rc = _native.lib().tac_overlap_add_f32(_native.ptr(frames), desc, _native.ptr(out), g.length,
                                                _native.stream_ptr(wave.device))
         _native.check(rc, 'tac_overlap_add_f32')
-        _count('tac_overlap_add_f32')
+        _count('tac_overlap_add_f32', out)
     return out
 
 
@@ -960,24 +1047,22 @@ def stft_backward(grad_spec, wave, window, n_fft, hop, win_length, center, pad_m
         gn = gn if gn.is_contiguous() else gn.contiguous()
         if gn.dtype != torch.float32:
             gn = gn.float()
-    out = torch.empty(tuple(wave.shape), dtype=torch.float32, device=wave.device)
-    if POISON_OUTPUTS:
-        out.fill_(float('nan'))
+    out = _empty(tuple(wave.shape), device=wave.device)
     if gs is None and g.desc is not None:
         # fft_length 256 … 2048 with hop a multiple of fft_length / 16, fft_length 400 with hop a multiple of 4: overlap-add
         # inside the kernel, no frame gradients in memory
         need = _native.lib().tac_spectrogram_backward_ola_workspace(g.desc)
         if need >= 0:
-            work = torch.empty(max(int(need), 4) // 4, dtype=torch.float32, device=wave.device)
+            work = _empty(max(int(need), 4) // 4, device=wave.device)  # (scratch: poisoned, not checked)
             with _native.on_device(wave.device):
                 rc = _native.lib().tac_spectrogram_backward_ola_f32(
                     _native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc, _native.ptr(gn), float(power),
                     _native.ptr(work), int(need), _native.ptr(out), g.length, _native.stream_ptr(wave.device))
             if rc != _native.TAC_E_UNSUPPORTED:
                 _native.check(rc, 'tac_spectrogram_backward_ola_f32')
-                _count('tac_spectrogram_backward_ola_f32')
+                _count('tac_spectrogram_backward_ola_f32', out)
                 return out
-    frames = torch.empty((g.rows, g.n_frames, n_fft), dtype=torch.float32, device=wave.device)
+    frames = _empty((g.rows, g.n_frames, n_fft), device=wave.device)
     desc = _native.StftDesc(rows=g.rows, length=g.length, row_stride=g.length, n_fft=n_fft, hop=hop,
                             win_length=win_length, center=1 if center else 0, pad_mode=_native.PAD_MODES[pad_mode],
                             normalized=1 if normalized else 0, onesided=1, reserved=0)
@@ -986,22 +1071,22 @@ def stft_backward(grad_spec, wave, window, n_fft, hop, win_length, center, pad_m
             rc = _native.lib().tac_stft_backward_f32(_native.ptr(gs), _native.ptr(window), desc, _native.ptr(frames),
                                                      _native.stream_ptr(wave.device))
             _native.check(rc, 'tac_stft_backward_f32')
-            _count('tac_stft_backward_f32')
+            _count('tac_stft_backward_f32', frames)
         elif gs is None:
             rc = _native.lib().tac_spectrogram_backward_f32(_native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc,
                                                             _native.ptr(gn), float(power), _native.ptr(frames),
                                                             _native.stream_ptr(wave.device))
             _native.check(rc, 'tac_spectrogram_backward_f32')
-            _count('tac_spectrogram_backward_f32')
+            _count('tac_spectrogram_backward_f32', frames)
         else:
             rc = _native.lib().tac_stft_norm_backward_f32(_native.ptr(gs), _native.ptr(gn), float(power), _native.ptr(window),
                                                           desc, _native.ptr(frames), _native.stream_ptr(wave.device))
             _native.check(rc, 'tac_stft_norm_backward_f32')
-            _count('tac_stft_norm_backward_f32')
+            _count('tac_stft_norm_backward_f32', frames)
         rc = _native.lib().tac_overlap_add_f32(_native.ptr(frames), desc, _native.ptr(out), g.length,
                                                _native.stream_ptr(wave.device))
         _native.check(rc, 'tac_overlap_add_f32')
-        _count('tac_overlap_add_f32')
+        _count('tac_overlap_add_f32', out)
     return out
 
 
@@ -1015,24 +1100,24 @@ def fold_twosided(grad, n_fft, width):
     """physical frame-major gradient of a two-sided output (*, T, n_fft[, 2]) -> the one-sided bins (*, T, F[, 2])."""
     n_bins = n_fft // 2 + 1
     lead = tuple(grad.shape[:-2]) if width == 2 else tuple(grad.shape[:-1])
-    out = torch.empty(lead + ((n_bins, 2) if width == 2 else (n_bins,)), dtype=torch.float32, device=grad.device)
+    out = _empty(lead + ((n_bins, 2) if width == 2 else (n_bins,)), device=grad.device)
     frames = out.numel() // (n_bins * width)
     with _native.on_device(grad.device):
         rc = _native.lib().tac_fold_twosided_f32(_native.ptr(grad), frames, n_fft, width, _native.ptr(out),
                                                  _native.stream_ptr(grad.device))
     _native.check(rc, 'tac_fold_twosided_f32')
-    _count('tac_fold_twosided_f32')
+    _count('tac_fold_twosided_f32', out)
     return out
 
 
 def sum_slabs(x):
     """(S, ...) -> (...): the slabs added up in order (deterministic)."""
-    out = torch.empty(tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    out = _empty(tuple(x.shape[1:]), device=x.device)
     with _native.on_device(x.device):
         rc = _native.lib().tac_sum_slabs_f32(_native.ptr(x), x.shape[0], out.numel(), _native.ptr(out),
                                              _native.stream_ptr(x.device))
     _native.check(rc, 'tac_sum_slabs_f32')
-    _count('tac_sum_slabs_f32')
+    _count('tac_sum_slabs_f32', out)
     return out
 
 
@@ -1072,13 +1157,13 @@ def _desc(g, row_stride=None, onesided=None):
 
 def _frame_gradients(gs, window, g):
     """one-sided gradient spectrum (rows, T, F, 2) -> frame gradients (rows, T, n_fft), window and scale applied."""
-    frames = torch.empty((g.rows, g.n_frames, g.n_fft), dtype=torch.float32, device=gs.device)
+    frames = _empty((g.rows, g.n_frames, g.n_fft), device=gs.device)
     with _native.on_device(gs.device):
         if fft_kernel_size(g.n_fft) or g.mixed_radix or smooth_fft_size(g.n_fft) or g.n_fft == 8192:
             rc = _native.lib().tac_stft_backward_f32(_native.ptr(gs), _native.ptr(window), _desc(g, onesided=1),
                                                      _native.ptr(frames), _native.stream_ptr(gs.device))
             _native.check(rc, 'tac_stft_backward_f32')
-            _count('tac_stft_backward_f32')
+            _count('tac_stft_backward_f32', frames)
         else:
             n_cols = 2 * (g.n_fft // 2 + 1)
             mat_t = _dft_matrix_t(window, g.n_fft, g.win_length, g.normalized)
@@ -1086,7 +1171,7 @@ def _frame_gradients(gs, window, g):
                 _native.ptr(gs), g.rows, n_cols, g.n_frames, g.n_frames * n_cols, 1, n_cols, _native.ptr(mat_t), None,
                 g.n_fft, _native.ptr(frames), _native.stream_ptr(gs.device))
             _native.check(rc, 'tac_apply_filterbank_f32 (DFT matrix, adjoint)')
-            _count('tac_apply_filterbank_f32')
+            _count('tac_apply_filterbank_f32', frames)
     return frames
 
 
@@ -1104,12 +1189,12 @@ def stft_backward_general(grad_spec, wave, window, n_fft, hop, win_length, cente
     grad_wave = grad_window = None
     if need_wave:
         frames = _frame_gradients(gs, window, g)
-        grad_wave = torch.empty(tuple(wave.shape), dtype=torch.float32, device=dev)
+        grad_wave = _empty(tuple(wave.shape), device=dev)
         with _native.on_device(dev):
             rc = _native.lib().tac_overlap_add_f32(_native.ptr(frames), _desc(g), _native.ptr(grad_wave), g.length,
                                                    _native.stream_ptr(dev))
         _native.check(rc, 'tac_overlap_add_f32')
-        _count('tac_overlap_add_f32')
+        _count('tac_overlap_add_f32', grad_wave)
         del frames
     if need_window:
         unwindowed = _frame_gradients(gs, _ones_window(dev, win_length), g)
@@ -1118,12 +1203,12 @@ def stft_backward_general(grad_spec, wave, window, n_fft, hop, win_length, cente
         n_part = int(_native.lib().tac_window_grad_partials(desc))
         if n_part < 0:
             _native.check(n_part, 'tac_window_grad_partials')
-        partial = torch.empty((n_part, n_fft), dtype=torch.float32, device=dev)
+        partial = _empty((n_part, n_fft), device=dev)
         with _native.on_device(dev):
             rc = _native.lib().tac_window_grad_f32(_native.ptr(unwindowed), _native.ptr(src), desc, _native.ptr(partial),
                                                    n_part, _native.stream_ptr(dev))
         _native.check(rc, 'tac_window_grad_f32')
-        _count('tac_window_grad_f32')
+        _count('tac_window_grad_f32', partial)
         off = (n_fft - win_length) // 2
         grad_window = sum_slabs(partial)[off:off + win_length]
     return grad_wave, grad_window
@@ -1140,14 +1225,14 @@ def filterbank_grad(spec, grad_out):
     total = sp.numel() // n_freqs
     if total >= 2 ** 31:
         raise NotImplementedError('filterbank gradient: more than 2^31 frames in one call')
-    out = torch.empty((n_freqs, n_mels), dtype=torch.float32, device=sp.device)
+    out = _empty((n_freqs, n_mels), device=sp.device)
     if total == 0:
         return out.zero_()
     with _native.on_device(sp.device):
         rc = _native.lib().tac_apply_filterbank_f32(_native.ptr(sp), 1, total, n_freqs, 0, n_freqs, 1, _native.ptr(gm), None,
                                                     n_mels, _native.ptr(out), _native.stream_ptr(sp.device))
     _native.check(rc, 'tac_apply_filterbank_f32 (filterbank gradient)')
-    _count('tac_apply_filterbank_f32')
+    _count('tac_apply_filterbank_f32', out)
     return out
 
 
@@ -1173,14 +1258,14 @@ def complex_norm_backward(z, grad_out, power):
     else:
         go = torch.empty_strided(z.shape[:-1], want, dtype=torch.float32, device=z.device)
         go.copy_(grad_out)
-    gz = torch.empty_strided(z.shape, z.stride(), dtype=torch.float32, device=z.device)
+    gz = _empty_strided(z.shape, z.stride(), device=z.device)
     n = go.numel()
     if n:
         with _native.on_device(z.device):
             rc = _native.lib().tac_complex_norm_backward_f32(_native.ptr(z), _native.ptr(go), n, float(power),
                                                              _native.ptr(gz), _native.stream_ptr(z.device))
         _native.check(rc, 'tac_complex_norm_backward_f32')
-        _count('tac_complex_norm_backward_f32')
+        _count('tac_complex_norm_backward_f32', gz)
     return gz
 
 
@@ -1197,7 +1282,7 @@ def magphase_backward(z, grad_mag, grad_phase, power):
         go.copy_(g)
         return go
     gm, gp = ordered(grad_mag), ordered(grad_phase)
-    gz = torch.empty_strided(z.shape, z.stride(), dtype=torch.float32, device=z.device)
+    gz = _empty_strided(z.shape, z.stride(), device=z.device)
     n = z.numel() // 2
     if n:
         with _native.on_device(z.device):
@@ -1205,7 +1290,7 @@ def magphase_backward(z, grad_mag, grad_phase, power):
                                                          None if gp is None else _native.ptr(gp), n, float(power),
                                                          _native.ptr(gz), _native.stream_ptr(z.device))
         _native.check(rc, 'tac_magphase_backward_f32')
-        _count('tac_magphase_backward_f32')
+        _count('tac_magphase_backward_f32', gz)
     return gz
 
 
@@ -1216,13 +1301,13 @@ def db_to_amplitude_backward(x, grad_out, ref):
     else:
         go = torch.empty_like(x)
         go.copy_(grad_out)
-    gx = torch.empty_like(x)
+    gx = _empty_like(x)
     if x.numel():
         with _native.on_device(x.device):
             rc = _native.lib().tac_db_to_amplitude_backward_f32(_native.ptr(x), _native.ptr(go), x.numel(), float(ref),
                                                                 _native.ptr(gx), _native.stream_ptr(x.device))
         _native.check(rc, 'tac_db_to_amplitude_backward_f32')
-        _count('tac_db_to_amplitude_backward_f32')
+        _count('tac_db_to_amplitude_backward_f32', gx)
     return gx
 
 
@@ -1233,13 +1318,13 @@ def amplitude_to_db_backward(x, grad_out, amin):
     else:
         go = torch.empty_like(x)
         go.copy_(grad_out)
-    gx = torch.empty_like(x)
+    gx = _empty_like(x)
     if x.numel():
         with _native.on_device(x.device):
             rc = _native.lib().tac_amplitude_to_db_backward_f32(_native.ptr(x), _native.ptr(go), x.numel(), float(amin),
                                                                 _native.ptr(gx), _native.stream_ptr(x.device))
         _native.check(rc, 'tac_amplitude_to_db_backward_f32')
-        _count('tac_amplitude_to_db_backward_f32')
+        _count('tac_amplitude_to_db_backward_f32', gx)
     return gx
 
 
@@ -1257,7 +1342,7 @@ def hpss(mag, kernel_f, kernel_t, power, hard, masks_only=False):
     if rows.data_ptr() != mag.data_ptr():                          # leading dims do not collapse in this layout
         mag = mag.contiguous()
         rows = mag.reshape(-1, n_freqs, n_frames)
-    outs = [torch.empty_like(mag) for _ in range(2 if masks_only else 4)]
+    outs = [_empty_like(mag) for _ in range(2 if masks_only else 4)]
     if mag.numel():
         null = ctypes.c_void_p(0)
         with _native.on_device(mag.device):
@@ -1268,7 +1353,7 @@ def hpss(mag, kernel_f, kernel_t, power, hard, masks_only=False):
                                             null if masks_only else _native.ptr(outs[1]), _native.ptr(outs[-2]),
                                             _native.ptr(outs[-1]), _native.stream_ptr(mag.device))
         _native.check(rc, 'tac_hpss_f32')
-        _count('tac_hpss_f32')
+        _count('tac_hpss_f32', *outs)
     return tuple(outs)
 
 
@@ -1308,12 +1393,12 @@ def hpss_backward(mag, kernel_f, kernel_t, power, hard, grads):
 def pcm16_to_f32(x):
     """int16 PCM -> float32 in [-1, 1): x * 2^-15 (for the kernels without a coded frame load)."""
     x = x if x.is_contiguous() else x.contiguous()
-    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    out = _empty(x.shape, device=x.device)
     if x.numel():
         with _native.on_device(x.device):
             rc = _native.lib().tac_pcm16_to_f32(_native.ptr(x), x.numel(), _native.ptr(out), _native.stream_ptr(x.device))
         _native.check(rc, 'tac_pcm16_to_f32')
-        _count('tac_pcm16_to_f32')
+        _count('tac_pcm16_to_f32', out)
     return out
 
 
@@ -1339,7 +1424,7 @@ def melspectrogram_coded(samples, window, fb, n_fft, hop, win_length, center, pa
     fmt = _SAMPLE_FORMATS[samples.dtype]
     lut = _mulaw_tables(samples.device)[4] if fmt != _native.SAMPLES_I16 else None
     src = _rows_of(samples, g)
-    out = torch.empty(g.lead + (g.n_frames, fb.shape[1]), dtype=torch.float32, device=samples.device)
+    out = _empty(g.lead + (g.n_frames, fb.shape[1]), device=samples.device)
     with _native.on_device(samples.device):
         rc = _native.lib().tac_melspec_sparse_coded_f32(
             _native.ptr(src), fmt, None if lut is None else _native.ptr(lut), _native.ptr(window), g.desc, float(power),
@@ -1348,5 +1433,5 @@ def melspectrogram_coded(samples, window, fb, n_fft, hop, win_length, center, pa
     if rc == _native.TAC_E_UNSUPPORTED:
         return None
     _native.check(rc, 'tac_melspec_sparse_coded_f32')
-    _count('tac_melspec_sparse_coded_f32')
+    _count('tac_melspec_sparse_coded_f32', out)
     return out.transpose(-2, -1)

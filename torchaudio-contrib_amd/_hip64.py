@@ -50,27 +50,32 @@ def _desc(g):
         onesided=1 if g.onesided else 0, reserved=0)
 
 
-def _launch(name, dev, *args):
+def _empty(shape, device):
+    return H._empty(shape, dtype=_F64, device=device)
+
+
+def _launch(name, dev, filled, *args):
+    """One launch of ``name``; ``filled``: the tensors (or slices) it fills, checked for poison while that is on."""
     with _native.on_device(dev):
         rc = getattr(_native.lib(), name)(*args, _native.stream_ptr(dev))
     _native.check(rc, name)
-    H._count(name)
+    H._count(name, *filled)
 
 
 def stft(wave, window, n_fft, hop, win_length, center, pad_mode, normalized, onesided):
     g = H.geometry(wave, n_fft, hop, win_length, center, pad_mode, normalized, onesided)
     src = H._rows_of(wave, g)
     window = window.contiguous()
-    out = torch.empty(g.stft_shape, dtype=_F64, device=wave.device)
-    _launch('tac_stft_f64', wave.device, _native.ptr(src), _native.ptr(window), _desc(g), _native.ptr(out))
+    out = _empty(g.stft_shape, wave.device)
+    _launch('tac_stft_f64', wave.device, (out,), _native.ptr(src), _native.ptr(window), _desc(g), _native.ptr(out))
     return out.transpose(-3, -2)
 
 
 def _spectrogram_rows(wave, window, g, power, db, ref, amin):
     src = H._rows_of(wave, g)
     window = window.contiguous()
-    out = torch.empty(g.spec_shape, dtype=_F64, device=wave.device)
-    _launch('tac_spectrogram_f64', wave.device, _native.ptr(src), _native.ptr(window), _desc(g), float(power),
+    out = _empty(g.spec_shape, wave.device)
+    _launch('tac_spectrogram_f64', wave.device, (out,), _native.ptr(src), _native.ptr(window), _desc(g), float(power),
             1 if db else 0, float(ref), float(amin), _native.ptr(out))
     return out                                                            # physical (…, T, F)
 
@@ -86,16 +91,16 @@ def apply_filterbank(spec, fb, db=None):
     n_freqs, n_frames = spec.shape[-2], spec.shape[-1]
     lead = tuple(spec.shape[:-2])
     n_mels = fb.shape[1]
-    out = torch.empty(lead + (n_frames, n_mels), dtype=_F64, device=spec.device)
+    out = _empty(lead + (n_frames, n_mels), spec.device)
     if out.numel():
         rows = spec.reshape(-1, n_freqs, n_frames)                       # a view for both layouts the ops here produce
         step = 65535                                                      # grid.z
         for r0 in range(0, rows.shape[0], step):
             part = rows[r0:r0 + step]
-            _launch('tac_apply_filterbank_f64', spec.device, _native.ptr(part), part.shape[0], n_freqs, n_frames,
+            dst = out.reshape(-1, n_frames, n_mels)[r0:r0 + step]          # (each launch fills its slab of rows)
+            _launch('tac_apply_filterbank_f64', spec.device, (dst,), _native.ptr(part), part.shape[0], n_freqs, n_frames,
                     part.stride(0), part.stride(1), part.stride(2), _native.ptr(fb), n_mels, 0 if db is None else 1,
-                    1.0 if db is None else float(db[0]), 0.0 if db is None else float(db[1]),
-                    _native.ptr(out.reshape(-1, n_frames, n_mels)[r0:r0 + step]))
+                    1.0 if db is None else float(db[0]), 0.0 if db is None else float(db[1]), _native.ptr(dst))
     return out.transpose(-2, -1)
 
 
@@ -110,11 +115,11 @@ def melspectrogram(wave, window, fb, n_fft, hop, win_length, center, pad_mode, n
 def _pair_call(z, power, want_mag, want_phase):
     z = H._pairs(z)
     shape, strides = z.shape[:-1], tuple(s // 2 for s in z.stride()[:-1])
-    mag = torch.empty_strided(shape, strides, dtype=_F64, device=z.device) if want_mag else None
-    phase = torch.empty_strided(shape, strides, dtype=_F64, device=z.device) if want_phase else None
+    mag = H._empty_strided(shape, strides, dtype=_F64, device=z.device) if want_mag else None
+    phase = H._empty_strided(shape, strides, dtype=_F64, device=z.device) if want_phase else None
     n = (mag if want_mag else phase).numel()
     if n:
-        _launch('tac_magphase_f64', z.device, _native.ptr(z), n, float(power), None if mag is None else _native.ptr(mag),
+        _launch('tac_magphase_f64', z.device, (mag, phase), _native.ptr(z), n, float(power), None if mag is None else _native.ptr(mag),
                 None if phase is None else _native.ptr(phase))
     return mag, phase
 
@@ -133,9 +138,9 @@ def magphase(z, power):
 
 def _unary(x, name, *params):
     x = x if H.is_dense(x) else x.contiguous()
-    out = torch.empty_like(x)
+    out = H._empty_like(x)
     if x.numel():
-        _launch(name, x.device, _native.ptr(x), x.numel(), *params, _native.ptr(out))
+        _launch(name, x.device, (out,), _native.ptr(x), x.numel(), *params, _native.ptr(out))
     return out
 
 

@@ -31,6 +31,8 @@ typedef int (*melspec_fn)(const float*, const float*, const void*, float, const 
                           int, float, float, float*, void*);
 
 std::atomic<int64_t> g_epoch{0};            // mirrors _hip._epoch (invalidate() without arguments)
+std::atomic<bool> g_poison{false};          // mirrors _hip.set_poison_outputs(): outputs start as _hip.POISON_BITS[float32]
+constexpr int32_t kPoisonF32 = 0x7FC0DEAD;  // (a quiet NaN with a payload no kernel produces; the caller checks what was written)
 
 struct MelPlan {
     melspec_fn fn = nullptr;
@@ -64,6 +66,7 @@ struct MelPlan {
         RECORD_USER_SCOPE("tac_amd::melspectrogram (planned)");
         const c10::hip::HIPGuard device_guard(dev);
         at::Tensor out = at::empty(out_shape, wave.options());
+        if (g_poison.load(std::memory_order_relaxed)) out.view(at::kInt).fill_(kPoisonF32);
         void* stream = c10::hip::getCurrentHIPStream(dev).stream();
         const int rc = fn(wave.data_ptr<float>(), static_cast<const float*>(win_ptr), desc.data(), power, wpack.data_ptr<float>(),
                           dsc.data_ptr<int32_t>(), info.data(), n_mels, db, ref, amin, out.data_ptr<float>(), stream);
@@ -175,6 +178,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "compiled binding of the fused Melspectrogram launch (C ABI of libtac_amd.so behind it)";
     m.attr("ABI") = 1;
     m.def("set_epoch", [](int64_t e) { g_epoch.store(e, std::memory_order_relaxed); });
+    m.def("set_poison", [](bool on) { g_poison.store(on, std::memory_order_relaxed); });
     m.def("drop_plan", [](int64_t id) {
         std::lock_guard<std::mutex> lock(g_mutex);
         if (id >= 0 && id < (int64_t)g_plans.size()) g_plans[id].reset();
