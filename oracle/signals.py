@@ -36,3 +36,42 @@ def audio_like(shape, seed=0):
     rows = x.reshape(-1, shape[-1])
     gains = (2.0 ** -(np.arange(rows.shape[0]) % 8)).astype(np.float32)
     return (rows * gains[:, None]).reshape(shape)
+
+
+def gained_with_silence(shape, seed=0, n_fft=512, hop=128):
+    """``uniform`` with dynamic range and silence, for per-frame checks: row r (over the flattened leading dims) scaled by
+    2^-(r mod 13); in every third row (r = 0, 3, 6, ...) three spans of ``n_fft + hop`` zeros — the start of the row, mid-row
+    off the hop grid, the end of the row — where the row holds them without overlap (start and end from 2 spans, the middle
+    one from 3); row 1 all zeros whenever there are at least 3 rows.
+
+    A span of ``n_fft + hop`` samples holds at least one whole frame on the hop grid (centred or not), and with both edge
+    spans in place the first and last frames are silent for every pad mode (reflect, replicate and circular read only
+    those spans).  A pure function of (shape, seed, n_fft, hop)."""
+    x = uniform(shape, seed)
+    rows = x.reshape(-1, shape[-1])
+    n_rows, length = rows.shape
+    rows *= (2.0 ** -(np.arange(n_rows) % 13)).astype(np.float32)[:, None]
+    for r, lo, hi in silent_spans(shape, n_fft, hop):
+        rows[r, lo:hi] = 0.0
+    if n_rows >= 3:
+        rows[1] = 0.0
+    return rows.reshape(shape)
+
+
+def silent_spans(shape, n_fft, hop):
+    """The (row, start, stop) spans ``gained_with_silence`` zeroes (row 1 of 3 or more rows aside, which is zero whole)."""
+    n_rows, length = int(np.prod(shape[:-1])), int(shape[-1])
+    span = n_fft + hop
+    out = []
+    for r in range(0, n_rows, 3):
+        if length >= 2 * span:
+            out += [(r, 0, span), (r, length - span, length)]
+        if length >= 3 * span:
+            mid = min(max(span, length // 2 + hop // 3), length - 2 * span)
+            out.append((r, mid, mid + span))
+    return out
+
+
+def has_silence(shape, n_fft, hop):
+    """Whether ``gained_with_silence`` of this shape holds a silent row or silent spans (hence silent frames)."""
+    return int(np.prod(shape[:-1])) >= 3 or int(shape[-1]) >= 2 * (n_fft + hop)

@@ -8,6 +8,11 @@ the value is not at cancellation level.
 
 dB outputs are compared where the linear reference exceeds 1e-6 of its maximum (see tests/test_gpu_parity.py: below
 that the float32 FFT's own rounding decides the digits); every bin is checked on the linear output first.
+
+Per frame (tests/frame_bounds.py): inputs come from ``signals.gained_with_silence`` (row gains 2^0 ... 2^-12, silent spans,
+a silent row), and every op is also compared frame by frame (gradients row by row) with its float64 reference — the oracle
+evaluated in float64 on the module's own window and filterbank — where a silent frame (row) must come out exactly zero and
+the dB masks follow from the linear bounds.  ``TAC_FUZZ_REPORT=path`` appends one JSON line per check.
 """
 import os
 
@@ -15,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import frame_bounds as fbnd
 from conftest import rel_err
 from oracle import signals, torch_ref
 
@@ -26,6 +32,34 @@ DB_ABS = 1e-3
 FFT_SIZES = [32, 64, 128, 256, 400, 512, 1024, 2048, 4096]
 ODD_SIZES = [100, 300, 1000, 1536, 3000, 882, 960, 6000,      # generic Stockham kernel (even, 7-smooth half: csrc/stft_smooth.hip)
              77, 501, 1018, 2602]                          # windowed-DFT matrix route (odd, or a half with a larger prime factor)
+FRAME = 2e-6        # complex rows and |X|, per frame
+FRAME_DFT = 5e-6    # complex rows and |X| of the windowed-DFT matrix route (one fp32 dot product of fft_length terms per
+                    # bin): 4.1e-6 measured at fft_length 2602 (deep run, seed 0); the per-tensor bound beside it is 5e-6
+FRAME_POW = 2e-5    # |X|^p (p != 1), power and mel, per frame
+GRAD = 1e-4         # waveform gradients of linear / power / mel outputs, per row
+GRAD_DB = 1e-3      # ... through dB or |X|, per row
+
+
+def frame_tol(n):
+    """Per-frame bound on complex rows and |X| for the route fft_length ``n`` takes."""
+    return FRAME_DFT if n in ODD_SIZES[8:] else FRAME
+
+
+def silent_input(shape, seed, n, hop):
+    """(waveform, whether it holds a silent frame for every pad mode and centring)."""
+    return signals.gained_with_silence(shape, seed, n, hop), signals.has_silence(shape, n, hop)
+
+
+def mel_db_mask(x, n, hop, window, fb, amin, **kw):
+    """1 where the dB value of the float32 mel chain is determined to DB_ABS by fbnd.POW_TOL (check_mel_grad's rule), else 0:
+    (*, M, T) float64, for the weights of a gradient through dB."""
+    with torch.no_grad():
+        pw = fbnd.ref64(x, n, hop, window, 2.0, **kw)
+        mel = torch_ref.apply_filterbank(pw, fb.detach().cpu().double())
+        lin = fbnd.mel_linear_bound(fbnd.frames_of(pw, 'spec'), fb.detach().cpu(), fbnd.POW_TOL).transpose(-1, -2)
+        lin = lin.reshape(mel.shape)
+    bound = fbnd.DB_PER_REL * lin / mel.abs().clamp(min=amin ** 0.5)
+    return (((mel - lin).clamp(min=0) ** 2 > amin) & (bound <= DB_ABS)).double()
 
 
 @pytest.fixture(scope='module')
@@ -75,7 +109,7 @@ def test_fuzz_stft(tac):
         n, hop, win_length, center, pad_mode, lead, length = draw_stft_args(
             rng, FFT_SIZES + (ODD_SIZES if case % 4 == 0 else []))
         normalized, onesided = bool(rng.random() < 0.3), bool(rng.random() < 0.7)
-        x = signals.audio_like(lead + (length,), seed=5000 + case + 7919 * SEED)
+        x, silent = silent_input(lead + (length,), 5000 + case + 7919 * SEED, n, hop)
         window = None if rng.random() < 0.5 else \
             torch.from_numpy(signals.uniform((win_length,), seed=6000 + case) * 0.5 + 0.75)
         kw = dict(win_length=win_length, center=center, pad_mode=pad_mode, normalized=normalized, onesided=onesided)
@@ -84,6 +118,8 @@ def test_fuzz_stft(tac):
         tag = ('stft', case, n, hop, kw, lead, length, window is not None)
         assert got.shape == want.shape, tag
         assert rel_err(got, want) < 5e-6, tag
+        want64 = fbnd.ref64(x, n, hop, torch.hann_window(win_length, device='cuda') if window is None else window, **kw)
+        fbnd.check_frames(got, want64, 'complex', frame_tol(n), 'fuzz_stft', tag, n, silent)
 
 
 def test_fuzz_stft_big(tac):
@@ -100,7 +136,7 @@ def test_fuzz_stft_big(tac):
         lo = n + 1 if center else n
         length = int(rng.integers(lo, lo + 6 * n))
         normalized, onesided = bool(rng.random() < 0.3), bool(rng.random() < 0.7)
-        x = signals.audio_like(lead + (length,), seed=5500 + case + 7919 * SEED)
+        x, silent = silent_input(lead + (length,), 5500 + case + 7919 * SEED, n, hop)
         window = None if rng.random() < 0.5 else \
             torch.from_numpy(signals.uniform((win_length,), seed=6500 + case) * 0.5 + 0.75)
         kw = dict(win_length=win_length, center=center, pad_mode=pad_mode, normalized=normalized, onesided=onesided)
@@ -112,11 +148,17 @@ def test_fuzz_stft_big(tac):
         assert tac._hip.launches['tac_stft_f32'] - before.get('tac_stft_f32', 0) == 1, tag
         assert got.shape == tuple(want.shape), tag
         assert rel_err(got, want.numpy()) < 5e-6, tag
+        want64 = fbnd.ref64(x, n, hop, torch.hann_window(win_length, device='cuda') if window is None else window, **kw)
+        fbnd.check_frames(got, want64, 'complex', FRAME, 'fuzz_stft_big', tag, n, silent)
         power = float(rng.choice([1.0, 2.0, 0.7]))
         mag = torch_ref.complex_norm(want.double(), power)
         gs = host(torch.ops.tac_amd.spectrogram(dev(x), torch.hann_window(win_length).cuda() if wdev is None else wdev, n, hop, win_length,
                                                  center, pad_mode, normalized, onesided, power, False, 1.0, 1e-7))
         assert rel_err(gs, mag.numpy()) < 2e-5, tag + (power,)
+        if window is None:                  # (the op got the host-built window here)
+            want64 = fbnd.ref64(x, n, hop, torch.hann_window(win_length), **kw)
+        fbnd.check_frames(gs, torch_ref.complex_norm(want64, power), 'spec', FRAME if power == 1.0 else FRAME_POW,
+                          'fuzz_stft_big', tag + (power,), n, silent)
 
 
 def test_fuzz_spectrogram(tac):
@@ -126,7 +168,7 @@ def test_fuzz_spectrogram(tac):
             rng, FFT_SIZES + (ODD_SIZES if case % 4 == 0 else []))
         power = float(rng.choice([1.0, 2.0, 2.0, 0.7, 3.0]))
         normalized = bool(rng.random() < 0.3)
-        x = signals.audio_like(lead + (length,), seed=7000 + case + 7919 * SEED)
+        x, silent = silent_input(lead + (length,), 7000 + case + 7919 * SEED, n, hop)
         layer = tac.Spectrogram(n, hop, win_length, power=power, center=center, pad_mode=pad_mode,
                                 normalized=normalized).cuda()
         z = torch_ref.stft(torch.from_numpy(x), n, hop, win_length=win_length, center=center, pad_mode=pad_mode,
@@ -145,6 +187,12 @@ def test_fuzz_spectrogram(tac):
         # maximum amplitude through, where 3.6e-7 of the maximum is 1.6e-3 dB: soak seed 8, case 108, fft_length 2602)
         big = want > (3e-2 ** power) * want.max()
         assert np.abs(got_db - want_db)[big].max() < DB_ABS, tag
+        mag64 = fbnd.ref64(x, n, hop, layer[0].window, 1.0, win_length=win_length, center=center, pad_mode=pad_mode,
+                      normalized=normalized)
+        fbnd.check_frames(got, mag64 ** power, 'spec', frame_tol(n) if power == 1.0 else FRAME_POW, 'fuzz_spectrogram', tag, n,
+                          silent)
+        fbnd.check_power_db64(got_db, x, n, hop, power, 'fuzz_spectrogram', tag, frame_tol(n), layer[0].window, amin=1e-10,
+                              win_length=win_length, center=center, pad_mode=pad_mode, normalized=normalized)
 
 
 def test_fuzz_melspectrogram(tac):
@@ -159,7 +207,7 @@ def test_fuzz_melspectrogram(tac):
         htk = bool(rng.random() < 0.5)
         min_freq = float(rng.choice([0.0, 20.0, 125.0]))
         max_freq = None if rng.random() < 0.6 else float(sr // 2 - int(rng.integers(0, sr // 8)))
-        x = signals.uniform(lead + (length,), seed=8000 + case + 7919 * SEED)
+        x, silent = silent_input(lead + (length,), 8000 + case + 7919 * SEED, n, hop)
         mel = tac.Melspectrogram(num_mels=num_mels, sample_rate=sr, min_freq=min_freq, max_freq=max_freq, htk=htk,
                                  fft_length=n, hop_length=hop, win_length=win_length, center=center,
                                  pad_mode=pad_mode).cuda()
@@ -176,6 +224,11 @@ def test_fuzz_melspectrogram(tac):
         big = want > 1e-6 * want.max()
         if big.any():
             assert np.abs(got_db - want_db)[big].max() < DB_ABS, tag
+        kw = dict(win_length=win_length, center=center, pad_mode=pad_mode)
+        pw64 = fbnd.ref64(x, n, hop, mel[0].window, 2.0, **kw)
+        mel64 = torch_ref.apply_filterbank(pw64, mel[2].filterbank.cpu().double())
+        fbnd.check_frames(got, mel64, 'spec', FRAME_POW, 'fuzz_melspectrogram', tag, n, silent)
+        fbnd.check_mel_db64(got_db, x, n, hop, mel[2].filterbank, 'fuzz_melspectrogram', tag, mel[0].window, **kw)
 
 
 def test_fuzz_apply_filterbank(tac):
@@ -201,7 +254,9 @@ def test_fuzz_apply_filterbank(tac):
                 fb[lo:lo + ln, m] = rng.random(ln).astype(np.float32) + 0.05
                 if ln > 4 and rng.random() < 0.3:
                     fb[lo + 1:lo + ln // 2, m] = 0.0
-        spec = np.abs(signals.uniform(lead + (n_freqs, n_frames), seed=9500 + case)) + 0.01
+        # frames with gains 2^0 ... 2^-12, runs of zero bins, a silent frame (the generator's rows are this spectrogram's frames)
+        spec = np.swapaxes(np.abs(signals.gained_with_silence(lead + (n_frames, n_freqs), 9500 + case, max(1, n_freqs // 8), 1)), -1, -2)
+        silent = signals.has_silence(lead + (n_frames, n_freqs), n_freqs, 0)
         want = np.einsum('...ft,fm->...mt', spec.astype(np.float64), fb.astype(np.float64))
         frame_major = dev(np.swapaxes(spec, -1, -2)).transpose(-1, -2)          # the layout the kernels here write
         for name, s in (('bin-major', dev(spec)), ('frame-major', frame_major)):
@@ -209,6 +264,43 @@ def test_fuzz_apply_filterbank(tac):
             tag = ('fb', case, name, n_freqs, n_mels, lead, n_frames, kind)
             assert got.shape == want.shape, tag
             assert rel_err(got, want) < 1e-5, tag
+            fbnd.check_frames(got, want, 'spec', 1e-5, 'fuzz_apply_filterbank', tag, n_freqs, silent)
+
+
+def check_gradient_per_row(tac_, module, kind, x, w, n, hop, kw, test, tag, db=None):
+    """Waveform gradient of (w * module(x)).sum(), row by row, against float64 autograd through the oracle on the module's
+    window and filterbank.  Weights are zeroed where the float32 forward does not determine the output's derivative: mel
+    bands whose dB value it does not fix to DB_ABS (``db`` = (ref, amin)), and |X| below 1e-3 of its row's maximum
+    (``magnitude``; |X| is not differentiable at 0).  A silent row (row 1 of 3 or more) must get an exactly zero gradient:
+    from its full weights for power, mel and mel + dB (the clamp of dB has a defined zero derivative there, so the silent row
+    keeps its weights); for ``magnitude`` its weights are all zero, so there the condition only says that zero weights give
+    an exactly zero gradient."""
+    stft_mod = module if kind == 'stft' else module[0]
+    window = stft_mod.window
+    fb = None if kind in ('stft', 'power', 'magnitude') else module[2].filterbank
+    x64 = torch.from_numpy(x).double().requires_grad_(True)
+    if kind == 'stft':
+        y64 = fbnd.ref64(x64, n, hop, window, **kw)
+    else:
+        y64 = fbnd.ref64(x64, n, hop, window, 1.0 if kind == 'magnitude' else 2.0, fb=fb, **kw)
+    w = torch.from_numpy(np.asarray(w, dtype=np.float64))
+    if kind == 'magnitude':
+        rows = y64.detach().reshape(-1, y64.shape[-2] * y64.shape[-1])
+        w = w * (rows > 1e-3 * rows.amax(-1, keepdim=True)).reshape(y64.shape)
+    n_rows = int(np.prod(x.shape[:-1]))
+    if db is not None:
+        ref, amin = db
+        masked = w * mel_db_mask(x, n, hop, window, fb, amin, **kw)
+        if n_rows >= 3:
+            masked.reshape(n_rows, -1)[1] = w.reshape(n_rows, -1)[1]
+        w = masked
+        y64 = torch_ref.amplitude_to_db(y64, ref=ref, amin=amin)
+    (want,) = torch.autograd.grad((y64 * w).sum(), x64)
+    xg = dev(x).requires_grad_(True)
+    (got,) = torch.autograd.grad((module(xg) * dev(w.float())).sum(), xg)
+    silent_rows = (1,) if kind != 'stft' and n_rows >= 3 else ()
+    fbnd.check_rows(host(got), want, GRAD_DB if (db is not None or kind == 'magnitude') else GRAD, test, tag, n,
+                    silent_rows=silent_rows)
 
 
 def test_fuzz_gradients(tac):
@@ -224,16 +316,18 @@ def test_fuzz_gradients(tac):
         num_mels = int(rng.choice([13, 40, 80, 128]))
         if num_mels > n // 4:
             num_mels = max(2, n // 8)
-        x = signals.audio_like(lead + (length,), seed=9900 + case + 7919 * SEED)
+        x = signals.gained_with_silence(lead + (length,), seed=9900 + case + 7919 * SEED, n_fft=n, hop=hop)
         xc = torch.from_numpy(x).requires_grad_(True)
         xg = dev(x).requires_grad_(True)
         kw = dict(win_length=win_length, center=center, pad_mode=pad_mode, normalized=normalized)
         if kind == 'stft':
             want_y = torch_ref.stft(xc, n, hop, **kw)
-            y = tac.STFT(n, hop, **kw).cuda()(xg)
+            module = tac.STFT(n, hop, **kw).cuda()
+            y = module(xg)
         elif kind == 'power':
             want_y = torch_ref.complex_norm(torch_ref.stft(xc, n, hop, **kw), 2.0)
-            y = tac.Spectrogram(n, hop, power=2.0, **kw).cuda()(xg)
+            module = tac.Spectrogram(n, hop, power=2.0, **kw).cuda()
+            y = module(xg)
         else:
             want_y = torch_ref.melspectrogram(xc, num_mels=num_mels, sample_rate=16000, n_fft=n, hop=hop, **kw)
             chain = tac.Melspectrogram(num_mels=num_mels, sample_rate=16000, fft_length=n, hop_length=hop, **kw)
@@ -242,13 +336,16 @@ def test_fuzz_gradients(tac):
                 ref = max(1.0, 2.0 * floor * floor)                  # (the layer insists on ref > amin, layers.py:369)
                 want_y = torch_ref.amplitude_to_db(want_y, ref=ref, amin=floor * floor)
                 chain = torch.nn.Sequential(*chain, tac.AmplitudeToDb(ref=ref, amin=floor * floor))
-            y = chain.cuda()(xg)
+            module = chain.cuda()
+            y = module(xg)
         tag = ('grad', case, kind, n, hop, kw, num_mels, lead, length)
         assert tuple(y.shape) == tuple(want_y.shape), tag
         w = signals.uniform(tuple(want_y.shape), seed=9950 + case)
         (want,) = torch.autograd.grad((want_y * torch.from_numpy(w)).sum(), xc)
         (got,) = torch.autograd.grad((y * dev(w)).sum(), xg)
         assert rel_err(host(got), want.numpy()) < (1e-3 if kind == 'mel_db' else 1e-4), tag
+        check_gradient_per_row(tac, module, kind, x, w, n, hop, kw, 'fuzz_gradients', tag,
+                               None if kind != 'mel_db' else (ref, floor * floor))
 
 
 def test_fuzz_gradients_overlap_add_in_lds(tac):
@@ -272,7 +369,7 @@ def test_fuzz_gradients_overlap_add_in_lds(tac):
         lo = n + 1 if center else n
         length = int(rng.integers(lo, lo + int(rng.choice([3, 40, 400])) * hop + 7))
         kind = ['power', 'mel', 'mel_db', 'magnitude'][case % 4]
-        x = signals.audio_like(lead + (length,), seed=9700 + case + 7919 * SEED)
+        x = signals.gained_with_silence(lead + (length,), seed=9700 + case + 7919 * SEED, n_fft=n, hop=hop)
         xc = torch.from_numpy(x).requires_grad_(True)
         xg = dev(x).requires_grad_(True)
         kw = dict(win_length=win_length, center=center, pad_mode=pad_mode, normalized=normalized)
@@ -280,7 +377,8 @@ def test_fuzz_gradients_overlap_add_in_lds(tac):
         if kind in ('power', 'magnitude'):
             power = 2.0 if kind == 'power' else 1.0
             want_y = torch_ref.complex_norm(torch_ref.stft(xc, n, hop, **kw), power)
-            y = tac.Spectrogram(n, hop, power=power, **kw).cuda()(xg)
+            module = tac.Spectrogram(n, hop, power=power, **kw).cuda()
+            y = module(xg)
         else:
             mels = min(64, n // 8)
             want_y = torch_ref.melspectrogram(xc, num_mels=mels, sample_rate=16000, n_fft=n, hop=hop, **kw)
@@ -290,7 +388,8 @@ def test_fuzz_gradients_overlap_add_in_lds(tac):
                 ref = max(1.0, 2.0 * floor * floor)
                 want_y = torch_ref.amplitude_to_db(want_y, ref=ref, amin=floor * floor)
                 chain = torch.nn.Sequential(*chain, tac.AmplitudeToDb(ref=ref, amin=floor * floor))
-            y = chain.cuda()(xg)
+            module = chain.cuda()
+            y = module(xg)
         tag = ('grad-ola', case, kind, n, hop, kw, lead, length)
         w = signals.uniform(tuple(want_y.shape), seed=9750 + case)
         if kind == 'magnitude':            # |z| is not differentiable at 0: weight only bins that carry signal
@@ -304,6 +403,8 @@ def test_fuzz_gradients_overlap_add_in_lds(tac):
         assert ran.get(entry) == 1 and 'tac_overlap_add_f32' not in ran, (tag, ran)
         assert entry == 'tac_spectrogram_backward_ola_f32' or 'tac_apply_filterbank_adjoint_f32' not in ran, (tag, ran)
         assert rel_err(host(got), want.numpy()) < (1e-3 if kind in ('mel_db', 'magnitude') else 1e-4), tag
+        check_gradient_per_row(tac, module, kind, x, signals.uniform(tuple(want_y.shape), seed=9750 + case), n, hop, kw,
+                               'fuzz_gradients_ola', tag, None if kind != 'mel_db' else (ref, floor * floor))
 
 
 def test_fuzz_float64_chain(tac):
@@ -317,8 +418,8 @@ def test_fuzz_float64_chain(tac):
         n, hop, win_length, center, pad_mode, lead, length = draw_stft_args(rng, sizes, max_rows=3, max_len_factor=5)
         hop = max(hop, n // 16)                                          # (keeps the direct-transform cases small)
         normalized, onesided = bool(rng.random() < 0.3), bool(rng.random() < 0.7)
-        x = signals.audio_like(lead + (length,), seed=5500 + case + 7919 * SEED).astype(np.float64)
-        x += 1e-9 * np.random.default_rng(case).standard_normal(x.shape)   # bits below float32
+        x = signals.gained_with_silence(lead + (length,), seed=5500 + case + 7919 * SEED, n_fft=n, hop=hop).astype(np.float64)
+        x *= 1.0 + 1e-9 * np.random.default_rng(case).standard_normal(x.shape)   # bits below float32 (silence stays exact)
         window = torch.from_numpy(signals.uniform((win_length,), seed=6500 + case).astype(np.float64) * 0.5 + 0.75)
         kw = dict(win_length=win_length, center=center, pad_mode=pad_mode, normalized=normalized)
         tag = ('f64', case, n, hop, kw, onesided, lead, length)
@@ -327,6 +428,7 @@ def test_fuzz_float64_chain(tac):
         got = host(tac.stft(dev(x), n, hop_length=hop, window=window.cuda(), onesided=onesided, **kw))
         assert got.dtype == np.float64 and got.shape == want.shape, tag
         assert np.abs(got - want).max() <= 2e-12 * max(np.abs(want).max(), 1e-300), tag
+        fbnd.check_frames(got, want, 'complex', 2e-12, 'fuzz_float64_chain', tag, n, signals.has_silence(x.shape, n, hop))
         power = float(rng.choice([1.0, 2.0, 0.7]))
         mels = int(rng.choice([5, 40, 80]))
         bank = torch.from_numpy(signals.uniform((n // 2 + 1, mels), seed=6600 + case).astype(np.float64))

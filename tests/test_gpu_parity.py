@@ -10,11 +10,16 @@ maximum (the ``big`` masks below).  Every bin, masked or not, is first checked o
 maximum); below 1e-6 of the maximum that bound is wider than the value itself — the float32 FFT's own rounding (1e-7 of the
 frame's largest bin) decides those digits, for the reference's CPU FFT as much as for these kernels — so their logarithm
 is not comparable to 1e-3 dB.  The golden vectors g1 / g2 / g4 / g9 / g10 pin dB outputs UNMASKED on audio-like inputs.
+
+The route sweeps and geometry tests draw their inputs from ``signals.gained_with_silence`` (row gains 2^0 ... 2^-12, silent
+spans, a silent row) and also hold every frame to its own maximum against the oracle in float64 on the module's window and
+bank (tests/frame_bounds.py): a silent frame must come out exactly zero, dB masks follow from the linear bounds.
 """
 import numpy as np
 import pytest
 import torch
 
+import frame_bounds as fbnd
 from conftest import rel_err
 from oracle import signals, torch_ref, numpy_ref
 
@@ -23,6 +28,8 @@ pytestmark = pytest.mark.gpu
 REL = 1e-4        # north_star tolerance
 TIGHT = 2e-6      # what fp32 kernels should really achieve on linear outputs
 DB_ABS = 1e-3     # absolute dB
+FRAME = 2e-6      # complex rows and |X|, per frame (frame_bounds)
+FRAME_POW = 2e-5  # power and mel, per frame
 
 
 @pytest.fixture(scope='module')
@@ -237,7 +244,7 @@ def test_fused_mel_parameter_sweep_vs_oracle(tac):
         min_freq = float(rng.choice([0.0, 20.0, 125.0]))
         max_freq = None if case % 4 else float(sr // 2 - int(rng.integers(0, sr // 8)))
         shape = (int(rng.integers(1, 4)), int(rng.integers(1, 3)), int(rng.integers(2 * n, 6 * n)) + case % 2)
-        x = signals.uniform(shape, seed=300 + case)
+        x = signals.gained_with_silence(shape, 300 + case, n, hop)
         mel = tac.Melspectrogram(num_mels=num_mels, sample_rate=sr, min_freq=min_freq, max_freq=max_freq, htk=htk,
                                  fft_length=n, hop_length=hop, win_length=win_length).cuda()
         want = torch_ref.melspectrogram(torch.from_numpy(x), num_mels=num_mels, sample_rate=sr, min_freq=min_freq,
@@ -251,6 +258,10 @@ def test_fused_mel_parameter_sweep_vs_oracle(tac):
         got_db = host(chain(dev(x)))
         big = want.numpy() > 1e-6 * want.numpy().max()
         assert np.abs(got_db - want_db)[big].max() < DB_ABS, tag
+        silent = signals.has_silence(shape, n, hop)
+        fbnd.check_frames(got, fbnd.ref64(x, n, hop, mel[0].window, 2.0, mel[2].filterbank, win_length=win_length), 'spec', FRAME_POW,
+                          'fused_mel_sweep', tag, n, silent)
+        fbnd.check_mel_db64(got_db, x, n, hop, mel[2].filterbank, 'fused_mel_sweep', tag, mel[0].window, win_length=win_length)
 
 
 def test_non_power_of_two_and_large_n_fft(tac, golden):
@@ -294,7 +305,7 @@ def test_smooth_fft_lengths_generic_stockham_kernel(tac):
     44.1 kHz; csrc/stft_smooth.hip, round 5: radix 4 / 2 / 3 / 5 / 7 Stockham passes, `group` frames per workgroup) against the
     float64 restatement: complex rows one- and two-sided, pad modes, centre off, short windows, odd hops (scalar loads),
     normalisation, tiny and maximal sizes; |X|^p rows and dB; the Melspectrogram chain.  Strict mode is on."""
-    x = signals.audio_like((3, 2, 20000), seed=78)
+    x = signals.gained_with_silence((3, 2, 20000), 78, 4096, 1024)     # (six rows: row 1 silent for every case)
     cases = [(480, 120, {}), (882, 441, {}), (960, 240, dict(onesided=False)), (1200, 300, dict(center=False, normalized=True)),
              (1920, 480, dict(pad_mode='constant', win_length=1000)), (3000, 751, dict(pad_mode='replicate')),
              (6000, 1500, dict(win_length=4800)), (8100, 2025, dict(pad_mode='circular')), (12, 5, dict(onesided=False)),
@@ -308,22 +319,29 @@ def test_smooth_fft_lengths_generic_stockham_kernel(tac):
         ref = numpy_ref.stft(x, n, hop, **kw)
         assert got.shape[:-1] == ref.shape
         assert rel_err(got[..., 0] + 1j * got[..., 1], ref) < 5e-6, (n, hop, kw)
+        fbnd.check_frames(got, fbnd.ref64(x, n, hop, **kw), 'complex', FRAME, 'smooth', (n, hop, kw), n, True)
     got = host(tac.stft(dev(x[0, :, :700]), 960, hop_length=240))          # rows shorter than a frame
     assert rel_err(got[..., 0] + 1j * got[..., 1], numpy_ref.stft(x[0, :, :700], 960, 240)) < 5e-6
+    fbnd.check_frames(got, fbnd.ref64(x[0, :, :700], 960, 240), 'complex', FRAME, 'smooth', 'short rows', 960, True)
     for n, hop in ((960, 240), (1200, 300), (882, 441), (6000, 1500)):
         mag2 = np.abs(numpy_ref.stft(x, n, hop)) ** 2
+        mag64 = fbnd.ref64(x, n, hop, torch.hann_window(n), 1.0)                # (the modules' host-built window)
         for power in (2.0, 1.0, 0.7):
             before = launches(tac)
             got = host(tac.Spectrogram(n, hop, power=power).cuda()(dev(x)))
             assert launched_since(tac, before) == {'tac_spectrogram_f32': 1}
             assert rel_err(got, mag2 ** (power / 2)) < 1e-5, (n, power)
+            fbnd.check_frames(got, mag64 ** power, 'spec', FRAME if power == 1.0 else 1e-5, 'smooth', (n, power), n, True)
         chain = torch.nn.Sequential(*tac.Spectrogram(n, hop, power=2.), tac.AmplitudeToDb()).cuda()
         want_db = 10.0 * np.log10(np.maximum(mag2 ** 2, 1e-7))                 # (amplitude_to_db squares its input)
         big = mag2 > 1e-6 * mag2.max()
         assert np.abs(host(chain(dev(x))) - want_db)[big].max() < DB_ABS, n
+        fbnd.check_power_db64(host(chain(dev(x))), x, n, hop, 2.0, 'smooth', n, FRAME, chain[0].window)
         mel = tac.Melspectrogram(num_mels=40, sample_rate=48000, fft_length=n, hop_length=hop).cuda()
         want_mel = torch_ref.melspectrogram(torch.from_numpy(x), num_mels=40, sample_rate=48000, n_fft=n, hop=hop).numpy()
         assert rel_err(host(mel(dev(x))), want_mel) < 2e-5, n
+        fbnd.check_frames(host(mel(dev(x))), fbnd.ref64(x, n, hop, mel[0].window, 2.0, mel[2].filterbank), 'spec', FRAME_POW,
+                          'smooth_mel', n, n, True)
     xg = dev(x).requires_grad_(True)                       # gradients keep the DFT-matrix adjoint: no stock-torch route
     routed = dict(tac._ops.composite_calls)
     (g1,) = torch.autograd.grad(tac.Spectrogram(960, 240, power=2.).cuda()(xg).sum(), xg)
@@ -331,6 +349,7 @@ def test_smooth_fft_lengths_generic_stockham_kernel(tac):
     xr = torch.from_numpy(x).double().requires_grad_(True)
     (g0,) = torch.autograd.grad(torch_ref.spectrogram(xr, 960, 240, window=torch.hann_window(960, dtype=torch.float64), power=2.0).sum(), xr)
     assert rel_err(host(g1), g0.numpy()) < 1e-4
+    fbnd.check_rows(host(g1), g0, 1e-4, 'smooth_grad', 960, 960, silent_rows=(1,))
 
 
 def test_fft_length_8192_to_32768_four_step_kernel(tac):
@@ -339,7 +358,8 @@ def test_fft_length_8192_to_32768_four_step_kernel(tac):
     restatement (oracle/numpy_ref.py): complex rows one- and two-sided, every pad mode, centre off, short windows, hops that are
     not 16-byte aligned (the gathered load), normalisation; |X|^p rows with p = 2, 1, 0.7 and the dB epilogue; the Melspectrogram
     chain (two launches).  Strict mode is on: nothing here may touch torch's operators."""
-    x = signals.audio_like((2, 1, 90000), seed=77)
+    x = signals.gained_with_silence((2, 1, 90000), 77, 8192, 2048)
+    # (row 0's edge spans of 10240 samples hold the first frame of every case up to fft_length 16384; none at 32768)
     cases = [(8192, 2048, {}), (16384, 4096, {}), (32768, 8192, {}), (16384, 1000, dict(onesided=False)),
              (8192, 4099, dict(center=False, normalized=True)), (32768, 16384, dict(pad_mode='constant', win_length=30000)),
              (16384, 2050, dict(pad_mode='replicate', win_length=401)), (8192, 512, dict(pad_mode='circular', onesided=False)),
@@ -352,23 +372,30 @@ def test_fft_length_8192_to_32768_four_step_kernel(tac):
         ref = numpy_ref.stft(x, n, hop, **kw)
         assert got.shape[:-1] == ref.shape
         assert rel_err(got[..., 0] + 1j * got[..., 1], ref) < 5e-6, (n, hop, kw)
+        fbnd.check_frames(got, fbnd.ref64(x, n, hop, **kw), 'complex', FRAME, 'big', (n, hop, kw), n, n < 32768)
     xs = x[0, :, :40000]                                   # a row shorter than the 32768 frame + padding on both sides
     got = host(tac.stft(dev(xs), 32768, hop_length=8192))
     assert rel_err(got[..., 0] + 1j * got[..., 1], numpy_ref.stft(xs, 32768, 8192)) < 5e-6
+    fbnd.check_frames(got, fbnd.ref64(xs, 32768, 8192), 'complex', FRAME, 'big', 'short row', 32768)
     for n, hop in ((8192, 2048), (16384, 4096), (32768, 8192)):
         mag2 = np.abs(numpy_ref.stft(x, n, hop)) ** 2
+        mag64 = fbnd.ref64(x, n, hop, torch.hann_window(n), 1.0)                # (the modules' host-built window)
         for power in (2.0, 1.0, 0.7):
             before = launches(tac)
             got = host(tac.Spectrogram(n, hop, power=power).cuda()(dev(x)))
             assert launched_since(tac, before) == {'tac_spectrogram_f32': 1}
             assert rel_err(got, mag2 ** (power / 2)) < 1e-5, (n, power)
+            fbnd.check_frames(got, mag64 ** power, 'spec', FRAME if power == 1.0 else 1e-5, 'big', (n, power), n, n < 32768)
         chain = torch.nn.Sequential(*tac.Spectrogram(n, hop, power=2.), tac.AmplitudeToDb()).cuda()
         want_db = 10.0 * np.log10(np.maximum(mag2 ** 2, 1e-7))                 # (amplitude_to_db squares its input)
         big = mag2 > 1e-6 * mag2.max()
         assert np.abs(host(chain(dev(x))) - want_db)[big].max() < DB_ABS, n
+        fbnd.check_power_db64(host(chain(dev(x))), x, n, hop, 2.0, 'big', n, FRAME, chain[0].window)
         mel = tac.Melspectrogram(num_mels=64, sample_rate=44100, fft_length=n, hop_length=hop).cuda()
         want_mel = torch_ref.melspectrogram(torch.from_numpy(x), num_mels=64, sample_rate=44100, n_fft=n, hop=hop).numpy()
         assert rel_err(host(mel(dev(x))), want_mel) < 2e-5, n
+        fbnd.check_frames(host(mel(dev(x))), fbnd.ref64(x, n, hop, mel[0].window, 2.0, mel[2].filterbank), 'spec', FRAME_POW,
+                          'big_mel', n, n, n < 32768)
     # gradients: 8192 through the generic Stockham adjoint (csrc/stft_smooth.hip: radix-4 / 2 passes, one frame per workgroup);
     # above that the op is differentiated through torch's operators (announced)
     xg = dev(x[:, :, :40000]).requires_grad_(True)
@@ -379,6 +406,7 @@ def test_fft_length_8192_to_32768_four_step_kernel(tac):
     xr = torch.from_numpy(x[:, :, :40000]).double().requires_grad_(True)
     (g0,) = torch.autograd.grad(torch_ref.spectrogram(xr, 8192, 2048, window=torch.hann_window(8192, dtype=torch.float64), power=2.0).sum(), xr)
     assert rel_err(host(g1), g0.numpy()) < 1e-4
+    fbnd.check_rows(host(g1), g0, 1e-4, 'big_grad', 8192, 8192)
     with pytest.raises(RuntimeError, match='strict mode'):
         tac.stft(xg, 16384, hop_length=4096).square().sum().backward()
 
@@ -391,10 +419,13 @@ def test_rows_shorter_than_a_frame(tac):
     for n in (64, 256, 400, 512, 1024, 2048, 4096):
         for length in (n // 2 + 3, n - 1, n - 7):
             for rows in ((1, 1), (3, 2)):
-                x = torch.rand(*rows, length) * 2 - 1
+                x = torch.from_numpy(signals.gained_with_silence(rows + (length,), n + length, n, n // 4))
+                tag = (n, length, rows)
+                silent = signals.has_silence(rows + (length,), n, n // 4)          # (the silent row of six)
                 z_want = tac.STFT(n, n // 4)(x)
                 z = tac.realize(tac.STFT(n, n // 4).cuda()(x.cuda())).cpu()
                 assert float((z - z_want).abs().max()) < 2e-6 * max(1.0, float(z_want.abs().max())) * 50, (n, length, rows)
+                fbnd.check_frames(z, fbnd.ref64(x, n, n // 4, torch.hann_window(n)), 'complex', FRAME, 'short_rows', tag, n, silent)
                 chains = [torch.nn.Sequential(*tac.Spectrogram(n, n // 4, power=2.), tac.AmplitudeToDb())]
                 if n >= 256:
                     chains.append(torch.nn.Sequential(*tac.Melspectrogram(num_mels=40, sample_rate=16000, fft_length=n, hop_length=n // 4),
@@ -404,6 +435,10 @@ def test_rows_shorter_than_a_frame(tac):
                     got = tac.realize(m.cuda()(x.cuda())).cpu()
                     big = want > want.max() - 50.0                       # dB values within 50 dB of the peak (see the note in the test below)
                     assert float((got - want)[big].abs().max()) < DB_ABS, (n, length, rows, len(m))
+                    if len(m) == 3:
+                        fbnd.check_power_db64(got, x, n, n // 4, 2.0, 'short_rows', tag, FRAME, m[0].window)
+                    else:
+                        fbnd.check_mel_db64(got, x, n, n // 4, m[2].filterbank, 'short_rows_mel', tag, m[0].window)
                 if n < 256 or length != n - 7:
                     continue
                 # ... and their gradients (the backward kernels re-read the frames with the same clamped requests)
@@ -417,6 +452,11 @@ def test_rows_shorter_than_a_frame(tac):
                     xg = x.cuda().requires_grad_(True)
                     (gg,) = torch.autograd.grad((tac.realize(m.cuda()(xg)) * wgt.cuda()).sum(), xg)
                     assert float((gg.cpu() - gw).abs().max() / gw.abs().max()) < 1e-3, (n, length, rows)
+                    x64 = x.double().requires_grad_(True)
+                    fb = m[2].filterbank if len(m) == 3 else None
+                    y64 = fbnd.ref64(x64, n, n // 4, m[0].window, 2.0, fb)
+                    (g64,) = torch.autograd.grad((y64 * wgt.double()).sum(), x64)
+                    fbnd.check_rows(gg, g64, 1e-3, 'short_rows_grad', tag, n, silent_rows=(1,) if silent else ())
 
 
 def test_tiny_inputs_every_kernel_family(tac):
@@ -427,23 +467,30 @@ def test_tiny_inputs_every_kernel_family(tac):
         hop = n // 4
         for length, center in ((n, False), (n + hop, False), (n, True), (3 * n + 5, True)):
             for rows in ((1, 1), (3, 1)):
-                x = signals.audio_like(rows + (length,), seed=n + length)
+                x = signals.gained_with_silence(rows + (length,), n + length, n, hop)
+                tag = (n, length, center, rows)
                 got = host(tac.stft(dev(x), n, hop_length=hop, center=center))
                 ref = numpy_ref.stft(x, n, hop, center=center)
                 assert got.shape[:-1] == ref.shape, (n, length, center, rows)
                 assert rel_err(got[..., 0] + 1j * got[..., 1], ref) < 5e-6, (n, length, center, rows)
+                silent = signals.has_silence(x.shape, n, hop)
+                fbnd.check_frames(got, fbnd.ref64(x, n, hop, center=center), 'complex', FRAME, 'tiny', tag,
+                                  n, silent)
                 spec = host(torch.nn.Sequential(*tac.Spectrogram(n, hop, center=center, power=2.), tac.AmplitudeToDb()).cuda()(dev(x)))
                 want = 10.0 * np.log10(np.maximum((np.abs(ref) ** 2) ** 2, 1e-7))
                 # (amplitude_to_db squares the power: a bin 50 dB under the frame's peak carries ~3e-5 of relative fp32 FFT
                 #  noise in |X|, 1.2e-4 in |X|^4, 5e-4 dB — bins further down are beyond DB_ABS for ANY float32 transform)
                 big = np.abs(ref) ** 2 > 1e-5 * (np.abs(ref) ** 2).max()
                 assert np.abs(spec - want)[big].max() < DB_ABS, (n, length, center, rows)
+                fbnd.check_power_db64(spec, x, n, hop, 2.0, 'tiny', tag, FRAME, center=center)
                 if n >= 256:
                     mel = tac.Melspectrogram(num_mels=40, sample_rate=16000, fft_length=n, hop_length=hop, center=center).cuda()
                     gm = host(tac.realize(mel(dev(x))))
                     wm = torch_ref.melspectrogram(torch.from_numpy(x), num_mels=40, sample_rate=16000, n_fft=n, hop=hop,
                                                   center=center).numpy()
                     assert gm.shape == wm.shape and rel_err(gm, wm) < 2e-5, (n, length, center, rows)
+                    fbnd.check_frames(gm, fbnd.ref64(x, n, hop, mel[0].window, 2.0, mel[2].filterbank, center=center), 'spec',
+                                      FRAME_POW, 'tiny', tag, n, silent)
 
 
 def test_short_input_raises_runtime_error(tac):
@@ -487,7 +534,7 @@ def test_stft_parameter_sweep_vs_oracle(tac):
         onesided = bool(case % 6)
         rows = (int(rng.integers(1, 4)), int(rng.integers(1, 3)))
         length = int(rng.integers(n + 1, 3 * n + 40)) + (case % 2)
-        x = signals.audio_like(rows + (length,), seed=100 + case)
+        x = signals.gained_with_silence(rows + (length,), 100 + case, n, hop)
         window = None if case % 3 else torch.from_numpy(signals.uniform((win_length,), seed=200 + case) * 0.5 + 0.75)
         kw = dict(win_length=win_length, window=window, center=center, pad_mode=pad_mode, normalized=normalized,
                   onesided=onesided)
@@ -497,6 +544,9 @@ def test_stft_parameter_sweep_vs_oracle(tac):
                             normalized=normalized, onesided=onesided))
         assert got.shape == want.shape, (case, n, hop, kw)
         assert rel_err(got, want) < 5e-6, (case, n, hop, win_length, center, pad_mode, normalized, onesided, length)
+        kw.pop('window')
+        fbnd.check_frames(got, fbnd.ref64(x, n, hop, window, **kw), 'complex', FRAME, 'stft_sweep',
+                          (case, n, hop, kw, rows, length), n, signals.has_silence(x.shape, n, hop))
         checked += 1
     assert checked == 64
 
@@ -511,33 +561,44 @@ def test_hop_ring_rows_on_every_chunk_shape(tac):
              ((40, 1, 6144), {}), ((2, 1, 70000), {'win_length': 1200}), ((1, 3, 40000), {'pad_mode': 'constant'}),
              ((5, 1, 2048 * 4 + 4), {})]
     for shape, kw in cases:
-        x = signals.audio_like(shape, seed=sum(shape))
+        x = signals.gained_with_silence(shape, sum(shape), 2048, 512)
+        silent = signals.has_silence(shape, 2048, 512)
         want = torch_ref.stft(torch.from_numpy(x), 2048, 512, **kw)
         got = tac.stft(dev(x), 2048, 512, **kw)
         assert tac._native.lib().tac_last_route().startswith(b'stft_ring3_kernel<1024, 16, 0,'), (shape, kw)
         assert rel_err(host(got), want.numpy()) < 2e-6, (shape, kw)
+        fbnd.check_frames(host(got), fbnd.ref64(x, 2048, 512, **kw), 'complex', FRAME, 'hop_ring', (shape, kw), 2048, silent)
         p_want = torch_ref.complex_norm(want, 2.0).numpy()
         spec = tac.Spectrogram(2048, 512, power=2., **kw).cuda()
         assert rel_err(host(spec(dev(x))), p_want) < 1e-5, (shape, kw)
+        fbnd.check_frames(host(spec(dev(x))), fbnd.ref64(x, 2048, 512, spec[0].window, 2.0, **kw), 'spec', 1e-5, 'hop_ring',
+                          (shape, kw), 2048, silent)
         assert tac._native.lib().tac_last_route().startswith(b'stft_ring3_kernel<1024, 16, 1,'), (shape, kw)
         db = host(torch.nn.Sequential(tac.Spectrogram(2048, 512, power=2., **kw), tac.AmplitudeToDb()).cuda()(dev(x)))
         keep = p_want > 1e-6 * p_want.max()
         assert np.abs(db - torch_ref.amplitude_to_db(torch.from_numpy(p_want)).numpy())[keep].max() < DB_ABS, (shape, kw)
+        fbnd.check_power_db64(db, x, 2048, 512, 2.0, 'hop_ring', (shape, kw), FRAME, **kw)
     # hop = fft_length / 8 takes the ring too (eight 1 KB hops per frame)
     for shape, kw in (((2, 1, 30000), {}), ((1, 2, 9000), {'center': False}), ((9, 1, 4100), {})):
-        x = signals.audio_like(shape, seed=sum(shape) + 1)
+        x = signals.gained_with_silence(shape, sum(shape) + 1, 2048, 256)
         want = torch_ref.stft(torch.from_numpy(x), 2048, 256, **kw)
         assert rel_err(host(tac.stft(dev(x), 2048, 256, **kw)), want.numpy()) < 2e-6, (shape, kw)
+        fbnd.check_frames(host(tac.stft(dev(x), 2048, 256, **kw)), fbnd.ref64(x, 2048, 256, **kw), 'complex', FRAME, 'hop_ring_h256',
+                          (shape, kw), 2048, signals.has_silence(shape, 2048, 256))
         assert tac._native.lib().tac_last_route().startswith(b'stft_ring3_kernel<1024, 16, 0, 12, 8>'), (shape, kw)
         spec = tac.Spectrogram(2048, 256, power=1., **kw).cuda()
         assert rel_err(host(spec(dev(x))), torch_ref.complex_norm(want, 1.0).numpy()) < 1e-5, (shape, kw)
+        fbnd.check_frames(host(spec(dev(x))), fbnd.ref64(x, 2048, 256, spec[0].window, 1.0, **kw), 'spec', FRAME, 'hop_ring_h256',
+                          (shape, kw), 2048, signals.has_silence(shape, 2048, 256))
     # the same rows with a hop the ring does not take (and rows whose hops are not 16-byte aligned) still agree: the other kernel
-    x = signals.audio_like((3, 1, 20000), seed=5)
+    x = signals.gained_with_silence((3, 1, 20000), 5, 2048, 500)
     assert rel_err(host(tac.stft(dev(x), 2048, 500)), torch_ref.stft(torch.from_numpy(x), 2048, 500).numpy()) < 2e-6
     assert tac._native.lib().tac_last_route().startswith(b'stft_stream3_kernel<1024, 16, 0,')
-    xo = dev(signals.audio_like((3, 1, 20001), seed=6))[..., 1:]                 # row starts off a 16-byte boundary
+    fbnd.check_frames(host(tac.stft(dev(x), 2048, 500)), fbnd.ref64(x, 2048, 500), 'complex', FRAME, 'stream3', 'hop500', 2048, True)
+    xo = dev(signals.gained_with_silence((3, 1, 20001), 6, 2048, 512))[..., 1:]  # row starts off a 16-byte boundary
     assert rel_err(host(tac.stft(xo, 2048, 512)), torch_ref.stft(xo.cpu(), 2048, 512).numpy()) < 2e-6
     assert not tac._native.lib().tac_last_route().startswith(b'stft_ring3')
+    fbnd.check_frames(host(tac.stft(xo, 2048, 512)), fbnd.ref64(xo, 2048, 512), 'complex', FRAME, 'unaligned_rows', 'off1', 2048, True)
 
 
 @pytest.mark.parametrize('power', [1, 2, 0.7])
@@ -633,8 +694,8 @@ def test_fused_kernels_on_custom_filterbanks(tac, path, n_fft, monkeypatch):
     the band-sparse form rejects (falls back to the MFMA form or to spectrogram + MFMA GEMM kernels) — all through the layer chain."""
     monkeypatch.setattr(tac._hip, 'MEL_PATH', path)
     fused = 'tac_melspec_sparse_f32' if path == 'sparse' else 'tac_melspec_f32' 
-    x = signals.audio_like((3, 2, 20000), seed=41)
     hop, f_bins = n_fft // 4, n_fft // 2 + 1
+    x = signals.gained_with_silence((3, 2, 20000), 41, n_fft, hop)
     rng = np.random.default_rng(7)
     fb = np.zeros((f_bins, 50), dtype=np.float32)
     for m in range(50):
@@ -660,9 +721,14 @@ def test_fused_kernels_on_custom_filterbanks(tac, path, n_fft, monkeypatch):
     assert np.abs(host(y) - want).max() < DB_ABS
     lin = torch.nn.Sequential(*list(chain)[:3])(dev(x))
     assert rel_err(host(lin), mel) < 1e-5
+    tag = (path, n_fft)
+    window = chain[0].window
+    fbnd.check_mel_db64(host(y), x, n_fft, hop, fb, 'custom_banks', tag, window)
+    fbnd.check_frames(host(lin), fbnd.ref64(x, n_fft, hop, window, 2.0, fb), 'spec', 1e-5, 'custom_banks', tag, n_fft, True)
     # magnitude (power = 1) chain takes the same kernels
     chain1 = torch.nn.Sequential(tac.STFT(n_fft, hop), tac.ComplexNorm(1.0), tac.ApplyFilterbank(torch.from_numpy(fb))).cuda()
     assert rel_err(host(chain1(dev(x))), np.einsum('...ft,fm->...mt', np.sqrt(p), fb.astype(np.float64))) < 1e-5
+    fbnd.check_frames(host(chain1(dev(x))), fbnd.ref64(x, n_fft, hop, window, 1.0, fb), 'spec', 1e-5, 'custom_banks_mag', tag, n_fft, True)
     # dense random bank: not fusable, still exact
     dense = signals.uniform((f_bins, 24), seed=42)
     chain2 = torch.nn.Sequential(tac.STFT(n_fft, hop), tac.ComplexNorm(2.0), tac.ApplyFilterbank(torch.from_numpy(dense))).cuda()
@@ -671,6 +737,7 @@ def test_fused_kernels_on_custom_filterbanks(tac, path, n_fft, monkeypatch):
     if path == 'sparse' and n_fft == 1024:           # (a small dense bank still fits the MFMA form's step budget)
         assert launched_since(tac, before) == {'tac_spectrogram_f32': 1, 'tac_apply_filterbank_f32': 1}
     assert rel_err(host(y2), np.einsum('...ft,fm->...mt', p, dense.astype(np.float64))) < 1e-5
+    fbnd.check_frames(host(y2), fbnd.ref64(x, n_fft, hop, window, 2.0, dense), 'spec', 1e-5, 'custom_banks_dense', tag, n_fft, True)
 
 
 def test_filterbank_buffer_replaced_in_place_is_repacked(tac):
@@ -1985,7 +2052,7 @@ def test_melspectrogram_2048_common_banks_take_the_band_sparse_kernel(tac):
     melspec_stream3_kernel, but until round 6 the packer asked the older two-waves-per-SIMD kernel's LDS formula and refused them, so
     the 2.1 x slower MFMA form ran.  Banks whose band count is not a multiple of 64 are laid out from their widest end (info[2] carries
     ST_REV_MARK = 256): outputs must land on their own bands.  Against the float64 oracle, float32 and int16 PCM input."""
-    x = signals.audio_like((3, 1, 30000), seed=620)
+    x = signals.gained_with_silence((3, 1, 30000), 620, 2048, 512)
     for n_mels, sr, rev in ((40, 16000, True), (64, 16000, False), (80, 16000, True), (80, 22050, True), (100, 22050, True), (160, 16000, True)):
         chain = torch.nn.Sequential(*tac.Melspectrogram(num_mels=n_mels, sample_rate=sr, fft_length=2048, hop_length=512),
                                     tac.AmplitudeToDb()).cuda()
@@ -2001,6 +2068,9 @@ def test_melspectrogram_2048_common_banks_take_the_band_sparse_kernel(tac):
         assert np.abs(got - want)[live].max() < DB_ABS, n_mels
         lin = host(tac.realize(torch.nn.Sequential(*list(chain)[:3])(dev(x))))
         assert rel_err(lin, mel) < 1e-5, n_mels
+        fbnd.check_mel_db64(got, x, 2048, 512, chain[2].filterbank, 'mel2048_banks', (n_mels, sr), chain[0].window)
+        fbnd.check_frames(lin, fbnd.ref64(x, 2048, 512, chain[0].window, 2.0, chain[2].filterbank), 'spec', 1e-5, 'mel2048_banks',
+                          (n_mels, sr), 2048, True)
     # int16 PCM through the coded-input form of the same kernel, 80 bands (reversed cells)
     pcm = np.round(x * 32767.0).astype(np.int16)
     chain = torch.nn.Sequential(*tac.Melspectrogram(num_mels=80, sample_rate=16000, fft_length=2048, hop_length=512)).cuda()
@@ -2008,6 +2078,8 @@ def test_melspectrogram_2048_common_banks_take_the_band_sparse_kernel(tac):
     fb = chain[2].filterbank.double().cpu().numpy()
     want = np.einsum('...ft,fm->...mt', np.abs(numpy_ref.stft(pcm.astype(np.float64) / 32768.0, 2048, 512)) ** 2, fb)
     assert rel_err(got, want) < 1e-5
+    fbnd.check_frames(got, fbnd.ref64(pcm.astype(np.float64) / 32768.0, 2048, 512, chain[0].window, 2.0, chain[2].filterbank),
+                      'spec', 1e-5, 'mel2048_banks', 'int16', 2048, True)
 
 
 def test_melspectrogram_4096_one_launch_geometries(tac):
@@ -2032,7 +2104,14 @@ def test_melspectrogram_4096_one_launch_geometries(tac):
             assert np.abs(got - want)[live].max() < DB_ABS
         else:
             assert rel_err(got, mel) < 1e-5
-    x = signals.audio_like((2, 3, 41000), seed=611)
+        tag = (n_mels, sr, hop, power, db, kw, x.shape)
+        kw64 = dict(center=kw.get('center', True), pad_mode=kw.get('pad_mode', 'reflect'))
+        if db:
+            fbnd.check_mel_db64(got, x, 4096, hop, layers[2].filterbank, 'mel4096', tag, layers[0].window, power, **kw64)
+        else:
+            fbnd.check_frames(got, fbnd.ref64(x, 4096, hop, layers[0].window, power, layers[2].filterbank, **kw64), 'spec', 1e-5,
+                              'mel4096', tag, 4096, signals.has_silence(x.shape, 4096, hop))
+    x = signals.gained_with_silence((2, 3, 41000), 611, 4096, 1024)
     for n_mels, sr in ((40, 16000), (64, 22050), (80, 44100), (128, 44100), (200, 48000), (256, 48000)):
         check(x, n_mels, sr, 1024, 2.0, True)
     check(x, 128, 48000, 1024, 1.0, True)
@@ -2040,11 +2119,12 @@ def test_melspectrogram_4096_one_launch_geometries(tac):
     check(x, 128, 48000, 2048, 2.0, True, center=False)
     for mode in ('constant', 'replicate', 'circular'):
         check(x, 80, 44100, 512, 2.0, True, pad_mode=mode)
-    check(signals.audio_like((1, 1, 4096), seed=612), 128, 44100, 1024, 2.0, True)          # five frames, four of them padded
-    check(signals.audio_like((5, 1, 4096 + 1024 * 13), seed=613), 128, 44100, 1024, 2.0, True, center=False)   # 14 frames per row
+    check(signals.gained_with_silence((1, 1, 4096), 612, 4096, 1024), 128, 44100, 1024, 2.0, True)          # five frames, four of them padded
+    check(signals.gained_with_silence((5, 1, 4096 + 1024 * 13), 613, 4096, 1024), 128, 44100, 1024, 2.0, True, center=False)   # 14 frames per row
     check(x, 128, 48000, 1000, 2.0, True)                                   # hop a multiple of four samples: still aligned
     check(x, 128, 48000, 1023, 2.0, False)                                  # frames off the 16-byte grid: the two-launch chain
-    check(signals.audio_like((2, 1, 3000), seed=614), 128, 44100, 1024, 2.0, False)          # rows shorter than one frame
+    check(signals.gained_with_silence((2, 1, 3000), 614, 4096, 1024), 128, 44100, 1024, 2.0, False)          # rows shorter than one frame
+    check(signals.gained_with_silence((2, 3, 9000), 615, 4096, 1023), 128, 48000, 1023, 2.0, False, db=False)  # declined, linear
 
 
 def test_compiled_binding_carries_the_fused_call(tac):
@@ -2125,6 +2205,11 @@ def test_coded_waveforms_fused_into_the_frame_load(tac, golden):
     reference chain MuLawDecoding -> Melspectrogram -> AmplitudeToDb (golden g9), at fft_length 2048 and (round 3) 256 / 400 /
     512 / 1024; other fft sizes convert first."""
     g = golden('g9_mulaw_mel')
+    lut = golden('g5_mulaw')['lut256']                                  # the reference's decoded values (float32)
+
+    def decoded64(codes_):
+        """The decoded waveform in float64: the table's float32 values, exact."""
+        return lut[np.asarray(codes_)].astype(np.float64)
     for dtype in (torch.int64, torch.uint8):
         codes = torch.from_numpy(g['codes']).to(dtype).cuda()
         for n_fft, hop, mels, fused in ((2048, 512, 128, True), (512, 128, 40, True)):
@@ -2140,13 +2225,16 @@ def test_coded_waveforms_fused_into_the_frame_load(tac, golden):
             else:
                 assert 'tac_melspec_sparse_f32' in ran and any(k.startswith('tac_mulaw_decode') for k in ran), ran
             assert np.abs(host(y) - g['mel_db_n%d' % n_fft]).max() < DB_ABS
+            fbnd.check_mel_db64(host(y), decoded64(g['codes']), n_fft, hop, model[3].filterbank, 'coded_mulaw', (n_fft, str(dtype)),
+                                model[1].window)
     # a decoded waveform used by anything else is an ordinary tensor with the table's bits
     w = tac.MuLawDecoding(256)(torch.from_numpy(g['codes']).cuda())
     assert isinstance(w, tac.DeferredWave) and np.array_equal(host(w + 0.0).view(np.uint32),
                                                               golden('g5_mulaw')['lut256'].view(np.uint32)[g['codes']])
     # int16 PCM: every frame position incl. the reflected edges, odd row offsets (unaligned pairs -> gather path), vs the
     # float32 path on sample * 2^-15
-    pcm = (signals.audio_like((3, 2, 30001), seed=63) * 25000).astype(np.int16)
+    pcm = (signals.gained_with_silence((3, 2, 30001), 63, 2048, 512) * 25000).astype(np.int16)
+    pcm64 = pcm.astype(np.float64) / 32768.0                            # the decoded waveform in float64 (exact)
     mel = torch.nn.Sequential(*tac.Melspectrogram(num_mels=128, sample_rate=16000, fft_length=2048, hop_length=512),
                               tac.AmplitudeToDb()).cuda()
     before = launches(tac)
@@ -2156,6 +2244,11 @@ def test_coded_waveforms_fused_into_the_frame_load(tac, golden):
     assert np.abs(host(got) - host(want)).max() < 1e-4
     odd = dev(pcm)[:, :, 1:]                                            # row base no longer 4-byte aligned
     assert np.abs(host(mel(odd)) - host(mel(dev(pcm.astype(np.float32)[:, :, 1:] / 32768.0)))).max() < 1e-4
+    fbnd.check_mel_db64(host(got), pcm64, 2048, 512, mel[2].filterbank, 'coded_int16', 2048, mel[0].window)
+    fbnd.check_mel_db64(host(mel(odd)), pcm64[:, :, 1:], 2048, 512, mel[2].filterbank, 'coded_int16', (2048, 'odd'), mel[0].window)
+    fbnd.check_frames(host(tac.realize(torch.nn.Sequential(*list(mel)[:3])(dev(pcm)))),
+                      fbnd.ref64(pcm64, 2048, 512, mel[0].window, 2.0, mel[2].filterbank), 'spec', FRAME_POW, 'coded_int16', 2048, 2048,
+                      True)
     # the same at the sizes of the 2 / 4 / 8-frames-per-wave kernels and the mixed-radix 400 one
     for n_fft, hop, mels in ((1024, 256, 80), (512, 128, 80), (256, 64, 40), (400, 160, 80)):
         chain = torch.nn.Sequential(*tac.Melspectrogram(num_mels=mels, sample_rate=16000, fft_length=n_fft, hop_length=hop),
@@ -2166,6 +2259,12 @@ def test_coded_waveforms_fused_into_the_frame_load(tac, golden):
         assert ran == {'tac_melspec_sparse_coded_f32': 1}, (n_fft, ran)
         assert np.abs(host(got) - host(chain(dev(pcm.astype(np.float32) / 32768.0)))).max() < 1e-4, n_fft
         assert np.abs(host(chain(odd)) - host(chain(dev(pcm.astype(np.float32)[:, :, 1:] / 32768.0)))).max() < 1e-4, n_fft
+        fbnd.check_mel_db64(host(got), pcm64, n_fft, hop, chain[2].filterbank, 'coded_int16', n_fft, chain[0].window)
+        fbnd.check_mel_db64(host(chain(odd)), pcm64[:, :, 1:], n_fft, hop, chain[2].filterbank, 'coded_int16', (n_fft, 'odd'),
+                            chain[0].window)
+        fbnd.check_frames(host(tac.realize(torch.nn.Sequential(*list(chain)[:3])(dev(pcm)))),
+                          fbnd.ref64(pcm64, n_fft, hop, chain[0].window, 2.0, chain[2].filterbank), 'spec', FRAME_POW, 'coded_int16',
+                          n_fft, n_fft, True)
     # mu-law codes at the speech configuration (400 / 160 / 40 mels), both storage types, against decode-then-float32
     codes = torch.from_numpy(g['codes'])
     for dtype in (torch.int64, torch.uint8):
@@ -2177,15 +2276,20 @@ def test_coded_waveforms_fused_into_the_frame_load(tac, golden):
         assert launched_since(tac, before) == {'tac_melspec_sparse_coded_f32': 1}
         wave = tac.MuLawDecoding(256)(codes.cuda()) + 0.0
         assert np.abs(host(got) - host(chain[1:](wave))).max() < 1e-4
+        fbnd.check_mel_db64(host(got), decoded64(codes), 400, 160, chain[3].filterbank, 'coded_mulaw', (400, str(dtype)),
+                            chain[1].window)
         assert np.abs(host(chain(codes.to(dtype).cuda()[..., 3:])) - host(chain[1:](wave[..., 3:].contiguous()))).max() < 1e-4
     # rows shorter than a frame (every frame gathers): the coded kernels decline, the chain converts first — same values
-    tiny = (signals.audio_like((2, 1, 333), seed=64) * 20000).astype(np.int16)
+    tiny = (signals.gained_with_silence((2, 1, 333), 64, 400, 160) * 20000).astype(np.int16)
     for n_fft, hop in ((400, 160), (512, 128)):
         chain = torch.nn.Sequential(*tac.Melspectrogram(num_mels=40, sample_rate=16000, fft_length=n_fft, hop_length=hop),
                                     tac.AmplitudeToDb()).cuda()
         assert np.abs(host(chain(dev(tiny))) - host(chain(dev(tiny.astype(np.float32) / 32768.0)))).max() < 1e-4, n_fft
+        fbnd.check_mel_db64(host(chain(dev(tiny))), tiny.astype(np.float64) / 32768.0, n_fft, hop, chain[2].filterbank, 'coded_int16',
+                            (n_fft, 'tiny'), chain[0].window)
     z = tac.stft(dev(pcm), 512, 128)                                    # no coded frame load there: converted by a kernel first
     assert rel_err(host(z), host(tac.stft(dev(pcm.astype(np.float32) / 32768.0), 512, 128))) < 1e-6
+    fbnd.check_frames(host(z), fbnd.ref64(pcm64, 512, 128), 'complex', FRAME, 'coded_int16', 'stft', 512, True)
 
 
 # ------------------------------------------------------------------ size-independent properties at BASELINE sizes
