@@ -218,6 +218,37 @@ int tac_phase_vocoder_backward_f32(const float* spec, int64_t rows, int32_t n_fr
                                    int64_t stride_f, int64_t stride_t, const int32_t* idx0, const int32_t* idx1, const float* alpha,
                                    int64_t n_out, const float* grad_out, float* grad_spec, void* stream);
 
+/* (5d) STFT -> TimeStretch -> ComplexNorm on magnitudes alone (stretch.hip).  complex_norm(phase_vocoder(X), power) is
+ *      (alpha |X[t1]| + (1 - alpha) |X[t0]|)^power whatever the phases are — the running phase, phase_advance, the wrap and the
+ *      cumulative sum cancel — so the chain is tac_spectrogram_f32(power = 1) followed by one of these.
+ *      mag: float[rows][n_frames][n_freqs] magnitudes, frame-major (bins contiguous; stride_t floats between frames, stride_r
+ *      between rows) — what tac_spectrogram_f32 writes with power = 1.  idx0 / alpha (device, n_out each): the first source frame
+ *      and the weight of the second (idx0 + 1) per output frame, the grid of tac_phase_vocoder_f32; source frames >= n_frames are
+ *      the reference's zero padding.  out[r][j][f] = (alpha[j] mag[r][idx0[j]+1][f] + (1 - alpha[j]) mag[r][idx0[j]][f])^power,
+ *      followed by amplitude_to_db when db != 0 (db_ref / db_amin as in tac_spectrogram_f32).   out: float[rows][n_out][n_freqs].
+ *      Non-finite input looks like the reference: a NaN source value makes every LATER output frame of its bin NaN (the reference's
+ *      cumulative phase), an infinite one only the frames interpolated from it.  flags: a caller-provided WORKSPACE of `rows`
+ *      int32 (device; contents on entry ignored, undefined afterwards) in which the kernel notes the first affected frame per row;
+ *      a second, near-empty launch rewrites what lies behind it. */
+int tac_stretch_norm_f32(const float* mag, int64_t rows, int32_t n_freqs, int64_t n_frames, int64_t stride_r, int64_t stride_t,
+                         const int32_t* idx0, const float* alpha, int64_t n_out, float power, int db, float db_ref, float db_amin,
+                         float* out, int32_t* flags, void* stream);
+/* ... with apply_filterbank (and amplitude_to_db when db != 0) in the same launch: the interpolated, powered row is built in LDS
+ *      and contracted with the band-sparse bank packed by tac_melbank_pack(..., n_fft = 0, ...).   out: float[rows][n_out][n_mels].
+ *      A non-finite bin makes its whole frame NaN, as the reference's dense matmul does.  TAC_E_UNSUPPORTED for a pack in the tile
+ *      layout or a bank outside 8..128 bands: callers then chain tac_stretch_norm_f32 and tac_apply_filterbank_*_f32. */
+int tac_stretch_mel_f32(const float* mag, int64_t rows, int32_t n_freqs, int64_t n_frames, int64_t stride_r, int64_t stride_t,
+                        const int32_t* idx0, const float* alpha, int64_t n_out, float power, const float* wpack, const int32_t* desc,
+                        const int32_t* info_host, int32_t n_mels, int db, float db_ref, float db_amin, float* out, int32_t* flags,
+                        void* stream);
+/* ... and the gradient of tac_stretch_norm_f32 (db = 0) with respect to mag, as a gather per source frame: bounds (device,
+ *      n_frames + 1 int32) holds bounds[t] = number of output frames with idx0 < t, so the outputs that read frame t are
+ *      [bounds[t - 1], bounds[t + 1]).  grad_out: float[rows][n_out][n_freqs], grad_mag: float[rows][n_frames][n_freqs], both dense;
+ *      every element of grad_mag is written (no zero-initialisation, no atomics: bit-reproducible). */
+int tac_stretch_norm_backward_f32(const float* mag, int64_t rows, int32_t n_freqs, int64_t n_frames, int64_t stride_r,
+                                  int64_t stride_t, const int32_t* idx0, const float* alpha, const int32_t* bounds, int64_t n_out,
+                                  float power, const float* grad_out, float* grad_mag, void* stream);
+
 /* (1d)-(6d) The path in float64 (the reference keeps f64 -> f64: functional.py:48-113, :116-128, :172-184, :187-201,
  *      :277-314).  Same argument meaning as the _f32 entry points with double data; d->n_fft: any even length <= 8192 whose
  *      half is 5-smooth (N/2-point mixed-radix complex Stockham transform per workgroup in LDS), or any other length

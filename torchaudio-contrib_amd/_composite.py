@@ -130,6 +130,31 @@ def phase_vocoder(spec, rate, phase_advance):
     return torch.stack([length * running.cos(), length * running.sin()], dim=-1)
 
 
+def stretch_norm(mag, rate, power, db, ref, amin):
+    """``complex_norm(phase_vocoder(X, rate, phase_advance), power)`` from ``mag = |X|`` alone (reference functional.py:233-274
+    followed by :126-128): the vocoder returns ``(length cos phi, length sin phi)`` with ``length = frac |X[t1]| + (1 - frac) |X[t0]|``,
+    whose norm is ``length`` whatever ``phi`` is — the running phase, ``phase_advance``, the wrap and the cumulative sum cancel.
+    What does not cancel is how the reference loses values: a NaN component has a NaN angle, which the cumulative sum carries into
+    every later frame of its bin (an infinite magnitude has a finite angle and stays where it is interpolated)."""
+    n_frames = mag.shape[-1]
+    t = torch.arange(0, n_frames, rate, device=mag.device)       # default dtype, as the reference evaluates it
+    frac = t % 1.0
+    tail_padded = TF.pad(mag, [0, 2])
+    len_l = tail_padded.index_select(-1, t.long())
+    len_r = tail_padded.index_select(-1, (t + 1).long())
+    length = frac * len_r + (1 - frac) * len_l
+    out = length if power == 1.0 else length.pow(power)
+    lost = (len_l.isnan() | len_r.isnan()).cumsum(-1) > 0
+    out = torch.where(lost, torch.full((), float('nan'), dtype=out.dtype, device=out.device), out)
+    return amplitude_to_db(out, ref, amin) if db else out
+
+
+def stretch_mel(mag, bank, rate, power, db, ref, amin):
+    """``stretch_norm`` followed by reference functional.py:183-184 (+ :291-296 when db)."""
+    out = apply_filterbank(stretch_norm(mag, rate, power, False, 1.0, 1e-7), bank)
+    return amplitude_to_db(out, ref, amin) if db else out
+
+
 def hpss(mag, kernel_f, kernel_t, power, hard):
     """reference beta_hpss.py:104-127 without its Python loops: reflect-pad both axes, running medians along frequency
     (percussive) and time (harmonic) as ``unfold(...).median``, ``pow``, soft / hard masks.  Masks come back as floats

@@ -36,7 +36,7 @@ def _count(name, *filled):
 # through an alias created before the cache, ``from_dlpack`` / raw-pointer writers — cannot be seen without reading the
 # tensor back on every call; after such a write call ``invalidate(t)`` (or ``invalidate()`` for everything).
 _epoch = 0
-_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT')
+_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite')
 
 
 _unstamped = itertools.count()
@@ -778,6 +778,130 @@ def phase_vocoder_backward(spec, rate, grad_out):
         _native.check(rc, 'tac_phase_vocoder_backward_f32')
         _count('tac_phase_vocoder_backward_f32')
     return gs.transpose(-3, -2)
+
+
+# ----------------------------------------------------------------------------- stretch on magnitudes (csrc/stretch.hip)
+_PV_BOUNDS_CACHE = {}
+
+
+def _stretch_bounds(n_frames, rate, device):
+    """``bounds[t]`` = number of output frames whose first source frame lies below ``t`` (t = 0 .. n_frames), from the same host
+    evaluation of the grid as ``_phase_vocoder_grid``: the first source frames are non-decreasing, so the outputs that read frame
+    ``t`` are ``[bounds[t - 1], bounds[t + 1])`` — the ranges the gather of ``tac_stretch_norm_backward_f32`` walks."""
+    key = (int(n_frames), float(rate), str(device), torch.get_default_dtype())
+    hit = _PV_BOUNDS_CACHE.get(key)
+    if hit is None:
+        first = torch.arange(0, n_frames, rate).long()
+        if len(_PV_BOUNDS_CACHE) > 64:
+            _PV_BOUNDS_CACHE.clear()
+        hit = torch.searchsorted(first, torch.arange(n_frames + 1)).to(torch.int32).to(device)
+        _PV_BOUNDS_CACHE[key] = hit
+    return hit
+
+
+def finite_table(t):
+    """Whether every element of a constant table (``TimeStretch.phase_advance``) is finite: read back once per buffer version
+    (one host synchronisation) and cached on the tensor like the tables derived from windows and filterbanks."""
+    hit = getattr(t, '_tac_finite', None)
+    if hit is not None and hit[0] == _stamp(t):
+        return hit[1]
+    ok = bool(torch.isfinite(t).all())
+    try:
+        t._tac_finite = (_stamp(t), ok)
+    except Exception:
+        pass
+    return ok
+
+
+def _magnitude_rows(mag):
+    """``mag`` (*, F, T) as frame-major rows [R][T][F] with contiguous bins — a view of what the spectrogram kernels return."""
+    n_freqs, n_frames = mag.shape[-2], mag.shape[-1]
+    fm = mag.transpose(-2, -1)
+    if fm.stride(-1) != 1 and n_freqs > 1:
+        fm = fm.contiguous()
+    rows = fm.reshape(-1, n_frames, n_freqs)
+    if (rows.stride(2) != 1 and n_freqs > 1) or (n_frames > 1 and rows.stride(1) < n_freqs) or (rows.shape[0] > 1 and rows.stride(0) < 0):
+        rows = rows.contiguous()
+    return rows
+
+
+def _stretch_strides(rows):
+    return (rows.stride(0) if rows.shape[0] > 1 else 0), (rows.stride(1) if rows.shape[1] > 1 else rows.shape[2])
+
+
+def stretch_norm(mag, rate, power, db, ref, amin):
+    """``complex_norm(phase_vocoder(X, rate), power)`` [-> dB] from ``mag = |X|`` (*, F, T): one streaming kernel plus the
+    near-empty launch that restores the reference's handling of non-finite values.  Result (*, F, n_out), frame-major."""
+    n_freqs, n_frames = mag.shape[-2], mag.shape[-1]
+    lead = tuple(mag.shape[:-2])
+    idx0, _, alpha = _phase_vocoder_grid(n_frames, rate, mag.device, torch.float32)
+    n_out = idx0.numel()
+    out = _empty(lead + (n_out, n_freqs), device=mag.device)
+    if out.numel():
+        rows = _magnitude_rows(mag)
+        stride_r, stride_t = _stretch_strides(rows)
+        flags = torch.empty(rows.shape[0], dtype=torch.int32, device=mag.device)       # the kernels' workspace: one word per row
+        with _native.on_device(mag.device):
+            rc = _native.lib().tac_stretch_norm_f32(
+                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t, _native.ptr(idx0), _native.ptr(alpha),
+                n_out, float(power), 1 if db else 0, float(ref), float(amin), _native.ptr(out), _native.ptr(flags),
+                _native.stream_ptr(mag.device))
+        _native.check(rc, 'tac_stretch_norm_f32')
+        _count('tac_stretch_norm_f32', out)
+    return out.transpose(-2, -1)
+
+
+def stretch_mel(mag, fb, rate, power, db, ref, amin):
+    """``stretch_norm`` -> ``apply_filterbank`` [-> dB] in one launch when the bank packs into the one-frame-per-wave lane layout;
+    any other bank (dense, custom, too few / too many bands): the rows form, then the filterbank kernels."""
+    n_freqs, n_frames = mag.shape[-2], mag.shape[-1]
+    if fb.dim() != 2 or fb.shape[0] != n_freqs:
+        raise RuntimeError('apply_filterbank: size mismatch, spectrogram has %d bins, filterbank %s' % (n_freqs, tuple(fb.shape)))
+    fb = fb if fb.is_contiguous() else fb.contiguous()
+    lead = tuple(mag.shape[:-2])
+    n_mels = fb.shape[1]
+    idx0, _, alpha = _phase_vocoder_grid(n_frames, rate, mag.device, torch.float32)
+    n_out = idx0.numel()
+    pack = _melbank_pack(fb, 0) if (MEL_PATH != 'mfma' and n_out and n_mels and mag.numel()) else None
+    if pack is not None:
+        wpack, desc, info = pack
+        rows = _magnitude_rows(mag)
+        stride_r, stride_t = _stretch_strides(rows)
+        out = _empty(lead + (n_out, n_mels), device=mag.device)
+        flags = torch.empty(rows.shape[0], dtype=torch.int32, device=mag.device)
+        with _native.on_device(mag.device):
+            rc = _native.lib().tac_stretch_mel_f32(
+                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t, _native.ptr(idx0), _native.ptr(alpha),
+                n_out, float(power), _native.ptr(wpack), _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), n_mels,
+                1 if db else 0, float(ref), float(amin), _native.ptr(out), _native.ptr(flags), _native.stream_ptr(mag.device))
+        if rc != _native.TAC_E_UNSUPPORTED:
+            _native.check(rc, 'tac_stretch_mel_f32')
+            _count('tac_stretch_mel_f32', out)
+            return out.transpose(-2, -1)
+    spec = stretch_norm(mag, rate, power, False, 1.0, 1e-7)
+    return apply_filterbank(spec, fb, db=(ref, amin) if db else None)
+
+
+def stretch_norm_backward(mag, rate, power, grad_out):
+    """Gradient of ``stretch_norm`` (without dB) with respect to ``mag``: a gather per source frame over the cached output ranges."""
+    n_freqs, n_frames = mag.shape[-2], mag.shape[-1]
+    lead = tuple(mag.shape[:-2])
+    idx0, _, alpha = _phase_vocoder_grid(n_frames, rate, mag.device, torch.float32)
+    n_out = idx0.numel()
+    gm = _empty(lead + (n_frames, n_freqs), device=mag.device)
+    if gm.numel():
+        bounds = _stretch_bounds(n_frames, rate, mag.device)
+        rows = _magnitude_rows(mag)
+        stride_r, stride_t = _stretch_strides(rows)
+        go = torch.empty(lead + (n_out, n_freqs), dtype=torch.float32, device=mag.device)          # frame-major, dense
+        go.transpose(-2, -1).copy_(grad_out)
+        with _native.on_device(mag.device):
+            rc = _native.lib().tac_stretch_norm_backward_f32(
+                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t, _native.ptr(idx0), _native.ptr(alpha),
+                _native.ptr(bounds), n_out, float(power), _native.ptr(go), _native.ptr(gm), _native.stream_ptr(mag.device))
+        _native.check(rc, 'tac_stretch_norm_backward_f32')
+        _count('tac_stretch_norm_backward_f32', gm)
+    return gm.transpose(-2, -1)
 
 
 # ----------------------------------------------------------------------------- elementwise

@@ -6,7 +6,11 @@ fusion boundary cannot be a container we own.  Instead ``STFT.forward`` returns 
 ``torch.Tensor`` wrapper subclass with the right shape / strides / dtype / device but no storage — and
 ``ComplexNorm`` / ``ApplyFilterbank`` extend the recipe when handed one.  ``AmplitudeToDb`` is terminal (nothing can
 fuse behind it): it launches the single fused ``tac_amd::melspectrogram`` op at once and returns an ordinary
-tensor.  A recipe that is still pending when it reaches anything else (any torch op, ``.cpu()``, printing,
+tensor.  ``TimeStretch`` between ``STFT`` and ``ComplexNorm`` (the reference's own layer test composes that chain) records
+its rate in the recipe: ``complex_norm(phase_vocoder(X))`` is ``(a |X[t1]| + (1 - a) |X[t0]|) ** power`` whatever the phases
+are, so the stretched chain runs as the ``|X|`` spectrogram kernel plus one ``tac_amd::stretch_norm`` / ``stretch_mel``
+launch and no complex tensor exists; a stretched recipe that reaches anything but ``ComplexNorm`` is the STFT kernel
+followed by the phase-vocoder kernel, as without deferral.  A recipe that is still pending when it reaches anything else (any torch op, ``.cpu()``, printing,
 ``realize()``) is materialised through ``__torch_dispatch__``.
 
 Safety of the deferral (the reference is eager; these make the difference unobservable or loud):
@@ -138,7 +142,7 @@ class _Source(object):
         for tensor, version, address, what in self.stamps:
             if tensor._version != version or tensor.data_ptr() != address:
                 raise RuntimeError(
-                    'torchaudio_contrib_amd: the %s handed to STFT was modified in place before its deferred '
+                    'torchaudio_contrib_amd: the %s handed to the STFT chain was modified in place before its deferred '
                     'spectrogram was used (the fused kernel had not been launched yet).  Use the result — or call '
                     'torchaudio_contrib_amd.realize() on it — before overwriting the input, finish the chain with '
                     'AmplitudeToDb (which launches immediately), or disable deferral with set_lazy_fusion(False).'
@@ -149,7 +153,7 @@ class DeferredSpectral(torch.Tensor):
     """Result of an STFT-rooted layer chain that has not been launched yet."""
 
     @staticmethod
-    def __new__(cls, src, stage, shape, strides, power=None, filterbank=None):
+    def __new__(cls, src, stage, shape, strides, power=None, filterbank=None, stretch=None):
         r = torch.Tensor._make_wrapper_subclass(cls, shape, strides=strides, dtype=torch.float32,
                                                 device=src.wave.device, requires_grad=src.grad)
         r._src = src
@@ -157,6 +161,7 @@ class DeferredSpectral(torch.Tensor):
         r._stage = stage            # 'stft' | 'spec' | 'mel'
         r._power = power
         r._fb = filterbank
+        r._stretch = stretch        # None | (rate, phase_advance, n_out): a TimeStretch sits behind the STFT
         r._value = None
         return r
 
@@ -191,8 +196,22 @@ class DeferredSpectral(torch.Tensor):
     def pending(self):
         return self._value is None
 
+    def with_stretch(self, rate, phase_advance):
+        """``TimeStretch`` behind a pending STFT: same recipe, ``n_out`` frames; ``phase_advance`` is watched like the window (it
+        cancels in the magnitude chain, but a stretched recipe that is realised as complex pairs reads it)."""
+        from ._hip import phase_vocoder_out_frames
+        s = self._src
+        s.watch(phase_advance, 'phase_advance')
+        n_out = phase_vocoder_out_frames(s.n_frames, rate)
+        return DeferredSpectral(s, 'stft', s.lead + (s.n_bins, n_out, 2),
+                                _transposed_strides(s.lead, (n_out, s.n_bins, 2), -3, -2), stretch=(rate, phase_advance, n_out))
+
     def with_norm(self, power):
         s = self._src
+        if self._stretch is not None:
+            n_out = self._stretch[2]
+            return DeferredSpectral(s, 'spec', s.lead + (s.n_bins, n_out),
+                                    _transposed_strides(s.lead, (n_out, s.n_bins), -2, -1), power=power, stretch=self._stretch)
         lay = s.spec_layout
         if lay is not None:
             return DeferredSpectral(s, 'spec', lay[0], lay[1], power=power)
@@ -204,9 +223,10 @@ class DeferredSpectral(torch.Tensor):
         s.watch(fb, 'filterbank')
         if torch.is_grad_enabled() and fb.requires_grad:
             s.grad = True
-        return DeferredSpectral(s, 'mel', s.lead + (fb.shape[1], s.n_frames),
-                                _transposed_strides(s.lead, (s.n_frames, fb.shape[1]), -2, -1),
-                                power=self._power, filterbank=fb)
+        n_frames = s.n_frames if self._stretch is None else self._stretch[2]
+        return DeferredSpectral(s, 'mel', s.lead + (fb.shape[1], n_frames),
+                                _transposed_strides(s.lead, (n_frames, fb.shape[1]), -2, -1),
+                                power=self._power, filterbank=fb, stretch=self._stretch)
 
     # -- materialisation --------------------------------------------------------
     def _launch(self, db):
@@ -219,6 +239,17 @@ class DeferredSpectral(torch.Tensor):
             return call('amplitude_to_db', self._launch(None), float(db[0]), float(db[1]))
         ref, amin = db if db is not None else (1.0, 1e-7)
         wave = s.wave
+        if self._stretch is not None:
+            rate, advance = self._stretch[0], self._stretch[1]
+            if s.decode is not None:
+                wave = call('mu_law_decoding', wave, s.decode, torch.float32)
+            if self._stage == 'stft':           # complex pairs are wanted: the STFT kernel, then the phase vocoder, as without deferral
+                return call('phase_vocoder', call('stft', wave, s.window, *s.args), advance.reshape(s.n_bins, 1), rate)
+            # |X| rows (half the bytes of the complex rows), then ONE launch: interpolate, power [, filterbank] [, dB]
+            mag = call('spectrogram', wave, s.window, *s.args, 1.0, False, 1.0, 1e-7)
+            if self._stage == 'spec':
+                return call('stretch_norm', mag, rate, float(self._power), db is not None, float(ref), float(amin))
+            return call('stretch_mel', mag, self._fb, rate, float(self._power), db is not None, float(ref), float(amin))
         if s.decode is not None:
             if self._stage == 'mel':            # codes decoded inside the fused kernel's frame load
                 return call('melspectrogram_mulaw', wave, s.window, self._fb, s.decode, *s.args, float(self._power),
@@ -288,7 +319,8 @@ class DeferredSpectral(torch.Tensor):
         s.check_unchanged()
         device = s.wave.device
         if torch._C._cuda_getCurrentRawStream(device.index) == s.stream:
-            v = self._launch_planned(db) if (self._stage == 'mel' and not self._tracks_grad and s.decode is None) \
+            v = self._launch_planned(db) if (self._stage == 'mel' and not self._tracks_grad and s.decode is None
+                                            and self._stretch is None) \
                 else self._launch(db)
         else:                                   # enqueue where forward() was called, then order the consumer behind it
             now = torch.cuda.current_stream(device)

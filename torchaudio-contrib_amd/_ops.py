@@ -6,6 +6,8 @@ see them by name.
     tac_amd::stft           gfx950 kernels through the C ABI (_hip.py)  stock torch ops       shapes + strides
     tac_amd::spectrogram        "      (STFT + |.|^p [+ dB] fused)      (_composite.py)
     tac_amd::melspectrogram     "      (the whole chain in ONE kernel)
+    tac_amd::stretch_norm       complex_norm(phase_vocoder(X)) [+ dB] from |X| alone (csrc/stretch.hip)
+    tac_amd::stretch_mel            "      + apply_filterbank in the same launch
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -301,6 +303,30 @@ def _phase_vocoder_hip_backward(saved, rest, needs, grads):
             torch.zeros_like(phase_advance) if needs[1] else None]       # (the wrap and the advance cancel: zero, as autograd finds)
 
 
+def _stretch_norm_hip_backward(saved, rest, needs, grads):
+    rate, power, db, ref, amin = rest
+    if grads[0] is None:
+        return None
+    mag, g = saved[0], grads[0]
+    if db:      # the linear values the dB gradient needs: one more launch of the forward kernel (nothing was saved)
+        g = H.amplitude_to_db_backward(H.stretch_norm(mag, rate, power, False, 1.0, 1e-7), g, amin)
+    return [H.stretch_norm_backward(mag, rate, power, g)]
+
+
+def _stretch_mel_hip_backward(saved, rest, needs, grads):
+    rate, power, db, ref, amin = rest
+    if grads[0] is None:
+        return None
+    mag, bank = saved
+    g = grads[0]
+    if db:
+        g = H.amplitude_to_db_backward(H.stretch_mel(mag, bank, rate, power, False, 1.0, 1e-7), g, amin)
+    # the bank's gradient the way apply_filterbank finds it: from the rows the bank was applied to
+    grad_bank = H.filterbank_grad(H.stretch_norm(mag, rate, power, False, 1.0, 1e-7), g) if needs[1] else None
+    grad_mag = H.stretch_norm_backward(mag, rate, power, H.apply_filterbank_backward(g, bank)) if needs[0] else None
+    return [grad_mag, grad_bank]
+
+
 def _hpss_hip_backward(saved, rest, needs, grads):
     kernel_f, kernel_t, power, hard = rest
     if all(g is None for g in grads) or not H.hpss_supported(kernel_f, kernel_t):
@@ -321,7 +347,8 @@ _HIP_BACKWARD = {'stft': _stft_hip_backward, 'spectrogram': _spectrogram_hip_bac
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
-                 'phase_vocoder': _phase_vocoder_hip_backward, 'hpss': _hpss_hip_backward, 'hpss_masks': _hpss_hip_backward}
+                 'phase_vocoder': _phase_vocoder_hip_backward, 'stretch_norm': _stretch_norm_hip_backward,
+                 'stretch_mel': _stretch_mel_hip_backward, 'hpss': _hpss_hip_backward, 'hpss_masks': _hpss_hip_backward}
 
 
 #: the CUDA-key kernels by op name: `call` below invokes them directly when the dispatcher has nothing to add
@@ -574,6 +601,44 @@ def _phase_vocoder_fake(spec, phase_advance, rate):
 
 _register('phase_vocoder', '(Tensor spec, Tensor phase_advance, float rate) -> Tensor', _phase_vocoder_cuda,
           _phase_vocoder_cpu, _phase_vocoder_fake, 2)
+
+
+# ============================================================================= stretch on magnitudes
+def _stretch_norm_cuda(mag, rate, power, db, ref, amin):
+    reason = _hip_dtype(mag)            # (float64 included: a float64 kernel of this op is not written)
+    if reason is not None:
+        _composite_route('stretch_norm', reason)
+        return C.stretch_norm(mag, rate, power, db, ref, amin)
+    out = H.stretch_norm(_f32(mag), rate, power, db, ref, amin)
+    return out if mag.dtype == out.dtype else out.to(mag.dtype)
+
+
+def _stretch_norm_fake(mag, rate, power, db, ref, amin):
+    n_out = H.phase_vocoder_out_frames(mag.shape[-1], rate)
+    return _swapped(mag.shape[:-2], (n_out, mag.shape[-2]), mag.dtype, mag.device, -2, -1)
+
+
+_register('stretch_norm', '(Tensor mag, float rate, float power, bool db, float ref, float amin) -> Tensor', _stretch_norm_cuda,
+          C.stretch_norm, _stretch_norm_fake, 1)
+
+
+def _stretch_mel_cuda(mag, bank, rate, power, db, ref, amin):
+    _same_device('stretch_mel', mag, bank)
+    reason = _hip_dtype(mag, bank)
+    if reason is not None:
+        _composite_route('stretch_mel', reason)
+        return C.stretch_mel(mag, bank, rate, power, db, ref, amin)
+    out = H.stretch_mel(_f32(mag), _f32(bank), rate, power, db, ref, amin)
+    return out if mag.dtype == out.dtype else out.to(mag.dtype)
+
+
+def _stretch_mel_fake(mag, bank, rate, power, db, ref, amin):
+    n_out = H.phase_vocoder_out_frames(mag.shape[-1], rate)
+    return _swapped(mag.shape[:-2], (n_out, bank.shape[1]), mag.dtype, mag.device, -2, -1)
+
+
+_register('stretch_mel', '(Tensor mag, Tensor filterbank, float rate, float power, bool db, float ref, float amin) -> Tensor',
+          _stretch_mel_cuda, C.stretch_mel, _stretch_mel_fake, 2)
 
 
 # ============================================================================= dB

@@ -174,6 +174,8 @@ int tac_last_hip_error(void) { return tac::g_last_hip_error; }
 //    launchers added during round 3 are counted from here as well (a library older than the binding fails its version check
 //    in _native.lib() instead of at the first missing symbol)
 // 5: round 6 — tac_set_fft_pipe
+//    (tac_stretch_norm_f32 / tac_stretch_mel_f32 / tac_stretch_norm_backward_f32, stretch.hip, are additions: no existing
+//    signature or meaning changed, a binding written against 5 keeps working, so the number stays)
 int tac_abi_version(void) { return 5; }
 
 int tac_set_fft_pipe(int mode) {

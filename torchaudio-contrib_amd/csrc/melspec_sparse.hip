@@ -15,6 +15,7 @@
 // return TAC_E_UNSUPPORTED and take the MFMA kernels instead.
 #include "mel_common.hpp"
 #include "mel_lanes.hpp"
+#include "fb_lanes.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -467,12 +468,7 @@ static int launch_stream(FrameGeom g, const Tables& tb, const SparseArgs& sm, co
 // 0.092 -> 0.080 ms on cfg-2's 1025 x 128, 4.0 -> 4.6 TB/s; twelve waves 0.081); wider rows (fft_length 4096): eight waves, 16 steps
 // in flight — sixteen row buffers of 8 KB do not fit next to 41 KB of weights.  The packed layout depends on the steps in flight
 // (lm_group), so the pack and the launch use the same rule.
-constexpr int FBL_CHUNKS = 5, FBL_CHUNKS_WIDE = 9;   // 16-byte chunks per lane and frame: up to 1280 / 2304 bins (fft_length 2048 / 4096)
-__host__ __device__ inline bool fbl_is_wide(int n_freqs) { return (n_freqs + 3) / 4 > FBL_CHUNKS * 64; }
-__host__ __device__ inline int fbl_waves(int n_freqs) { return fbl_is_wide(n_freqs) ? 8 : 16; }
-__host__ __device__ inline int fbl_fly(int n_freqs) { return fbl_is_wide(n_freqs) ? 16 : 8; }
-__host__ __device__ inline int fbl_pitch(int n_freqs) { return (n_freqs + 3 + 3) & ~3; }
-inline size_t fbl_base_lds(int n_freqs) { return (size_t)fbl_waves(n_freqs) * (fbl_pitch(n_freqs) + LM_MAX_MELS + 4) * sizeof(float) + 16; }
+// (FBL_CHUNKS, fbl_waves / fbl_fly / fbl_pitch / fbl_base_lds: fb_lanes.hpp, shared with stretch.hip)
 
 template <int S, int CHUNKS, int FBL_WAVES, int FBL_FLY>
 __global__ void __launch_bounds__(FBL_WAVES * 64, FBL_WAVES / 4)

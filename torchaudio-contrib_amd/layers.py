@@ -177,8 +177,10 @@ class MelFilterbank(Filterbank):
 
 
 class TimeStretch(_ModuleNoStateBuffers):
-    """Phase-vocoder time stretch of a complex spectrogram (reference layers.py:215-264).  Sits
-    outside the Melspectrogram hot path; a deferred STFT handed to it is materialised first."""
+    """Phase-vocoder time stretch of a complex spectrogram (reference layers.py:215-264).  Handed a deferred STFT it records
+    the rate in the recipe: behind ``ComplexNorm`` the phases cancel, and ``STFT -> TimeStretch -> ComplexNorm [-> ApplyFilterbank]
+    [-> AmplitudeToDb]`` runs on magnitudes alone (``_lazy.py``, csrc/stretch.hip); anything else that takes the stretched result
+    gets the STFT kernel followed by the phase-vocoder kernel.  A realised tensor is stretched at once."""
 
     def __init__(self, hop_length, num_freqs, fixed_rate=None):
         super(TimeStretch, self).__init__()
@@ -193,7 +195,16 @@ class TimeStretch(_ModuleNoStateBuffers):
                              ", must pass a valid rate to the forward method.")
         if rate == 1.0:
             return complex_specgrams
-        return F.phase_vocoder(complex_specgrams, rate, self.phase_advance)
+        x, pa = complex_specgrams, self.phase_advance
+        if isinstance(x, DeferredSpectral) and x.pending() and x._stage == 'stft' and x._stretch is None \
+                and isinstance(rate, (int, float)) and rate > 0 and type(pa) is torch.Tensor and pa.dtype == torch.float32 \
+                and pa.device == x._src.wave.device and pa.dim() >= 2 and pa.shape[-1] == 1 and pa.shape[-2] == x._src.n_bins \
+                and pa.numel() == x._src.n_bins and not (pa.requires_grad and torch.is_grad_enabled()) and _hip.finite_table(pa):
+            # (phase_advance cancels behind ComplexNorm, but a non-finite one poisons the reference: that case, like every
+            # argument F.phase_vocoder would refuse, takes the ordinary route below)
+            d = x.with_stretch(float(rate), pa)
+            return d.realize() if _lazy.ends_chain(self) else d
+        return F.phase_vocoder(x, rate, pa)
 
     def __repr__(self):
         return self.__class__.__name__ + '(fixed_rate={})'.format(self.fixed_rate)
