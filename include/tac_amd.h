@@ -426,6 +426,37 @@ int tac_debug_clock_probe(uint64_t* buf, int32_t capacity_pairs);
  *      TAC_FFT_PIPE=valu|mfma, else the build's default).  Returns the previous mode. */
 int tac_set_fft_pipe(int mode);
 
+/* (13) Inverse STFT (what torch.istft computes for the one-sided layout (1) writes): out[r][i] = num[i + pad] / env[i + pad],
+ *      num the overlap-add of window * irfft(X_t) (times sqrt(n_fft) when d->normalized), env the overlap-add of window^2,
+ *      pad = n_fft / 2 when d->center.  In `d`, `length` is the number of samples to WRITE per row (positions pad .. pad + length of the
+ *      hop (T - 1) + n_fft padded ones, as torch.istft slices them; zeros past the last) and `row_stride` the row stride of `out`; pad_mode is ignored.
+ *      Geometries: every n_fft tac_stft_backward_f32 takes (powers of two 32 .. 4096, 400, even lengths with a 7-smooth half,
+ *      8192), one-sided; TAC_E_UNSUPPORTED otherwise.
+ *      tac_istft_workspace: bytes of scratch tac_istft_f32 needs (the windowed frames, float[rows][T][n_fft]); 0 where the fused
+ *      one-launch route takes the geometry (n_fft 2048, hop 256 / 512 / 1024, center, row_stride a multiple of 4: call
+ *      tac_istft_f32 with workspace = NULL; a workspace of rows * T * n_fft floats selects the two-launch route instead);
+ *      negative = TAC_E_*.
+ *      tac_istft_envelope_f32: inv_env[p] = 1 / env[p] (and env[p] itself when `env` is not NULL) for the hop (T - 1) + n_fft
+ *      padded positions; a function of the window and the geometry only — callers cache it and check min env (the NOLA
+ *      condition of torch.istft) once.
+ *      tac_istft_f32: spec is frame-major, the F pairs of a frame contiguous, stride_t floats between frames and stride_r
+ *      between rows — dense rows only (stride_t == 2 F, stride_r == T stride_t: what (1) and the phase vocoder write),
+ *      TAC_E_UNSUPPORTED for any other layout.  Two launches: the frame kernels of tac_stft_backward_f32 in their inverse operand
+ *      mode, then a gather that writes every output element once.  tac_last_route() names the route.
+ *      tac_istft_grad_input_f32 / tac_istft_grad_bins_f32: the two elementwise halves of the gradient w.r.t. spec around
+ *      tac_stft_f32 (center = 0 on `padded`): padded[r][p] = grad_out[r][p - pad] * inv_env[p] inside the kept range, else 0
+ *      (float[rows][hop (T - 1) + n_fft]; d as for tac_istft_f32, grad_stride the row stride of grad_out); then in place
+ *      spec[frame][k] *= 2 s (0 < k < n_fft / 2), (s, 0) for the DC and Nyquist bins, s = (normalized ? sqrt(n_fft) : 1) / n_fft. */
+int64_t tac_istft_workspace(const tac_stft_desc* d, int64_t n_frames);
+int tac_istft_envelope_f32(const float* window, const tac_stft_desc* d, int64_t n_frames, float* inv_env, float* env,
+                           void* stream);
+int tac_istft_f32(const float* spec, int64_t stride_r, int64_t stride_t, int64_t n_frames, const float* window,
+                  const float* inv_env, const tac_stft_desc* d, void* workspace, int64_t workspace_bytes, float* out,
+                  void* stream);
+int tac_istft_grad_input_f32(const float* grad_out, int64_t grad_stride, const float* inv_env, const tac_stft_desc* d,
+                             int64_t n_frames, float* padded, void* stream);
+int tac_istft_grad_bins_f32(float* spec, int64_t n_frames_total, int n_fft, int normalized, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,10 +12,10 @@ from ._lazy import realize, set_lazy_fusion, lazy_fusion_enabled, DeferredSpectr
 from . import functional
 from . import layers
 from .functional import *      # noqa: F401,F403
-from .functional import (stft, complex_norm, create_mel_filter, apply_filterbank, angle, magphase,
+from .functional import (stft, istft, complex_norm, create_mel_filter, apply_filterbank, angle, magphase,
                          phase_vocoder, amplitude_to_db, db_to_amplitude, mu_law_encoding,
                          mu_law_decoding, hpss)
-from .layers import (STFT, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
+from .layers import (STFT, ISTFT, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
                      MuLawDecoding, HPSS)
 from . import distributed

@@ -39,6 +39,18 @@ def stft(wave, window, n_fft, hop, win_length, center, pad_mode, normalized, one
     return pairs.reshape(batch_shape + pairs.shape[1:])
 
 
+def istft(spec, window, n_fft, hop, win_length, center, normalized, onesided, length):
+    """the inverse of ``stft`` above the way the reference would wrap it: fold the leading dims into the batch, ``torch.istft``
+    on the complex view of the trailing-2 pairs, unfold."""
+    batch_shape = spec.shape[:-3]
+    pairs = spec.reshape((-1,) + tuple(spec.shape[-3:]))
+    if pairs.stride(-1) != 1 or any(s % 2 for s in pairs.stride()[:-1]):
+        pairs = pairs.contiguous()
+    out = torch.istft(torch.view_as_complex(pairs), n_fft, hop_length=hop, win_length=win_length, window=window,
+                      center=center, normalized=normalized, onesided=onesided, length=length, return_complex=False)
+    return out.reshape(tuple(batch_shape) + out.shape[1:])
+
+
 def complex_norm(z, power):
     """reference functional.py:126-128: 2-norm of the (re, im) pair; the exponent is a second pass."""
     length = z.norm(p=2, dim=-1)

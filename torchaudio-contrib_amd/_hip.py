@@ -36,7 +36,7 @@ def _count(name, *filled):
 # through an alias created before the cache, ``from_dlpack`` / raw-pointer writers — cannot be seen without reading the
 # tensor back on every call; after such a write call ``invalidate(t)`` (or ``invalidate()`` for everything).
 _epoch = 0
-_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite')
+_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite', '_tac_istft')
 
 
 _unstamped = itertools.count()
@@ -305,6 +305,147 @@ def spectrogram(wave, window, n_fft, hop, win_length, center, pad_mode, normaliz
     _native.check(rc, 'tac_spectrogram_f32')
     _count('tac_spectrogram_f32', out)
     return out.transpose(-2, -1)
+
+
+# ----------------------------------------------------------------------------- inverse STFT (csrc/istft.hip)
+#: how the last calls of ``istft`` got their frame-major rows: used in place (what ``stft`` / ``phase_vocoder`` return) or copied
+istft_layout = {'in_place': 0, 'copied': 0}
+
+
+def istft_covers(n_fft):
+    """the fft_lengths the frame kernels invert: every one ``tac_stft_backward_f32`` takes"""
+    return bool(fft_kernel_size(n_fft) or mixed_radix_size(n_fft) or smooth_fft_size(n_fft) or n_fft == 8192)
+
+
+def istft_full_length(n_frames, n_fft, hop, center):
+    """samples the frames determine: ``hop (T - 1) + n_fft`` minus the two halves ``center`` padded"""
+    return hop * (n_frames - 1) + n_fft - (2 * (n_fft // 2) if center else 0)
+
+
+def _istft_desc(rows, out_len, row_stride, n_fft, hop, win_length, center, normalized):
+    return _native.StftDesc(rows=rows, length=out_len, row_stride=row_stride, n_fft=n_fft, hop=hop, win_length=win_length,
+                            center=1 if center else 0, pad_mode=0, normalized=1 if normalized else 0, onesided=1, reserved=0)
+
+
+def istft_envelope(window, n_fft, hop, win_length, center, n_frames, kept):
+    """``1 / env`` of ``hop (T - 1) + n_fft`` padded positions as a device tensor, env the overlap-add of the squared window —
+    a constant of (window contents, geometry), cached on the window tensor like the other derived tables.  The first use of an
+    entry for a kept range of ``kept`` samples reads min env once (a host synchronisation) and raises the ``RuntimeError``
+    ``torch.istft`` raises when the window overlap-add vanishes there (NOLA); later calls synchronise nothing."""
+    cache = getattr(window, '_tac_istft', None)
+    stamp = _stamp(window)
+    if cache is None or cache[0] != stamp:
+        cache = (stamp, {})
+        try:
+            window._tac_istft = cache
+        except Exception:
+            pass
+    key = (n_fft, hop, win_length, bool(center), n_frames)
+    entry = cache[1].get(key)
+    if entry is None:
+        n_pos = hop * (n_frames - 1) + n_fft
+        with torch.inference_mode(False):
+            inv_env = torch.empty(n_pos, dtype=torch.float32, device=window.device)
+        desc = _istft_desc(1, 1, 1, n_fft, hop, win_length, center, False)
+        with _native.on_device(window.device):
+            rc = _native.lib().tac_istft_envelope_f32(_native.ptr(window), desc, n_frames, _native.ptr(inv_env),
+                                                      None, _native.stream_ptr(window.device))
+        _native.check(rc, 'tac_istft_envelope_f32')
+        launches['tac_istft_envelope_f32'] = launches.get('tac_istft_envelope_f32', 0) + 1
+        if len(cache[1]) > 64:
+            cache[1].clear()
+        entry = cache[1][key] = (inv_env, set())
+    if kept not in entry[1]:
+        pad = n_fft // 2 if center else 0
+        peak = float(entry[0][pad:pad + kept].max().item())         # (one table serves both: min env = 1 / max (1 / env))
+        lowest = 1.0 / peak if peak > 0.0 else float('inf')
+        if not lowest >= 1e-11:
+            raise RuntimeError('istft: window overlap add min: %g is below 1e-11 (fft_length=%d, hop_length=%d, center=%s): '
+                               'the window does not satisfy the NOLA condition' % (lowest, n_fft, hop, bool(center)))
+        entry[1].add(kept)
+    return entry[0]
+
+
+def _istft_rows(spec):
+    """logical (*, F, T, 2) -> the frame-major (rows, T, F, 2) tensor the kernels read, without a copy where the input already
+    is one (the strided views ``stft`` and ``phase_vocoder`` return)."""
+    sp = spec.transpose(-3, -2)
+    if sp.is_contiguous() and sp.data_ptr() % 16 == 0:
+        istft_layout['in_place'] += 1
+    else:
+        istft_layout['copied'] += 1
+        sp = sp.contiguous()
+    return sp.reshape((-1,) + tuple(sp.shape[-3:]))
+
+
+def istft(spec, window, n_fft, hop, win_length, center, normalized, length, route=None):
+    """one-sided ``(*, F, T, 2)`` float32 -> ``(*, samples)`` (tac_istft_f32).  fft_length 2048 with hop 256 / 512 / 1024 and
+    ``center``: one fused launch — inverse transform, window and overlap-add in LDS, no frame in memory, no workspace.  Every
+    other geometry (and ``route='general'``, the measuring tools' A/B switch): the frame kernels in inverse mode into a workspace,
+    then the gather that divides by the window envelope.  Either way every output element is written by the launch."""
+    n_frames = int(spec.shape[-2])
+    full = istft_full_length(n_frames, n_fft, hop, center)
+    if full <= 0:
+        raise RuntimeError('istft: %d frame(s) of fft_length %d leave no samples after removing the centre padding'
+                           % (n_frames, n_fft))
+    out_len = full if length is None else int(length)
+    inv_env = istft_envelope(window, n_fft, hop, win_length, center, n_frames, min(full + (n_fft // 2 if center else 0), out_len))
+    lead = tuple(int(s) for s in spec.shape[:-3])
+    rows = _istft_rows(spec)
+    n_rows = int(rows.shape[0])
+    out = _empty(lead + (out_len,), device=spec.device)
+    desc = _istft_desc(n_rows, out_len, out_len, n_fft, hop, win_length, center, normalized)
+    need = int(_native.lib().tac_istft_workspace(desc, n_frames))
+    if need < 0:
+        _native.check(need, 'tac_istft_workspace')
+
+    def launch(work, nbytes):
+        with _native.on_device(spec.device):
+            return _native.lib().tac_istft_f32(_native.ptr(rows), rows.stride(0), rows.stride(1), n_frames, _native.ptr(window),
+                                               _native.ptr(inv_env), desc, None if work is None else _native.ptr(work), nbytes,
+                                               _native.ptr(out), _native.stream_ptr(spec.device))
+
+    rc = _native.TAC_E_UNSUPPORTED
+    if need == 0 and route != 'general':
+        rc = launch(None, 0)
+    if rc == _native.TAC_E_UNSUPPORTED:                                 # (the general route takes any geometry and alignment)
+        need = n_rows * n_frames * n_fft * 4
+        work = torch.empty(need // 4, dtype=torch.float32, device=spec.device)      # scratch: every frame is written before it is read
+        rc = launch(work, need)
+    _native.check(rc, 'tac_istft_f32')
+    _count('tac_istft_f32', out)
+    return out
+
+
+def istft_backward(grad_out, window, n_fft, hop, win_length, center, normalized, n_frames):
+    """gradient of ``istft`` w.r.t. the spectrogram, ``(*, samples) -> (*, F, T, 2)``: ``stft`` (center=False framing, same
+    window) of ``grad_out / env`` zero-extended to the padded length, then the bin weights of irfft's adjoint — 1 for the real
+    parts of the DC and Nyquist bins, 0 for their imaginary parts, 2 elsewhere, times the inverse's 1 / N (sqrt(N) / N)."""
+    out_len = int(grad_out.shape[-1])
+    full = istft_full_length(n_frames, n_fft, hop, center)
+    inv_env = istft_envelope(window, n_fft, hop, win_length, center, n_frames, min(full + (n_fft // 2 if center else 0), out_len))
+    lead = tuple(int(s) for s in grad_out.shape[:-1])
+    go = grad_out.reshape(-1, out_len)
+    go = go if go.is_contiguous() else go.contiguous()
+    n_rows, n_pos, n_bins = int(go.shape[0]), hop * (n_frames - 1) + n_fft, n_fft // 2 + 1
+    padded = _empty((n_rows, n_pos), device=go.device)
+    gspec = _empty(lead + (n_frames, n_bins, 2), device=go.device)
+    with _native.on_device(go.device):
+        stream = _native.stream_ptr(go.device)
+        rc = _native.lib().tac_istft_grad_input_f32(
+            _native.ptr(go), out_len, _native.ptr(inv_env),
+            _istft_desc(n_rows, out_len, out_len, n_fft, hop, win_length, center, normalized), n_frames, _native.ptr(padded), stream)
+        _native.check(rc, 'tac_istft_grad_input_f32')
+        _count('tac_istft_grad_input_f32', padded)
+        fwd = _native.StftDesc(rows=n_rows, length=n_pos, row_stride=n_pos, n_fft=n_fft, hop=hop, win_length=win_length, center=0,
+                               pad_mode=0, normalized=0, onesided=1, reserved=0)
+        rc = _native.lib().tac_stft_f32(_native.ptr(padded), _native.ptr(window), fwd, _native.ptr(gspec), stream)
+        _native.check(rc, 'tac_stft_f32')
+        _count('tac_stft_f32', gspec)
+        rc = _native.lib().tac_istft_grad_bins_f32(_native.ptr(gspec), n_rows * n_frames, n_fft, 1 if normalized else 0, stream)
+        _native.check(rc, 'tac_istft_grad_bins_f32')
+        _count('tac_istft_grad_bins_f32', gspec)
+    return gspec.transpose(-3, -2)
 
 
 # ----------------------------------------------------------------------------- poisoned outputs (test hook)

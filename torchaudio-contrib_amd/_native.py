@@ -37,6 +37,7 @@ EXPORTS = (
     'tac_stft_f64', 'tac_spectrogram_f64', 'tac_apply_filterbank_f64', 'tac_magphase_f64', 'tac_amplitude_to_db_f64',
     'tac_db_to_amplitude_f64',
     'tac_last_route', 'tac_debug_clock_probe', 'tac_melbank_plan_pieces_host', 'tac_set_fft_pipe',
+    'tac_istft_workspace', 'tac_istft_envelope_f32', 'tac_istft_f32', 'tac_istft_grad_input_f32', 'tac_istft_grad_bins_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -175,6 +176,12 @@ def lib():
         h.tac_mulaw_encode_f64_i64.argtypes = [_P, _I64, _I32, _P, _P]
         h.tac_mulaw_decode_f64.argtypes = [_P, _I32, _I64, _I32, _P, _P]
         h.tac_mulaw_decode_f64.restype = ctypes.c_int
+        h.tac_istft_workspace.argtypes = [_DESC, _I64]
+        h.tac_istft_workspace.restype = _I64
+        h.tac_istft_envelope_f32.argtypes = [_P, _DESC, _I64, _P, _P, _P]
+        h.tac_istft_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _DESC, _P, _I64, _P, _P]
+        h.tac_istft_grad_input_f32.argtypes = [_P, _I64, _P, _DESC, _I64, _P, _P]
+        h.tac_istft_grad_bins_f32.argtypes = [_P, _I64, _I32, _I32, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

@@ -343,7 +343,16 @@ def _db_to_amplitude_hip_backward(saved, rest, needs, grads):
     return [H.db_to_amplitude_backward(saved[0], grads[0], rest[0])]
 
 
-_HIP_BACKWARD = {'stft': _stft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+def _istft_hip_backward(saved, rest, needs, grads):
+    spec, window = saved
+    n_fft, hop, win_length, center, normalized, onesided, length = rest
+    if grads[0] is None or needs[1] or not onesided or not H.istft_covers(n_fft):
+        return None                 # (the window's gradient: the stock-torch route, announced)
+    return [H.istft_backward(grads[0], window.contiguous(), n_fft, hop, win_length, center, normalized,
+                             int(spec.shape[-2])) if needs[0] else None, None]
+
+
+_HIP_BACKWARD = {'stft': _stft_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -421,6 +430,29 @@ def _stft_fake(wave, window, n_fft, hop, win_length, center, pad_mode, normalize
 
 
 _register('stft', '(Tensor wave, Tensor window, %s) -> Tensor' % _STFT_ARGS, _stft_cuda, C.stft, _stft_fake, 2)
+
+
+# ============================================================================= istft
+def _istft_cuda(spec, window, n_fft, hop, win_length, center, normalized, onesided, length):
+    _same_device('istft', spec, window)
+    reason = _hip_dtype(spec, window)
+    if reason is None and not onesided:
+        reason = 'onesided=False'
+    if reason is None and not H.istft_covers(n_fft):
+        reason = 'fft_length %d' % n_fft
+    if reason is not None:
+        _composite_route('istft', reason)
+        return C.istft(spec, window, n_fft, hop, win_length, center, normalized, onesided, length)
+    return H.istft(_f32(spec), _f32(window).contiguous(), n_fft, hop, win_length, center, normalized, length)
+
+
+def _istft_fake(spec, window, n_fft, hop, win_length, center, normalized, onesided, length):
+    n_out = H.istft_full_length(spec.shape[-2], n_fft, hop, center) if length is None else length
+    return torch.empty(tuple(spec.shape[:-3]) + (n_out,), dtype=_out_dtype(spec), device=spec.device)
+
+
+_register('istft', '(Tensor spec, Tensor window, int n_fft, int hop, int win_length, bool center, bool normalized, '
+          'bool onesided, int? length) -> Tensor', _istft_cuda, C.istft, _istft_fake, 2)
 
 
 # ============================================================================= spectrogram (stft + |.|^p [+ dB])

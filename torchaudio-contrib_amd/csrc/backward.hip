@@ -28,7 +28,7 @@ namespace tac {
 
 int launch_n400_backward(const FrameGeom& g, const float* gspec, const float* gnorm, float power, float* frames,
                          hipStream_t stream, bool from_wave, const AdjEntry* adj = nullptr, int n_mels = 0, float* gpad = nullptr,
-                         float* edge = nullptr, const OlaPlan* plan = nullptr);     // stft_n400.hip
+                         float* edge = nullptr, const OlaPlan* plan = nullptr, bool inverse = false);     // stft_n400.hip
 
 constexpr int BW_WAVES = 4;
 
@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(BW_WAVES * 64, 2)
 stft_backward_kernel(FrameGeom g, Tables tb, const float* __restrict__ gspec, const float* __restrict__ gnorm, float power,
                      float* __restrict__ frames) {
     using F = WaveFft<NC, E>;
-    constexpr bool NORM = (SRC != SRC_GRAD);
+    constexpr bool NORM = (SRC == SRC_NORM || SRC == SRC_WAVE);
     constexpr int N = 2 * NC, NBINS = NC + 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int lane = threadIdx.x & 63;
@@ -200,8 +200,9 @@ stft_backward_kernel(FrameGeom g, Tables tb, const float* __restrict__ gspec, co
                 }
                 if (b == 0 && q == 0) {                                    // (k == 0 can only be the lane's first element)
                     if (k == 0) {
-                        hk = mkc(2.0f * hk.x, 0.0f);
-                        hm = mkc(2.0f * hm.x, 0.0f);
+                        constexpr float ends = (SRC == SRC_INV) ? 1.0f : 2.0f;   // irfft takes Re X[0], Re X[NC] once
+                        hk = mkc(ends * hk.x, 0.0f);
+                        hm = mkc(ends * hm.x, 0.0f);
                     }
                 }
                 if (!live) hk = hm = mkc(0.0f, 0.0f);
@@ -898,7 +899,7 @@ db_to_amplitude_backward_kernel(const float* __restrict__ x, const float* __rest
 
 template <int NC, int E>
 static int launch_stft_backward(const FrameGeom& g, const Tables& tb, const float* gspec, const float* gnorm, float power,
-                                float* frames, hipStream_t stream, bool from_wave) {
+                                float* frames, hipStream_t stream, bool from_wave, bool inverse = false) {
     using F = WaveFft<NC, E>;
     const size_t lds_bytes = (size_t)BW_WAVES * (((F::G * F::PADDED + 1) / 2) * 2) * sizeof(cf) +
                              (from_wave ? (size_t)(NC + NC / 2 + 2) * sizeof(cf) : 0);
@@ -914,6 +915,8 @@ static int launch_stft_backward(const FrameGeom& g, const Tables& tb, const floa
             kern = pow2 ? stft_backward_kernel<NC, E, SRC_WAVE, true> : stft_backward_kernel<NC, E, SRC_WAVE, false>;
         else
             return TAC_E_UNSUPPORTED;                  // (32 elements per lane: no registers for two transforms)
+    } else if (inverse) {
+        kern = stft_backward_kernel<NC, E, SRC_INV, false>;
     } else if (gnorm) {
         kern = pow2 ? stft_backward_kernel<NC, E, SRC_NORM, true> : stft_backward_kernel<NC, E, SRC_NORM, false>;
     } else {
@@ -926,7 +929,8 @@ static int launch_stft_backward(const FrameGeom& g, const Tables& tb, const floa
 }
 
 bool stft_smooth_covers(int n_fft);                                                                           // stft_smooth.hip
-int launch_stft_smooth_backward(int n_fft, const FrameGeom& g, const float* grad_spec, float* grad_frames, hipStream_t stream);
+int launch_stft_smooth_backward(int n_fft, const FrameGeom& g, const float* grad_spec, float* grad_frames, hipStream_t stream,
+                                bool inverse = false);
 
 static int stft_backward_entry(const float* spec, const float* gnorm, float power, const float* window, const tac_stft_desc* d,
                                float* grad_frames, void* stream, bool from_wave = false, const AdjEntry* adj = nullptr,
@@ -959,6 +963,27 @@ static int stft_backward_entry(const float* spec, const float* gnorm, float powe
         case 1024: return launch_stft_backward<512, 16>(g, tb, spec, gnorm, power, grad_frames, s, from_wave);
         case 2048: return launch_stft_backward<1024, 16>(g, tb, spec, gnorm, power, grad_frames, s, from_wave);
         case 4096: return launch_stft_backward<2048, 32>(g, tb, spec, gnorm, power, grad_frames, s, from_wave);
+        default: return TAC_E_UNSUPPORTED;
+    }
+}
+
+// The frame kernels in inverse mode (istft.hip): spec[rows][T][F][2] -> frames[rows][T][N] = window * irfft(X_t) with the factor
+// 2 / N (times sqrt(N) when normalized) in g.scale — the gradient mode's window factor g.scale / 2 then is the 1 / N of irfft.
+int launch_istft_frames(int n_fft, const FrameGeom& g, const float* spec, float* frames, hipStream_t s) {
+    if (stft_smooth_covers(n_fft) || n_fft == 8192) return launch_stft_smooth_backward(n_fft, g, spec, frames, s, true);
+    if (n_fft == 400) return launch_n400_backward(g, spec, nullptr, 0.0f, frames, s, false, nullptr, 0, nullptr, nullptr, nullptr, true);
+    Tables tb;
+    const int rc = get_tables(n_fft, &tb);
+    if (rc != TAC_OK) return rc;
+    switch (n_fft) {
+        case 32: return launch_stft_backward<16, 16>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
+        case 64: return launch_stft_backward<32, 16>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
+        case 128: return launch_stft_backward<64, 16>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
+        case 256: return launch_stft_backward<128, 16>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
+        case 512: return launch_stft_backward<256, 16>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
+        case 1024: return launch_stft_backward<512, 16>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
+        case 2048: return launch_stft_backward<1024, 16>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
+        case 4096: return launch_stft_backward<2048, 32>(g, tb, spec, nullptr, 0.0f, frames, s, false, true);
         default: return TAC_E_UNSUPPORTED;
     }
 }

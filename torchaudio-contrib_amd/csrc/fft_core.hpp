@@ -574,7 +574,9 @@ struct WaveFft {
 // ---------------------------------------------------------------- gradient helpers (backward.hip, stft_n400.hip)
 // sources of the inverse transform's gradient spectrum: given, formed from the spectrum and the gradient of |z|^power, or
 // with the spectrum itself recomputed from the waveform inside the kernel
-enum { SRC_GRAD = 0, SRC_NORM = 1, SRC_WAVE = 2 };
+// SRC_INV: the operand is a spectrum to INVERT (istft.hip), not a gradient — H[0] = Re X[0], H[NC] = Re X[NC] enter the C2R
+// transform once where the adjoint of the one-sided forward transform doubles them
+enum { SRC_GRAD = 0, SRC_NORM = 1, SRC_WAVE = 2, SRC_INV = 3 };
 
 // d/dz of |z|^power (norm then pow, functional.py:126-128): g * power * |z|^(power-2) * z, 0 at z == 0
 __device__ __noinline__ inline float norm_pow_factor_general(float s, float power) {      // one copy of powf per kernel

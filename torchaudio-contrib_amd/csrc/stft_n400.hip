@@ -517,6 +517,7 @@ int pack_n400(const std::vector<float>& h, int n_freqs, int n_mels, float* wpack
 // frame gradients are overlap-added out of the staging area: complete positions of clean frames go straight into the
 // waveform gradient, the segment's border zone to gpad, its tail to edge[row][segment] (ola_fold_kernel finishes those and
 // the padding images) — so neither the 1600 bytes of frame gradient per frame nor the gather kernel's pass over them exist.
+// (SRC_INV: the inverse transform of a spectrum for istft — bins 0 and 200 enter once, not doubled; fft_core.hpp)
 template <int SRC, bool POW2, bool MELADJ = false, bool OLA = false>
 __global__ void __launch_bounds__(Q4_WAVES * 64, 2)
 stft_n400_backward_kernel(FrameGeom g, Q4Tables tb, const float* __restrict__ gspec, const float* __restrict__ gnorm,
@@ -716,7 +717,8 @@ stft_n400_backward_kernel(FrameGeom g, Q4Tables tb, const float* __restrict__ gs
                 if (idx < Q4_G * ROWC) {
                     cf x = idx < live ? val[i] : mkc(0.0f, 0.0f);
                     const int k = idx % ROWC;
-                    if (k == 0 || k == 200) x = mkc(2.0f * x.x, 0.0f);      // H[0] = 2 Re G[0], H[200] = 2 Re G[200]
+                    constexpr float ends = (SRC == SRC_INV) ? 1.0f : 2.0f;
+                    if (k == 0 || k == 200) x = mkc(ends * x.x, 0.0f);      // H[0] = 2 Re G[0], H[200] = 2 Re G[200] (SRC_INV: Re X[0], Re X[200])
                     wstage[idx] = x;
                 }
             }
@@ -814,7 +816,7 @@ stft_n400_backward_kernel(FrameGeom g, Q4Tables tb, const float* __restrict__ gs
 // tac_stft_backward_f32 / tac_stft_norm_backward_f32 for fft_length 400 (backward.hip's dispatcher calls this)
 int launch_n400_backward(const FrameGeom& g, const float* gspec, const float* gnorm, float power, float* frames,
                          hipStream_t stream, bool from_wave, const AdjEntry* adj, int n_mels, float* gpad, float* edge,
-                         const OlaPlan* plan) {
+                         const OlaPlan* plan, bool inverse) {
     Q4Tables tb;
     const int rc = q4_tables(&tb);
     if (rc != TAC_OK) return rc;
@@ -839,7 +841,7 @@ int launch_n400_backward(const FrameGeom& g, const float* gspec, const float* gn
         if (!gnorm) return TAC_E_INVALID;
         if (adj) kern = power == 2.0f ? stft_n400_backward_kernel<SRC_WAVE, true, true> : stft_n400_backward_kernel<SRC_WAVE, false, true>;
         else kern = power == 2.0f ? stft_n400_backward_kernel<SRC_WAVE, true> : stft_n400_backward_kernel<SRC_WAVE, false>;
-    } else if (!gnorm) kern = stft_n400_backward_kernel<SRC_GRAD, false>;
+    } else if (!gnorm) kern = inverse ? stft_n400_backward_kernel<SRC_INV, false> : stft_n400_backward_kernel<SRC_GRAD, false>;
     else kern = power == 2.0f ? stft_n400_backward_kernel<SRC_NORM, true> : stft_n400_backward_kernel<SRC_NORM, false>;
     if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Q4_WAVES * 64), bytes, stream, g, tb, gspec, gnorm, power, frames, adj,

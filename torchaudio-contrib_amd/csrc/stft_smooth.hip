@@ -251,7 +251,9 @@ stft_smooth_kernel(FrameGeom g, const cf* __restrict__ tw, StftEpilogue ep, Smoo
 //     Z[k] = (G[k] + conj G[M-k]) / 2 + (i / 2) conj(W_N^k) (G[k] - conj G[M-k])   (0 < k < M),   Z[0] = Re(G[0] + G[M]) + i Re(G[0] - G[M]),
 //     z = IDFT_M(Z) = conj(DFT_M(conj Z)),  y[2m] = Re z[m],  y[2m+1] = Im z[m]
 // — the forward passes run on conj Z and the result is conjugated on the way out.
-template <int TPF, bool FULL = true>
+// INV: the inverse transform of a spectrum for istft (istft.hip) — G[0] and G[M] enter at the same weight 1/2 as every other
+// bin pair, where the adjoint takes them whole.
+template <int TPF, bool FULL = true, bool INV = false>
 __global__ void __launch_bounds__(SM_THREADS)
 stft_smooth_backward_kernel(FrameGeom g, const cf* __restrict__ tw, const cf* __restrict__ grad_spec, float* __restrict__ grad_frames,
                             SmoothPlan plan, int N) {
@@ -282,7 +284,8 @@ stft_smooth_backward_kernel(FrameGeom g, const cf* __restrict__ tw, const cf* __
             cf zc;                                                            // conj Z[k]
             if (k == 0) {
                 const cf g0 = G[0], gm = G[M];
-                zc = mkc(g0.x + gm.x, -(g0.x - gm.x));
+                constexpr float ends = INV ? 0.5f : 1.0f;
+                zc = mkc((g0.x + gm.x) * ends, -(g0.x - gm.x) * ends);
             } else {
                 const cf a = G[k], braw = G[M - k];
                 const cf b = mkc(braw.x, -braw.y);
@@ -346,7 +349,8 @@ int launch_stft_smooth(int n_fft, const FrameGeom& g, const StftEpilogue& ep, in
 
 // Frame gradients from a one-sided gradient spectrum (stft_backward_entry of backward.hip): grad_spec[rows][T][M + 1][2] ->
 // grad_frames[rows][T][N].
-int launch_stft_smooth_backward(int n_fft, const FrameGeom& g, const float* grad_spec, float* grad_frames, hipStream_t stream) {
+int launch_stft_smooth_backward(int n_fft, const FrameGeom& g, const float* grad_spec, float* grad_frames, hipStream_t stream,
+                                bool inverse) {
     SmoothPlan plan;
     if (!smooth_plan(n_fft, &plan, n_fft == 8192)) return TAC_E_UNSUPPORTED;
     const cf* tw = nullptr;
@@ -369,8 +373,13 @@ int launch_stft_smooth_backward(int n_fft, const FrameGeom& g, const float* grad
                            grad_frames, plan, n_fft);
         return TAC_OK;
     };
-    const int rl = tpf == 64 ? go(stft_smooth_backward_kernel<64>)
-                             : (full ? go(stft_smooth_backward_kernel<256>) : go(stft_smooth_backward_kernel<256, false>));
+    int rl;
+    if (inverse)
+        rl = tpf == 64 ? go(stft_smooth_backward_kernel<64, true, true>)
+                       : (full ? go(stft_smooth_backward_kernel<256, true, true>) : go(stft_smooth_backward_kernel<256, false, true>));
+    else
+        rl = tpf == 64 ? go(stft_smooth_backward_kernel<64>)
+                       : (full ? go(stft_smooth_backward_kernel<256>) : go(stft_smooth_backward_kernel<256, false>));
     if (rl != TAC_OK) return rl;
     TAC_HIP(hipGetLastError());
     return TAC_OK;

@@ -21,7 +21,7 @@ from . import _hip
 from . import _ops
 from ._lazy import realize as _realize
 
-__all__ = ['stft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
+__all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss']
 
 _call = _ops.call
@@ -86,6 +86,40 @@ def stft(waveforms, fft_length, hop_length=None, win_length=None, window=None,
     n_fft, hop, win_length, window = resolve_stft_args(x, fft_length, hop_length, win_length, window)
     _hip.check_stft_args(x.shape, n_fft, hop, win_length, center, pad_mode)
     return _call('stft', x, window, n_fft, hop, win_length, bool(center), pad_mode, bool(normalized), bool(onesided))
+
+
+def istft(complex_specgrams, fft_length, hop_length=None, win_length=None, window=None,
+          center=True, normalized=False, onesided=True, length=None):
+    """Inverse short-time Fourier transform of ``(*, channel, num_freqs, time, complex=2)`` spectrograms →
+    ``(*, channel, samples)`` waveforms: ``torch.istft`` wrapped the way ``stft`` wraps ``torch.stft`` (leading dims
+    flattened and restored; ``window=None`` means a periodic Hann window of ``win_length or fft_length``).
+
+    ``samples`` is ``hop_length * (time - 1)`` with ``center`` (``+ fft_length`` without), or ``length`` when given (trimmed /
+    zero-padded).  A window whose squared overlap-add vanishes inside the kept range raises ``RuntimeError`` as ``torch.istft``
+    does (e.g. Hann with ``hop_length == fft_length``, or Hann with ``center=False``).
+    On a HIP device, float32 one-sided input runs on the gfx950 kernels: one inverse real FFT per frame, then a gather
+    overlap-add that divides by the window envelope.  The frame-major views ``stft`` and ``phase_vocoder`` return are read in place.
+    """
+    z = _tensor(complex_specgrams, 'complex_specgrams')
+    if z.dim() < 3 or z.shape[-1] != 2:
+        raise RuntimeError('istft: expected a tensor of shape (*, num_freqs, time, complex=2), got %s' % (tuple(z.shape),))
+    if not z.is_floating_point():
+        raise RuntimeError('istft: expected a floating point tensor, got %s' % z.dtype)
+    if any(int(s) == 0 for s in z.shape):
+        raise RuntimeError('istft: expected a non-empty tensor, got %s' % (tuple(z.shape),))
+    n_fft, hop, win_length, window = resolve_stft_args(z, fft_length, hop_length, win_length, window)
+    if n_fft <= 0 or hop <= 0 or hop > win_length:
+        raise RuntimeError('istft: expected 0 < hop_length <= win_length <= n_fft, got n_fft=%d hop_length=%d win_length=%d'
+                           % (n_fft, hop, win_length))
+    n_bins = n_fft // 2 + 1 if onesided else n_fft
+    if z.shape[-3] != n_bins:
+        raise RuntimeError('istft: expected %d frequency bins for fft_length=%d, onesided=%s, got %d'
+                           % (n_bins, n_fft, bool(onesided), z.shape[-3]))
+    if length is not None:
+        length = int(length)
+        if length <= 0:
+            raise RuntimeError('istft: expected length > 0, got %d' % length)
+    return _call('istft', z, window, n_fft, hop, win_length, bool(center), bool(normalized), bool(onesided), length)
 
 
 def complex_norm(complex_tensor, power=1.0):

@@ -100,6 +100,38 @@ class STFT(_ModuleNoStateBuffers):
         return self.__class__.__name__ + head + tail
 
 
+class ISTFT(_ModuleNoStateBuffers):
+    """Inverse short-time Fourier transform layer: ``(*, channel, num_freqs, time, 2)`` → ``(*, channel, samples)``.
+
+    Mirrors ``STFT``: ``hop_length`` defaults to ``fft_length // 4``, ``win_length`` to ``fft_length``, ``window`` to a periodic
+    Hann window of ``win_length`` (a buffer that follows ``.to()`` and stays out of ``state_dict()``);
+    ``center``/``normalized``/``onesided`` as in ``torch.istft``.  ``forward(complex_specgrams, length=None)``.
+    """
+
+    def __init__(self, fft_length, hop_length=None, win_length=None,
+                 window=None, center=True, normalized=False, onesided=True):
+        super(ISTFT, self).__init__()
+        self.fft_length = fft_length
+        self.hop_length = hop_length
+        self.win_length = win_length
+        self.center = center
+        self.normalized = normalized
+        self.onesided = onesided
+        if window is None:
+            window = torch.hann_window(fft_length if win_length is None else win_length)
+        self.register_buffer('window', window)
+
+    def forward(self, complex_specgrams, length=None):
+        return F.istft(complex_specgrams, self.fft_length, self.hop_length, self.win_length, self.window, self.center,
+                       self.normalized, self.onesided, length)
+
+    def __repr__(self):
+        head = '(fft_length={}, hop_length={}, win_length={})'.format(
+            self.fft_length, self.hop_length, self.win_length)
+        tail = '(center={}, normalized={}, onesided={})'.format(self.center, self.normalized, self.onesided)
+        return self.__class__.__name__ + head + tail
+
+
 class ComplexNorm(nn.Module):
     """``|z| ** power`` over the trailing complex dim (reference layers.py:112-135)."""
 
