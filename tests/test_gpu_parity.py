@@ -740,6 +740,43 @@ def test_fused_kernels_on_custom_filterbanks(tac, path, n_fft, monkeypatch):
     fbnd.check_frames(host(y2), fbnd.ref64(x, n_fft, hop, window, 2.0, dense), 'spec', 1e-5, 'custom_banks_dense', tag, n_fft, True)
 
 
+# The launch helper (csrc/host_common.hpp) asks for a kernel's dynamic-LDS ceiling only when a launch needs more than 64 KB.
+# launch_stft_smooth (csrc/stft_smooth.hip) runs every fft_length with a 7-smooth half up to 2048 on ONE instantiation per row kind,
+# stft_smooth_kernel<kind, 64>, with (n_fft + 2 * (n_fft / 2) * 4) * 8 = 40 n_fft bytes of dynamic LDS (four frames per workgroup):
+#   fft_length 1200 -> 48 000 bytes (no attribute call);   fft_length 2016 -> 80 640 bytes (above 64 KB; 1008 = 2^4 3^2 7 is the
+#   largest half these kernels take, so whatever ran before in the process, the first launch at this length raises the ceiling).
+# (The fused mel launchers cannot serve: their FFT buffers are fixed per kernel — 110 480 bytes and up for the lane forms of fft_length
+# 256 ... 1024, at most 58 KB for the tile forms up to 512 — so no filterbank moves one kernel across 64 KB.)
+LDS_ORDER_FFT = {'small': 1200, 'large': 2016}
+
+
+@pytest.mark.parametrize('kind,order', [('spec', ('small', 'large', 'small')), ('complex', ('large', 'small', 'large'))])
+def test_dynamic_lds_crosses_64_kb_in_both_orders(tac, kind, order):
+    """One kernel launched below, above and again below 64 KB of dynamic LDS in one process (|X|^2 rows: the first launch above
+    64 KB of stft_smooth_kernel<1, 64> follows one that set no ceiling) and, on the complex rows' instantiation, starting above
+    it (the launch below 64 KB then leaves the ceiling alone): every launch is the one entry point on that kernel, writes every
+    element and meets the float64 reference within the per-frame bounds of the smooth-length tests."""
+    shape = (2, 4096)
+    for step, name in enumerate(order):
+        n = LDS_ORDER_FFT[name]
+        hop = n // 4
+        x = signals.gained_with_silence(shape, 77, n, hop)
+        tag = (kind, order, step, n)
+        before = launches(tac)
+        if kind == 'complex':
+            got = host(tac.stft(dev(x), n, hop_length=hop))
+            entry, route, want, tol = 'tac_stft_f32', 'stft_smooth_kernel<0, 64>', fbnd.ref64(x, n, hop), FRAME
+        else:
+            spec = tac.Spectrogram(n, hop, power=2.).cuda()
+            got = host(spec(dev(x)))
+            entry, route, want, tol = 'tac_spectrogram_f32', 'stft_smooth_kernel<1, 64>', fbnd.ref64(x, n, hop, spec[0].window, 2.0), 1e-5
+        assert launched_since(tac, before) == {entry: 1}, tag
+        assert tac._native.lib().tac_last_route().decode() == route, tag
+        assert not tac._hip.poison_report(), tag
+        assert got.shape == tuple(want.shape), tag
+        fbnd.check_frames(got, want, kind, tol, 'lds_order', tag, n, signals.has_silence(shape, n, hop))
+
+
 def test_filterbank_buffer_replaced_in_place_is_repacked(tac):
     """The pack / plan ride on the filterbank tensor and follow in-place edits (no stale cache)."""
     x = dev(signals.audio_like((2, 1, 9000), seed=43))

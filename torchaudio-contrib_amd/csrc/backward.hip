@@ -904,10 +904,6 @@ static int launch_stft_backward(const FrameGeom& g, const Tables& tb, const floa
     const size_t lds_bytes = (size_t)BW_WAVES * (((F::G * F::PADDED + 1) / 2) * 2) * sizeof(cf) +
                              (from_wave ? (size_t)(NC + NC / 2 + 2) * sizeof(cf) : 0);
     const long long groups = g.rows * ((g.n_frames + F::G - 1) / F::G);
-    long long blocks = (groups + BW_WAVES - 1) / BW_WAVES;
-    const long long cap = (long long)device_cu_count() * 2;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
     const bool pow2 = (power == 2.0f);
     void (*kern)(FrameGeom, Tables, const float*, const float*, float, float*);
     if (from_wave) {
@@ -922,10 +918,8 @@ static int launch_stft_backward(const FrameGeom& g, const Tables& tb, const floa
     } else {
         kern = stft_backward_kernel<NC, E, SRC_GRAD, false>;
     }
-    if (lds_bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BW_WAVES * 64), lds_bytes, stream, g, tb, gspec, gnorm, power, frames);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(kern, persistent_blocks(groups, BW_WAVES, (long long)device_cu_count() * 2), BW_WAVES * 64, lds_bytes, stream, g, tb,
+                         gspec, gnorm, power, frames);
 }
 
 bool stft_smooth_covers(int n_fft);                                                                           // stft_smooth.hip
@@ -1095,11 +1089,7 @@ static long long ola_workspace_floats(const FrameGeom& g, const OlaPlan& plan, i
     return g.rows * plan.pad_len + g.rows * (long long)(plan.segs_per_row - 1) * (plan.n_fft - hop);
 }
 
-static unsigned bw_blocks(long long n) {
-    long long want = (n + 255) / 256, cap = (long long)device_cu_count() * 16;
-    if (want < 1) want = 1;
-    return (unsigned)(want < cap ? want : cap);
-}
+static long long bw_blocks(long long n) { return persistent_blocks(n, 256, (long long)device_cu_count() * 16); }
 
 }  // namespace tac
 
@@ -1140,9 +1130,9 @@ int tac_filterbank_adjoint_pack(const float* fb, int32_t n_freqs, int32_t n_mels
     // the counter sits behind the table (caller allocates 16·n_freqs + 16 bytes)
     int* counter = reinterpret_cast<int*>(static_cast<AdjEntry*>(table) + n_freqs);
     TAC_HIP(hipMemsetAsync(counter, 0, sizeof(int), s));
-    hipLaunchKernelGGL(fb_adjoint_pack_kernel, dim3((unsigned)((n_freqs + 255) / 256)), dim3(256), 0, s, fb, (int)n_freqs,
-                       (int)n_mels, static_cast<AdjEntry*>(table), counter);
-    TAC_HIP(hipGetLastError());
+    const int rc = launch_kernel(fb_adjoint_pack_kernel, (n_freqs + 255) / 256, 256, 0, s, fb, (int)n_freqs, (int)n_mels,
+                                 static_cast<AdjEntry*>(table), counter);
+    if (rc != TAC_OK) return rc;
     TAC_HIP(hipMemcpyAsync(max_nonzeros_host, counter, sizeof(int), hipMemcpyDeviceToHost, s));
     TAC_HIP(hipStreamSynchronize(s));
     return TAC_OK;
@@ -1156,14 +1146,9 @@ int tac_apply_filterbank_adjoint_f32(const float* grad_mel, int64_t rows_times_f
     if (n_mels > 512) return TAC_E_UNSUPPORTED;
     const size_t lds_bytes = (size_t)n_freqs * sizeof(AdjEntry) + (size_t)ADJ_WAVES * n_mels * sizeof(float);
     if (lds_bytes > 64 * 1024) return TAC_E_UNSUPPORTED;
-    long long blocks = (rows_times_frames + ADJ_WAVES - 1) / ADJ_WAVES;
-    const long long cap = (long long)device_cu_count() * 4;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(fb_adjoint_kernel, dim3((unsigned)blocks), dim3(ADJ_WAVES * 64), lds_bytes, (hipStream_t)stream,
-                       grad_mel, (long long)rows_times_frames, (int)n_mels, static_cast<const AdjEntry*>(table), (int)n_freqs,
-                       grad_spec);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(fb_adjoint_kernel, persistent_blocks(rows_times_frames, ADJ_WAVES, (long long)device_cu_count() * 4), ADJ_WAVES * 64,
+                         lds_bytes, (hipStream_t)stream, grad_mel, (long long)rows_times_frames, (int)n_mels,
+                         static_cast<const AdjEntry*>(table), (int)n_freqs, grad_spec);
 }
 
 int64_t tac_spectrogram_backward_ola_workspace(const tac_stft_desc* d) {
@@ -1218,27 +1203,15 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
     } else {
     rc = TAC_OK;
     OlaFuse fz{nullptr, 0, 0, 16};
-    auto launch = [&](auto kern, size_t lds_bytes, int streams_per_wave, int waves = OLA_WAVES) -> int {
-        const long long nwork = (g.rows * (long long)plan.segs_per_row + streams_per_wave - 1) / streams_per_wave;
-        long long blocks = (nwork + waves - 1) / waves;
-        const long long cap = (long long)device_cu_count() * 2 * OLA_WAVES / waves;
-        if (blocks > cap) blocks = cap;
-        TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(waves * 64), lds_bytes, s, g, tb, grad, power, gpad,
-                           edge, plan, fz);
-        TAC_HIP(hipGetLastError());
-        return TAC_OK;
+    // units of work: the segments of all rows, `streams_per_wave` of them a wave
+    auto units = [&](int streams_per_wave) { return (g.rows * (long long)plan.segs_per_row + streams_per_wave - 1) / streams_per_wave; };
+    auto launch = [&](auto kern, size_t lds_bytes, int streams_per_wave, int waves = OLA_WAVES) {
+        return launch_kernel(kern, persistent_blocks(units(streams_per_wave), waves, (long long)device_cu_count() * 2 * OLA_WAVES / waves),
+                             waves * 64, lds_bytes, s, g, tb, grad, power, gpad, edge, plan, fz);
     };
-    auto launch_multi = [&](auto kern, size_t lds_bytes, int streams_per_wave) -> int {
-        const long long nwork = (g.rows * (long long)plan.segs_per_row + streams_per_wave - 1) / streams_per_wave;
-        long long blocks = (nwork + OLA_WAVES - 1) / OLA_WAVES;
-        const long long cap = (long long)device_cu_count() * 2;
-        if (blocks > cap) blocks = cap;
-        TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(OLA_WAVES * 64), lds_bytes, s, g, tb, grad, power, gpad,
-                           edge, plan);
-        TAC_HIP(hipGetLastError());
-        return TAC_OK;
+    auto launch_multi = [&](auto kern, size_t lds_bytes, int streams_per_wave) {
+        return launch_kernel(kern, persistent_blocks(units(streams_per_wave), OLA_WAVES, (long long)device_cu_count() * 2), OLA_WAVES * 64,
+                             lds_bytes, s, g, tb, grad, power, gpad, edge, plan);
     };
     // LDS: per wave the exchange area(s) of its frame(s) + N floats of ring per frame stream (8 KB either way), then the
     // window pairs and the R2C twiddles
@@ -1264,14 +1237,9 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
         fz.mel_stride = adj ? (n_mels + 63) & ~63 : 0;
         fz.ring_slots = 16 - (d->hop >> 7);
         const size_t lds = ring3_lds_bytes<OLA_NC, OLA_E>(fz.mel_stride);
-        const long long nseg = g.rows * (long long)plan.segs_per_row;
-        long long blocks = (nseg + BR_WAVES - 1) / BR_WAVES;
-        if (blocks > device_cu_count()) blocks = device_cu_count();
-        auto go = [&](auto kern) -> int {
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds));
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BR_WAVES * 64), lds, s, g, tb, grad, power, gpad, edge, plan, fz);
-            TAC_HIP(hipGetLastError());
-            return TAC_OK;
+        auto go = [&](auto kern) {
+            return launch_kernel(kern, persistent_blocks(units(1), BR_WAVES, device_cu_count()), BR_WAVES * 64, lds, s, g, tb, grad, power, gpad,
+                                 edge, plan, fz);
         };
         auto pick = [&](auto h_tag) -> int {
             constexpr int HH = decltype(h_tag)::value;
@@ -1302,14 +1270,9 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
         const int G = 2048 / d->n_fft;
         const size_t lds = d->n_fft == 1024 ? ring3_multi_lds_bytes<512>(fz.mel_stride) : ring3_multi_lds_bytes<256>(fz.mel_stride);
         if (lds > 160 * 1024) return TAC_E_UNSUPPORTED;
-        const long long ngroups = (g.rows * (long long)plan.segs_per_row + G - 1) / G;
-        long long blocks = (ngroups + BR_WAVES - 1) / BR_WAVES;
-        if (blocks > device_cu_count()) blocks = device_cu_count();
-        auto go = [&](auto kern) -> int {
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds));
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BR_WAVES * 64), lds, s, g, tb, grad, power, gpad, edge, plan, fz);
-            TAC_HIP(hipGetLastError());
-            return TAC_OK;
+        auto go = [&](auto kern) {
+            return launch_kernel(kern, persistent_blocks(units(G), BR_WAVES, device_cu_count()), BR_WAVES * 64, lds, s, g, tb, grad, power, gpad,
+                                 edge, plan, fz);
         };
         auto pick = [&](auto nc_tag, auto h_tag) -> int {
             constexpr int NCC = decltype(nc_tag)::value, HH = decltype(h_tag)::value;
@@ -1383,17 +1346,13 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
         const long long zone_quads = (long long)(plan.segs_per_row - 1) * runs.zone_frames * (hop >> 2);
         if (zone_quads >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
         const int zone_blocks = (int)std::min<long long>((zone_quads + 255) / 256, 2 * per_row);
-        if (ht_blocks + zone_blocks > 0)
-            hipLaunchKernelGGL(ola_fold_runs_kernel, dim3((unsigned)(zone_blocks + ht_blocks), fold_y), dim3(256), 0, s, g, gpad, edge,
-                               plan, runs, zone_blocks, grad_wave, (long long)grad_row_stride);
-    } else {
-        // ~16 workgroups per CU in flight, each thread walking its row with a stride: rows on y, a row's samples on x
-        const unsigned fold_x = (unsigned)std::min<long long>((g.length + 1023) / 1024, per_row);
-        hipLaunchKernelGGL(ola_fold_kernel, dim3(fold_x, fold_y), dim3(256), 0, s, g, gpad, edge, plan, grad_wave,
-                           (long long)grad_row_stride);
+        if (ht_blocks + zone_blocks == 0) return TAC_OK;
+        return launch_kernel(ola_fold_runs_kernel, dim3((unsigned)(zone_blocks + ht_blocks), fold_y), 256, 0, s, g, gpad, edge, plan, runs,
+                             zone_blocks, grad_wave, (long long)grad_row_stride);
     }
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    // ~16 workgroups per CU in flight, each thread walking its row with a stride: rows on y, a row's samples on x
+    const unsigned fold_x = (unsigned)std::min<long long>((g.length + 1023) / 1024, per_row);
+    return launch_kernel(ola_fold_kernel, dim3(fold_x, fold_y), 256, 0, s, g, gpad, edge, plan, grad_wave, (long long)grad_row_stride);
 }
 }  // namespace tac
 
@@ -1427,10 +1386,8 @@ int tac_overlap_add_f32(const float* grad_frames, const tac_stft_desc* d, float*
     if (rc != TAC_OK) return rc;
     const int vec4 = ((d->hop & 3) == 0 && (d->n_fft & 3) == 0 && (g.center_pad & 3) == 0 &&
                       (reinterpret_cast<uintptr_t>(grad_frames) & 15u) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(overlap_add_kernel, dim3(bw_blocks(g.rows * ((g.length + 3) / 4))), dim3(256), 0, (hipStream_t)stream, g,
-                       (int)d->n_fft, grad_frames, grad_wave, (long long)grad_row_stride, vec4);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(overlap_add_kernel, bw_blocks(g.rows * ((g.length + 3) / 4)), 256, 0, (hipStream_t)stream, g, (int)d->n_fft,
+                         grad_frames, grad_wave, (long long)grad_row_stride, vec4);
 }
 
 int64_t tac_window_grad_partials(const tac_stft_desc* d) {
@@ -1453,10 +1410,7 @@ int tac_window_grad_f32(const float* grad_frames_unwindowed, const float* wave, 
     if (rc != TAC_OK) return rc;
     const long long total = g.rows * (long long)T;
     const long long per = (total + n_partials - 1) / n_partials;
-    hipLaunchKernelGGL(window_grad_kernel, dim3((unsigned)n_partials), dim3(256), 0, (hipStream_t)stream, g, (int)d->n_fft,
-                       grad_frames_unwindowed, per, partial);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(window_grad_kernel, n_partials, 256, 0, (hipStream_t)stream, g, (int)d->n_fft, grad_frames_unwindowed, per, partial);
 }
 
 int tac_complex_norm_backward_f32(const float* z, const float* grad_out, int64_t n, float power, float* grad_z,
@@ -1464,10 +1418,7 @@ int tac_complex_norm_backward_f32(const float* z, const float* grad_out, int64_t
     using namespace tac;
     if (n == 0) return TAC_OK;
     if (!z || !grad_out || !grad_z || n < 0) return TAC_E_INVALID;
-    hipLaunchKernelGGL(complex_norm_backward_kernel, dim3(bw_blocks(n)), dim3(256), 0, (hipStream_t)stream, z, grad_out,
-                       (long long)n, power, grad_z);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(complex_norm_backward_kernel, bw_blocks(n), 256, 0, (hipStream_t)stream, z, grad_out, (long long)n, power, grad_z);
 }
 
 int tac_magphase_backward_f32(const float* z, const float* grad_mag, const float* grad_phase, int64_t n, float power,
@@ -1475,20 +1426,16 @@ int tac_magphase_backward_f32(const float* z, const float* grad_mag, const float
     using namespace tac;
     if (n == 0) return TAC_OK;
     if (!z || !grad_z || (!grad_mag && !grad_phase) || n < 0) return TAC_E_INVALID;
-    hipLaunchKernelGGL(magphase_backward_kernel, dim3(bw_blocks(n)), dim3(256), 0, (hipStream_t)stream, z, grad_mag, grad_phase,
-                       (long long)n, power, grad_z);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(magphase_backward_kernel, bw_blocks(n), 256, 0, (hipStream_t)stream, z, grad_mag, grad_phase, (long long)n, power,
+                         grad_z);
 }
 
 int tac_db_to_amplitude_backward_f32(const float* x, const float* grad_out, int64_t n, float ref, float* grad_x, void* stream) {
     using namespace tac;
     if (n == 0) return TAC_OK;
     if (!x || !grad_out || !grad_x || n < 0 || !(ref > 0.0f)) return TAC_E_INVALID;
-    hipLaunchKernelGGL(db_to_amplitude_backward_kernel, dim3(bw_blocks(n)), dim3(256), 0, (hipStream_t)stream, x, grad_out,
-                       (long long)n, log10f(ref), grad_x);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(db_to_amplitude_backward_kernel, bw_blocks(n), 256, 0, (hipStream_t)stream, x, grad_out, (long long)n, log10f(ref),
+                         grad_x);
 }
 
 int tac_amplitude_to_db_backward_f32(const float* x, const float* grad_out, int64_t n, float amin, float* grad_x,
@@ -1497,14 +1444,8 @@ int tac_amplitude_to_db_backward_f32(const float* x, const float* grad_out, int6
     if (n == 0) return TAC_OK;
     if (!x || !grad_out || !grad_x || n < 0) return TAC_E_INVALID;
     const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_x)) & 15u) == 0;
-    if (vec)
-        hipLaunchKernelGGL(amplitude_to_db_backward_kernel<true>, dim3(bw_blocks((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x,
-                           grad_out, (long long)n, amin, grad_x);
-    else
-        hipLaunchKernelGGL(amplitude_to_db_backward_kernel<false>, dim3(bw_blocks(n)), dim3(256), 0, (hipStream_t)stream, x,
-                           grad_out, (long long)n, amin, grad_x);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(vec ? amplitude_to_db_backward_kernel<true> : amplitude_to_db_backward_kernel<false>, bw_blocks(vec ? (n + 3) / 4 : n),
+                         256, 0, (hipStream_t)stream, x, grad_out, (long long)n, amin, grad_x);
 }
 
 }  // extern "C"

@@ -324,30 +324,17 @@ int launch_stft_f64(const double* wave, const double* window, const tac_stft_des
     rc = twiddles_f64(d->n_fft, &tw);
     if (rc != TAC_OK) return rc;
     const long long units = g.rows * g.n_frames;
-    long long blocks = units;
     const long long cap = (long long)device_cu_count() * 8;
-    if (blocks > cap) blocks = cap;
     const int N = d->n_fft, M = N / 2;
     PlanD plan;
     if (plan_f64(N, &plan)) {
         const bool tw_lds = N <= 4096;
         const size_t lds = ((size_t)(tw_lds ? M + 1 : 0) + 2 * (size_t)M * plan.group) * sizeof(cd);
-        blocks = (units + plan.group - 1) / plan.group;
-        if (blocks > cap) blocks = cap;
-        if (tw_lds) {
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(stft_f64_kernel<true>), (int)lds));
-            hipLaunchKernelGGL(stft_f64_kernel<true>, dim3((unsigned)blocks), dim3(D_THREADS), lds, stream, g, tw, ep, plan, out);
-        } else {
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(stft_f64_kernel<false>), (int)lds));
-            hipLaunchKernelGGL(stft_f64_kernel<false>, dim3((unsigned)blocks), dim3(D_THREADS), lds, stream, g, tw, ep, plan, out);
-        }
-    } else {
-        const size_t lds = (size_t)N * sizeof(cd) + (size_t)N * sizeof(double);
-        TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(stft_f64_direct_kernel), (int)lds));
-        hipLaunchKernelGGL(stft_f64_direct_kernel, dim3((unsigned)blocks), dim3(D_THREADS), lds, stream, g, tw, ep, out);
+        return launch_kernel(tw_lds ? stft_f64_kernel<true> : stft_f64_kernel<false>, persistent_blocks(units, plan.group, cap), D_THREADS,
+                             lds, stream, g, tw, ep, plan, out);
     }
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    const size_t lds = (size_t)N * sizeof(cd) + (size_t)N * sizeof(double);
+    return launch_kernel(stft_f64_direct_kernel, persistent_blocks(units, 1, cap), D_THREADS, lds, stream, g, tw, ep, out);
 }
 
 // ------------------------------------------------------------------ filterbank contraction, float64
@@ -427,12 +414,8 @@ template <int OP>
 int launch_ew(const double* x, int64_t n, double p0, double p1, double* out, double* out2, void* stream) {
     if (!x || n < 0 || (!out && !out2)) return TAC_E_INVALID;
     if (n == 0) return TAC_OK;
-    long long blocks = (n + 255) / 256;
-    const long long cap = (long long)device_cu_count() * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(ew_f64_kernel<OP>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, (long long)n, p0, p1, out, out2);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(ew_f64_kernel<OP>, persistent_blocks(n, 256, (long long)device_cu_count() * 16), 256, 0, (hipStream_t)stream, x,
+                         (long long)n, p0, p1, out, out2);
 }
 
 }  // namespace
@@ -462,11 +445,9 @@ int tac_apply_filterbank_f64(const double* spec, int64_t rows, int32_t n_freqs, 
     if (n_frames >= 0x7fffffffLL || rows > 65535) return TAC_E_UNSUPPORTED;
     const dim3 grid((unsigned)((n_frames + FB_TM - 1) / FB_TM), (unsigned)((n_mels + FB_TN - 1) / FB_TN), (unsigned)rows);
     if (grid.y > 65535) return TAC_E_UNSUPPORTED;
-    hipLaunchKernelGGL(fb_f64_kernel, grid, dim3(256), 0, (hipStream_t)stream, spec, (long long)stride_r, (long long)stride_f,
-                       (long long)stride_t, (int)n_freqs, (int)n_frames, fb, (int)n_mels,
-                       EpiD{1, db ? 1 : 0, 1.0, db_amin, db ? std::log10(db_ref) : 0.0}, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(fb_f64_kernel, grid, 256, 0, (hipStream_t)stream, spec, (long long)stride_r, (long long)stride_f,
+                         (long long)stride_t, (int)n_freqs, (int)n_frames, fb, (int)n_mels,
+                         EpiD{1, db ? 1 : 0, 1.0, db_amin, db ? std::log10(db_ref) : 0.0}, out);
 }
 
 int tac_magphase_f64(const double* z, int64_t n, double power, double* mag, double* phase, void* stream) {

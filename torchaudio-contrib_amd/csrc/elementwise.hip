@@ -29,11 +29,8 @@ static inline int ew_blocks_override() {
     static const int v = [] { const char* e = getenv("TAC_EW_BLOCKS_PER_CU"); const int n = e ? atoi(e) : 0; return n > 0 ? n : 0; }();
     return v;
 }
-static inline unsigned ew_blocks(long long work_items, int per_cu = EW_DEFAULT) {
-    long long cap = (long long)device_cu_count() * (ew_blocks_override() ? ew_blocks_override() : per_cu);
-    long long want = (work_items + EW_THREADS - 1) / EW_THREADS;
-    if (want < 1) want = 1;
-    return (unsigned)(want < cap ? want : cap);
+static inline long long ew_blocks(long long work_items, int per_cu = EW_DEFAULT) {
+    return persistent_blocks(work_items, EW_THREADS, (long long)device_cu_count() * (ew_blocks_override() ? ew_blocks_override() : per_cu));
 }
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -263,11 +260,8 @@ static int launch_unary(const float* x, int64_t n, Op op, float* out, void* stre
     if (n == 0) return TAC_OK;
     if (!x || !out || n < 0) return TAC_E_INVALID;
     const bool vec = aligned16(x) && aligned16(out);
-    const unsigned blocks = ew_blocks(vec ? (n + 3) / 4 : n);
-    if (vec) hipLaunchKernelGGL((unary_kernel<true, Op>), dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, x, (long long)n, op, out);
-    else hipLaunchKernelGGL((unary_kernel<false, Op>), dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, x, (long long)n, op, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(vec ? unary_kernel<true, Op> : unary_kernel<false, Op>, ew_blocks(vec ? (n + 3) / 4 : n), EW_THREADS, 0,
+                         (hipStream_t)stream, x, (long long)n, op, out);
 }
 
 __global__ void __launch_bounds__(EW_THREADS) pcm16_kernel(const short* __restrict__ x, long long n, float* __restrict__ out) {
@@ -313,9 +307,7 @@ int tac_pcm16_to_f32(const int16_t* x, int64_t n, float* out, void* stream) {
     using namespace tac;
     if (n == 0) return TAC_OK;
     if (!x || !out || n < 0) return TAC_E_INVALID;
-    hipLaunchKernelGGL(pcm16_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, (hipStream_t)stream, x, (long long)n, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(pcm16_kernel, ew_blocks(n), EW_THREADS, 0, (hipStream_t)stream, x, (long long)n, out);
 }
 
 int tac_complex_norm_f32(const float* x, int64_t n, float power, float* out, void* stream) {
@@ -323,11 +315,8 @@ int tac_complex_norm_f32(const float* x, int64_t n, float power, float* out, voi
     if (n == 0) return TAC_OK;
     if (!x || !out || n < 0) return TAC_E_INVALID;
     const bool vec = aligned16(x) && aligned16(out);
-    const unsigned blocks = ew_blocks(vec ? (n + 3) / 4 : n, EW_COMPLEX_NORM);
-    if (vec) hipLaunchKernelGGL(complex_norm_kernel<true>, dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, x, (long long)n, power, out);
-    else hipLaunchKernelGGL(complex_norm_kernel<false>, dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, x, (long long)n, power, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(vec ? complex_norm_kernel<true> : complex_norm_kernel<false>, ew_blocks(vec ? (n + 3) / 4 : n, EW_COMPLEX_NORM),
+                         EW_THREADS, 0, (hipStream_t)stream, x, (long long)n, power, out);
 }
 
 int tac_magphase_f32(const float* x, int64_t n, float power, float* mag, float* phase, void* stream) {
@@ -335,17 +324,9 @@ int tac_magphase_f32(const float* x, int64_t n, float power, float* mag, float* 
     if (n == 0) return TAC_OK;
     if (!x || !phase || n < 0) return TAC_E_INVALID;
     const bool vec = aligned16(x) && aligned16(phase) && (!mag || aligned16(mag));
-    const unsigned blocks = ew_blocks(vec ? (n + 3) / 4 : n, EW_MAGPHASE);
-    const hipStream_t s = (hipStream_t)stream;
-    if (mag) {
-        if (vec) hipLaunchKernelGGL((magphase_kernel<true, true>), dim3(blocks), dim3(EW_THREADS), 0, s, x, (long long)n, power, mag, phase);
-        else hipLaunchKernelGGL((magphase_kernel<false, true>), dim3(blocks), dim3(EW_THREADS), 0, s, x, (long long)n, power, mag, phase);
-    } else {
-        if (vec) hipLaunchKernelGGL((magphase_kernel<true, false>), dim3(blocks), dim3(EW_THREADS), 0, s, x, (long long)n, power, mag, phase);
-        else hipLaunchKernelGGL((magphase_kernel<false, false>), dim3(blocks), dim3(EW_THREADS), 0, s, x, (long long)n, power, mag, phase);
-    }
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(mag ? (vec ? magphase_kernel<true, true> : magphase_kernel<false, true>)
+                             : (vec ? magphase_kernel<true, false> : magphase_kernel<false, false>),
+                         ew_blocks(vec ? (n + 3) / 4 : n, EW_MAGPHASE), EW_THREADS, 0, (hipStream_t)stream, x, (long long)n, power, mag, phase);
 }
 
 int tac_amplitude_to_db_f32(const float* x, int64_t n, float ref, float amin, float* out, void* stream) {
@@ -365,12 +346,9 @@ int tac_mulaw_encode_f32_i64(const float* x, int64_t n, int32_t n_quantize, cons
     const float mu = (float)(n_quantize - 1);
     const float l1p = exact_log1pf(mu);
     const bool vec = aligned16(x) && aligned16(out);
-    const unsigned blocks = ew_blocks(vec ? (n + 3) / 4 : n, EW_MULAW_ENCODE);
-    long long* o = reinterpret_cast<long long*>(out);
-    if (vec) hipLaunchKernelGGL(mulaw_encode_kernel<true>, dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, x, (long long)n, mu, l1p, thresholds, n_pos, n_neg, zero_code, o);
-    else hipLaunchKernelGGL(mulaw_encode_kernel<false>, dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, x, (long long)n, mu, l1p, thresholds, n_pos, n_neg, zero_code, o);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(vec ? mulaw_encode_kernel<true> : mulaw_encode_kernel<false>, ew_blocks(vec ? (n + 3) / 4 : n, EW_MULAW_ENCODE),
+                         EW_THREADS, 0, (hipStream_t)stream, x, (long long)n, mu, l1p, thresholds, n_pos, n_neg, zero_code,
+                         reinterpret_cast<long long*>(out));
 }
 
 int tac_mulaw_decode_i64_f32(const int64_t* codes, int64_t n, int32_t n_quantize, const float* lut, float* out,
@@ -381,12 +359,8 @@ int tac_mulaw_decode_i64_f32(const int64_t* codes, int64_t n, int32_t n_quantize
     const float mu = (float)(n_quantize - 1);
     const float l1p = exact_log1pf(mu);
     const bool vec = aligned16(codes) && aligned16(out);
-    const unsigned blocks = ew_blocks(vec ? (n + 3) / 4 : n);
-    const long long* c = reinterpret_cast<const long long*>(codes);
-    if (vec) hipLaunchKernelGGL(mulaw_decode_i64_kernel<true>, dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, c, (long long)n, n_quantize, mu, l1p, lut, out);
-    else hipLaunchKernelGGL(mulaw_decode_i64_kernel<false>, dim3(blocks), dim3(EW_THREADS), 0, (hipStream_t)stream, c, (long long)n, n_quantize, mu, l1p, lut, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(vec ? mulaw_decode_i64_kernel<true> : mulaw_decode_i64_kernel<false>, ew_blocks(vec ? (n + 3) / 4 : n), EW_THREADS,
+                         0, (hipStream_t)stream, reinterpret_cast<const long long*>(codes), (long long)n, n_quantize, mu, l1p, lut, out);
 }
 
 int tac_mulaw_decode_f32_f32(const float* codes, int64_t n, int32_t n_quantize, const float* lut, float* out,
@@ -404,10 +378,8 @@ int tac_mulaw_encode_f64_i64(const double* x, int64_t n, int32_t n_quantize, int
     using namespace tac;
     if (n == 0) return TAC_OK;
     if (!x || !out || n < 0 || n_quantize < 2) return TAC_E_INVALID;
-    hipLaunchKernelGGL(mulaw_encode_f64_kernel, dim3(ew_blocks(n, EW_MULAW_ENCODE)), dim3(EW_THREADS), 0, (hipStream_t)stream, x,
-                       (long long)n, (double)(n_quantize - 1), reinterpret_cast<long long*>(out));
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(mulaw_encode_f64_kernel, ew_blocks(n, EW_MULAW_ENCODE), EW_THREADS, 0, (hipStream_t)stream, x, (long long)n,
+                         (double)(n_quantize - 1), reinterpret_cast<long long*>(out));
 }
 
 int tac_mulaw_decode_f64(const void* codes, int32_t codes_are_i64, int64_t n, int32_t n_quantize, double* out, void* stream) {
@@ -416,13 +388,10 @@ int tac_mulaw_decode_f64(const void* codes, int32_t codes_are_i64, int64_t n, in
     if (!codes || !out || n < 0 || n_quantize < 2) return TAC_E_INVALID;
     const double mu = (double)(n_quantize - 1);
     if (codes_are_i64)
-        hipLaunchKernelGGL(mulaw_decode_f64_kernel<long long>, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                           static_cast<const long long*>(codes), (long long)n, mu, out);
-    else
-        hipLaunchKernelGGL(mulaw_decode_f64_kernel<double>, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, (hipStream_t)stream,
-                           static_cast<const double*>(codes), (long long)n, mu, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+        return launch_kernel(mulaw_decode_f64_kernel<long long>, ew_blocks(n), EW_THREADS, 0, (hipStream_t)stream,
+                             static_cast<const long long*>(codes), (long long)n, mu, out);
+    return launch_kernel(mulaw_decode_f64_kernel<double>, ew_blocks(n), EW_THREADS, 0, (hipStream_t)stream,
+                         static_cast<const double*>(codes), (long long)n, mu, out);
 }
 
 // ---- helpers of the general gradient routes (gradients of two-sided outputs, of the window and of the filterbank)
@@ -433,20 +402,15 @@ int tac_fold_twosided_f32(const float* grad, int64_t n_frames_total, int32_t n_f
     if (!grad || !out || n_frames_total < 0 || n_fft < 1 || (width != 1 && width != 2)) return TAC_E_INVALID;
     const int n_bins = n_fft / 2 + 1;
     const long long n = (long long)n_frames_total * n_bins * width;
-    hipLaunchKernelGGL(fold_twosided_kernel, dim3(ew_blocks(n)), dim3(EW_THREADS), 0, (hipStream_t)stream, grad, n, n_fft,
-                       n_bins, width, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(fold_twosided_kernel, ew_blocks(n), EW_THREADS, 0, (hipStream_t)stream, grad, n, n_fft, n_bins, width, out);
 }
 
 int tac_sum_slabs_f32(const float* x, int64_t n_slabs, int64_t slab_elems, float* out, void* stream) {
     using namespace tac;
     if (slab_elems == 0) return TAC_OK;
     if (!x || !out || n_slabs < 1 || slab_elems < 0) return TAC_E_INVALID;
-    hipLaunchKernelGGL(sum_slabs_kernel, dim3(ew_blocks(slab_elems)), dim3(EW_THREADS), 0, (hipStream_t)stream, x,
-                       (long long)n_slabs, (long long)slab_elems, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(sum_slabs_kernel, ew_blocks(slab_elems), EW_THREADS, 0, (hipStream_t)stream, x, (long long)n_slabs,
+                         (long long)slab_elems, out);
 }
 
 }  // extern "C"

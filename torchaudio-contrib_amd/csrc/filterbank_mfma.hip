@@ -209,11 +209,8 @@ int tac_apply_filterbank_f32(const float* spec, int64_t rows, int32_t n_freqs, i
     const bool va = stride_f == 1 && n_freqs >= 4, vb = (n_mels & 3) == 0;
     auto kern = va ? (vb ? gemm_fb_kernel<true, true> : gemm_fb_kernel<true, false>)
                    : (vb ? gemm_fb_kernel<false, true> : gemm_fb_kernel<false, false>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(GM_THREADS), 0, (hipStream_t)stream, spec,
-                       (long long)stride_r, (long long)stride_f, (long long)stride_t, n_freqs, (long long)n_frames,
-                       frame_tiles, col_tiles, fb, fb_plan, n_mels, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(kern, blocks, GM_THREADS, 0, (hipStream_t)stream, spec, (long long)stride_r, (long long)stride_f,
+                         (long long)stride_t, n_freqs, (long long)n_frames, frame_tiles, col_tiles, fb, fb_plan, n_mels, out);
 }
 
 }  // extern "C"

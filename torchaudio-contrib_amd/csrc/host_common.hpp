@@ -83,7 +83,52 @@ bool fft_pipe_mfma();
 // on each of them; thread-safe.
 hipError_t allow_dynamic_lds(const void* kernel, int bytes);
 
+// Grid of a persistent launch: one block per per_block units of work, at most max_blocks, never fewer than one (the
+// kernels loop on a unit counter, so a block without work just leaves).
+inline long long persistent_blocks(long long units, long long per_block, long long max_blocks) {
+    const long long want = (units + per_block - 1) / per_block;
+    const long long blocks = want < max_blocks ? want : max_blocks;
+    return blocks < 1 ? 1 : blocks;
+}
+
+#if defined(__HIPCC__)
+// THE kernel launch of this library: raise the kernel's dynamic-LDS ceiling where the launch needs more than the 64 KB
+// every kernel may use without asking, launch, pick up the launch error.  Returns TAC_OK or TAC_E_LAUNCH.
+// The attribute is only a ceiling the launch has to fit under — it changes nothing that runs on the device — so sites
+// that used to grant 160 KB once, or their exact byte count every time, lose nothing by asking only above 64 KB
+// (allow_dynamic_lds raises the ceiling again when a later launch of the same kernel asks for more).  Launches of
+// 64 KB or less take no lock.
+template <class... KArgs, class... Args>
+int launch_kernel(void (*kern)(KArgs...), dim3 grid, int threads, size_t lds_bytes, hipStream_t stream, Args&&... args) {
+    if (lds_bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes));
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds_bytes, stream, static_cast<Args&&>(args)...);
+    TAC_HIP(hipGetLastError());
+    return TAC_OK;
+}
+template <class... KArgs, class... Args>
+int launch_kernel(void (*kern)(KArgs...), long long blocks, int threads, size_t lds_bytes, hipStream_t stream, Args&&... args) {
+    return launch_kernel(kern, dim3((unsigned)blocks), threads, lds_bytes, stream, static_cast<Args&&>(args)...);
+}
+#endif
+
 inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// The real-row epilogue (spectral_row_value's MODE) of a one-sided STFT-family launch: 0 complex rows, 1 / 2 = |X|^2 / |X|,
+// 3 / 4 the same in dB; -1 where the pipelined kernels have no form (two-sided rows, other powers).  mode: 0 complex rows.
+inline int row_pmode(const StftEpilogue& ep, int mode) {
+    if (!ep.onesided) return -1;
+    if (mode == 0) return 0;
+    if (ep.power == 2.0f) return ep.db ? 3 : 1;
+    if (ep.power == 1.0f) return ep.db ? 4 : 2;
+    return -1;
+}
+
+// Coded samples (int16 PCM, mu-law codes) come in pairs fetched as one access of the format: FrameGeom::vec2_ok for them.
+inline bool coded_pairs_aligned(const FrameGeom& g, const void* samples, int fmt) {
+    const uintptr_t pair = fmt == FMT_I16 ? 4 : (fmt == FMT_MULAW_U8 ? 2 : 8);
+    return ((g.hop & 1) == 0) && ((g.center_pad & 1) == 0) && ((g.row_stride & 1) == 0) &&
+           ((reinterpret_cast<uintptr_t>(samples) & (pair - 1)) == 0);
+}
 
 // Validates a descriptor the way torch.stft does and fills the device-side geometry.
 // Returns TAC_OK or an error code.  T is written to *n_frames.

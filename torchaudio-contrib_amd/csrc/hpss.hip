@@ -642,15 +642,15 @@ hpss_kernel(const float* __restrict__ x, long long rows, int F, int T, long long
 }
 
 template <int K>
-static void launch_tile(const float* mag, long long rows, int F, int T, long long sr, long long sf, long long st,
-                        float power, int hard, float* harm, float* perc, float* mh, float* mp, hipStream_t stream) {
+static int launch_tile(const float* mag, long long rows, int F, int T, long long sr, long long sf, long long st,
+                       float power, int hard, float* harm, float* perc, float* mh, float* mp, hipStream_t stream) {
     const bool t_fast = st <= sf;
     const int NA = t_fast ? F : T, NB = t_fast ? T : F;
     const long long sa = t_fast ? sf : st, sb = t_fast ? st : sf;
     const int ta = (NA + HP_TILE - 1) / HP_TILE, tb = (NB + HP_TILE - 1) / HP_TILE;
     const long long total_tiles = rows * (long long)ta * tb;
-    hipLaunchKernelGGL(hpss_tile8_kernel<K>, dim3(hp_grid_for(total_tiles)), dim3(256), 0, stream, mag, NA, NB, sr, sa, sb, ta, tb,
-                       total_tiles, t_fast ? 1 : 0, power, hard, harm, perc, mh, mp);
+    return launch_kernel(hpss_tile8_kernel<K>, hp_grid_for(total_tiles), 256, 0, stream, mag, NA, NB, sr, sa, sb, ta, tb, total_tiles,
+                         t_fast ? 1 : 0, power, hard, harm, perc, mh, mp);
 }
 
 }  // namespace tac
@@ -743,14 +743,9 @@ int tac_hpss_backward_f32(const float* mag, int64_t rows, int32_t n_freqs, int32
         return TAC_E_UNSUPPORTED;
     if (kernel_f / 2 >= n_freqs || kernel_t / 2 >= n_frames) return TAC_E_SHORT_INPUT;
     const long long total = rows * n_freqs * (long long)n_frames;
-    long long blocks = (total + 255) / 256;
-    const long long cap = (long long)device_cu_count() * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(hpss_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mag, (long long)rows, (int)n_freqs,
-                       (int)n_frames, (long long)stride_r, (long long)stride_f, (long long)stride_t, (int)kernel_f, (int)kernel_t, power, hard,
-                       grad_harm, grad_perc, grad_mask_harm, grad_mask_perc, grad_mag);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(hpss_backward_kernel, persistent_blocks(total, 256, (long long)device_cu_count() * 16), 256, 0, (hipStream_t)stream,
+                         mag, (long long)rows, (int)n_freqs, (int)n_frames, (long long)stride_r, (long long)stride_f, (long long)stride_t,
+                         (int)kernel_f, (int)kernel_t, power, hard, grad_harm, grad_perc, grad_mask_harm, grad_mask_perc, grad_mag);
 }
 
 int tac_hpss_f32(const float* mag, int64_t rows, int32_t n_freqs, int32_t n_frames, int64_t stride_r, int64_t stride_f,
@@ -783,15 +778,13 @@ int tac_hpss_f32(const float* mag, int64_t rows, int32_t n_freqs, int32_t n_fram
     if (kernel_f == kernel_t && kernel_f >= 9 && kernel_f <= 31 && tiles < 0x7fffffffLL) {
 #define TAC_HPSS_CASE(K)                                                                                                   \
     case K:                                                                                                               \
-        launch_tile<K>(mag, rows, n_freqs, n_frames, stride_r, stride_f, stride_t, power, hard, harm, perc, mask_harm,   \
-                       mask_perc, (hipStream_t)stream);                                                                  \
-        break;
+        return launch_tile<K>(mag, rows, n_freqs, n_frames, stride_r, stride_f, stride_t, power, hard, harm, perc,      \
+                              mask_harm, mask_perc, (hipStream_t)stream);
         switch (kernel_f) {
             TAC_HPSS_CASE(9) TAC_HPSS_CASE(11) TAC_HPSS_CASE(13) TAC_HPSS_CASE(15) TAC_HPSS_CASE(17) TAC_HPSS_CASE(19)
             TAC_HPSS_CASE(21) TAC_HPSS_CASE(23) TAC_HPSS_CASE(25) TAC_HPSS_CASE(27) TAC_HPSS_CASE(29) TAC_HPSS_CASE(31)
         }
 #undef TAC_HPSS_CASE
-        TAC_HIP(hipGetLastError());
         return TAC_OK;
     }
     if (tiles < 0x7fffffffLL) {
@@ -800,39 +793,34 @@ int tac_hpss_f32(const float* mag, int64_t rows, int32_t n_freqs, int32_t n_fram
         const long long sa = t_fast ? stride_f : stride_t, sb = t_fast ? stride_t : stride_f;
         const int ka = t_fast ? kernel_f : kernel_t, kb = t_fast ? kernel_t : kernel_f;
         const int ta = (NA + HP_TILE - 1) / HP_TILE, tb = (NB + HP_TILE - 1) / HP_TILE;
-        const dim3 grid(hp_grid_for(tiles));
+        const unsigned grid = hp_grid_for(tiles);
+        int rc = TAC_OK;
 #define TAC_HPSS_ODD(M) M(1) M(3) M(5) M(7) M(9) M(11) M(13) M(15) M(17) M(19) M(21) M(23) M(25) M(27) M(29) M(31)            \
     M(33) M(35) M(37) M(39) M(41) M(43) M(45) M(47) M(49) M(51) M(53) M(55) M(57) M(59) M(61) M(63)
 #define TAC_HPSS_A(K)                                                                                                     \
     case K:                                                                                                               \
-        hipLaunchKernelGGL(hpss_axis_a_kernel<K>, grid, dim3(256), 0, (hipStream_t)stream, mag, NA, NB,                   \
+        rc = launch_kernel(hpss_axis_a_kernel<K>, grid, 256, 0, (hipStream_t)stream, mag, NA, NB,                         \
                            (long long)stride_r, sa, sb, ta, tb, (long long)tiles, mask_perc);                             \
         break;
 #define TAC_HPSS_B(K)                                                                                                     \
     case K:                                                                                                               \
-        hipLaunchKernelGGL(hpss_axis_b_kernel<K>, grid, dim3(256), 0, (hipStream_t)stream, mag, NA, NB,                   \
+        rc = launch_kernel(hpss_axis_b_kernel<K>, grid, 256, 0, (hipStream_t)stream, mag, NA, NB,                         \
                            (long long)stride_r, sa, sb, ta, tb, (long long)tiles, t_fast ? 1 : 0, power, hard, harm, perc, mask_harm, \
                            mask_perc);                                                                                    \
         break;
         switch (ka) { TAC_HPSS_ODD(TAC_HPSS_A) }
-        TAC_HIP(hipGetLastError());
+        if (rc != TAC_OK) return rc;
         switch (kb) { TAC_HPSS_ODD(TAC_HPSS_B) }
 #undef TAC_HPSS_A
 #undef TAC_HPSS_B
 #undef TAC_HPSS_ODD
-        TAC_HIP(hipGetLastError());
-        return TAC_OK;
+        return rc;
     }
     if (kernel_f > 32 || kernel_t > 32) return TAC_E_UNSUPPORTED;      // (the one-thread-per-element form sorts 32 taps)
     const long long total = rows * (long long)n_freqs * n_frames;
-    long long blocks = (total + 255) / 256;
-    const long long cap = (long long)device_cu_count() * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(hpss_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, mag, (long long)rows,
-                       (int)n_freqs, (int)n_frames, (long long)stride_r, (long long)stride_f, (long long)stride_t,
-                       (int)kernel_f, (int)kernel_t, power, hard, harm, perc, mask_harm, mask_perc);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(hpss_kernel, persistent_blocks(total, 256, (long long)device_cu_count() * 16), 256, 0, (hipStream_t)stream, mag,
+                         (long long)rows, (int)n_freqs, (int)n_frames, (long long)stride_r, (long long)stride_f, (long long)stride_t,
+                         (int)kernel_f, (int)kernel_t, power, hard, harm, perc, mask_harm, mask_perc);
 }
 
 }  // extern "C"

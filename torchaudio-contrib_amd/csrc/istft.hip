@@ -29,12 +29,7 @@ bool stft_smooth_covers(int n_fft);                                             
 
 namespace {
 
-inline long long grid_for(long long work, int threads = 256) {
-    long long blocks = (work + threads - 1) / threads;
-    const long long cap = (long long)device_cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return blocks < 1 ? 1 : blocks;
-}
+inline long long grid_for(long long work) { return persistent_blocks(work, 256, (long long)device_cu_count() * 8); }
 
 // env[p] = sum over the frames covering padded position p of w[p - t hop]^2 (accumulated in double: a constant table), and
 // its reciprocal.  P = hop (T - 1) + N positions.
@@ -271,14 +266,9 @@ int launch_istft_fused(const FrameGeom& g, const Tables& tb, const float* spec, 
     istft_fused_plan(g.rows, (int)g.n_frames, HOP, &seg_frames, &segs_per_row);
     const size_t lds_bytes = (size_t)IF_WAVES * ((((F::PADDED + 1) / 2) * 2) * sizeof(cf) + 2048 * sizeof(float));
     const long long units = g.rows * segs_per_row;
-    long long blocks = (units + IF_WAVES - 1) / IF_WAVES;
-    const long long cap = (long long)device_cu_count() * 2;
-    if (blocks > cap) blocks = cap;
-    auto kern = istft_fused_kernel<HOP>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(IF_WAVES * 64), lds_bytes, s, g, tb, spec, inv_env, out, out_stride, L, valid,
-                       seg_frames, segs_per_row);
-    TAC_HIP(hipGetLastError());
+    const int rc = launch_kernel(istft_fused_kernel<HOP>, persistent_blocks(units, IF_WAVES, (long long)device_cu_count() * 2), IF_WAVES * 64,
+                                 lds_bytes, s, g, tb, spec, inv_env, out, out_stride, L, valid, seg_frames, segs_per_row);
+    if (rc != TAC_OK) return rc;
     set_last_route("istft_fused_kernel<%d>", HOP);
     return TAC_OK;
 }
@@ -323,10 +313,8 @@ int tac_istft_envelope_f32(const float* window, const tac_stft_desc* d, int64_t 
     int64_t P = 0, valid = 0;
     const int rc = tac::istft_check(d, n_frames, &P, &valid);
     if (rc != TAC_OK) return rc;
-    hipLaunchKernelGGL(tac::istft_envelope_kernel, dim3((unsigned)tac::grid_for(P)), dim3(256), 0, (hipStream_t)stream, window,
-                       d->win_length, (d->n_fft - d->win_length) / 2, d->n_fft, d->hop, (int)n_frames, (int)P, inv_env, env);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return tac::launch_kernel(tac::istft_envelope_kernel, tac::grid_for(P), 256, 0, (hipStream_t)stream, window, d->win_length,
+                              (d->n_fft - d->win_length) / 2, d->n_fft, d->hop, (int)n_frames, (int)P, inv_env, env);
 }
 
 int tac_istft_f32(const float* spec, int64_t stride_r, int64_t stride_t, int64_t n_frames, const float* window,
@@ -378,10 +366,9 @@ int tac_istft_f32(const float* spec, int64_t stride_r, int64_t stride_t, int64_t
     const int vec4 = (d->hop % 4 == 0) && (g.center_pad % 4 == 0) && (d->n_fft % 4 == 0) &&
                      (reinterpret_cast<uintptr_t>(inv_env) & 15u) == 0;
     const long long work = d->rows * ((d->length + 3) / 4);
-    hipLaunchKernelGGL(tac::istft_ola_kernel, dim3((unsigned)tac::grid_for(work)), dim3(256), 0, s, frames, inv_env, out,
-                       (long long)d->row_stride, (long long)d->rows, (int)n_frames, d->n_fft, d->hop, g.center_pad, (int)d->length,
-                       (int)valid, vec4);
-    TAC_HIP(hipGetLastError());
+    const int ro = tac::launch_kernel(tac::istft_ola_kernel, tac::grid_for(work), 256, 0, s, frames, inv_env, out, (long long)d->row_stride,
+                                      (long long)d->rows, (int)n_frames, d->n_fft, d->hop, g.center_pad, (int)d->length, (int)valid, vec4);
+    if (ro != TAC_OK) return ro;
     tac::set_last_route("istft_general<%d>: frame kernel (inverse mode) + istft_ola_kernel<vec4=%d>", d->n_fft, vec4);
     return TAC_OK;
 }
@@ -393,20 +380,15 @@ int tac_istft_grad_input_f32(const float* grad_out, int64_t grad_stride, const f
     const int rc = tac::istft_check(d, n_frames, &P, &valid);
     if (rc != TAC_OK) return rc;
     if (grad_stride < d->length) return TAC_E_INVALID;
-    hipLaunchKernelGGL(tac::istft_grad_input_kernel, dim3((unsigned)tac::grid_for(d->rows * P)), dim3(256), 0, (hipStream_t)stream,
-                       grad_out, (long long)grad_stride, inv_env, (long long)d->rows, (int)P, d->center ? d->n_fft / 2 : 0, (int)valid,
-                       padded);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return tac::launch_kernel(tac::istft_grad_input_kernel, tac::grid_for(d->rows * P), 256, 0, (hipStream_t)stream, grad_out,
+                              (long long)grad_stride, inv_env, (long long)d->rows, (int)P, d->center ? d->n_fft / 2 : 0, (int)valid, padded);
 }
 
 int tac_istft_grad_bins_f32(float* spec, int64_t n_frames_total, int n_fft, int normalized, void* stream) {
     if (!spec || n_frames_total <= 0 || n_fft <= 0 || (n_fft & 1)) return TAC_E_INVALID;
     const float scale = (float)((normalized ? std::sqrt((double)n_fft) : 1.0) / (double)n_fft);
-    hipLaunchKernelGGL(tac::istft_grad_bins_kernel, dim3((unsigned)tac::grid_for(n_frames_total * (n_fft / 2 + 1))), dim3(256), 0,
-                       (hipStream_t)stream, spec, (long long)n_frames_total, n_fft / 2 + 1, scale);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return tac::launch_kernel(tac::istft_grad_bins_kernel, tac::grid_for(n_frames_total * (n_fft / 2 + 1)), 256, 0, (hipStream_t)stream,
+                              spec, (long long)n_frames_total, n_fft / 2 + 1, scale);
 }
 
 }  // extern "C"

@@ -273,15 +273,9 @@ static int launch_mel_budget(const FrameGeom& g, const Tables& tb, MelArgs m, co
     int per_cu = (int)(160 * 1024 / lds_bytes);
     if (per_cu > 2) per_cu = 2;
     if (per_cu < 1) per_cu = 1;
-    long long max_blocks = (long long)device_cu_count() * per_cu;
-    long long blocks = tiles < max_blocks ? tiles : max_blocks;
-    if (blocks < 1) blocks = 1;
     const bool pow2 = (m.power == 2.0f);
-    auto kern = pow2 ? melspec_kernel<NC, E, TILE, BUDGET, true> : melspec_kernel<NC, E, TILE, BUDGET, false>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::WAVES * 64), lds_bytes, stream, g, tb, m, plan);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(pow2 ? melspec_kernel<NC, E, TILE, BUDGET, true> : melspec_kernel<NC, E, TILE, BUDGET, false>,
+                         persistent_blocks(tiles, 1, (long long)device_cu_count() * per_cu), C::WAVES * 64, lds_bytes, stream, g, tb, m, plan);
 }
 
 // Register budget: the weights of a wave's share stay in VGPRs for the whole kernel, so the capacity is compiled
@@ -342,8 +336,8 @@ int tac_filterbank_plan(const float* fb, int32_t n_freqs, int32_t n_mels, int32_
     using namespace tac;
     if (!fb || !plan || n_freqs <= 0 || n_mels <= 0) return TAC_E_INVALID;
     const int nt = (n_mels + 15) / 16;
-    hipLaunchKernelGGL(fb_plan_kernel, dim3(nt), dim3(256), 0, (hipStream_t)stream, fb, n_freqs, n_mels, plan);
-    TAC_HIP(hipGetLastError());
+    const int rc = launch_kernel(fb_plan_kernel, nt, 256, 0, (hipStream_t)stream, fb, n_freqs, n_mels, plan);
+    if (rc != TAC_OK) return rc;
     if (plan_host) {
         TAC_HIP(hipMemcpyAsync(plan_host, plan, sizeof(int32_t) * 2 * nt, hipMemcpyDeviceToHost, (hipStream_t)stream));
         TAC_HIP(hipStreamSynchronize((hipStream_t)stream));

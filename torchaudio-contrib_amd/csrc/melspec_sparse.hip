@@ -346,15 +346,9 @@ static int launch_sparse(const FrameGeom& g, const Tables& tb, const SparseArgs&
     int per_cu = (int)(160 * 1024 / lds_bytes);
     if (per_cu > 2) per_cu = 2;
     if (per_cu < 1) per_cu = 1;
-    long long max_blocks = (long long)device_cu_count() * per_cu;
-    long long blocks = tiles < max_blocks ? tiles : max_blocks;
-    if (blocks < 1) blocks = 1;
     const bool pow2 = (power == 2.0f);
-    auto kern = pow2 ? melspec_sparse_kernel<NC, E, true> : melspec_sparse_kernel<NC, E, false>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(C::WAVES * 64), lds_bytes, stream, g, tb, m);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(pow2 ? melspec_sparse_kernel<NC, E, true> : melspec_sparse_kernel<NC, E, false>,
+                         persistent_blocks(tiles, 1, (long long)device_cu_count() * per_cu), C::WAVES * 64, lds_bytes, stream, g, tb, m);
 }
 
 // fft_length 2048: the barrier-free streaming kernel (melspec_stream.hpp), one persistent workgroup per CU.
@@ -367,16 +361,9 @@ static int launch_stream(FrameGeom g, const Tables& tb, const SparseArgs& sm, co
     if (g.length < 2 * NC) return TAC_E_UNSUPPORTED;                       // (its clamped sample requests need a whole frame)
     const size_t lds_bytes = stream_lds_bytes<NC, E>(sm.wtot);
     if (info_host[1] < 1 || info_host[1] > ST_MAX_SLOTS) return TAC_E_UNSUPPORTED;
-    if (FMT != FMT_F32) {                                                  // sample pairs fetched as one access of the format
-        const uintptr_t pair = FMT == FMT_I16 ? 4 : (FMT == FMT_MULAW_U8 ? 2 : 8);
-        g.vec2_ok = ((g.hop & 1) == 0) && ((g.center_pad & 1) == 0) && ((g.row_stride & 1) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(samples) & (pair - 1)) == 0);
-    }
+    if (FMT != FMT_F32) g.vec2_ok = coded_pairs_aligned(g, samples, FMT);
     StreamArgs m{sm.wpack, sm.desc, info_host[1], {info_host[4], info_host[5], info_host[6], info_host[7]}, sm.wtot,
                  sm.n_mels, sm.db, sm.amin, sm.log10_ref, sm.out, total, samples, lut, 0, nullptr, (info_host[2] & ST_REV_MARK) ? 1 : 0};
-    long long blocks = (total + 2 * ST_WAVES - 1) / (2 * ST_WAVES);
-    if (blocks > device_cu_count()) blocks = device_cu_count();
-    if (blocks < 1) blocks = 1;
     const bool pow2 = (power == 2.0f);
     // the band predicate of the row stores is compiled out for whole slots of 64 bands (float32 input only: the coded
     // formats keep one instantiation per power)
@@ -402,15 +389,11 @@ static int launch_stream(FrameGeom g, const Tables& tb, const SparseArgs& sm, co
             if (fast2 && fshort) km = pow2 ? melspec_mfma_kernel<true, ST_FAST_STEPS1_SHORT, WM> : melspec_mfma_kernel<false, ST_FAST_STEPS1_SHORT, WM>;
             else if (fast2) km = pow2 ? melspec_mfma_kernel<true, ST_FAST_STEPS1, WM> : melspec_mfma_kernel<false, ST_FAST_STEPS1, WM>;
             else km = pow2 ? melspec_mfma_kernel<true, 0, WM> : melspec_mfma_kernel<false, 0, WM>;
-            long long bm = (total + WM - 1) / WM;
-            if (bm > device_cu_count()) bm = device_cu_count();
+            const long long bm = persistent_blocks(total, WM, device_cu_count());
             m.chunk = (total + bm - 1) / bm;
             m.probe = (g_clock_probe && g_clock_probe_pairs >= bm) ? g_clock_probe : nullptr;
             set_last_route("melspec_mfma_kernel<%s, %d, %d>", pow2 ? "true" : "false", fast2 ? (fshort ? ST_FAST_STEPS1_SHORT : ST_FAST_STEPS1) : 0, WM);
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(km), 160 * 1024));
-            hipLaunchKernelGGL(km, dim3((unsigned)bm), dim3(WM * 64), ldsm, stream, g, tb, m);
-            TAC_HIP(hipGetLastError());
-            return TAC_OK;
+            return launch_kernel(km, bm, WM * 64, ldsm, stream, g, tb, m);
         }
     }
     const size_t lds3 = stream3_lds_bytes<NC, E>(sm.wtot, waves3, coded) + ((FMT == FMT_F32 && fast2) ? S3_TW2L_BYTES : 0);   // (FAST1 kernels: + their pass-2 twiddle table)
@@ -426,18 +409,14 @@ static int launch_stream(FrameGeom g, const Tables& tb, const SparseArgs& sm, co
         } else {
             k3 = pow2 ? melspec_stream3_kernel<NC, E, true, FMT, 0, S3_WAVES> : melspec_stream3_kernel<NC, E, false, FMT, 0, S3_WAVES>;
         }
-        long long b3 = (total + waves3 - 1) / waves3;
-        if (b3 > device_cu_count()) b3 = device_cu_count();
+        const long long b3 = persistent_blocks(total, waves3, device_cu_count());
         m.chunk = (total + b3 - 1) / b3;
         m.probe = (g_clock_probe && g_clock_probe_pairs >= b3) ? g_clock_probe : nullptr;
         {
             const int fast1 = (FMT == FMT_F32 && fast2) ? (fshort ? ST_FAST_STEPS1_SHORT : ST_FAST_STEPS1) : 0;
             set_last_route("melspec_stream3_kernel<%d, %d, %s, %d, %d, %d>", NC, E, pow2 ? "true" : "false", FMT, fast1, waves3);
         }
-        TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(k3), 160 * 1024));
-        hipLaunchKernelGGL(k3, dim3((unsigned)b3), dim3(waves3 * 64), lds3, stream, g, tb, m);
-        TAC_HIP(hipGetLastError());
-        return TAC_OK;
+        return launch_kernel(k3, b3, waves3 * 64, lds3, stream, g, tb, m);
     }
     void (*kern)(FrameGeom, Tables, StreamArgs);
     if constexpr (FMT == FMT_F32) {
@@ -452,10 +431,7 @@ static int launch_stream(FrameGeom g, const Tables& tb, const SparseArgs& sm, co
         kern = pow2 ? melspec_stream_kernel<NC, E, true, false, FMT, 0> : melspec_stream_kernel<NC, E, false, false, FMT, 0>;
     }
     if (lds_bytes > 160 * 1024) return TAC_E_UNSUPPORTED;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(ST_WAVES * 64), lds_bytes, stream, g, tb, m);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(kern, persistent_blocks(total, 2 * ST_WAVES, device_cu_count()), ST_WAVES * 64, lds_bytes, stream, g, tb, m);
 }
 
 // ---------------------------------------------------------------- standalone band-sparse filterbank, wave-autonomous form
@@ -549,14 +525,8 @@ static int launch_fb_lanes(const float* spec, long long rows, int n_freqs, long 
     if (bytes > 160 * 1024) return TAC_E_UNSUPPORTED;
     const long long total = rows * n_frames;
     if (total >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
-    long long blocks = (total + FBL_WAVES - 1) / FBL_WAVES;
-    if (blocks > device_cu_count()) blocks = device_cu_count();
-    auto kern = fb_lanes_kernel<S, CHUNKS, FBL_WAVES, FBL_FLY>;
-    if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(FBL_WAVES * 64), bytes, stream, spec, rows, n_freqs, n_frames, stride_r,
-                       stride_t, mel);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(fb_lanes_kernel<S, CHUNKS, FBL_WAVES, FBL_FLY>, persistent_blocks(total, FBL_WAVES, device_cu_count()),
+                         FBL_WAVES * 64, bytes, stream, spec, rows, n_freqs, n_frames, stride_r, stride_t, mel);
 }
 
 // Lane layout of the streaming kernel: cell c = 64 s + l (slot s, lane l) holds band c — or, for banks whose band count is not a
@@ -889,14 +859,9 @@ int tac_apply_filterbank_sparse_db_f32(const float* spec, int64_t rows, int32_t 
     if (tiles >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     int per_cu = (int)(160 * 1024 / lds_bytes);
     if (per_cu > 2) per_cu = 2;
-    long long blocks = (long long)device_cu_count() * per_cu;
-    if (blocks > tiles) blocks = tiles;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(fb_sparse_kernel), 160 * 1024));
-    hipLaunchKernelGGL(fb_sparse_kernel, dim3((unsigned)blocks), dim3(FBS_WAVES * 64), lds_bytes, (hipStream_t)stream, spec,
-                       (long long)rows, (int)n_freqs, (long long)n_frames, (long long)stride_r, (long long)stride_t, prow,
-                       m);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(fb_sparse_kernel, persistent_blocks(tiles, 1, (long long)device_cu_count() * per_cu), FBS_WAVES * 64, lds_bytes,
+                         (hipStream_t)stream, spec, (long long)rows, (int)n_freqs, (long long)n_frames, (long long)stride_r,
+                         (long long)stride_t, prow, m);
 }
 
 }  // extern "C"

@@ -275,11 +275,9 @@ static int launch_phase_vocoder(const T* spec, int64_t rows, int32_t n_freqs, in
     if (n_frames >= 0x7fffffffLL || n_out >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     const long long blocks = (rows * (long long)n_freqs + PV_THREADS - 1) / PV_THREADS;
     if (blocks >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
-    hipLaunchKernelGGL(phase_vocoder_kernel<T>, dim3((unsigned)blocks), dim3(PV_THREADS), 0, (hipStream_t)stream, spec,
-                       (long long)rows, (int)n_freqs, (int)n_frames, (long long)stride_r, (long long)stride_f,
-                       (long long)stride_t, phase_advance, idx0, idx1, alpha, (int)n_out, out);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(phase_vocoder_kernel<T>, blocks, PV_THREADS, 0, (hipStream_t)stream, spec, (long long)rows, (int)n_freqs,
+                         (int)n_frames, (long long)stride_r, (long long)stride_f, (long long)stride_t, phase_advance, idx0, idx1, alpha,
+                         (int)n_out, out);
 }
 
 }  // namespace tac
@@ -303,11 +301,9 @@ int tac_phase_vocoder_backward_f32(const float* spec, int64_t rows, int32_t n_fr
     if (n_frames >= 0x7fffffffLL || n_out >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     const long long blocks = (rows * (long long)n_freqs + PV_THREADS - 1) / PV_THREADS;
     if (blocks >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
-    hipLaunchKernelGGL(phase_vocoder_backward_kernel, dim3((unsigned)blocks), dim3(PV_THREADS), 0, (hipStream_t)stream, spec,
-                       (long long)rows, (int)n_freqs, (int)n_frames, (long long)stride_r, (long long)stride_f, (long long)stride_t,
-                       idx0, idx1, alpha, (int)n_out, grad_out, grad_spec);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(phase_vocoder_backward_kernel, blocks, PV_THREADS, 0, (hipStream_t)stream, spec, (long long)rows, (int)n_freqs,
+                         (int)n_frames, (long long)stride_r, (long long)stride_f, (long long)stride_t, idx0, idx1, alpha, (int)n_out,
+                         grad_out, grad_spec);
 }
 
 int tac_phase_vocoder_f64(const double* spec, int64_t rows, int32_t n_freqs, int64_t n_frames, int64_t stride_r,

@@ -195,13 +195,11 @@ static int launch_big(const FrameGeom& g, const StftEpilogue& ep, hipStream_t st
     const long long units = g.rows * g.n_frames;
     const int bytes = S * BIG_WS * (int)sizeof(cf);
     constexpr int WAVES = S == 16 ? 8 : S;      // (S = 8 as two 4-wave workgroups per CU: +28 %, tools/ablation/README.md)
-    long long blocks = (long long)device_cu_count() * (8 / WAVES);     // eight waves per CU: the twiddles need 256 registers
-    if (blocks > units) blocks = units;
+    // eight waves per CU: the twiddles need 256 registers
+    const long long blocks = persistent_blocks(units, 1, (long long)device_cu_count() * (8 / WAVES));
     const int win_vec4 = g.win_length == 2048 * S && (reinterpret_cast<uintptr_t>(g.window) & 15u) == 0;
-    auto kern = stft_big_kernel<S, MODE, WAVES>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * WAVES), bytes, stream, g, tb1k, tbn, ep, win_vec4);
-    TAC_HIP(hipGetLastError());
+    rc = launch_kernel(stft_big_kernel<S, MODE, WAVES>, blocks, 64 * WAVES, bytes, stream, g, tb1k, tbn, ep, win_vec4);
+    if (rc != TAC_OK) return rc;
     set_last_route("stft_big_kernel<%d, %d, %d>", S, MODE, WAVES);
     return TAC_OK;
 }

@@ -437,14 +437,8 @@ static int launch_pipe(const FrameGeom& g, const Tables& tb, const StftEpilogue&
     using F = WaveFft<NC, E>;
     constexpr int WAVES = PIPE_WAVES;
     const size_t bytes = (size_t)WAVES * (((F::PADDED + 1) / 2) * 2) * sizeof(cf) + (size_t)64 * (E + 2) * sizeof(cf) + 16;
-    long long blocks = (groups + WAVES - 1) / WAVES;
-    const long long cap = (long long)device_cu_count() * (8 / WAVES);
-    if (blocks > cap) blocks = cap;
-    auto kern = stft_pipe_kernel<NC, E, PMODE, WAVES>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), bytes, stream, g, tb, ep);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    const long long blocks = persistent_blocks(groups, WAVES, (long long)device_cu_count() * (8 / WAVES));
+    return launch_kernel(stft_pipe_kernel<NC, E, PMODE, WAVES>, blocks, WAVES * 64, bytes, stream, g, tb, ep);
 }
 
 // three waves per SIMD (stft_stream3.hpp); TAC_STFT_PIPE2=1 keeps the two-wave pipelined kernel above
@@ -466,14 +460,9 @@ static int launch_pipe3(const FrameGeom& g, const Tables& tb, const StftEpilogue
     const long long frames_total = g.rows * g.n_frames;
     const int plain = forced >= 0 ? forced : 0;
     auto go = [&](auto kern, int W, size_t bytes) {
-        long long blocks = (groups + W - 1) / W;
-        if (blocks > device_cu_count()) blocks = device_cu_count();
-        if (blocks < 1) blocks = 1;
+        const long long blocks = persistent_blocks(groups, W, device_cu_count());
         const Stream3Launch lp{(frames_total + blocks - 1) / blocks, plain};
-        TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(W * 64), bytes, stream, g, tb, ep, lp);
-        TAC_HIP(hipGetLastError());
-        return (int)TAC_OK;
+        return launch_kernel(kern, blocks, W * 64, bytes, stream, g, tb, ep, lp);
     };
     {
         // Round 5: the samples through the LDS hop ring (stft_ring3.hpp) — every hop loaded ONCE per CU by a loader wave (LDS-DMA,
@@ -486,16 +475,10 @@ static int launch_pipe3(const FrameGeom& g, const Tables& tb, const StftEpilogue
         auto ring = [&](auto hpf_tag) {
             constexpr int HPF = decltype(hpf_tag)::value;
             using RC = Ring3Cfg<NC, E, PMODE, TWv, HPF>;
-            long long blocks = (groups + TWv - 1) / TWv;
-            if (blocks > device_cu_count()) blocks = device_cu_count();
-            if (blocks < 1) blocks = 1;
+            const long long blocks = persistent_blocks(groups, TWv, device_cu_count());
             const Stream3Launch lp{(frames_total + blocks - 1) / blocks, plain};
-            auto kern = stft_ring3_kernel<NC, E, PMODE, TWv, HPF>;
             set_last_route("stft_ring3_kernel<%d, %d, %d, %d, %d>", NC, E, PMODE, TWv, HPF);
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), RC::BYTES));
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((TWv + 1) * 64), RC::BYTES, stream, g, tb, ep, lp);
-            TAC_HIP(hipGetLastError());
-            return (int)TAC_OK;
+            return launch_kernel(stft_ring3_kernel<NC, E, PMODE, TWv, HPF>, blocks, (TWv + 1) * 64, RC::BYTES, stream, g, tb, ep, lp);
         };
         const int hpf = g.hop > 0 && (2 * NC) % g.hop == 0 ? 2 * NC / g.hop : 0;
         if (!off && !waves_env && (hpf == 4 || hpf == 8) && g.vec4_ok && (g.center_pad % g.hop) == 0 &&
@@ -520,13 +503,7 @@ static int launch_stft(const FrameGeom& g, const Tables& tb, const StftEpilogue&
     if (groups >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     if constexpr (F::G == 1 && E == 16) {
         // pipelined kernel: one-sided complex rows, or |X| / |X|^2 rows with or without the dB epilogue
-        int pmode = -1;
-        if (ep.onesided) {
-            if (MODE == 0) pmode = 0;
-            else if (ep.power == 2.0f) pmode = ep.db ? 3 : 1;
-            else if (ep.power == 1.0f) pmode = ep.db ? 4 : 2;
-        }
-        switch (pmode) {
+        switch (row_pmode(ep, MODE)) {
             case 0: return launch_pipe3<NC, E, 0>(g, tb, ep, groups, stream);
             case 1: return launch_pipe3<NC, E, 1>(g, tb, ep, groups, stream);
             case 2: return launch_pipe3<NC, E, 2>(g, tb, ep, groups, stream);
@@ -545,20 +522,11 @@ static int launch_stft(const FrameGeom& g, const Tables& tb, const StftEpilogue&
     int per_cu = wide ? 1 : (int)(160 * 1024 / lds_bytes);
     if (per_cu > 2) per_cu = 2;
     if (per_cu < 1) per_cu = 1;
-    long long max_blocks = (long long)device_cu_count() * per_cu;
-    long long want = (groups + waves - 1) / waves;
-    long long blocks = want < max_blocks ? want : max_blocks;
-    if (blocks < 1) blocks = 1;
-    auto launch = [&](auto kern) {
-        if (lds_bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(waves * 64), lds_bytes, stream, g, tb, ep);
-        TAC_HIP(hipGetLastError());
-        return (int)TAC_OK;
-    };
+    const long long blocks = persistent_blocks(groups, waves, (long long)device_cu_count() * per_cu);
     if constexpr (WIDE_FITS) {
-        if (wide) return launch(stft_kernel<NC, E, MODE, NF, HOIST, 2 * STFT_WAVES>);
+        if (wide) return launch_kernel(stft_kernel<NC, E, MODE, NF, HOIST, 2 * STFT_WAVES>, blocks, waves * 64, lds_bytes, stream, g, tb, ep);
     }
-    return launch(stft_kernel<NC, E, MODE, NF, HOIST, STFT_WAVES>);
+    return launch_kernel(stft_kernel<NC, E, MODE, NF, HOIST, STFT_WAVES>, blocks, waves * 64, lds_bytes, stream, g, tb, ep);
 }
 
 int try_launch_n4096(const FrameGeom& g, const StftEpilogue& ep, int mode, hipStream_t stream);

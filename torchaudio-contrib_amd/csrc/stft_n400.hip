@@ -387,15 +387,9 @@ static int launch_n400(const FrameGeom& g, const Q4Tables& tb, const StftEpilogu
     const long long units = g.rows * ((g.n_frames + Q4_G - 1) / Q4_G);
     if (units >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     const size_t bytes = q4_lds_bytes(0);
-    long long blocks = (units + Q4_WAVES - 1) / Q4_WAVES;
-    const long long cap = (long long)device_cu_count();
-    if (blocks > cap) blocks = cap;
     // (the twelve-wave form, stft_n400_s3.hpp, serves the fused mel chain only: on these store-bound rows it measured 0-4 % slower)
-    auto kern = stft_n400_kernel<MODE, false, 1>;
-    if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Q4_WAVES * 64), bytes, stream, g, tb, ep, LaneMel{});
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(stft_n400_kernel<MODE, false, 1>, persistent_blocks(units, Q4_WAVES, device_cu_count()), Q4_WAVES * 64, bytes,
+                         stream, g, tb, ep, LaneMel{});
 }
 
 template <int MODE, int S>
@@ -404,29 +398,16 @@ static int launch_n400_mel_mode(const FrameGeom& g, const Q4Tables& tb, const La
     if (units >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     const size_t bytes = q4_lds_bytes(0) + lm_lds_bytes(8, mel.wtot);
     if (bytes > 160 * 1024) return TAC_E_UNSUPPORTED;
-    long long blocks = (units + Q4_WAVES - 1) / Q4_WAVES;
-    const long long cap = (long long)device_cu_count();
-    if (blocks > cap) blocks = cap;
+    const long long cap = device_cu_count();
+    const StftEpilogue ep{nullptr, 1, 1, MODE == 1 ? 2.0f : 1.0f, 0, 0.0f, 0.0f};
     if (q4_three_waves() && g.length >= 400) {
         const size_t b3 = q4s3_lds_bytes(MODE, true) + lm_lds_bytes(8, mel.wtot);
-        if (b3 <= 160 * 1024) {
-            long long bl = (units + Q4S3_WAVES - 1) / Q4S3_WAVES;
-            if (bl > cap) bl = cap;
-            auto k3 = stft_n400_s3_kernel<MODE, true, S>;
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(k3), (int)b3));
-            hipLaunchKernelGGL(k3, dim3((unsigned)bl), dim3(Q4S3_WAVES * 64), b3, stream, g, tb,
-                               StftEpilogue{nullptr, 1, 1, MODE == 1 ? 2.0f : 1.0f, 0, 0.0f, 0.0f}, mel, (const void*)nullptr,
-                               (const float*)nullptr);
-            TAC_HIP(hipGetLastError());
-            return TAC_OK;
-        }
+        if (b3 <= 160 * 1024)
+            return launch_kernel(stft_n400_s3_kernel<MODE, true, S>, persistent_blocks(units, Q4S3_WAVES, cap), Q4S3_WAVES * 64, b3,
+                                 stream, g, tb, ep, mel, (const void*)nullptr, (const float*)nullptr);
     }
-    auto kern = stft_n400_kernel<MODE, true, S>;
-    if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Q4_WAVES * 64), bytes, stream, g, tb,
-                       StftEpilogue{nullptr, 1, 1, MODE == 1 ? 2.0f : 1.0f, 0, 0.0f, 0.0f}, mel);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(stft_n400_kernel<MODE, true, S>, persistent_blocks(units, Q4_WAVES, cap), Q4_WAVES * 64, bytes, stream, g, tb,
+                         ep, mel);
 }
 
 // int16 PCM / mu-law codes read by the fused kernel itself (power 2, twelve-wave kernel only)
@@ -437,19 +418,9 @@ static int launch_n400_mel_coded(FrameGeom g, const Q4Tables& tb, const LaneMel&
     if (units >= 0x7fffffffLL || !q4_three_waves() || g.length < 400) return TAC_E_UNSUPPORTED;
     const size_t b3 = q4s3_lds_bytes(1, true) + lm_lds_bytes(8, mel.wtot) + 1024;
     if (b3 > 160 * 1024) return TAC_E_UNSUPPORTED;
-    {                                                                      // sample pairs fetched as one access of the format
-        const uintptr_t pair = FMT == FMT_I16 ? 4 : (FMT == FMT_MULAW_U8 ? 2 : 8);
-        g.vec2_ok = ((g.hop & 1) == 0) && ((g.center_pad & 1) == 0) && ((g.row_stride & 1) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(samples) & (pair - 1)) == 0);
-    }
-    long long bl = (units + Q4S3_WAVES - 1) / Q4S3_WAVES;
-    if (bl > device_cu_count()) bl = device_cu_count();
-    auto k3 = stft_n400_s3_kernel<1, true, S, FMT>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(k3), (int)b3));
-    hipLaunchKernelGGL(k3, dim3((unsigned)bl), dim3(Q4S3_WAVES * 64), b3, stream, g, tb, StftEpilogue{nullptr, 1, 1, 2.0f, 0, 0.0f, 0.0f},
-                       mel, samples, lut);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    g.vec2_ok = coded_pairs_aligned(g, samples, FMT);
+    return launch_kernel(stft_n400_s3_kernel<1, true, S, FMT>, persistent_blocks(units, Q4S3_WAVES, device_cu_count()), Q4S3_WAVES * 64,
+                         b3, stream, g, tb, StftEpilogue{nullptr, 1, 1, 2.0f, 0, 0.0f, 0.0f}, mel, samples, lut);
 }
 
 template <int FMT>
@@ -829,9 +800,6 @@ int launch_n400_backward(const FrameGeom& g, const float* gspec, const float* gn
     if (adj && (!from_wave || n_mels < 1 || n_mels > 128)) return TAC_E_UNSUPPORTED;
     const size_t bytes = q4_lds_bytes(0) + (size_t)16 * Q4_ROW * sizeof(cf) +
                          (adj ? (size_t)Q4_BINS * sizeof(AdjEntry) + (size_t)Q4_WAVES * Q4_G * 128 * sizeof(float) : 0);
-    long long blocks = (units + Q4_WAVES - 1) / Q4_WAVES;
-    const long long cap = (long long)device_cu_count();
-    if (blocks > cap) blocks = cap;
     void (*kern)(FrameGeom, Q4Tables, const float*, const float*, float, float*, const AdjEntry*, int, float*, float*, OlaPlan);
     if (from_wave && plan) {
         if (!gnorm) return TAC_E_INVALID;
@@ -843,21 +811,14 @@ int launch_n400_backward(const FrameGeom& g, const float* gspec, const float* gn
         else kern = power == 2.0f ? stft_n400_backward_kernel<SRC_WAVE, true> : stft_n400_backward_kernel<SRC_WAVE, false>;
     } else if (!gnorm) kern = inverse ? stft_n400_backward_kernel<SRC_INV, false> : stft_n400_backward_kernel<SRC_GRAD, false>;
     else kern = power == 2.0f ? stft_n400_backward_kernel<SRC_NORM, true> : stft_n400_backward_kernel<SRC_NORM, false>;
-    if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(Q4_WAVES * 64), bytes, stream, g, tb, gspec, gnorm, power, frames, adj,
-                       n_mels, gpad, edge, plan ? *plan : OlaPlan{});
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(kern, persistent_blocks(units, Q4_WAVES, device_cu_count()), Q4_WAVES * 64, bytes, stream, g, tb, gspec, gnorm,
+                         power, frames, adj, n_mels, gpad, edge, plan ? *plan : OlaPlan{});
 }
 
 // Entry used by stft_kernels.hip's dispatcher: TAC_E_UNSUPPORTED when this form does not apply (two-sided output,
 // |X|^p with p outside {1, 2}); the caller then evaluates the DFT as a matrix product.
 int try_launch_n400(const FrameGeom& g, const StftEpilogue& ep, int mode, hipStream_t stream) {
-    if (!ep.onesided) return TAC_E_UNSUPPORTED;
-    int pmode = -1;
-    if (mode == 0) pmode = 0;
-    else if (ep.power == 2.0f) pmode = ep.db ? 3 : 1;
-    else if (ep.power == 1.0f) pmode = ep.db ? 4 : 2;
+    const int pmode = row_pmode(ep, mode);
     if (pmode < 0) return TAC_E_UNSUPPORTED;
     Q4Tables tb;
     const int rc = q4_tables(&tb);

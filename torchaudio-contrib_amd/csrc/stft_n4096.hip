@@ -285,14 +285,8 @@ static int launch_n4096_s3(const FrameGeom& g, const Tables& tb2k, const Tables&
     if (units >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     const size_t bytes = n4096_s3_lds_bytes(WAVES) + (MEL ? n4096_mel_lds_bytes(mel.rounds, mel.np, mel.wtot) : 0) + (TBL ? N4S_ROW_TABLE_BYTES : 0);
     if (bytes > 160 * 1024) return TAC_E_UNSUPPORTED;
-    long long blocks = (units + WAVES - 1) / WAVES;
-    const long long cap = (long long)device_cu_count();      // one workgroup per CU
-    if (blocks > cap) blocks = cap;
-    auto kern = stft_n4096_s3_kernel<MODE, WAVES, MEL, TBL>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), bytes, stream, g, tb2k, tb4k, ep, mel);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    const long long blocks = persistent_blocks(units, WAVES, device_cu_count());      // one workgroup per CU
+    return launch_kernel(stft_n4096_s3_kernel<MODE, WAVES, MEL, TBL>, blocks, WAVES * 64, bytes, stream, g, tb2k, tb4k, ep, mel);
 }
 
 // ---- the filterbank table of the fused form (tac_melbank_pack, n_fft == 4096; layout: stft_n4096_s3.hpp).  A band's run of quads
@@ -480,25 +474,15 @@ static int launch_n4096(const FrameGeom& g, const Tables& tb1k, const Tables& tb
     if (units >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     constexpr int WS = ((F::PADDED + 1) / 2) * 2;
     const size_t bytes = (size_t)N4K_WAVES * 2 * WS * sizeof(cf) + (size_t)64 * 17 * sizeof(f4) + 16;
-    long long blocks = (units + N4K_WAVES - 1) / N4K_WAVES;
-    const long long cap = (long long)device_cu_count();      // one 8-wave workgroup per CU (157 KB of LDS)
-    if (blocks > cap) blocks = cap;
-    auto kern = stft_n4096_kernel<MODE>;
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(N4K_WAVES * 64), bytes, stream, g, tb1k, tb4k, ep);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    const long long blocks = persistent_blocks(units, N4K_WAVES, device_cu_count());      // one 8-wave workgroup per CU (157 KB of LDS)
+    return launch_kernel(stft_n4096_kernel<MODE>, blocks, N4K_WAVES * 64, bytes, stream, g, tb1k, tb4k, ep);
 }
 
 // Entry used by stft_kernels.hip's dispatcher: returns TAC_E_UNSUPPORTED when this form does not apply (two-sided
 // output, |X|^p with p outside {1, 2}, frames that are not 16-byte aligned) so that the generic kernel takes over.
 int try_launch_n4096(const FrameGeom& g, const StftEpilogue& ep, int mode, hipStream_t stream) {
-    if (!ep.onesided || !g.vec4_ok) return TAC_E_UNSUPPORTED;
-    int pmode = -1;
-    if (mode == 0) pmode = 0;
-    else if (ep.power == 2.0f) pmode = ep.db ? 3 : 1;
-    else if (ep.power == 1.0f) pmode = ep.db ? 4 : 2;
-    if (pmode < 0) return TAC_E_UNSUPPORTED;
+    const int pmode = row_pmode(ep, mode);
+    if (pmode < 0 || !g.vec4_ok) return TAC_E_UNSUPPORTED;
     Tables tb1k, tb4k;
     int rc = get_tables(2048, &tb1k);
     if (rc != TAC_OK) return rc;

@@ -222,20 +222,12 @@ static int launch_small(const FrameGeom& g, const Tables& tb, const StftEpilogue
     if (units >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     constexpr int WAVE_SLOTS = ((F::G * F::PADDED + 1) / 2) * 2;
     const size_t bytes = (size_t)SM_WAVES * WAVE_SLOTS * sizeof(cf) + (size_t)F::LPF * 18 * sizeof(cf) + 16;
-    long long blocks = (units + SM_WAVES - 1) / SM_WAVES;
-    const long long cap = (long long)device_cu_count();
-    if (blocks > cap) blocks = cap;
+    const long long cap = device_cu_count();
     if (small3_waves()) {
         // three / four waves per SIMD (stft_small3.hpp); TAC_SMALL2=1 keeps the two-wave kernel below
-        auto go = [&](auto k3, int W) -> int {
-            const size_t b3 = small3_lds_bytes<NC>(W);
-            long long bl = (units + W - 1) / W;
-            if (bl > cap) bl = cap;
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(k3), (int)b3));
-            hipLaunchKernelGGL(k3, dim3((unsigned)bl), dim3(W * 64), b3, stream, g, tb, ep, LaneMel{}, (const void*)nullptr,
-                               (const float*)nullptr);
-            TAC_HIP(hipGetLastError());
-            return TAC_OK;
+        auto go = [&](auto k3, int W) {
+            return launch_kernel(k3, persistent_blocks(units, W, cap), W * 64, small3_lds_bytes<NC>(W), stream, g, tb, ep, LaneMel{},
+                                 (const void*)nullptr, (const float*)nullptr);
         };
         // complex rows are bound by their stores (12 waves measure like the two-wave kernel, 16 slower); real rows gain 8-10 %
         // from the fourth wave per SIMD (profiles/r03/ab_stream3.txt)
@@ -246,11 +238,8 @@ static int launch_small(const FrameGeom& g, const Tables& tb, const StftEpilogue
     if constexpr (NC < 256) {
         return TAC_E_UNSUPPORTED;                            // fft_length 256 has no two-wave form: the generic kernel
     } else {
-        auto kern = stft_small_kernel<NC, MODE, false, 1>;
-        if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(SM_WAVES * 64), bytes, stream, g, tb, ep, LaneMel{});
-        TAC_HIP(hipGetLastError());
-        return TAC_OK;
+        return launch_kernel(stft_small_kernel<NC, MODE, false, 1>, persistent_blocks(units, SM_WAVES, cap), SM_WAVES * 64, bytes,
+                             stream, g, tb, ep, LaneMel{});
     }
 }
 
@@ -268,32 +257,19 @@ static int launch_small_mel(const FrameGeom& g, const Tables& tb, const LaneMel&
     if (units >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
     const size_t bytes = small_lds_bytes<NC>() + lm_lds_bytes(F::LPF, mel.wtot);
     if (bytes > 160 * 1024) return TAC_E_UNSUPPORTED;
-    long long blocks = (units + SM_WAVES - 1) / SM_WAVES;
-    const long long cap = (long long)device_cu_count();
-    if (blocks > cap) blocks = cap;
+    const long long cap = device_cu_count();
+    const StftEpilogue ep{nullptr, 1, 1, MODE == 1 ? 2.0f : 1.0f, 0, 0.0f, 0.0f};
     if (small3_waves()) {
         const size_t b3 = small3_lds_bytes<NC>(12) + lm_lds_bytes(F::LPF, mel.wtot);
-        if (b3 <= 160 * 1024) {
-            auto k3 = stft_small3_kernel<NC, MODE, true, S, 12>;
-            long long bl = (units + 12 - 1) / 12;
-            if (bl > cap) bl = cap;
-            TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(k3), (int)b3));
-            hipLaunchKernelGGL(k3, dim3((unsigned)bl), dim3(12 * 64), b3, stream, g, tb,
-                               StftEpilogue{nullptr, 1, 1, MODE == 1 ? 2.0f : 1.0f, 0, 0.0f, 0.0f}, mel, (const void*)nullptr,
-                               (const float*)nullptr);
-            TAC_HIP(hipGetLastError());
-            return TAC_OK;
-        }
+        if (b3 <= 160 * 1024)
+            return launch_kernel(stft_small3_kernel<NC, MODE, true, S, 12>, persistent_blocks(units, 12, cap), 12 * 64, b3, stream, g,
+                                 tb, ep, mel, (const void*)nullptr, (const float*)nullptr);
     }
     if constexpr (NC < 256) {
         return TAC_E_UNSUPPORTED;
     } else {
-        auto kern = stft_small_kernel<NC, MODE, true, S>;
-        if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(SM_WAVES * 64), bytes, stream, g, tb,
-                           StftEpilogue{nullptr, 1, 1, MODE == 1 ? 2.0f : 1.0f, 0, 0.0f, 0.0f}, mel);
-        TAC_HIP(hipGetLastError());
-        return TAC_OK;
+        return launch_kernel(stft_small_kernel<NC, MODE, true, S>, persistent_blocks(units, SM_WAVES, cap), SM_WAVES * 64, bytes,
+                             stream, g, tb, ep, mel);
     }
 }
 
@@ -306,19 +282,9 @@ static int launch_small_mel_coded(FrameGeom g, const Tables& tb, const LaneMel& 
     if (units >= 0x7fffffffLL || !small3_waves()) return TAC_E_UNSUPPORTED;
     const size_t b3 = small3_lds_bytes<NC>(12) + lm_lds_bytes(F::LPF, mel.wtot) + 1024;
     if (b3 > 160 * 1024) return TAC_E_UNSUPPORTED;
-    {                                                                      // sample pairs fetched as one access of the format
-        const uintptr_t pair = FMT == FMT_I16 ? 4 : (FMT == FMT_MULAW_U8 ? 2 : 8);
-        g.vec2_ok = ((g.hop & 1) == 0) && ((g.center_pad & 1) == 0) && ((g.row_stride & 1) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(samples) & (pair - 1)) == 0);
-    }
-    auto k3 = stft_small3_kernel<NC, 1, true, S, 12, FMT>;
-    long long bl = (units + 12 - 1) / 12;
-    if (bl > device_cu_count()) bl = device_cu_count();
-    TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(k3), (int)b3));
-    hipLaunchKernelGGL(k3, dim3((unsigned)bl), dim3(12 * 64), b3, stream, g, tb, StftEpilogue{nullptr, 1, 1, 2.0f, 0, 0.0f, 0.0f}, mel,
-                       samples, lut);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    g.vec2_ok = coded_pairs_aligned(g, samples, FMT);
+    return launch_kernel(stft_small3_kernel<NC, 1, true, S, 12, FMT>, persistent_blocks(units, 12, device_cu_count()), 12 * 64, b3,
+                         stream, g, tb, StftEpilogue{nullptr, 1, 1, 2.0f, 0, 0.0f, 0.0f}, mel, samples, lut);
 }
 
 template <int NC, int FMT>
@@ -407,11 +373,7 @@ static int launch_small_mode(int pmode, const FrameGeom& g, const Tables& tb, co
 // apply (two-sided output, |X|^p with p outside {1, 2}) so that the generic kernel takes over.
 int try_launch_small(int n_fft, const FrameGeom& g, const Tables& tb, const StftEpilogue& ep, int mode,
                      hipStream_t stream) {
-    if (!ep.onesided) return TAC_E_UNSUPPORTED;
-    int pmode = -1;
-    if (mode == 0) pmode = 0;
-    else if (ep.power == 2.0f) pmode = ep.db ? 3 : 1;
-    else if (ep.power == 1.0f) pmode = ep.db ? 4 : 2;
+    const int pmode = row_pmode(ep, mode);
     if (pmode < 0) return TAC_E_UNSUPPORTED;
     if (n_fft == 1024) return launch_small_mode<512>(pmode, g, tb, ep, stream);
     if (n_fft == 512) return launch_small_mode<256>(pmode, g, tb, ep, stream);

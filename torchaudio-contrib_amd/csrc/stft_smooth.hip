@@ -330,19 +330,12 @@ int launch_stft_smooth(int n_fft, const FrameGeom& g, const StftEpilogue& ep, in
     const size_t lds = full ? lds_full : lds_half;
     int per_cu = (int)((160 * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    long long blocks = (units + slots - 1) / slots;
-    const long long cap = (long long)device_cu_count() * per_cu;
-    if (blocks > cap) blocks = cap;
+    const long long blocks = persistent_blocks(units, slots, (long long)device_cu_count() * per_cu);
     const int win_vec2 = g.win_length == n_fft && (reinterpret_cast<uintptr_t>(g.window) & 7u) == 0;
-    auto go = [&](auto kern) -> int {
-        TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(SM_THREADS), lds, stream, g, tw, ep, plan, n_fft, win_vec2);
-        return TAC_OK;
-    };
+    auto go = [&](auto kern) { return launch_kernel(kern, blocks, SM_THREADS, lds, stream, g, tw, ep, plan, n_fft, win_vec2); };
     const int rl = mode == 0 ? (tpf == 64 ? go(stft_smooth_kernel<0, 64>) : (full ? go(stft_smooth_kernel<0, 256>) : go(stft_smooth_kernel<0, 256, false>)))
                              : (tpf == 64 ? go(stft_smooth_kernel<1, 64>) : (full ? go(stft_smooth_kernel<1, 256>) : go(stft_smooth_kernel<1, 256, false>)));
     if (rl != TAC_OK) return rl;
-    TAC_HIP(hipGetLastError());
     set_last_route("stft_smooth_kernel<%d, %d>", mode == 0 ? 0 : 1, tpf);
     return TAC_OK;
 }
@@ -364,25 +357,15 @@ int launch_stft_smooth_backward(int n_fft, const FrameGeom& g, const float* grad
     const size_t lds = full ? lds_full : lds_half;
     int per_cu = (int)((160 * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    long long blocks = (units + slots - 1) / slots;
-    const long long cap = (long long)device_cu_count() * per_cu;
-    if (blocks > cap) blocks = cap;
-    auto go = [&](auto kern) -> int {
-        TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(SM_THREADS), lds, stream, g, tw, reinterpret_cast<const cf*>(grad_spec),
-                           grad_frames, plan, n_fft);
-        return TAC_OK;
+    const long long blocks = persistent_blocks(units, slots, (long long)device_cu_count() * per_cu);
+    auto go = [&](auto kern) {
+        return launch_kernel(kern, blocks, SM_THREADS, lds, stream, g, tw, reinterpret_cast<const cf*>(grad_spec), grad_frames, plan, n_fft);
     };
-    int rl;
     if (inverse)
-        rl = tpf == 64 ? go(stft_smooth_backward_kernel<64, true, true>)
+        return tpf == 64 ? go(stft_smooth_backward_kernel<64, true, true>)
                        : (full ? go(stft_smooth_backward_kernel<256, true, true>) : go(stft_smooth_backward_kernel<256, false, true>));
-    else
-        rl = tpf == 64 ? go(stft_smooth_backward_kernel<64>)
-                       : (full ? go(stft_smooth_backward_kernel<256>) : go(stft_smooth_backward_kernel<256, false>));
-    if (rl != TAC_OK) return rl;
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return tpf == 64 ? go(stft_smooth_backward_kernel<64>)
+                     : (full ? go(stft_smooth_backward_kernel<256>) : go(stft_smooth_backward_kernel<256, false>));
 }
 
 }  // namespace tac

@@ -287,13 +287,8 @@ static int launch_stretch_mel(const StretchArgs& a, const LaneMel& mel, unsigned
     if (bytes > 160 * 1024) return TAC_E_UNSUPPORTED;
     const long long total = a.rows * a.n_out;
     if (total >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
-    long long blocks = (total + WAVES - 1) / WAVES;
-    if (blocks > device_cu_count()) blocks = device_cu_count();
-    auto kern = stretch_mel_kernel<PMODE, S, CHUNKS, WAVES, FLY>;
-    if (bytes > 64 * 1024) TAC_HIP(allow_dynamic_lds(reinterpret_cast<const void*>(kern), (int)bytes));
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WAVES * 64), bytes, stream, a, mel, flags);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(stretch_mel_kernel<PMODE, S, CHUNKS, WAVES, FLY>, persistent_blocks(total, WAVES, device_cu_count()), WAVES * 64,
+                         bytes, stream, a, mel, flags);
 }
 
 template <int S, int CHUNKS>
@@ -389,14 +384,10 @@ int tac_stretch_norm_f32(const float* mag, int64_t rows, int32_t n_freqs, int64_
     while (span > 4 && rows * ((n_out + span - 1) / span) < 2LL * device_cu_count()) span >>= 1;
     const long long spans = (n_out + span - 1) / span;
     if (rows * spans >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
-    const dim3 grid((unsigned)(rows * spans)), block(SN_THREADS);
-    if (power == 1.0f) hipLaunchKernelGGL(stretch_rows_kernel<1>, grid, block, 0, s, a, out, fl, span, (int)spans);
-    else if (power == 2.0f) hipLaunchKernelGGL(stretch_rows_kernel<2>, grid, block, 0, s, a, out, fl, span, (int)spans);
-    else hipLaunchKernelGGL(stretch_rows_kernel<0>, grid, block, 0, s, a, out, fl, span, (int)spans);
-    TAC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(stretch_rows_fixup_kernel, dim3((unsigned)rows), block, 0, s, a, out, fl);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    const int lrc = launch_kernel(power == 1.0f ? stretch_rows_kernel<1> : (power == 2.0f ? stretch_rows_kernel<2> : stretch_rows_kernel<0>),
+                                  rows * spans, SN_THREADS, 0, s, a, out, fl, span, (int)spans);
+    if (lrc != TAC_OK) return lrc;
+    return launch_kernel(stretch_rows_fixup_kernel, rows, SN_THREADS, 0, s, a, out, fl);
 }
 
 int tac_stretch_mel_f32(const float* mag, int64_t rows, int32_t n_freqs, int64_t n_frames, int64_t stride_r, int64_t stride_t,
@@ -431,9 +422,7 @@ int tac_stretch_mel_f32(const float* mag, int64_t rows, int32_t n_freqs, int64_t
         default: return TAC_E_INVALID;
     }
     if (lrc != TAC_OK) return lrc;
-    hipLaunchKernelGGL(stretch_mel_fixup_kernel, dim3((unsigned)rows), dim3(SN_THREADS), 0, s, a, out, (int)n_mels, fl);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(stretch_mel_fixup_kernel, rows, SN_THREADS, 0, s, a, out, (int)n_mels, fl);
 }
 
 int tac_stretch_norm_backward_f32(const float* mag, int64_t rows, int32_t n_freqs, int64_t n_frames, int64_t stride_r,
@@ -446,12 +435,8 @@ int tac_stretch_norm_backward_f32(const float* mag, int64_t rows, int32_t n_freq
     const int rc = stretch_args(&a, mag, rows, n_freqs, n_frames, stride_r, stride_t, idx0, alpha, n_out, power, 0, 1.0f, 1e-7f);
     if (rc != TAC_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(rows * n_frames)), block(SN_THREADS);
-    if (power == 1.0f) hipLaunchKernelGGL(stretch_bwd_kernel<1>, grid, block, 0, s, a, bounds, grad_out, grad_mag);
-    else if (power == 2.0f) hipLaunchKernelGGL(stretch_bwd_kernel<2>, grid, block, 0, s, a, bounds, grad_out, grad_mag);
-    else hipLaunchKernelGGL(stretch_bwd_kernel<0>, grid, block, 0, s, a, bounds, grad_out, grad_mag);
-    TAC_HIP(hipGetLastError());
-    return TAC_OK;
+    return launch_kernel(power == 1.0f ? stretch_bwd_kernel<1> : (power == 2.0f ? stretch_bwd_kernel<2> : stretch_bwd_kernel<0>),
+                         rows * n_frames, SN_THREADS, 0, s, a, bounds, grad_out, grad_mag);
 }
 
 }  // extern "C"
