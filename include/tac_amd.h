@@ -457,6 +457,18 @@ int tac_istft_grad_input_f32(const float* grad_out, int64_t grad_stride, const f
                              int64_t n_frames, float* padded, void* stream);
 int tac_istft_grad_bins_f32(float* spec, int64_t n_frames_total, int n_fft, int normalized, void* stream);
 
+/* (14) functional.dct (the DCT-II of MFCC behind Melspectrogram -> AmplitudeToDb, and its adjoint with the transposed matrix):
+ *      out[r][t][c] = sum_m x[r][m][t]*mat[m][c], every sum one fused multiply-add chain in ascending m — one launch, each
+ *      output written once, no atomics, bit-identical from run to run; non-finite values propagate as in a dense matmul.
+ *      x element (r, m, t) lives at x[r*stride_r + m*stride_m + t*stride_t], any positive strides: frame-major rows
+ *      (stride_m == 1: what the mel kernels write; 16-byte loads where x and the strides are 16-byte multiples and n_in a
+ *      multiple of 4) and time-contiguous rows (stride_t == 1) are read coalesced.  mat: DEVICE float[n_in][n_out], held in
+ *      the LDS: 1 <= n_in, n_out <= 256 and n_in * n_out <= 32768, TAC_E_UNSUPPORTED (nothing launched) otherwise.
+ *      out: float[rows][T][n_out]. */
+int tac_dct_rows_f32(const float* x, int64_t rows, int32_t n_in, int64_t n_frames,
+                     int64_t stride_r, int64_t stride_m, int64_t stride_t,
+                     const float* mat, int32_t n_out, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

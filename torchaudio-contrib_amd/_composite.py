@@ -76,6 +76,11 @@ def apply_filterbank(spec, bank):
     return (frames_first @ bank).transpose(-1, -2)
 
 
+def dct(x, matrix):
+    """the same shape of call for the cepstral matrix: (…, n_in, time) x (n_in, n_out) -> (…, n_out, time)."""
+    return (x.transpose(-1, -2) @ matrix).transpose(-1, -2)
+
+
 def amplitude_to_db(x, ref, amin):
     """reference functional.py:291-296: the input is squared, the square clamped, then 10·(log10 − log10 ref)."""
     floor_applied = (x ** 2.0).clamp(min=amin)

@@ -36,7 +36,7 @@ def _count(name, *filled):
 # through an alias created before the cache, ``from_dlpack`` / raw-pointer writers — cannot be seen without reading the
 # tensor back on every call; after such a write call ``invalidate(t)`` (or ``invalidate()`` for everything).
 _epoch = 0
-_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite', '_tac_istft')
+_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite', '_tac_istft', '_tac_dct')
 
 
 _unstamped = itertools.count()
@@ -782,6 +782,57 @@ def apply_filterbank(spec, fb, allow_sparse=True, db=None):
         _count('tac_apply_filterbank_f32', out)
     out = out.transpose(-2, -1)
     return out if db is None else amplitude_to_db(out, db[0], db[1])
+
+
+# ----------------------------------------------------------------------------- DCT (MFCC)
+DCT_MAX_DIM, DCT_MAX_MATRIX = 256, 32768
+
+
+def dct_covers(n_in, n_out):
+    """The sizes ``tac_dct_rows_f32`` holds in the LDS (csrc/mfcc.hip) — symmetric, so that the gradient (the same kernel with
+    the transposed matrix) is covered whenever the forward is."""
+    return 1 <= n_in <= DCT_MAX_DIM and 1 <= n_out <= DCT_MAX_DIM and n_in * n_out <= DCT_MAX_MATRIX
+
+
+def _dct_matrix(mat, transposed):
+    """``mat`` (or its transpose, for the gradient) as a contiguous float32 tensor on its device; copies are cached on the tensor
+    object per version, like the filterbank's packs and its transpose."""
+    if not transposed and mat.dtype == torch.float32 and mat.is_contiguous():
+        return mat.detach()
+    hit = getattr(mat, '_tac_dct', None)
+    if hit is None or hit[0] != _stamp(mat):
+        hit = (_stamp(mat), {})
+        try:
+            mat._tac_dct = hit
+        except Exception:
+            pass
+    m = hit[1].get(transposed)
+    if m is None:
+        src = mat.detach().t() if transposed else mat.detach()
+        m = hit[1][transposed] = src.to(torch.float32).contiguous()
+    return m
+
+
+def dct_rows(x, mat, transposed=False):
+    """``(…, n_in, T) x (n_in, n_out) -> (…, n_out, T)``: ``tac_dct_rows_f32`` on ``x`` where it lies — any strides; the leading
+    dims are copied only when no single row stride expresses them.  ``transposed``: ``mat`` is ``(n_out, n_in)`` and applied as
+    its transpose (the gradient).  The result is the logical view of frame-major storage, like every spectral output here."""
+    m = _dct_matrix(mat, transposed)
+    n_in, n_out = m.shape
+    n_frames = x.shape[-1]
+    lead = tuple(x.shape[:-2])
+    out = _empty(lead + (n_frames, n_out), device=x.device)
+    if out.numel():
+        rows = x.reshape(-1, n_in, n_frames)            # a view wherever the leading dims collapse into one stride
+        if any(st <= 0 for st, n in zip(rows.stride(), rows.shape) if n > 1):
+            rows = rows.contiguous()                    # (expanded / flipped axes: the kernel takes positive strides)
+        with _native.on_device(x.device):
+            rc = _native.lib().tac_dct_rows_f32(
+                _native.ptr(rows), rows.shape[0], n_in, n_frames, rows.stride(0), rows.stride(1), rows.stride(2),
+                _native.ptr(m), n_out, _native.ptr(out), _native.stream_ptr(x.device))
+        _native.check(rc, 'tac_dct_rows_f32')
+        _count('tac_dct_rows_f32', out)
+    return out.transpose(-2, -1)
 
 
 # ----------------------------------------------------------------------------- complex pairs

@@ -8,6 +8,7 @@ see them by name.
     tac_amd::melspectrogram     "      (the whole chain in ONE kernel)
     tac_amd::stretch_norm       complex_norm(phase_vocoder(X)) [+ dB] from |X| alone (csrc/stretch.hip)
     tac_amd::stretch_mel            "      + apply_filterbank in the same launch
+    tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -352,7 +353,15 @@ def _istft_hip_backward(saved, rest, needs, grads):
                              int(spec.shape[-2])) if needs[0] else None, None]
 
 
-_HIP_BACKWARD = {'stft': _stft_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+def _dct_hip_backward(saved, rest, needs, grads):
+    x, matrix = saved
+    if grads[0] is None or needs[1] or not H.dct_covers(matrix.shape[0], matrix.shape[1]):
+        return None                 # (the matrix's gradient: the stock-torch route, announced)
+    # the same kernel with the transposed matrix; grad_out is read where it lies, whatever strides autograd gave it
+    return [H.dct_rows(grads[0], matrix, transposed=True) if needs[0] else None, None]
+
+
+_HIP_BACKWARD = {'stft': _stft_hip_backward, 'dct': _dct_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -567,6 +576,26 @@ def _apply_filterbank_fake(spec, bank):
 
 _register('apply_filterbank', '(Tensor spec, Tensor filterbank) -> Tensor', _apply_filterbank_cuda,
           C.apply_filterbank, _apply_filterbank_fake, 2)
+
+
+# ============================================================================= dct (MFCC)
+def _dct_cuda(x, matrix):
+    _same_device('dct', x, matrix)
+    reason = _hip_dtype(x, matrix)
+    if reason is None and not H.dct_covers(matrix.shape[0], matrix.shape[1]):
+        reason = 'a %d x %d matrix (beyond 256 x 256 / 32768 elements)' % tuple(matrix.shape)
+    if reason is not None:
+        _composite_route('dct', reason)
+        return C.dct(x, matrix)
+    out = H.dct_rows(_f32(x), matrix)
+    return out if x.dtype == out.dtype else out.to(x.dtype)
+
+
+def _dct_fake(x, matrix):
+    return _swapped(x.shape[:-2], (x.shape[-1], matrix.shape[1]), x.dtype, x.device, -2, -1)
+
+
+_register('dct', '(Tensor x, Tensor matrix) -> Tensor', _dct_cuda, C.dct, _dct_fake, 2)
 
 
 # ============================================================================= complex pairs

@@ -22,7 +22,8 @@ from . import _ops
 from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
-           'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss']
+           'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
+           'create_dct', 'dct']
 
 _call = _ops.call
 
@@ -182,6 +183,40 @@ def apply_filterbank(mag_specgrams, filterbank):
     if fb.device != spec.device:
         raise RuntimeError('apply_filterbank: spectrogram and filterbank must be on the same device')
     return _call('apply_filterbank', spec, fb)
+
+
+def create_dct(num_coeffs, num_mels, norm='ortho'):
+    """``(num_mels, num_coeffs)`` DCT-II matrix, float32: ``cos(pi / num_mels * (m + 0.5) * k)``, times 2 with ``norm=None``; with
+    ``norm='ortho'`` column 0 times ``1/sqrt(2)`` and everything times ``sqrt(2 / num_mels)`` (torchaudio's ``create_dct``; what
+    ``scipy.fft.dct(type=2, norm=norm)[..., :num_coeffs]`` multiplies by).  Evaluated in float64 and rounded once."""
+    if norm is not None and norm != 'ortho':
+        raise ValueError("create_dct: norm must be None or 'ortho', got %r" % (norm,))
+    num_coeffs, num_mels = int(num_coeffs), int(num_mels)
+    if not 1 <= num_coeffs <= num_mels:
+        raise ValueError('create_dct: expected 1 <= num_coeffs <= num_mels, got num_coeffs=%d, num_mels=%d'
+                         % (num_coeffs, num_mels))
+    m = torch.arange(num_mels, dtype=torch.float64).unsqueeze(1)
+    k = torch.arange(num_coeffs, dtype=torch.float64).unsqueeze(0)
+    d = torch.cos(math.pi / num_mels * (m + 0.5) * k)
+    if norm is None:
+        d = d * 2.0
+    else:
+        d[:, 0] *= 1.0 / math.sqrt(2.0)
+        d = d * math.sqrt(2.0 / num_mels)
+    return d.to(torch.float32)
+
+
+def dct(x, dct_matrix):
+    """``(…, num_mels, time) x (num_mels, num_coeffs) → (…, num_coeffs, time)``: the matrix of ``create_dct`` (or any other)
+    applied along dim −2 — behind ``Melspectrogram -> AmplitudeToDb`` these are the MFCCs.  On a HIP device one streaming
+    kernel that keeps the matrix in the LDS (csrc/mfcc.hip), for matrices up to 256 x 256 with at most 32768 elements."""
+    x = _tensor(x, 'x')
+    mat = _tensor(dct_matrix, 'dct_matrix')
+    if mat.dim() != 2 or x.dim() < 2 or x.shape[-2] != mat.shape[0]:
+        raise RuntimeError('dct: size mismatch, input %s vs dct_matrix %s' % (tuple(x.shape), tuple(mat.shape)))
+    if mat.device != x.device:
+        raise RuntimeError('dct: input and dct_matrix must be on the same device')
+    return _call('dct', x, mat)
 
 
 def _check_pairs(z, what):

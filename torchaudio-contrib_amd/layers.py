@@ -314,6 +314,31 @@ class AmplitudeToDb(_ModuleNoStateBuffers):
         return self.__class__.__name__ + '(ref={}, amin={})'.format(self.ref, self.amin)
 
 
+class DCT(_ModuleNoStateBuffers):
+    """Multiply the band axis of ``(…, num_mels, time)`` by a ``(num_mels, num_coeffs)`` matrix held as the non-persistent
+    buffer ``dct_matrix`` (``functional.create_dct``): ``(…, num_coeffs, time)``."""
+
+    def __init__(self, dct_matrix):
+        super(DCT, self).__init__()
+        self.register_buffer('dct_matrix', dct_matrix)
+
+    def forward(self, x):
+        return F.dct(x, self.dct_matrix)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(num_mels={}, num_coeffs={})'.format(*self.dct_matrix.shape)
+
+
+def MFCC(num_coeffs=40, norm='ortho', ref=1.0, amin=1e-7, **melkwargs):
+    """``Sequential(*Melspectrogram(**melkwargs), AmplitudeToDb(ref, amin), DCT(create_dct(num_coeffs, num_mels, norm)))``:
+    mel-frequency cepstral coefficients ``(*, channel, num_coeffs, time)`` of this package's mel dB values (``AmplitudeToDb``
+    squares its input, as the reference's does; no ``top_db``, no ``log_mels``).  On a HIP device two launches: the fused
+    Melspectrogram + dB kernel, then the DCT kernel.  The children stay individually usable."""
+    num_mels = melkwargs.get('num_mels', 128)
+    return nn.Sequential(*Melspectrogram(**melkwargs), AmplitudeToDb(ref, amin),
+                         DCT(F.create_dct(num_coeffs, num_mels, norm)))
+
+
 class DbToAmplitude(_ModuleNoStateBuffers):
     """Inverse of ``AmplitudeToDb`` (reference layers.py:384-412)."""
 
