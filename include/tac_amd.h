@@ -469,6 +469,21 @@ int tac_dct_rows_f32(const float* x, int64_t rows, int32_t n_in, int64_t n_frame
                      int64_t stride_r, int64_t stride_m, int64_t stride_t,
                      const float* mat, int32_t n_out, float* out, void* stream);
 
+/* (15) functional.resample (polyphase windowed-sinc resampling, and its adjoint with the transposed bank):
+ *      y[r][j*phases + p] = sum_{k < run[p]} bank[k][p] * x[r][j*step + off[p] + k]   for 0 <= j*phases + p < l_out,
+ *      x[r][i] = x[r*stride_r + i], taken as zero outside 0 <= i < l_in; out: float[rows][l_out], dense.  One launch, each output
+ *      one fused multiply-add chain over k ascending, written once: no atomics, bit-identical from run to run.  Taps behind a
+ *      phase's run are never multiplied: a non-finite input sample reaches exactly the outputs whose run covers it.
+ *      bank: DEVICE float[taps][phases] (tap-major), zero behind each run; table: DEVICE int32[2][phases] = off[], run[] with
+ *      off_min <= off[p] <= off_max (may be negative) and taps_min <= run[p] <= taps — values outside are clamped, so a wrong
+ *      table gives wrong sums, never an access outside the tile.  Forward: phases = new, step = orig; gradient: phases = orig,
+ *      step = new.  The bank and one tile's input span live in the LDS: phases <= 2048, phases * taps <= 20480
+ *      (RESAMPLE_MAX_BANK) and 256 outputs' span <= 14336 floats, TAC_E_UNSUPPORTED (nothing launched) otherwise.
+ *      16-byte loads where x and stride_r are 16-byte multiples, float loads otherwise. */
+int tac_polyphase_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride_r, const float* bank, const int32_t* table,
+                      int32_t phases, int32_t taps, int32_t taps_min, int32_t step, int32_t off_min, int32_t off_max,
+                      int64_t l_out, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

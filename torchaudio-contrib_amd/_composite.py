@@ -81,6 +81,25 @@ def dct(x, matrix):
     return (x.transpose(-1, -2) @ matrix).transpose(-1, -2)
 
 
+def resample(wave, orig, new, lowpass_filter_width, rolloff, method, beta):
+    """torchaudio's ``functional.resample`` in its own operator form: the full ``(new, 1, 2 width + orig)`` bank as a ``conv1d``
+    at stride ``orig`` over the input padded by ``(width, width + orig)``, the phases interleaved and cut to
+    ``ceil(new * L / orig)``.  ``orig`` / ``new`` are the reduced rates (``_resample.constants``)."""
+    from . import _resample as RS
+    length = wave.shape[-1]
+    n_out = RS.out_length(length, orig, new)
+    if orig == new:
+        return wave.clone()        # (an op may not return its input; ``functional.resample`` hands the input back itself)
+    if length == 0:
+        return wave.new_zeros(tuple(wave.shape[:-1]) + (0,))
+    width = RS.width_of(orig, new, lowpass_filter_width, rolloff)
+    kernel = RS.full_bank(orig, new, lowpass_filter_width, rolloff, method, beta).to(device=wave.device, dtype=wave.dtype)
+    rows = wave.reshape(-1, 1, length)
+    out = TF.conv1d(TF.pad(rows, (width, width + orig)), kernel.unsqueeze(1), stride=orig)     # (rows, new, L // orig + 1)
+    out = out.transpose(1, 2).reshape(rows.shape[0], -1)[:, :n_out].contiguous()      # dense, like the kernel's output
+    return out.reshape(tuple(wave.shape[:-1]) + (n_out,))
+
+
 def amplitude_to_db(x, ref, amin):
     """reference functional.py:291-296: the input is squared, the square clamped, then 10·(log10 − log10 ref)."""
     floor_applied = (x ** 2.0).clamp(min=amin)

@@ -15,6 +15,7 @@ import weakref
 import torch
 
 from . import _native
+from . import _resample
 
 _lock = threading.Lock()
 
@@ -833,6 +834,78 @@ def dct_rows(x, mat, transposed=False):
         _native.check(rc, 'tac_dct_rows_f32')
         _count('tac_dct_rows_f32', out)
     return out.transpose(-2, -1)
+
+
+# ----------------------------------------------------------------------------- resample
+#: floats of compact bank (phases * taps) ``tac_polyphase_f32`` holds in the LDS: 80 KiB, half of it.  Both banks of every pair
+#: among 8000 / 11025 / 12000 / 16000 / 22050 / 24000 / 32000 / 44100 / 48000 / 88200 / 96000 Hz at the default filter fit
+#: (the largest, the gradient of 32000 -> 11025 and 96000 -> 11025, is 1280 x 13 = 16640).
+RESAMPLE_MAX_BANK = 20480
+RESAMPLE_MAX_PHASES = 2048
+#: outputs per tile of the kernel (512 / 256 where 1024 outputs' input span does not fit), and the spans' limits in floats
+RESAMPLE_TILE = 1024
+_RS_SPAN_WIDE, _RS_SPAN_MAX = 8192, 14336
+
+
+def _rs_span_cap(b, tile, off_min, off_max):
+    return (3 + ((b.phases - 1 + tile - 1) // b.phases) * b.step + (off_max - off_min) + b.K + 3) & ~3
+
+
+def resample_tile(b):
+    """Outputs per tile ``tac_polyphase_f32`` takes for this bank (csrc/resample.hip), or None where it does not cover it."""
+    if b.phases > RESAMPLE_MAX_PHASES or b.phases * b.K > RESAMPLE_MAX_BANK:
+        return None
+    off_min, off_max = min(b.off), max(b.off)
+    for tile in (1024, 512, 256):
+        if _rs_span_cap(b, tile, off_min, off_max) <= (_RS_SPAN_MAX if tile == 256 else _RS_SPAN_WIDE):
+            return tile
+    return None
+
+
+def resample_covers(orig, new, lpw, rolloff, method, beta):
+    """True where the kernel holds BOTH banks of this (reduced) pair — the forward's and the gradient's — so that a call that
+    runs on the kernel also trains on it."""
+    return resample_tile(_resample.bank(orig, new, lpw, rolloff, method, beta)) is not None and \
+        resample_tile(_resample.adjoint_bank(orig, new, lpw, rolloff, method, beta)) is not None
+
+
+_resample_tables = {}
+
+
+def _resample_device_bank(key, adjoint, device):
+    """(Bank, tap-major float32 bank, int32 [off | run], off_min, off_max, run_min) on ``device``: rounded once from the
+    float64 bank, cached per argument tuple and device."""
+    hit = _resample_tables.get((key, adjoint, device))
+    if hit is None:
+        b = (_resample.adjoint_bank if adjoint else _resample.bank)(*key)
+        taps = b.taps.t().contiguous().to(torch.float32).to(device)
+        table = torch.tensor([b.off, b.run], dtype=torch.int32).to(device)
+        if len(_resample_tables) > 64:
+            _resample_tables.clear()
+        hit = _resample_tables[(key, adjoint, device)] = (b, taps, table, min(b.off), max(b.off), min(b.run))
+    return hit
+
+
+def polyphase(x, key, n_out, adjoint=False):
+    """``(…, L) -> (…, n_out)`` through ``tac_polyphase_f32`` with the forward bank of ``key`` (the reduced argument tuple of
+    ``_resample.bank``) or, ``adjoint``, with its transpose: one launch.  ``x`` is read where it lies when its leading dims
+    collapse into one positive row stride over unit-stride rows; it is copied otherwise."""
+    b, taps, table, off_min, off_max, run_min = _resample_device_bank(key, adjoint, x.device)
+    length = x.shape[-1]
+    out = _empty(tuple(x.shape[:-1]) + (n_out,), device=x.device)
+    if out.numel():
+        if length == 0:
+            return out.zero_()
+        rows = x.reshape(-1, length)
+        if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+            rows = rows.contiguous()
+        with _native.on_device(x.device):
+            rc = _native.lib().tac_polyphase_f32(
+                _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(taps), _native.ptr(table), b.phases, b.K,
+                run_min, b.step, off_min, off_max, n_out, _native.ptr(out), _native.stream_ptr(x.device))
+        _native.check(rc, 'tac_polyphase_f32')
+        _count('tac_polyphase_f32', out)
+    return out
 
 
 # ----------------------------------------------------------------------------- complex pairs

@@ -38,7 +38,7 @@ EXPORTS = (
     'tac_db_to_amplitude_f64',
     'tac_last_route', 'tac_debug_clock_probe', 'tac_melbank_plan_pieces_host', 'tac_set_fft_pipe',
     'tac_istft_workspace', 'tac_istft_envelope_f32', 'tac_istft_f32', 'tac_istft_grad_input_f32', 'tac_istft_grad_bins_f32',
-    'tac_dct_rows_f32',
+    'tac_dct_rows_f32', 'tac_polyphase_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -184,6 +184,7 @@ def lib():
         h.tac_istft_grad_input_f32.argtypes = [_P, _I64, _P, _DESC, _I64, _P, _P]
         h.tac_istft_grad_bins_f32.argtypes = [_P, _I64, _I32, _I32, _P]
         h.tac_dct_rows_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _I32, _P, _P]
+        h.tac_polyphase_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

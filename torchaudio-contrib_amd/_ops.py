@@ -9,6 +9,7 @@ see them by name.
     tac_amd::stretch_norm       complex_norm(phase_vocoder(X)) [+ dB] from |X| alone (csrc/stretch.hip)
     tac_amd::stretch_mel            "      + apply_filterbank in the same launch
     tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
+    tac_amd::resample           polyphase windowed-sinc resampling of the waveform (csrc/resample.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -33,6 +34,7 @@ from torch.library import Library
 from . import _composite as C
 from . import _hip as H
 from . import _hip64 as H64
+from . import _resample as RS
 
 NS = 'tac_amd'
 _lib = Library(NS, 'DEF')
@@ -361,7 +363,15 @@ def _dct_hip_backward(saved, rest, needs, grads):
     return [H.dct_rows(grads[0], matrix, transposed=True) if needs[0] else None, None]
 
 
-_HIP_BACKWARD = {'stft': _stft_hip_backward, 'dct': _dct_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+def _resample_hip_backward(saved, rest, needs, grads):
+    (wave,) = saved
+    if grads[0] is None or not needs[0] or rest[0] == rest[1] or not H.resample_covers(*rest):
+        return None
+    # the same kernel with the transposed bank; a grad_out autograd handed over with other than unit stride is copied
+    return [H.polyphase(grads[0], tuple(rest), int(wave.shape[-1]), adjoint=True)]
+
+
+_HIP_BACKWARD = {'stft': _stft_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -596,6 +606,34 @@ def _dct_fake(x, matrix):
 
 
 _register('dct', '(Tensor x, Tensor matrix) -> Tensor', _dct_cuda, C.dct, _dct_fake, 2)
+
+
+# ============================================================================= resample
+def _resample_cuda(wave, orig, new, lowpass_filter_width, rolloff, method, beta):
+    key = (orig, new, lowpass_filter_width, rolloff, method, beta)
+    length = wave.shape[-1]
+    if orig == new or wave.numel() == 0:
+        return C.resample(wave, *key)                          # the input itself / an empty output: nothing is launched
+    reason = _hip_dtype(wave)
+    if reason is None and not H.resample_covers(*key):
+        reason = 'a polyphase bank beyond %d floats (%d -> %d)' % (H.RESAMPLE_MAX_BANK, orig, new)
+    if reason is None and any(st <= 0 for st, n in zip(wave.stride(), wave.shape) if n > 1):
+        reason = 'non-positive strides'
+    if reason is not None:
+        _composite_route('resample', reason)
+        return C.resample(wave, *key)
+    out = H.polyphase(_f32(wave), key, RS.out_length(length, orig, new))
+    return out if wave.dtype == out.dtype else out.to(wave.dtype)
+
+
+def _resample_fake(wave, orig, new, lowpass_filter_width, rolloff, method, beta):
+    if orig == new:
+        return wave.clone()        # (a fake kernel may not alias its input)
+    return wave.new_empty(tuple(wave.shape[:-1]) + (RS.out_length(wave.shape[-1], orig, new),))
+
+
+_register('resample', '(Tensor wave, int orig, int new, int lowpass_filter_width, float rolloff, str method, float? beta) '
+          '-> Tensor', _resample_cuda, C.resample, _resample_fake, 1)
 
 
 # ============================================================================= complex pairs

@@ -19,11 +19,12 @@ import torch
 
 from . import _hip
 from . import _ops
+from . import _resample
 from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct']
+           'create_dct', 'dct', 'resample']
 
 _call = _ops.call
 
@@ -217,6 +218,24 @@ def dct(x, dct_matrix):
     if mat.device != x.device:
         raise RuntimeError('dct: input and dct_matrix must be on the same device')
     return _call('dct', x, mat)
+
+
+def resample(waveforms, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method='sinc_interp_hann',
+             beta=None):
+    """``(…, L) → (…, ceil(new_freq * L / orig_freq))``: torchaudio's ``functional.resample`` — a polyphase windowed-sinc
+    filter (Hann or Kaiser window, ``lowpass_filter_width`` zero crossings, cut-off at ``rolloff`` of the lower Nyquist rate);
+    the definition is in ``_resample.py``.  Both rates are positive ints and are reduced by their gcd; equal rates return the
+    input.  On a HIP device one streaming kernel that keeps the non-zero taps in the LDS (csrc/resample.hip); its gradient
+    w.r.t. the waveform is the same kernel with the transposed bank."""
+    x = _tensor(waveforms, 'waveforms')
+    args = _resample.constants(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+    if x.dim() < 1:
+        raise RuntimeError('resample: expected a tensor of shape (…, time), got a scalar')
+    if not x.is_floating_point():
+        raise RuntimeError('resample: expected a floating-point waveform, got %s' % x.dtype)
+    if args[0] == args[1]:
+        return x
+    return _call('resample', x, *args)
 
 
 def _check_pairs(z, what):

@@ -15,6 +15,7 @@ import torch.nn as nn
 from . import functional as F
 from . import _hip
 from . import _lazy
+from . import _resample
 from ._lazy import DeferredSpectral, DeferredWave, can_defer, can_defer_codes, lazy_fusion_enabled, realize
 
 
@@ -337,6 +338,33 @@ def MFCC(num_coeffs=40, norm='ortho', ref=1.0, amin=1e-7, **melkwargs):
     num_mels = melkwargs.get('num_mels', 128)
     return nn.Sequential(*Melspectrogram(**melkwargs), AmplitudeToDb(ref, amin),
                          DCT(F.create_dct(num_coeffs, num_mels, norm)))
+
+
+class Resample(_ModuleNoStateBuffers):
+    """``functional.resample`` as a layer: ``(…, time)`` → ``(…, ceil(new_freq * time / orig_freq))``.  The compact polyphase
+    bank — float32 ``(new, K)``, row ``p`` the taps of phase ``p`` from its first non-zero one — is the non-persistent buffer
+    ``bank`` (a derived constant: it follows ``.to()`` and stays out of ``state_dict()``; the kernel's own copy is cached per
+    argument tuple and device)."""
+
+    def __init__(self, orig_freq=16000, new_freq=16000, lowpass_filter_width=6, rolloff=0.99,
+                 resampling_method='sinc_interp_hann', beta=None):
+        super(Resample, self).__init__()
+        self.orig_freq = orig_freq
+        self.new_freq = new_freq
+        self.lowpass_filter_width = lowpass_filter_width
+        self.rolloff = rolloff
+        self.resampling_method = resampling_method
+        self.beta = beta
+        args = _resample.constants(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+        self.register_buffer('bank', _resample.bank(*args).taps.to(torch.float32))
+
+    def forward(self, waveforms):
+        return F.resample(waveforms, self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff,
+                          self.resampling_method, self.beta)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(orig_freq={}, new_freq={}, lowpass_filter_width={}, rolloff={}, resampling_method={}, beta={})'.format(
+            self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
 
 
 class DbToAmplitude(_ModuleNoStateBuffers):
