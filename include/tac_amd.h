@@ -484,6 +484,23 @@ int tac_polyphase_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride
                       int32_t phases, int32_t taps, int32_t taps_min, int32_t step, int32_t off_min, int32_t off_max,
                       int64_t l_out, float* out, void* stream);
 
+/* (16) functional.lfilter (and biquad, the cookbook biquads, preemphasis, deemphasis): a recursive filter of order <= 2 along a row,
+ *      a0 y[n] = sum_{k < n_coeffs} b[k] x[n-k] - sum_{1 <= k < n_coeffs} a[k] y[n-k],   zero initial state,
+ *      x[r][i] = x[r*stride_r + i], 0 <= i < length; out: float[rows][length], dense.  b, a: HOST double[n_coeffs], n_coeffs 1..3,
+ *      a[0] != 0 (TAC_E_INVALID otherwise; n_coeffs > 3 is TAC_E_UNSUPPORTED).  reverse != 0 runs the same filter from the END of
+ *      each row towards its start — the adjoint, i.e. the gradient w.r.t. x.  clamp != 0 limits the result to [-1, 1].
+ *      One launch, no workspace, no atomics, one writer per element, bit-identical from run to run; a row is walked by one workgroup
+ *      in tiles of 1024 * tac_lfilter_chunk() samples and no workgroup waits on another.  Loads and stores are float32; the
+ *      recursion, its state and the scan that joins the lanes' chunks are float64 (coefficients are divided by a[0] in float64).
+ *      A non-finite sample reaches the samples after it (before it, with reverse) in its own row, and nothing else.
+ *      16-byte loads where x and stride_r are 16-byte multiples, float loads otherwise.
+ *      tac_lfilter_supported: TAC_OK where tac_lfilter_f32 takes these coefficients; TAC_E_UNSUPPORTED also for a filter so
+ *      unstable that the largest matrix of the scan, M^(512 chunk), overflows float64 (nothing is launched for those). */
+int32_t tac_lfilter_chunk(void);
+int tac_lfilter_supported(const double* b, const double* a, int32_t n_coeffs);
+int tac_lfilter_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const double* b, const double* a,
+                    int32_t n_coeffs, int clamp, int reverse, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,10 +14,12 @@ from . import layers
 from .functional import *      # noqa: F401,F403
 from .functional import (stft, istft, complex_norm, create_mel_filter, apply_filterbank, angle, magphase,
                          phase_vocoder, amplitude_to_db, db_to_amplitude, mu_law_encoding,
-                         mu_law_decoding, hpss, create_dct, dct, resample)
+                         mu_law_decoding, hpss, create_dct, dct, resample, lfilter, biquad, lowpass_biquad,
+                         highpass_biquad, bandpass_biquad, bandreject_biquad, allpass_biquad, equalizer_biquad,
+                         preemphasis, deemphasis)
 from .layers import (STFT, ISTFT, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
-                     MuLawDecoding, HPSS, DCT, MFCC, Resample)
+                     MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis)
 from . import distributed
 
 __version__ = '0.1.0'

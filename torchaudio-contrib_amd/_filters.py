@@ -1,0 +1,87 @@
+"""Host side of ``functional.lfilter`` and the filters on top of it: argument checks and the RBJ audio-EQ-cookbook biquad designs,
+evaluated in float64 (Python floats) and handed to the op as float64 host tensors — they reach the kernel as the doubles computed
+here, never through float32.
+
+Every design returns ``(b, a)``, two tuples of three floats, with ``w0 = 2 pi f / sample_rate`` and ``alpha = sin(w0) / (2 Q)``;
+the denominator of all of them is ``a = (1 + alpha, -2 cos w0, 1 - alpha)`` except the equalizer's."""
+import math
+
+import torch
+
+
+def check_coeffs(a_coeffs, b_coeffs):
+    """``ValueError`` unless both are 1-D floating-point tensors of equal, non-zero length.  (``a_coeffs[0] != 0`` is checked on
+    the host values, ``leading_nonzero``.)  2-D coefficient banks — torchaudio's one filter per channel — are out of scope."""
+    for name, c in (('a_coeffs', a_coeffs), ('b_coeffs', b_coeffs)):
+        if not torch.is_tensor(c):
+            raise ValueError('lfilter: %s must be a tensor, got %s' % (name, type(c).__name__))
+        if c.dim() != 1:
+            raise ValueError('lfilter: %s must be 1-D, got shape %s (2-D coefficient banks are not supported)'
+                             % (name, tuple(c.shape)))
+        if not c.is_floating_point():
+            raise ValueError('lfilter: %s must be floating point, got %s' % (name, c.dtype))
+    if a_coeffs.numel() != b_coeffs.numel() or a_coeffs.numel() == 0:
+        raise ValueError('lfilter: a_coeffs and b_coeffs must have the same non-zero length, got %d and %d'
+                         % (a_coeffs.numel(), b_coeffs.numel()))
+
+
+def _w0_alpha(sample_rate, freq, Q):
+    if not sample_rate > 0:
+        raise ValueError('sample_rate must be positive, got %r' % (sample_rate,))
+    if not Q > 0:
+        raise ValueError('Q must be positive, got %r' % (Q,))
+    w0 = 2.0 * math.pi * float(freq) / float(sample_rate)
+    return w0, math.sin(w0) / (2.0 * float(Q))
+
+
+def lowpass(sample_rate, cutoff_freq, Q=0.707):
+    w0, alpha = _w0_alpha(sample_rate, cutoff_freq, Q)
+    c = math.cos(w0)
+    return ((1.0 - c) / 2.0, 1.0 - c, (1.0 - c) / 2.0), (1.0 + alpha, -2.0 * c, 1.0 - alpha)
+
+
+def highpass(sample_rate, cutoff_freq, Q=0.707):
+    w0, alpha = _w0_alpha(sample_rate, cutoff_freq, Q)
+    c = math.cos(w0)
+    return ((1.0 + c) / 2.0, -1.0 - c, (1.0 + c) / 2.0), (1.0 + alpha, -2.0 * c, 1.0 - alpha)
+
+
+def bandpass(sample_rate, central_freq, Q=0.707, const_skirt_gain=False):
+    w0, alpha = _w0_alpha(sample_rate, central_freq, Q)
+    t = math.sin(w0) / 2.0 if const_skirt_gain else alpha
+    return (t, 0.0, -t), (1.0 + alpha, -2.0 * math.cos(w0), 1.0 - alpha)
+
+
+def bandreject(sample_rate, central_freq, Q=0.707):
+    w0, alpha = _w0_alpha(sample_rate, central_freq, Q)
+    c = math.cos(w0)
+    return (1.0, -2.0 * c, 1.0), (1.0 + alpha, -2.0 * c, 1.0 - alpha)
+
+
+def allpass(sample_rate, central_freq, Q=0.707):
+    w0, alpha = _w0_alpha(sample_rate, central_freq, Q)
+    c = math.cos(w0)
+    return (1.0 - alpha, -2.0 * c, 1.0 + alpha), (1.0 + alpha, -2.0 * c, 1.0 - alpha)
+
+
+def equalizer(sample_rate, center_freq, gain, Q=0.707):
+    w0, alpha = _w0_alpha(sample_rate, center_freq, Q)
+    c = math.cos(w0)
+    A = 10.0 ** (float(gain) / 40.0)
+    return (1.0 + alpha * A, -2.0 * c, 1.0 - alpha * A), (1.0 + alpha / A, -2.0 * c, 1.0 - alpha / A)
+
+
+_tensors = {}
+
+
+def host_tensor(values):
+    """float64 host tensor of a tuple of floats, cached (built outside inference mode: it may be saved for a backward)."""
+    key = tuple(float(v) for v in values)
+    hit = _tensors.get(key)
+    if hit is None:
+        with torch.inference_mode(False):
+            hit = torch.tensor(key, dtype=torch.float64)
+        if len(_tensors) > 256:
+            _tensors.clear()
+        _tensors[key] = hit
+    return hit

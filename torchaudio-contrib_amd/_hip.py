@@ -37,7 +37,7 @@ def _count(name, *filled):
 # through an alias created before the cache, ``from_dlpack`` / raw-pointer writers — cannot be seen without reading the
 # tensor back on every call; after such a write call ``invalidate(t)`` (or ``invalidate()`` for everything).
 _epoch = 0
-_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite', '_tac_istft', '_tac_dct')
+_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite', '_tac_istft', '_tac_dct', '_tac_coef')
 
 
 _unstamped = itertools.count()
@@ -905,6 +905,83 @@ def polyphase(x, key, n_out, adjoint=False):
                 run_min, b.step, off_min, off_max, n_out, _native.ptr(out), _native.stream_ptr(x.device))
         _native.check(rc, 'tac_polyphase_f32')
         _count('tac_polyphase_f32', out)
+    return out
+
+
+# ----------------------------------------------------------------------------- lfilter
+#: samples per lane and per tile of ``tac_lfilter_f32`` (csrc/lfilter.hip: LF_C, LF_TILE = 1024 lanes * LF_C); checked against the
+#: library's own value at the first launch
+LFILTER_C = 16
+LFILTER_TILE = 1024 * LFILTER_C
+#: coefficients per side the kernel takes (order <= 2)
+LFILTER_MAX_COEFFS = 3
+
+_lfilter_ok = {}
+_lfilter_chunk_checked = False
+
+
+def _lfilter_arrays(b, a):
+    n = len(a)
+    return (ctypes.c_double * n)(*b), (ctypes.c_double * n)(*a)
+
+
+def lfilter_covers(b, a):
+    """True where ``tac_lfilter_f32`` takes these coefficients (tuples of Python floats, ``a[0] != 0`` already checked): at most
+    three per side, and a state transition over one tile that is finite in float64 (any stable filter, and the unstable ones up to
+    a pole radius of about 1.09)."""
+    key = (tuple(b), tuple(a))
+    hit = _lfilter_ok.get(key)
+    if hit is None:
+        if len(key[1]) > LFILTER_MAX_COEFFS or len(key[0]) != len(key[1]):
+            hit = False
+        else:
+            cb, ca = _lfilter_arrays(*key)
+            hit = _native.lib().tac_lfilter_supported(cb, ca, len(key[1])) == _native.TAC_OK
+        if len(_lfilter_ok) > 256:
+            _lfilter_ok.clear()
+        _lfilter_ok[key] = hit
+    return hit
+
+
+def host_coeffs(t):
+    """The coefficients of a 1-D tensor as a tuple of Python floats (float32 converts exactly).  A device tensor is read back once
+    per version of its contents (one host sync) and the tuple cached on the tensor object, like the tables of a window."""
+    if not t.is_cuda:
+        return tuple(t.detach().to(torch.float64).tolist())
+    cache = getattr(t, '_tac_coef', None)
+    stamp = _stamp(t)
+    if cache is None or cache[0] != stamp:
+        cache = (stamp, tuple(t.detach().to(torch.float64).tolist()))
+        try:
+            t._tac_coef = cache
+        except (AttributeError, RuntimeError):
+            pass
+    return cache[1]
+
+
+def lfilter_rows(x, b, a, clamp, reverse=False):
+    """``(…, L) -> (…, L)`` through ``tac_lfilter_f32``: one launch.  ``b`` / ``a`` are tuples of Python floats; ``reverse`` runs the
+    filter from the end of each row (the adjoint).  ``x`` is read where it lies when its leading dims collapse into one positive
+    row stride over unit-stride rows; it is copied otherwise."""
+    global _lfilter_chunk_checked
+    length = x.shape[-1]
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        h = _native.lib()
+        if not _lfilter_chunk_checked:
+            if h.tac_lfilter_chunk() != LFILTER_C:
+                raise RuntimeError('libtac_amd.so filters %d samples per lane, _hip.LFILTER_C says %d'
+                                   % (h.tac_lfilter_chunk(), LFILTER_C))
+            _lfilter_chunk_checked = True
+        rows = x.reshape(-1, length)
+        if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+            rows = rows.contiguous()
+        cb, ca = _lfilter_arrays(b, a)
+        with _native.on_device(x.device):
+            rc = h.tac_lfilter_f32(_native.ptr(rows), rows.shape[0], length, rows.stride(0), cb, ca, len(a), int(bool(clamp)),
+                                   int(bool(reverse)), _native.ptr(out), _native.stream_ptr(x.device))
+        _native.check(rc, 'tac_lfilter_f32')
+        _count('tac_lfilter_f32', out)
     return out
 
 

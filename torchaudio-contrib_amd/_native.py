@@ -38,7 +38,7 @@ EXPORTS = (
     'tac_db_to_amplitude_f64',
     'tac_last_route', 'tac_debug_clock_probe', 'tac_melbank_plan_pieces_host', 'tac_set_fft_pipe',
     'tac_istft_workspace', 'tac_istft_envelope_f32', 'tac_istft_f32', 'tac_istft_grad_input_f32', 'tac_istft_grad_bins_f32',
-    'tac_dct_rows_f32', 'tac_polyphase_f32',
+    'tac_dct_rows_f32', 'tac_polyphase_f32', 'tac_lfilter_chunk', 'tac_lfilter_supported', 'tac_lfilter_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -185,6 +185,10 @@ def lib():
         h.tac_istft_grad_bins_f32.argtypes = [_P, _I64, _I32, _I32, _P]
         h.tac_dct_rows_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _I32, _P, _P]
         h.tac_polyphase_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P, _P]
+        h.tac_lfilter_chunk.restype = _I32
+        h.tac_lfilter_chunk.argtypes = []
+        h.tac_lfilter_supported.argtypes = [_P, _P, _I32]
+        h.tac_lfilter_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, ctypes.c_int, ctypes.c_int, _P, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

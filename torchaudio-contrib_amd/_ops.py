@@ -10,6 +10,7 @@ see them by name.
     tac_amd::stretch_mel            "      + apply_filterbank in the same launch
     tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
     tac_amd::resample           polyphase windowed-sinc resampling of the waveform (csrc/resample.hip)
+    tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -128,7 +129,7 @@ def _plain_hip_f32(*tensors):
     return all(t is not None and type(t) is torch.Tensor and t.is_cuda and t.dtype == torch.float32 for t in tensors)
 
 
-def _register_autograd(op, fn, n_tensors, hip_backward=None):
+def _register_autograd(op, fn, n_tensors, hip_backward=None, n_plain=None, save_output=None):
     """Backward of ``tac_amd::<op>``.  ``hip_backward(tensors, rest, needs, grads)`` — the hand-written gradient
     kernels (csrc/backward.hip) — is used when it applies (float32 on a HIP device); it returns None otherwise and
     the op is then differentiated by re-evaluating it with differentiable torch operators (``_composite``) on the
@@ -139,26 +140,34 @@ def _register_autograd(op, fn, n_tensors, hip_backward=None):
     Double backward (``create_graph=True``; the reference, being stock torch operators, is twice differentiable): the
     gradient kernels produce values without a graph, so a backward pass that is itself recorded re-evaluates the op
     with torch operators on the SAVED tensors — still attached to the caller's graph — and differentiates that with
-    ``create_graph=True``."""
+    ``create_graph=True``.
+
+    ``n_plain``: how many of the leading tensors have to be float32 on a HIP device for the gradient kernels (all of them by
+    default; ``lfilter``'s coefficient tensors may be float64 and may live on the host).  ``save_output(inputs)``: where true
+    the op's output is saved too and handed to ``hip_backward`` behind the input tensors."""
 
     def setup_context(ctx, inputs, output):
-        ctx.save_for_backward(*inputs[:n_tensors])
+        if save_output is not None and save_output(inputs):
+            ctx.save_for_backward(*inputs[:n_tensors], output)
+        else:
+            ctx.save_for_backward(*inputs[:n_tensors])
         ctx.rest = tuple(inputs[n_tensors:])
 
     def backward(ctx, *grads):
         needs = ctx.needs_input_grad[:n_tensors]
-        saved = ctx.saved_tensors
+        kept = ctx.saved_tensors
+        saved = kept[:n_tensors]
         second_order = torch.is_grad_enabled()
         why = 'double backward (create_graph=True)' if second_order else None
         if why is None and hip_backward is not None:
-            if _plain_hip_f32(*saved) and all(g is None or _plain_hip_f32(g) for g in grads):
+            if _plain_hip_f32(*kept[n_tensors:], *saved[:n_plain]) and all(g is None or _plain_hip_f32(g) for g in grads):
                 with torch.no_grad():
-                    res = hip_backward(saved, ctx.rest, needs, grads)
+                    res = hip_backward(kept, ctx.rest, needs, grads)
                 if res is not None:
                     return tuple(res) + (None,) * len(ctx.rest)
                 why = 'this gradient has no gfx950 kernel'
             else:
-                why = _hip_dtype(*[t for t in tuple(saved) + tuple(grads) if t is not None]) or 'tensor subclass'
+                why = _hip_dtype(*[t for t in tuple(saved[:n_plain]) + tuple(grads) if t is not None]) or 'tensor subclass'
         elif why is None:
             why = 'the op has no gradient kernel'
         if any(t.is_cuda for t in saved):
@@ -371,7 +380,23 @@ def _resample_hip_backward(saved, rest, needs, grads):
     return [H.polyphase(grads[0], tuple(rest), int(wave.shape[-1]), adjoint=True)]
 
 
-_HIP_BACKWARD = {'stft': _stft_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+def _lfilter_hip_backward(saved, rest, needs, grads):
+    wave, a, b = saved[:3]
+    (clamp,) = rest
+    if grads[0] is None or needs[1] or needs[2]:
+        return None                 # (the coefficients' gradient: the stock-torch route, announced)
+    ha, hb = H.host_coeffs(a), H.host_coeffs(b)
+    if not H.lfilter_covers(hb, ha):
+        return None
+    g = grads[0]
+    if clamp:                       # the clamp passes the gradient where the saved output lies strictly inside (-1, 1)
+        y = saved[3]
+        g = g * ((y > -1.0) & (y < 1.0))
+    # the adjoint of a causal filter is the same filter run backwards in time: the same kernel, walking each row from its end
+    return [H.lfilter_rows(g, hb, ha, False, reverse=True) if needs[0] else None, None, None]
+
+
+_HIP_BACKWARD = {'stft': _stft_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -404,14 +429,14 @@ def call(op, *args):
     return getattr(ops, op)(*args)
 
 
-def _register(op, schema, cuda, cpu, fake, n_tensors, differentiable=True):
+def _register(op, schema, cuda, cpu, fake, n_tensors, differentiable=True, **autograd_kw):
     cuda_kernels[op] = cuda
     _lib.define(op + schema)
     _lib.impl(op, cuda, 'CUDA')
     _lib.impl(op, cpu, 'CPU')
     torch.library.register_fake('%s::%s' % (NS, op), fake, lib=_lib)
     if differentiable:
-        _register_autograd(op, cpu, n_tensors, _HIP_BACKWARD.get(op))
+        _register_autograd(op, cpu, n_tensors, _HIP_BACKWARD.get(op), **autograd_kw)
 
 
 # ============================================================================= stft
@@ -634,6 +659,35 @@ def _resample_fake(wave, orig, new, lowpass_filter_width, rolloff, method, beta)
 
 _register('resample', '(Tensor wave, int orig, int new, int lowpass_filter_width, float rolloff, str method, float? beta) '
           '-> Tensor', _resample_cuda, C.resample, _resample_fake, 1)
+
+
+# ============================================================================= lfilter
+def _lfilter_cuda(wave, a_coeffs, b_coeffs, clamp):
+    if wave.numel() == 0:
+        return torch.empty_like(wave, memory_format=torch.contiguous_format)
+    reason = _hip_dtype(wave)
+    if reason is None and a_coeffs.numel() > H.LFILTER_MAX_COEFFS:
+        reason = 'filter order %d (the kernel takes order <= 2)' % (a_coeffs.numel() - 1)
+    if reason is None and any(st <= 0 for st, n in zip(wave.stride(), wave.shape) if n > 1):
+        reason = 'non-positive strides'
+    if reason is None:
+        ha, hb = H.host_coeffs(a_coeffs), H.host_coeffs(b_coeffs)
+        if not H.lfilter_covers(hb, ha):
+            reason = 'a filter whose state transition over one tile overflows float64'
+    if reason is not None:
+        _composite_route('lfilter', reason)
+        return C.lfilter(wave, a_coeffs, b_coeffs, clamp)
+    out = H.lfilter_rows(_f32(wave), hb, ha, clamp)
+    return out if wave.dtype == out.dtype else out.to(wave.dtype)
+
+
+def _lfilter_fake(wave, a_coeffs, b_coeffs, clamp):
+    return torch.empty_like(wave, memory_format=torch.contiguous_format)
+
+
+# (the wave alone has to be a float32 HIP tensor for the gradient kernel; the output is saved where the clamp needs its mask)
+_register('lfilter', '(Tensor wave, Tensor a_coeffs, Tensor b_coeffs, bool clamp) -> Tensor', _lfilter_cuda, C.lfilter,
+          _lfilter_fake, 3, n_plain=1, save_output=lambda inputs: bool(inputs[3]))
 
 
 # ============================================================================= complex pairs

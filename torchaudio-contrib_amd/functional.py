@@ -19,12 +19,14 @@ import torch
 
 from . import _hip
 from . import _ops
+from . import _filters
 from . import _resample
 from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample']
+           'create_dct', 'dct', 'resample', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
 
 _call = _ops.call
 
@@ -236,6 +238,99 @@ def resample(waveforms, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.9
     if args[0] == args[1]:
         return x
     return _call('resample', x, *args)
+
+
+def _waveform(waveforms, what):
+    x = _tensor(waveforms, 'waveforms')
+    if x.dim() < 1:
+        raise RuntimeError('%s: expected a tensor of shape (…, time), got a scalar' % what)
+    if not x.is_floating_point():
+        raise RuntimeError('%s: expected a floating-point waveform, got %s' % (what, x.dtype))
+    return x
+
+
+def lfilter(waveforms, a_coeffs, b_coeffs, clamp=True):
+    """``(…, L) → (…, L)``: torchaudio's ``functional.lfilter`` — the difference equation
+
+        a0 y[n] = sum_k b_k x[n-k] - sum_{k>=1} a_k y[n-k]
+
+    along the last axis with zero initial state; ``clamp`` limits the result to [-1, 1].  ``a_coeffs`` and ``b_coeffs`` are 1-D
+    tensors of equal length with ``a_coeffs[0] != 0`` (``ValueError`` otherwise).  2-D coefficient banks (torchaudio's one filter
+    per channel) are out of scope and raise ``ValueError`` too.
+
+    float32 on a HIP device with at most three coefficients per side runs ONE launch of the gfx950 kernel (csrc/lfilter.hip):
+    float32 loads and stores around a float64 recursion, so the result is the float64 filter rounded once.  The coefficients reach
+    it as doubles (float32 tensors convert exactly; a device tensor is read back once and cached).  Its gradient w.r.t. the
+    waveform is the same kernel run from the end of each row.  Higher orders, float64, non-positive strides and the gradient
+    w.r.t. the coefficients take the time loop of ``_composite.lfilter`` (also the CPU path): correct and slow, announced with
+    ``CompositeRouteWarning`` on a device."""
+    x = _waveform(waveforms, 'lfilter')
+    _filters.check_coeffs(a_coeffs, b_coeffs)
+    if not torch.compiler.is_compiling() and _hip.host_coeffs(a_coeffs)[0] == 0.0:
+        raise ValueError('lfilter: a_coeffs[0] must not be zero')
+    return _call('lfilter', x, a_coeffs, b_coeffs, bool(clamp))
+
+
+def biquad(waveforms, b0, b1, b2, a0, a1, a2):
+    """torchaudio's ``functional.biquad``: ``lfilter`` with ``b = (b0, b1, b2)``, ``a = (a0, a1, a2)`` (Python numbers, kept in
+    float64), clamped to [-1, 1] as ``lfilter`` is by default."""
+    if float(a0) == 0.0:
+        raise ValueError('biquad: a0 must not be zero')
+    return lfilter(waveforms, _filters.host_tensor((a0, a1, a2)), _filters.host_tensor((b0, b1, b2)), True)
+
+
+def _design(waveforms, coeffs):
+    b, a = coeffs
+    return biquad(waveforms, b[0], b[1], b[2], a[0], a[1], a[2])
+
+
+def lowpass_biquad(waveforms, sample_rate, cutoff_freq, Q=0.707):
+    """Second-order low-pass (RBJ audio-EQ cookbook), computed in float64 on the host.  With ``w0 = 2 pi cutoff_freq /
+    sample_rate`` and ``alpha = sin(w0) / (2 Q)``: ``b = ((1 - cos w0) / 2, 1 - cos w0, (1 - cos w0) / 2)``,
+    ``a = (1 + alpha, -2 cos w0, 1 - alpha)``."""
+    return _design(waveforms, _filters.lowpass(sample_rate, cutoff_freq, Q))
+
+
+def highpass_biquad(waveforms, sample_rate, cutoff_freq, Q=0.707):
+    """Second-order high-pass: ``b = ((1 + cos w0) / 2, -(1 + cos w0), (1 + cos w0) / 2)``, ``a = (1 + alpha, -2 cos w0,
+    1 - alpha)``; ``w0``, ``alpha`` as for ``lowpass_biquad``."""
+    return _design(waveforms, _filters.highpass(sample_rate, cutoff_freq, Q))
+
+
+def bandpass_biquad(waveforms, sample_rate, central_freq, Q=0.707, const_skirt_gain=False):
+    """Second-order band-pass: ``b = (t, 0, -t)`` with ``t = alpha`` (0 dB peak gain) or, ``const_skirt_gain``,
+    ``t = sin(w0) / 2`` (peak gain Q); ``a = (1 + alpha, -2 cos w0, 1 - alpha)``."""
+    return _design(waveforms, _filters.bandpass(sample_rate, central_freq, Q, const_skirt_gain))
+
+
+def bandreject_biquad(waveforms, sample_rate, central_freq, Q=0.707):
+    """Second-order band-reject (notch): ``b = (1, -2 cos w0, 1)``, ``a = (1 + alpha, -2 cos w0, 1 - alpha)``."""
+    return _design(waveforms, _filters.bandreject(sample_rate, central_freq, Q))
+
+
+def allpass_biquad(waveforms, sample_rate, central_freq, Q=0.707):
+    """Second-order all-pass: ``b = (1 - alpha, -2 cos w0, 1 + alpha)``, ``a = (1 + alpha, -2 cos w0, 1 - alpha)``."""
+    return _design(waveforms, _filters.allpass(sample_rate, central_freq, Q))
+
+
+def equalizer_biquad(waveforms, sample_rate, center_freq, gain, Q=0.707):
+    """Peaking equalizer of ``gain`` dB at ``center_freq``: with ``A = 10^(gain / 40)``, ``b = (1 + alpha A, -2 cos w0,
+    1 - alpha A)``, ``a = (1 + alpha / A, -2 cos w0, 1 - alpha / A)``."""
+    return _design(waveforms, _filters.equalizer(sample_rate, center_freq, gain, Q))
+
+
+def preemphasis(waveforms, coeff=0.97):
+    """``y[n] = x[n] - coeff x[n-1]``, ``y[0] = x[0]`` (torchaudio's ``functional.preemphasis``); not clamped.  The same kernel
+    as ``lfilter`` with ``b = (1, -coeff)``, ``a = (1, 0)``: no recursion, one read and one write of the waveform."""
+    x = _waveform(waveforms, 'preemphasis')
+    return _call('lfilter', x, _filters.host_tensor((1.0, 0.0)), _filters.host_tensor((1.0, -float(coeff))), False)
+
+
+def deemphasis(waveforms, coeff=0.97):
+    """The inverse of ``preemphasis``: ``y[n] = x[n] + coeff y[n-1]``, i.e. ``lfilter`` with ``a = (1, -coeff)``, ``b = (1, 0)``;
+    not clamped."""
+    x = _waveform(waveforms, 'deemphasis')
+    return _call('lfilter', x, _filters.host_tensor((1.0, -float(coeff))), _filters.host_tensor((1.0, 0.0)), False)
 
 
 def _check_pairs(z, what):

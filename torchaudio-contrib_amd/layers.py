@@ -13,8 +13,10 @@ import torch
 import torch.nn as nn
 
 from . import functional as F
+from . import _filters
 from . import _hip
 from . import _lazy
+from . import _ops
 from . import _resample
 from ._lazy import DeferredSpectral, DeferredWave, can_defer, can_defer_codes, lazy_fusion_enabled, realize
 
@@ -365,6 +367,60 @@ class Resample(_ModuleNoStateBuffers):
     def __repr__(self):
         return self.__class__.__name__ + '(orig_freq={}, new_freq={}, lowpass_filter_width={}, rolloff={}, resampling_method={}, beta={})'.format(
             self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
+
+
+class LFilter(_ModuleNoStateBuffers):
+    """``functional.lfilter`` as a layer: ``(…, time)`` → ``(…, time)``.  The two 1-D coefficient tensors are the non-persistent
+    buffers ``a_coeffs`` / ``b_coeffs`` (kept in float64 unless given otherwise; they follow ``.to()`` — a change of dtype rounds
+    them like any buffer — and stay out of ``state_dict()``)."""
+
+    def __init__(self, a_coeffs, b_coeffs, clamp=True):
+        super(LFilter, self).__init__()
+        a = torch.as_tensor(a_coeffs, dtype=None if torch.is_tensor(a_coeffs) else torch.float64)
+        b = torch.as_tensor(b_coeffs, dtype=None if torch.is_tensor(b_coeffs) else torch.float64)
+        _filters.check_coeffs(a, b)
+        if _hip.host_coeffs(a)[0] == 0.0:
+            raise ValueError('lfilter: a_coeffs[0] must not be zero')
+        self.clamp = bool(clamp)
+        self.register_buffer('a_coeffs', a.detach().clone())
+        self.register_buffer('b_coeffs', b.detach().clone())
+
+    def forward(self, waveforms):
+        return _ops.call('lfilter', F._waveform(waveforms, 'lfilter'), self.a_coeffs, self.b_coeffs, self.clamp)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(order={}, clamp={})'.format(self.a_coeffs.numel() - 1, self.clamp)
+
+
+class Preemphasis(_ModuleNoStateBuffers):
+    """``functional.preemphasis`` as a layer: ``y[n] = x[n] - coeff x[n-1]``.  No buffers: ``coeff`` is a Python float, and the
+    two float64 host tensors the op takes are plain attributes (they stay float64 on the host whatever ``.to()`` is given)."""
+
+    def __init__(self, coeff=0.97):
+        super(Preemphasis, self).__init__()
+        self.coeff = float(coeff)
+        self._a, self._b = _filters.host_tensor((1.0, 0.0)), _filters.host_tensor((1.0, -self.coeff))
+
+    def forward(self, waveforms):
+        return _ops.call('lfilter', F._waveform(waveforms, 'preemphasis'), self._a, self._b, False)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(coeff={})'.format(self.coeff)
+
+
+class Deemphasis(_ModuleNoStateBuffers):
+    """``functional.deemphasis`` as a layer: ``y[n] = x[n] + coeff y[n-1]``.  No buffers, as ``Preemphasis``."""
+
+    def __init__(self, coeff=0.97):
+        super(Deemphasis, self).__init__()
+        self.coeff = float(coeff)
+        self._a, self._b = _filters.host_tensor((1.0, -self.coeff)), _filters.host_tensor((1.0, 0.0))
+
+    def forward(self, waveforms):
+        return _ops.call('lfilter', F._waveform(waveforms, 'deemphasis'), self._a, self._b, False)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(coeff={})'.format(self.coeff)
 
 
 class DbToAmplitude(_ModuleNoStateBuffers):
