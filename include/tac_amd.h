@@ -501,6 +501,47 @@ int tac_lfilter_supported(const double* b, const double* a, int32_t n_coeffs);
 int tac_lfilter_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const double* b, const double* a,
                     int32_t n_coeffs, int clamp, int reverse, float* out, void* stream);
 
+/* (17) functional.fftconvolve / convolve: uniformly partitioned overlap-save on (1) and the frame kernels of (13), and the kernel
+ *      between them.  B = n_fft / 2, F = B + 1, P = ceil(m / B) partitions, n_fft one of 2048 / 4096 / 8192.
+ *      tac_spectral_mac_f32 (the frequency-domain delay line):
+ *        Y[r][t][f] = sum_{p = 0 .. min(P-1, t)} X[r][t-p][f] * H[hrow(r)][p][f]     (complex, f < n_bins)
+ *      X, Y: float[rows][T][n_bins][2] frame-major (what (1) writes and (13) reads), H: float[h_rows][P][n_bins][2]; hrow: DEVICE
+ *      int32[rows] (values are clamped to 0 .. h_rows - 1), NULL = every row uses kernel 0; conj != 0 multiplies by conj(H).
+ *      One launch; a lane owns one bin of one row over tac_spectral_mac_tile(P) consecutive frames.  The real and the imaginary part
+ *      of an output are each ONE fused multiply-add chain in ascending p (x_r h_r, then -x_i h_i; x_r h_i, then x_i h_r); frames
+ *      with t - p < 0 are neither read nor multiplied; one writer per output, no atomics, no workspace, no LDS: bit-identical from
+ *      run to run.  P <= 16: H_p of the bin and a ring of the last frames of X in registers (instantiations for P <= 4 / 8 / 16);
+ *      16 < P <= 64: H streamed.  P > 64: TAC_E_UNSUPPORTED, nothing launched.  X, H, Y 8-byte aligned.
+ *      tac_fftconvolve_spectra_f32: H[hr][p] = the n_fft-point one-sided transform of [y[hr][p B .. (p+1) B) | B zeros] (y read from
+ *        its END when reverse != 0: the kernel of the gradient w.r.t. x); y[hr][i] = y[hr*stride_r + i], i < m.  A function of y and
+ *        n_fft only: callers cache it.  workspace: tac_fftconvolve_spectra_workspace(h_rows, m, n_fft) bytes, 16-byte aligned.
+ *      tac_fftconvolve_f32: out[r][j] = full[r][j + offset], j < l_out, full = x[r] * y[hrow(r)] of l_in + m - 1 samples
+ *        (offset + l_out <= l_in + m - 1); x[r][i] = x[r*stride_r + i] (any alignment), out[r][j] = out[r*out_stride + j].
+ *        Five steps per chunk of rows: padded copy, (1) at hop B with a window of ones, tac_spectral_mac_f32, the frame kernels of
+ *        (13) in inverse mode, and a gather of the kept second halves (never the discarded halves: a non-finite sample of input
+ *        block b reaches output blocks b .. b + P of its row and nothing else).  workspace: tac_fftconvolve_workspace(...) bytes
+ *        (16-byte aligned) — the padded copy, X and Y (the inverse's frames reuse X) for as many rows as fit under 1 GiB; the entry
+ *        point walks the rows in chunks of what the workspace it is given holds (any size from one row's need up).
+ *        tac_fftconvolve_supported: TAC_OK, or TAC_E_UNSUPPORTED for P > 64, another n_fft, 32-bit overflow or a row beyond 1 GiB.
+ *        tac_fftconvolve_default_n_fft: the smallest n_fft with P <= 8, else 8192.
+ *      tac_fftconvolve_direct_f32: the same result for ONE short shared kernel through (15) with one phase at step 1: bank = DEVICE
+ *        float[m], the kernel from its end; table = DEVICE int32[2] = {offset - (m - 1), m}.
+ *      tac_last_route() names the route: "spectral-2048" / "spectral-4096" / "spectral-8192" / "direct". */
+int32_t tac_spectral_mac_tile(int32_t n_parts);
+int tac_spectral_mac_f32(const float* X, const float* H, const int32_t* hrow, int64_t rows, int64_t n_frames, int32_t n_bins,
+                         int32_t n_parts, int32_t h_rows, int conj, float* Y, void* stream);
+int32_t tac_fftconvolve_default_n_fft(int64_t m);
+int tac_fftconvolve_supported(int64_t l_in, int64_t m, int32_t n_fft);
+int64_t tac_fftconvolve_spectra_workspace(int64_t h_rows, int64_t m, int32_t n_fft);
+int tac_fftconvolve_spectra_f32(const float* y, int64_t h_rows, int64_t m, int64_t stride_r, int32_t n_fft, int reverse,
+                                void* workspace, int64_t workspace_bytes, float* H, void* stream);
+int64_t tac_fftconvolve_workspace(int64_t rows, int64_t l_in, int64_t m, int32_t n_fft, int64_t offset, int64_t l_out);
+int tac_fftconvolve_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride_r, const float* H, const int32_t* hrow,
+                        int32_t h_rows, int64_t m, int32_t n_fft, int conj, int64_t offset, int64_t l_out, void* workspace,
+                        int64_t workspace_bytes, float* out, int64_t out_stride, void* stream);
+int tac_fftconvolve_direct_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride_r, const float* bank, const int32_t* table,
+                               int64_t m, int64_t offset, int64_t l_out, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,15 @@ def lfilter(wave, a_coeffs, b_coeffs, clamp):
     return y.reshape(wave.shape)
 
 
+def fftconvolve(x, y, n_fft=0):
+    """torchaudio's ``functional.fftconvolve`` in ``'full'`` mode: the one-shot form, ``irfft(rfft(x, n) * rfft(y, n), n)`` at
+    ``n = L + M - 1`` along the last dimension, the leading dimensions broadcast.  ``n_fft`` (the partition size of the gfx950
+    route) has no meaning here."""
+    n = x.shape[-1] + y.shape[-1] - 1
+    out = torch.fft.irfft(torch.fft.rfft(x, n=n, dim=-1) * torch.fft.rfft(y, n=n, dim=-1), n=n, dim=-1)
+    return out.contiguous()
+
+
 def amplitude_to_db(x, ref, amin):
     """reference functional.py:291-296: the input is squared, the square clamped, then 10·(log10 − log10 ref)."""
     floor_applied = (x ** 2.0).clamp(min=amin)

@@ -37,7 +37,7 @@ def _count(name, *filled):
 # through an alias created before the cache, ``from_dlpack`` / raw-pointer writers — cannot be seen without reading the
 # tensor back on every call; after such a write call ``invalidate(t)`` (or ``invalidate()`` for everything).
 _epoch = 0
-_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite', '_tac_istft', '_tac_dct', '_tac_coef')
+_CACHE_ATTRS = ('_tac_pack', '_tac_plan', '_tac_T', '_tac_adj', '_tac_dft', '_tac_dftT', '_tac_finite', '_tac_istft', '_tac_dct', '_tac_coef', '_tac_conv')
 
 
 _unstamped = itertools.count()
@@ -983,6 +983,157 @@ def lfilter_rows(x, b, a, clamp, reverse=False):
         _native.check(rc, 'tac_lfilter_f32')
         _count('tac_lfilter_f32', out)
     return out
+
+
+# ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
+#: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
+FFTCONV_SIZES = (2048, 4096, 8192)
+FFTCONV_MAX_PARTS = 64
+#: longest ONE shared kernel that takes ``tac_polyphase_f32`` (one phase, step 1) instead of the transforms.  256 is the unmeasured
+#: default; ``tools/bench_fftconvolve.py`` measures the crossover
+M_DIRECT = 256
+
+
+def fftconvolve_n_fft(m):
+    """The default transform length for a kernel of ``m`` taps: the smallest with at most 8 partitions, else 8192 (unmeasured
+    rule; ``tac_fftconvolve_default_n_fft`` is the same rule in the library)."""
+    for n in FFTCONV_SIZES[:-1]:
+        if -(-m // (n // 2)) <= 8:
+            return n
+    return FFTCONV_SIZES[-1]
+
+
+def fftconvolve_covers(length, m, n_fft=0):
+    """True where the partitioned route takes a kernel of ``m`` taps at ``n_fft`` (0: the default rule)."""
+    n = n_fft or fftconvolve_n_fft(m)
+    if n not in FFTCONV_SIZES or -(-m // (n // 2)) > FFTCONV_MAX_PARTS:
+        return False
+    return _native.lib().tac_fftconvolve_supported(length, m, n) == _native.TAC_OK
+
+
+def cached_on(t, attr, key, build):
+    """``build()`` once per (contents of ``t``, ``key``): the table lives on the tensor object under ``attr``, stamped like the
+    tables of a window (version counter, data pointer, invalidation epoch), so an in-place write to ``t`` rebuilds it."""
+    cache = getattr(t, attr, None)
+    stamp = _stamp(t)
+    if cache is None or cache[0] != stamp:
+        cache = (stamp, {})
+        try:
+            setattr(t, attr, cache)
+        except (AttributeError, RuntimeError):
+            pass
+    hit = cache[1].get(key)
+    if hit is None:
+        if len(cache[1]) > 16:
+            cache[1].clear()
+        with torch.inference_mode(False):
+            hit = cache[1][key] = build()
+    return hit
+
+
+def _conv_kernel_rows(y):
+    m = int(y.shape[-1])
+    rows = y.detach().reshape(-1, m)
+    return rows if rows.is_contiguous() else rows.contiguous()
+
+
+def _conv_spectra(y, n_fft, reverse):
+    """``H``: float32 ``(h_rows, P, n_fft / 2 + 1, 2)`` of ``tac_fftconvolve_spectra_f32``, cached on ``y``."""
+    def build():
+        rows = _conv_kernel_rows(y)
+        h_rows, m = int(rows.shape[0]), int(rows.shape[1])
+        h = _native.lib()
+        need = int(h.tac_fftconvolve_spectra_workspace(h_rows, m, n_fft))
+        if need < 0:
+            _native.check(need, 'tac_fftconvolve_spectra_workspace')
+        work = torch.empty(need // 4, dtype=torch.float32, device=y.device)      # scratch: written before it is read
+        out = _empty((h_rows, -(-m // (n_fft // 2)), n_fft // 2 + 1, 2), device=y.device)
+        with _native.on_device(y.device):
+            rc = h.tac_fftconvolve_spectra_f32(_native.ptr(rows), h_rows, m, rows.stride(0), n_fft, int(bool(reverse)),
+                                               _native.ptr(work), need, _native.ptr(out), _native.stream_ptr(y.device))
+        _native.check(rc, 'tac_fftconvolve_spectra_f32')
+        _count('tac_fftconvolve_spectra_f32', out)
+        return out
+    return cached_on(y, '_tac_conv', ('spectra', n_fft, bool(reverse)), build)
+
+
+def _conv_direct_bank(y, reverse, offset):
+    """the kernel from its end (from its start for the gradient) and the {offset, run} table of ``tac_fftconvolve_direct_f32``"""
+    def build():
+        row = _conv_kernel_rows(y)[0]
+        bank = (row.clone() if reverse else row.flip(0)).contiguous()
+        table = torch.tensor([offset - (int(row.shape[0]) - 1), int(row.shape[0])], dtype=torch.int32).to(y.device)
+        return bank, table
+    return cached_on(y, '_tac_conv', ('direct', bool(reverse), offset), build)
+
+
+def _conv_row_map(y, lead):
+    """int32 map from the rows of the broadcast leading shape ``lead`` to the rows of ``y`` (None: one shared kernel)"""
+    h_rows = 1
+    for n in y.shape[:-1]:
+        h_rows *= int(n)
+    if h_rows == 1:
+        return None
+
+    def build():
+        idx = torch.arange(h_rows, dtype=torch.int32).reshape(tuple(y.shape[:-1])).expand(lead)
+        return idx.reshape(-1).contiguous().to(y.device)
+    return cached_on(y, '_tac_conv', ('map', tuple(lead)), build)
+
+
+def fftconvolve_route(m, shared, n_fft=0):
+    """'direct' or the transform length the call takes"""
+    if not n_fft and shared and m <= M_DIRECT:
+        return 'direct'
+    return n_fft or fftconvolve_n_fft(m)
+
+
+def fftconvolve(x, y, n_fft=0, reverse=False, offset=0, out_len=None):
+    """``(*, L)``, ``(*, M)`` float32 -> ``(*, out_len)``: samples ``offset .. offset + out_len`` of the full convolution of
+    ``x`` with ``y`` (with ``y`` read from its end when ``reverse``: the gradient w.r.t. ``x``), the leading dimensions
+    broadcast.  ``x`` is read where it lies when its leading dims collapse into one positive row stride over unit-stride rows;
+    it is copied otherwise.  ``n_fft`` 0: the default rule, and the direct route for one shared kernel of at most ``M_DIRECT``
+    taps."""
+    length, m = int(x.shape[-1]), int(y.shape[-1])
+    lead = tuple(torch.broadcast_shapes(tuple(x.shape[:-1]), tuple(y.shape[:-1])))
+    out_len = length + m - 1 - offset if out_len is None else int(out_len)
+    out = _empty(lead + (out_len,), device=x.device)
+    if not out.numel():
+        return out
+    if tuple(x.shape[:-1]) != lead:
+        x = x.expand(lead + (length,))
+    rows = x.reshape(-1, length)
+    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) < length):
+        rows = rows.contiguous()
+    n_rows = int(rows.shape[0])
+    hrow = _conv_row_map(y, lead)
+    h = _native.lib()
+    route = fftconvolve_route(m, hrow is None, n_fft)
+    with _native.on_device(x.device):
+        stream = _native.stream_ptr(x.device)
+        if route == 'direct':
+            bank, table = _conv_direct_bank(y, reverse, offset)
+            rc = h.tac_fftconvolve_direct_f32(_native.ptr(rows), n_rows, length, rows.stride(0), _native.ptr(bank),
+                                              _native.ptr(table), m, offset, out_len, _native.ptr(out), stream)
+            _native.check(rc, 'tac_fftconvolve_direct_f32')
+            _count('tac_fftconvolve_direct_f32', out)
+            return out
+        spectra = _conv_spectra(y, route, reverse)
+        need = int(h.tac_fftconvolve_workspace(n_rows, length, m, route, offset, out_len))
+        if need < 0:
+            _native.check(need, 'tac_fftconvolve_workspace')
+        work = torch.empty(need // 4, dtype=torch.float32, device=x.device)      # scratch: every area is written before it is read
+        rc = h.tac_fftconvolve_f32(_native.ptr(rows), n_rows, length, rows.stride(0), _native.ptr(spectra),
+                                   None if hrow is None else _native.ptr(hrow), int(spectra.shape[0]), m, route, 0, offset,
+                                   out_len, _native.ptr(work), need, _native.ptr(out), out_len, stream)
+    _native.check(rc, 'tac_fftconvolve_f32')
+    _count('tac_fftconvolve_f32', out)
+    return out
+
+
+def last_route():
+    """``tac_last_route()`` of the calling thread"""
+    return _native.lib().tac_last_route().decode()
 
 
 # ----------------------------------------------------------------------------- complex pairs

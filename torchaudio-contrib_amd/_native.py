@@ -39,6 +39,9 @@ EXPORTS = (
     'tac_last_route', 'tac_debug_clock_probe', 'tac_melbank_plan_pieces_host', 'tac_set_fft_pipe',
     'tac_istft_workspace', 'tac_istft_envelope_f32', 'tac_istft_f32', 'tac_istft_grad_input_f32', 'tac_istft_grad_bins_f32',
     'tac_dct_rows_f32', 'tac_polyphase_f32', 'tac_lfilter_chunk', 'tac_lfilter_supported', 'tac_lfilter_f32',
+    'tac_spectral_mac_tile', 'tac_spectral_mac_f32', 'tac_fftconvolve_default_n_fft', 'tac_fftconvolve_supported',
+    'tac_fftconvolve_spectra_workspace', 'tac_fftconvolve_spectra_f32', 'tac_fftconvolve_workspace', 'tac_fftconvolve_f32',
+    'tac_fftconvolve_direct_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -189,6 +192,20 @@ def lib():
         h.tac_lfilter_chunk.argtypes = []
         h.tac_lfilter_supported.argtypes = [_P, _P, _I32]
         h.tac_lfilter_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, ctypes.c_int, ctypes.c_int, _P, _P]
+        h.tac_spectral_mac_tile.restype = _I32
+        h.tac_spectral_mac_tile.argtypes = [_I32]
+        h.tac_spectral_mac_f32.argtypes = [_P, _P, _P, _I64, _I64, _I32, _I32, _I32, ctypes.c_int, _P, _P]
+        h.tac_fftconvolve_default_n_fft.restype = _I32
+        h.tac_fftconvolve_default_n_fft.argtypes = [_I64]
+        h.tac_fftconvolve_supported.argtypes = [_I64, _I64, _I32]
+        h.tac_fftconvolve_spectra_workspace.restype = _I64
+        h.tac_fftconvolve_spectra_workspace.argtypes = [_I64, _I64, _I32]
+        h.tac_fftconvolve_spectra_f32.argtypes = [_P, _I64, _I64, _I64, _I32, ctypes.c_int, _P, _I64, _P, _P]
+        h.tac_fftconvolve_workspace.restype = _I64
+        h.tac_fftconvolve_workspace.argtypes = [_I64, _I64, _I64, _I32, _I64, _I64]
+        h.tac_fftconvolve_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, _I64, _I32, ctypes.c_int, _I64, _I64, _P, _I64, _P,
+                                          _I64, _P]
+        h.tac_fftconvolve_direct_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

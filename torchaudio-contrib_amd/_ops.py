@@ -10,6 +10,7 @@ see them by name.
     tac_amd::stretch_mel            "      + apply_filterbank in the same launch
     tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
     tac_amd::resample           polyphase windowed-sinc resampling of the waveform (csrc/resample.hip)
+    tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
@@ -396,7 +397,19 @@ def _lfilter_hip_backward(saved, rest, needs, grads):
     return [H.lfilter_rows(g, hb, ha, False, reverse=True) if needs[0] else None, None, None]
 
 
-_HIP_BACKWARD = {'stft': _stft_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+def _fftconvolve_hip_backward(saved, rest, needs, grads):
+    x, y = saved
+    (n_fft,) = rest
+    length, m = int(x.shape[-1]), int(y.shape[-1])
+    if grads[0] is None or needs[1]:
+        return None                 # (the kernel's gradient: the stock-torch route, announced)
+    if tuple(grads[0].shape[:-1]) != tuple(x.shape[:-1]) or not H.fftconvolve_covers(length + m - 1, m, n_fft):
+        return None                 # (x itself was broadcast: its gradient is a sum over rows)
+    # the same route with the kernel read from its end: samples M - 1 .. M - 1 + L of grad_out * reversed(y)
+    return [H.fftconvolve(grads[0], y, n_fft, reverse=True, offset=m - 1, out_len=length), None]
+
+
+_HIP_BACKWARD = {'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -659,6 +672,37 @@ def _resample_fake(wave, orig, new, lowpass_filter_width, rolloff, method, beta)
 
 _register('resample', '(Tensor wave, int orig, int new, int lowpass_filter_width, float rolloff, str method, float? beta) '
           '-> Tensor', _resample_cuda, C.resample, _resample_fake, 1)
+
+
+# ============================================================================= fftconvolve
+def _conv_shape(x, y):
+    return tuple(torch.broadcast_shapes(tuple(x.shape[:-1]), tuple(y.shape[:-1]))) + (x.shape[-1] + y.shape[-1] - 1,)
+
+
+def _fftconvolve_cuda(x, y, n_fft):
+    _same_device('fftconvolve', x, y)
+    length, m = x.shape[-1], y.shape[-1]
+    if x.numel() == 0 or y.numel() == 0:
+        return x.new_zeros(_conv_shape(x, y))
+    reason = _hip_dtype(x, y)
+    if reason is None and any(st <= 0 for t in (x, y) for st, n in zip(t.stride(), t.shape) if n > 1):
+        reason = 'non-positive strides'
+    if reason is None and not H.fftconvolve_covers(length, m, n_fft):
+        reason = 'a kernel of %d taps: more than %d partitions of %d samples' % (
+            m, H.FFTCONV_MAX_PARTS, (n_fft or H.fftconvolve_n_fft(m)) // 2)
+    if reason is not None:
+        _composite_route('fftconvolve', reason)
+        return C.fftconvolve(x, y, n_fft)
+    out = H.fftconvolve(_f32(x), _f32(y), n_fft)
+    dtype = torch.promote_types(x.dtype, y.dtype)
+    return out if dtype == out.dtype else out.to(dtype)
+
+
+def _fftconvolve_fake(x, y, n_fft):
+    return x.new_empty(_conv_shape(x, y), dtype=torch.promote_types(x.dtype, y.dtype))
+
+
+_register('fftconvolve', '(Tensor x, Tensor y, int n_fft) -> Tensor', _fftconvolve_cuda, C.fftconvolve, _fftconvolve_fake, 2)
 
 
 # ============================================================================= lfilter

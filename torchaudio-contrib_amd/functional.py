@@ -25,7 +25,7 @@ from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
 
 _call = _ops.call
@@ -238,6 +238,54 @@ def resample(waveforms, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.9
     if args[0] == args[1]:
         return x
     return _call('resample', x, *args)
+
+
+_CONV_MODES = ('full', 'valid', 'same')
+
+
+def _check_conv_mode(mode):
+    if mode not in _CONV_MODES:
+        raise ValueError('Unrecognized mode value %r. Please specify one of %s.' % (mode, list(_CONV_MODES)))
+
+
+def _conv_crop(full, x_length, y_length, mode):
+    """torchaudio's ``_apply_convolve_mode``: the centred crop of the full result, as a view"""
+    if mode == 'full':
+        return full
+    target = max(x_length, y_length) - min(x_length, y_length) + 1 if mode == 'valid' else x_length
+    return full.narrow(-1, (full.shape[-1] - target) // 2, target)
+
+
+def fftconvolve(x, y, mode='full', n_fft=None):
+    """``(*, L)``, ``(*, M)`` → ``(*, L + M - 1)`` (``'full'``), its centred crop to ``max(L, M) - min(L, M) + 1`` samples
+    (``'valid'``) or to ``L`` samples (``'same'``): torchaudio's ``functional.fftconvolve`` — the convolution of ``x`` with ``y``
+    along the last dimension, the leading dimensions broadcast against each other; a crop is a view of the full result.  On a HIP
+    device: uniformly partitioned overlap-save on the STFT kernels with a frequency-domain delay line between them
+    (csrc/fftconvolve.hip) — the error of every output block is relative to the signal around it, not to the loudest passage of
+    the row — or, for one shared kernel of at most ``_hip.M_DIRECT`` taps, the polyphase kernel of ``resample`` at one phase.  The
+    gradient w.r.t. ``x`` is the same route with the kernel reversed; the gradient w.r.t. ``y`` takes torch's FFT operators
+    (announced).  ``n_fft`` (2048 / 4096 / 8192) forces the partitioned route at that transform length."""
+    _check_conv_mode(mode)
+    x, y = _tensor(x, 'x'), _tensor(y, 'y')
+    if x.dim() < 1 or y.dim() < 1 or x.dim() != y.dim():
+        raise ValueError('fftconvolve: x and y must have the same number of dimensions (>= 1), got %d and %d'
+                         % (x.dim(), y.dim()))
+    for i in range(x.dim() - 1):
+        if x.shape[i] != y.shape[i] and x.shape[i] != 1 and y.shape[i] != 1:
+            raise ValueError('fftconvolve: leading dimensions of x and y are not broadcastable (got %s and %s)'
+                             % (tuple(x.shape), tuple(y.shape)))
+    if not (x.is_floating_point() and y.is_floating_point()):
+        raise RuntimeError('fftconvolve: expected floating-point tensors, got %s and %s' % (x.dtype, y.dtype))
+    if n_fft is not None and n_fft not in _hip.FFTCONV_SIZES:
+        raise ValueError('fftconvolve: n_fft must be one of %s, got %r' % (list(_hip.FFTCONV_SIZES), n_fft))
+    full = _call('fftconvolve', x, y, int(n_fft or 0))
+    return _conv_crop(full, x.shape[-1], y.shape[-1], mode)
+
+
+def convolve(x, y, mode='full', n_fft=None):
+    """torchaudio's ``functional.convolve``: the same function as ``fftconvolve`` here — one op, ``tac_amd::fftconvolve``, which
+    picks the direct or the partitioned form by the kernel's length."""
+    return fftconvolve(x, y, mode, n_fft)
 
 
 def _waveform(waveforms, what):

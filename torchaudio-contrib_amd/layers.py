@@ -423,6 +423,29 @@ class Deemphasis(_ModuleNoStateBuffers):
         return self.__class__.__name__ + '(coeff={})'.format(self.coeff)
 
 
+class FFTConvolve(_ModuleNoStateBuffers):
+    """``functional.fftconvolve`` as a layer (torchaudio's ``transforms.FFTConvolve``): ``forward(x, y)`` with ``mode`` one of
+    ``'full'``, ``'valid'``, ``'same'``."""
+
+    def __init__(self, mode='full'):
+        super(FFTConvolve, self).__init__()
+        F._check_conv_mode(mode)
+        self.mode = mode
+
+    def forward(self, x, y):
+        return F.fftconvolve(x, y, self.mode)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(mode={!r})'.format(self.mode)
+
+
+class Convolve(FFTConvolve):
+    """``functional.convolve`` as a layer (torchaudio's ``transforms.Convolve``)."""
+
+    def forward(self, x, y):
+        return F.convolve(x, y, self.mode)
+
+
 class DbToAmplitude(_ModuleNoStateBuffers):
     """Inverse of ``AmplitudeToDb`` (reference layers.py:384-412)."""
 
