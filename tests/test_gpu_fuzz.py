@@ -13,6 +13,10 @@ Per frame (tests/frame_bounds.py): inputs come from ``signals.gained_with_silenc
 a silent row), and every op is also compared frame by frame (gradients row by row) with its float64 reference — the oracle
 evaluated in float64 on the module's own window and filterbank — where a silent frame (row) must come out exactly zero and
 the dB masks follow from the linear bounds.  ``TAC_FUZZ_REPORT=path`` appends one JSON line per check.
+
+The gradients beside the main chain — window, filterbank, ``hpss``, ``phase_vocoder``, ``stretch_norm`` / ``stretch_mel`` — are swept
+in tests/test_gradient_sweeps_gpu.py (generators and bounds in tests/grad_rules.py, the same bodies on the CPU route in
+tests/test_grad_rules_cpu.py) under the same three knobs: ``TAC_FUZZ_CASES``, ``TAC_FUZZ_SEED``, ``TAC_FUZZ_REPORT``.
 """
 import os
 

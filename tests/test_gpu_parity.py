@@ -21,6 +21,7 @@ import torch
 
 import frame_bounds as fbnd
 from conftest import rel_err
+from grad_rules import hpss_unequal
 from oracle import signals, torch_ref, numpy_ref
 
 pytestmark = pytest.mark.gpu
@@ -1820,15 +1821,7 @@ def test_hpss_gradient_kernel(tac):
         mr = torch.from_numpy(mag_np).double().requires_grad_(True)
         outs_r = torch_ref.hpss(mr, ks[0], power) if ks[0] == ks[1] else None
         if outs_r is None:                                               # unequal widths: the documented behaviour, restated with torch ops
-            kf, kt = ks
-            pf = torch.nn.functional.pad(mr, (0, 0, kf // 2, kf // 2), mode='reflect')
-            pt = torch.nn.functional.pad(mr, (kt // 2, kt // 2, 0, 0), mode='reflect')
-            perc = pf.unfold(2, kf, 1).median(dim=-1)[0]
-            harm = pt.unfold(3, kt, 1).median(dim=-1)[0]
-            if power != 1.0:
-                perc, harm = perc.pow(power), harm.pow(power)
-            mh, mp = (harm + 1e-6) / (harm + perc + 1e-6), (perc + 1e-6) / (harm + perc + 1e-6)
-            outs_r = (mr * mh, mr * mp, mh, mp)
+            outs_r = hpss_unequal(mr, ks[0], ks[1], power)
         (want,) = torch.autograd.grad(outs_r, mr, [torch.from_numpy(g).double() for g in g_np], retain_graph=True)
         m = dev(mag_np).requires_grad_(True)
         before = launches(tac)

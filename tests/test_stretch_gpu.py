@@ -23,7 +23,8 @@ import torch
 
 import frame_bounds as fbnd
 from oracle import signals, torch_ref
-from stretch_rules import grid, interpolated, lost_positions, oracle_chain, phase_advance
+from grad_rules import grid, interpolated
+from stretch_rules import lost_positions, oracle_chain, phase_advance
 
 pytestmark = pytest.mark.gpu
 
