@@ -542,6 +542,36 @@ int tac_fftconvolve_f32(const float* x, int64_t rows, int64_t l_in, int64_t stri
 int tac_fftconvolve_direct_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride_r, const float* bank, const int32_t* table,
                                int64_t m, int64_t offset, int64_t l_out, float* out, void* stream);
 
+/* (18) functional.kaldi_fbank (torchaudio.compliance.kaldi.fbank): waveform rows to log mel rows in ONE launch (csrc/kaldi_fbank.hip).
+ *      W = win_length, S = shift, N = n_fft (256 / 512 / 1024, W <= N), eps = 2^-23.
+ *      tac_kaldi_num_frames: T = (length < W ? 0 : 1 + (length - W) / S) with snip_edges, else (length + S / 2) / S.
+ *      Frame t of row r is x[r*stride_r + j], j = t S - pad .. t S - pad + W: pad = 0 with snip_edges; otherwise pad = W/2 - S/2 and
+ *      the row is mirrored at both ends (j < 0 reads x[-j - 1], j >= length reads x[2 length - 1 - j]; length >= W, else
+ *      TAC_E_UNSUPPORTED).  Per frame, in this order: the mean is subtracted (TAC_KALDI_REMOVE_DC); e = log max(sum f^2, eps)
+ *      (TAC_KALDI_RAW_ENERGY); f[i] -= preemph * f[i-1] with f[-1] := f[0] (preemph != 0); f *= window (DEVICE float[W]); e as above
+ *      on the windowed frame (no TAC_KALDI_RAW_ENERGY); zero-padding on the right to N; P = |rfft f|^2 (TAC_KALDI_POWER) or |rfft f|;
+ *      out[b] = sum_k bank[b][k] P[k], then log max(., eps) (TAC_KALDI_LOG).  e = max(e, log energy_floor) where energy_floor > 0.
+ *      The bank is band-sparse: table = DEVICE int32[3][n_mels] = {first bin, bins, offset into weights} per band, weights = DEVICE
+ *      float[w_total] (w_total <= 4096), each band's run of consecutive bins; a run is clamped to bins 0 .. N/2 - 1 (the Nyquist
+ *      bin is never read) and to the weights.  4 <= n_mels <= 128.
+ *      out: float[rows][T][n_mels + 1 or 0], dense; with TAC_KALDI_USE_ENERGY e is column 0, or the last column with TAC_KALDI_HTK.
+ *      A wave owns 8 / 4 / 2 consecutive frames: their one contiguous span of samples is staged in the LDS with coalesced loads (any
+ *      row alignment, any shift), mean and energy are reductions over the frame's N / 32 lanes, every output element is ONE fused
+ *      multiply-add chain over its band's bins in ascending order.  One writer per element, no atomics, no workspace: bit-identical
+ *      from run to run.  A non-finite sample makes exactly the frames whose W samples contain it non-finite.  Another n_fft, W > N,
+ *      n_mels outside 4 .. 128: TAC_E_UNSUPPORTED, nothing launched. */
+#define TAC_KALDI_SNIP_EDGES 1
+#define TAC_KALDI_REMOVE_DC 2
+#define TAC_KALDI_RAW_ENERGY 4
+#define TAC_KALDI_USE_ENERGY 8
+#define TAC_KALDI_HTK 16
+#define TAC_KALDI_LOG 32
+#define TAC_KALDI_POWER 64
+int64_t tac_kaldi_num_frames(int64_t length, int32_t win_length, int32_t shift, int snip_edges);
+int tac_kaldi_fbank_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* window, const float* weights,
+                        const int32_t* table, int32_t n_fft, int32_t win_length, int32_t shift, int32_t n_mels, int32_t w_total,
+                        int32_t flags, float preemph, float energy_floor, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

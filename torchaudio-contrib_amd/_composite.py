@@ -23,6 +23,8 @@ import math
 import torch
 import torch.nn.functional as TF
 
+from . import _kaldi
+
 TWO_PI = 2.0 * math.pi
 
 
@@ -148,6 +150,73 @@ def fftconvolve(x, y, n_fft=0):
     n = x.shape[-1] + y.shape[-1] - 1
     out = torch.fft.irfft(torch.fft.rfft(x, n=n, dim=-1) * torch.fft.rfft(y, n=n, dim=-1), n=n, dim=-1)
     return out.contiguous()
+
+
+_kaldi_constants = {}
+
+
+def _kaldi_tables(p, w, n, dtype, device):
+    """(window (W,), bank (bins, n // 2)) of ``_kaldi`` — built in float64, rounded once — cached per argument set"""
+    key = (p.window_type, p.blackman_coeff, w, n, p.num_mel_bins, p.sample_frequency, p.low_freq, p.high_freq, dtype, str(device))
+    hit = _kaldi_constants.get(key)
+    if hit is None:
+        with torch.inference_mode(False):
+            window = _kaldi.window64(p.window_type, w, p.blackman_coeff).to(dtype).to(device)
+            bank = _kaldi.mel_bank64(p.num_mel_bins, n, p.sample_frequency, p.low_freq, p.high_freq)[:, :-1]
+            bank = bank.to(dtype).to(device)
+        if len(_kaldi_constants) > 32:
+            _kaldi_constants.clear()
+        hit = _kaldi_constants[key] = (window, bank)
+    return hit
+
+
+def kaldi_fbank(wave, *args):
+    """torchaudio's ``compliance.kaldi.fbank`` over ``(…, time)`` in torch operators, step by step as ``_kaldi`` defines it:
+    frames (an ``unfold`` view, or a gather through the mirrored index with ``snip_edges=False``), dither, mean removal (the
+    sum accumulated in float64, rounded once), energy, pre-emphasis with the first sample replicated, window, ``rfft`` at ``N``
+    points, the bank over the bins below the last one, the floored logarithm, the energy column, the mean over frames."""
+    p = _kaldi.Params(*args)
+    w, s, n = _kaldi.check(p)
+    work = wave if wave.dtype in (torch.float32, torch.float64) else wave.float()
+    length = work.shape[-1]
+    m = _kaldi.num_frames(length, w, s, p.snip_edges)
+    cols = p.num_mel_bins + (1 if p.use_energy else 0)
+    if m == 0 or work.numel() == 0:
+        return wave.new_zeros(tuple(wave.shape[:-1]) + (m, cols))
+    window, bank = _kaldi_tables(p, w, n, work.dtype, work.device)
+    if p.snip_edges:
+        frames = work.unfold(-1, w, s)
+    else:
+        frames = work[..., _kaldi.mirror_index(length, w, s, m).to(work.device)]
+    if p.dither != 0.0:
+        frames = frames + p.dither * torch.randn_like(frames)
+    if p.remove_dc_offset:
+        frames = frames - (frames.sum(-1, keepdim=True, dtype=torch.float64) / w).to(frames.dtype)
+    floor = torch.tensor(_kaldi.EPS, dtype=work.dtype, device=work.device)
+
+    def log_energy(f):
+        return torch.maximum(f.pow(2).sum(-1), floor).log()
+
+    energy = log_energy(frames) if p.raw_energy else None
+    if p.preemphasis_coefficient != 0.0:
+        frames = frames - p.preemphasis_coefficient * torch.cat([frames[..., :1], frames[..., :-1]], -1)
+    frames = frames * window
+    if energy is None:
+        energy = log_energy(frames)
+    spec = torch.fft.rfft(frames, n=n, dim=-1).abs()[..., :n // 2]
+    if p.use_power:
+        spec = spec.pow(2.0)
+    out = torch.matmul(spec, bank.t())
+    if p.use_log_fbank:
+        out = torch.maximum(out, floor).log()
+    if p.use_energy:
+        if p.energy_floor > 0.0:
+            energy = torch.maximum(energy, torch.tensor(math.log(p.energy_floor), dtype=work.dtype, device=work.device))
+        out = torch.cat([out, energy.unsqueeze(-1)] if p.htk_compat else [energy.unsqueeze(-1), out], -1)
+    if p.subtract_mean:
+        out = out - out.mean(dim=-2, keepdim=True)
+    out = out.contiguous()
+    return out if out.dtype == wave.dtype else out.to(wave.dtype)
 
 
 def amplitude_to_db(x, ref, amin):

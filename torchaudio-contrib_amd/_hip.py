@@ -14,6 +14,7 @@ import weakref
 
 import torch
 
+from . import _kaldi
 from . import _native
 from . import _resample
 
@@ -1134,6 +1135,56 @@ def fftconvolve(x, y, n_fft=0, reverse=False, offset=0, out_len=None):
 def last_route():
     """``tac_last_route()`` of the calling thread"""
     return _native.lib().tac_last_route().decode()
+
+
+# ----------------------------------------------------------------------------- kaldi fbank (csrc/kaldi_fbank.hip)
+#: what ``tac_kaldi_fbank_f32`` covers: the transform lengths of ``WaveFft<N/2, 16>`` with several frames per wave, and the bands
+KALDI_SIZES = (256, 512, 1024)
+KALDI_MAX_BINS = 128
+_KALDI_FLAGS = dict(snip_edges=1, remove_dc_offset=2, raw_energy=4, use_energy=8, htk_compat=16, use_log_fbank=32, use_power=64)
+
+_kaldi_tables = {}
+
+
+def _kaldi_device_tables(p, w, n, device):
+    """(window float32 (W,), packed weights, int32 table (3, bins)) on ``device``: built in float64 on the host, rounded once,
+    cached per argument set and device"""
+    key = (p.window_type, p.blackman_coeff, w, n, p.num_mel_bins, p.sample_frequency, p.low_freq, p.high_freq, device)
+    hit = _kaldi_tables.get(key)
+    if hit is None:
+        with torch.inference_mode(False):
+            window = _kaldi.window64(p.window_type, w, p.blackman_coeff).to(torch.float32)
+            bank = _kaldi.mel_bank64(p.num_mel_bins, n, p.sample_frequency, p.low_freq, p.high_freq).to(torch.float32)
+            weights, table = _kaldi.packed_runs(bank)
+            hit = (window.to(device), weights.to(device), table.contiguous().to(device), int(weights.numel()))
+        if len(_kaldi_tables) > 64:
+            _kaldi_tables.clear()
+        _kaldi_tables[key] = hit
+    return hit
+
+
+def kaldi_fbank(x, p, w, s, n, m):
+    """``(…, L)`` float32 -> ``(…, m, bins [+ 1])`` through ``tac_kaldi_fbank_f32``: one launch (``subtract_mean`` is the
+    caller's).  ``x`` is read where it lies when its leading dims collapse into one positive row stride over unit-stride rows;
+    it is copied otherwise."""
+    window, weights, table, w_total = _kaldi_device_tables(p, w, n, x.device)
+    length = int(x.shape[-1])
+    cols = p.num_mel_bins + (1 if p.use_energy else 0)
+    out = _empty(tuple(x.shape[:-1]) + (m, cols), device=x.device)
+    if not out.numel():
+        return out
+    rows = x.reshape(-1, length)
+    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+        rows = rows.contiguous()
+    flags = sum(bit for name, bit in _KALDI_FLAGS.items() if getattr(p, name))
+    with _native.on_device(x.device):
+        rc = _native.lib().tac_kaldi_fbank_f32(
+            _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(window), _native.ptr(weights), _native.ptr(table),
+            n, w, s, p.num_mel_bins, w_total, flags, p.preemphasis_coefficient, p.energy_floor, _native.ptr(out),
+            _native.stream_ptr(x.device))
+    _native.check(rc, 'tac_kaldi_fbank_f32')
+    _count('tac_kaldi_fbank_f32', out)
+    return out
 
 
 # ----------------------------------------------------------------------------- complex pairs

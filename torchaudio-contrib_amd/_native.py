@@ -41,7 +41,7 @@ EXPORTS = (
     'tac_dct_rows_f32', 'tac_polyphase_f32', 'tac_lfilter_chunk', 'tac_lfilter_supported', 'tac_lfilter_f32',
     'tac_spectral_mac_tile', 'tac_spectral_mac_f32', 'tac_fftconvolve_default_n_fft', 'tac_fftconvolve_supported',
     'tac_fftconvolve_spectra_workspace', 'tac_fftconvolve_spectra_f32', 'tac_fftconvolve_workspace', 'tac_fftconvolve_f32',
-    'tac_fftconvolve_direct_f32',
+    'tac_fftconvolve_direct_f32', 'tac_kaldi_num_frames', 'tac_kaldi_fbank_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -206,6 +206,9 @@ def lib():
         h.tac_fftconvolve_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, _I64, _I32, ctypes.c_int, _I64, _I64, _P, _I64, _P,
                                           _I64, _P]
         h.tac_fftconvolve_direct_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P]
+        h.tac_kaldi_num_frames.restype = _I64
+        h.tac_kaldi_num_frames.argtypes = [_I64, _I32, _I32, ctypes.c_int]
+        h.tac_kaldi_fbank_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

@@ -10,6 +10,7 @@ see them by name.
     tac_amd::stretch_mel            "      + apply_filterbank in the same launch
     tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
     tac_amd::resample           polyphase windowed-sinc resampling of the waveform (csrc/resample.hip)
+    tac_amd::kaldi_fbank        Kaldi log mel filterbank features: framing, FFT, mel bank and log in one launch (csrc/kaldi_fbank.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -36,6 +37,7 @@ from torch.library import Library
 from . import _composite as C
 from . import _hip as H
 from . import _hip64 as H64
+from . import _kaldi as K
 from . import _resample as RS
 
 NS = 'tac_amd'
@@ -703,6 +705,49 @@ def _fftconvolve_fake(x, y, n_fft):
 
 
 _register('fftconvolve', '(Tensor x, Tensor y, int n_fft) -> Tensor', _fftconvolve_cuda, C.fftconvolve, _fftconvolve_fake, 2)
+
+
+# ============================================================================= kaldi_fbank
+def _kaldi_shape(wave, p):
+    w, s, n = K.sizes(p.sample_frequency, p.frame_length, p.frame_shift, p.round_to_power_of_two)
+    m = K.num_frames(wave.shape[-1], w, s, p.snip_edges)
+    return tuple(wave.shape[:-1]) + (m, p.num_mel_bins + (1 if p.use_energy else 0))
+
+
+def _kaldi_fbank_cuda(wave, *args):
+    p = K.Params(*args)
+    w, s, n = K.check(p)
+    length = wave.shape[-1]
+    m = K.num_frames(length, w, s, p.snip_edges)
+    if m == 0 or wave.numel() == 0:
+        return wave.new_zeros(_kaldi_shape(wave, p))            # an empty output: nothing is launched
+    reason = _hip_dtype(wave)
+    if reason is None and not p.round_to_power_of_two:
+        reason = 'round_to_power_of_two=False'
+    if reason is None and n not in H.KALDI_SIZES:
+        reason = 'a transform of %d points (the kernel takes %s)' % (n, ' / '.join(str(v) for v in H.KALDI_SIZES))
+    if reason is None and p.num_mel_bins > H.KALDI_MAX_BINS:
+        reason = '%d mel bins (the kernel takes up to %d)' % (p.num_mel_bins, H.KALDI_MAX_BINS)
+    if reason is None and p.dither != 0.0:
+        reason = 'dither != 0'
+    if reason is None and any(st <= 0 for st, k in zip(wave.stride(), wave.shape) if k > 1):
+        reason = 'non-positive strides'
+    if reason is None and not p.snip_edges and length < w:
+        reason = 'snip_edges=False on a waveform shorter than a frame'
+    if reason is not None:
+        _composite_route('kaldi_fbank', reason)
+        return C.kaldi_fbank(wave, *args)
+    out = H.kaldi_fbank(_f32(wave), p, w, s, n, m)
+    if p.subtract_mean:
+        out = out - out.mean(dim=-2, keepdim=True)
+    return out if wave.dtype == out.dtype else out.to(wave.dtype)
+
+
+def _kaldi_fbank_fake(wave, *args):
+    return wave.new_empty(_kaldi_shape(wave, K.Params(*args)))
+
+
+_register('kaldi_fbank', '(Tensor wave, %s) -> Tensor' % K.SCHEMA_ARGS, _kaldi_fbank_cuda, C.kaldi_fbank, _kaldi_fbank_fake, 1)
 
 
 # ============================================================================= lfilter

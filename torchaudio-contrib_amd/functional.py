@@ -20,12 +20,13 @@ import torch
 from . import _hip
 from . import _ops
 from . import _filters
+from . import _kaldi
 from . import _resample
 from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
 
 _call = _ops.call
@@ -238,6 +239,41 @@ def resample(waveforms, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.9
     if args[0] == args[1]:
         return x
     return _call('resample', x, *args)
+
+
+def kaldi_fbank(waveforms, blackman_coeff=0.42, dither=0.0, energy_floor=1.0, frame_length=25.0, frame_shift=10.0, high_freq=0.0,
+                htk_compat=False, low_freq=20.0, num_mel_bins=23, preemphasis_coefficient=0.97, raw_energy=True,
+                remove_dc_offset=True, round_to_power_of_two=True, sample_frequency=16000.0, snip_edges=True, subtract_mean=False,
+                use_energy=False, use_log_fbank=True, use_power=True, vtln_high=-500.0, vtln_low=100.0, vtln_warp=1.0,
+                window_type='povey'):
+    """``(…, time)`` → ``(…, frames, num_mel_bins [+ 1])``: Kaldi's log mel filterbank features with the keywords and defaults of
+    ``torchaudio.compliance.kaldi.fbank`` (``kaldi.fbank`` is that function itself, for ``(channels, time)``), over any leading
+    dimensions.  Frames of ``W = int(sample_frequency * frame_length / 1000)`` samples every ``S = int(sample_frequency *
+    frame_shift / 1000)``; per frame the mean is removed, the frame pre-emphasised with its first sample replicated and
+    windowed, zero-padded to the next power of two ``N``, and ``|rfft|^2`` (or ``|rfft|``) is weighted by a bank that is
+    triangular in mel; the output is the natural logarithm floored at float32 epsilon, with the frame's log energy as the first
+    column (the last with ``htk_compat``) when ``use_energy``.  The definition is in ``_kaldi.py``.  On a HIP device float32
+    input is ONE launch from waveform rows to output rows (csrc/kaldi_fbank.hip) for ``N`` = 256 / 512 / 1024, up to 128 bins
+    and ``dither == 0``; the rest, and the backward pass, take torch operators, announced.  ``vtln_warp != 1`` is not
+    implemented."""
+    x = _tensor(waveforms, 'waveforms')
+    if x.dim() < 1:
+        raise RuntimeError('kaldi_fbank: expected a tensor of shape (…, time), got a scalar')
+    if not x.is_floating_point():
+        raise RuntimeError('kaldi_fbank: expected a floating-point waveform, got %s' % x.dtype)
+    if vtln_warp != 1.0:
+        raise NotImplementedError('kaldi_fbank: vtln_warp != 1 (vocal tract length normalisation) is not implemented')
+    p = _kaldi.Params(float(blackman_coeff), float(dither), float(energy_floor), float(frame_length), float(frame_shift),
+                      float(high_freq), bool(htk_compat), float(low_freq), int(num_mel_bins), float(preemphasis_coefficient),
+                      bool(raw_energy), bool(remove_dc_offset), bool(round_to_power_of_two), float(sample_frequency),
+                      bool(snip_edges), bool(subtract_mean), bool(use_energy), bool(use_log_fbank), bool(use_power),
+                      str(window_type))
+    _kaldi.check(p)
+    return _call('kaldi_fbank', x, *p)
+
+
+#: the keywords ``kaldi_fbank`` takes behind the waveform
+_KALDI_KEYWORDS = kaldi_fbank.__code__.co_varnames[1:kaldi_fbank.__code__.co_argcount]
 
 
 _CONV_MODES = ('full', 'valid', 'same')

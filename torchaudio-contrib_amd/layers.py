@@ -423,6 +423,26 @@ class Deemphasis(_ModuleNoStateBuffers):
         return self.__class__.__name__ + '(coeff={})'.format(self.coeff)
 
 
+class KaldiFbank(_ModuleNoStateBuffers):
+    """``functional.kaldi_fbank`` as a layer: ``(…, time)`` → ``(…, frames, num_mel_bins [+ 1])``, with the keywords and
+    defaults of ``torchaudio.compliance.kaldi.fbank`` (less ``channel`` and ``min_duration``, which belong to ``kaldi.fbank``).
+    No buffers: the window and the packed bank are cached per argument set and device."""
+
+    def __init__(self, **kwargs):
+        super(KaldiFbank, self).__init__()
+        unknown = sorted(set(kwargs) - set(F._KALDI_KEYWORDS))
+        if unknown:
+            raise TypeError('KaldiFbank: unexpected keyword(s) %s' % ', '.join(unknown))
+        self.options = dict(kwargs)
+        F.kaldi_fbank(torch.zeros(0), **self.options)          # argument errors surface here, not in the first forward
+
+    def forward(self, waveforms):
+        return F.kaldi_fbank(waveforms, **self.options)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(' + ', '.join('{}={!r}'.format(k, v) for k, v in self.options.items()) + ')'
+
+
 class FFTConvolve(_ModuleNoStateBuffers):
     """``functional.fftconvolve`` as a layer (torchaudio's ``transforms.FFTConvolve``): ``forward(x, y)`` with ``mode`` one of
     ``'full'``, ``'valid'``, ``'same'``."""
