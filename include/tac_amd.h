@@ -572,6 +572,47 @@ int tac_kaldi_fbank_f32(const float* x, int64_t rows, int64_t length, int64_t st
                         const int32_t* table, int32_t n_fft, int32_t win_length, int32_t shift, int32_t n_mels, int32_t w_total,
                         int32_t flags, float preemph, float energy_floor, float* out, void* stream);
 
+/* (19) functional.sliding_window_cmn (Kaldi's apply-cmvn-sliding): ONE launch over x[r*stride_r + t*stride_t + f*stride_f], r < rows,
+ *      t < n_frames = T, f < n_feats = F (strides in elements, positive for every axis longer than one), out: float[rows][T][F], dense
+ *      (csrc/cmn_deltas.hip).  W = cmn_window >= 1, M = min_cmn_window >= 1.  The window of frame t is [ws, we), n = we - ws:
+ *        center:      ws = min(max(t - W/2, 0), max(T - W, 0)), we = min(ws + W, T)
+ *        otherwise:   ws = max(t - W, 0), we = max(t + 1, M); where we > T: ws = max(ws - (we - T), 0), we = T   (W + 1 frames away
+ *                     from the ends, as in Kaldi)
+ *      out[t][f] = x[t][f] - mean(x[ws:we][f]); with norm_vars times (sum(x^2)/n - mean^2)^-1/2, and 0 where n == 1.
+ *      Lanes run along f; a thread owns one feature over tac_sliding_cmn_chunk(rows, T, F, W, M) consecutive frames: it sums the
+ *      window of its first frame directly and then moves both ends frame by frame.  The sums are float64 over the FINITE samples of
+ *      the window, beside an integer count of the non-finite ones: a NaN or an infinity makes exactly the frames whose window holds it
+ *      NaN.  The subtraction and the variance are float64, rounded to float32 once.  One writer per element, no atomics, no
+ *      workspace: bit-identical from run to run.
+ *      adjoint != 0 (norm_vars == 0 only, else TAC_E_UNSUPPORTED): x is grad_out and out[s] = x[s] - sum over {t : ws(t) <= s < we(t)}
+ *      of x[t] / n(t), the gradient w.r.t. the input: the same sliding sum over the interval of frames whose window holds s.
+ *      W and M may be any positive int64 (a window beyond the row is the row: they are capped before any sum is formed).
+ *      More than 2^31 - 1 workgroups, T > 2^40: TAC_E_UNSUPPORTED, nothing launched. */
+int64_t tac_sliding_cmn_chunk(int64_t rows, int64_t n_frames, int64_t n_feats, int64_t cmn_window, int64_t min_cmn_window);
+int tac_sliding_cmn_f32(const float* x, int64_t rows, int64_t n_frames, int64_t n_feats, int64_t stride_r, int64_t stride_t,
+                        int64_t stride_f, int64_t cmn_window, int64_t min_cmn_window, int center, int norm_vars, int adjoint,
+                        float* out, void* stream);
+
+/* (20) functional.compute_deltas: ONE launch over x[r*stride_r + f*stride_f + t*stride_t] (strides in elements, positive for every axis
+ *      longer than one), out: float[rows][F][T], dense (csrc/cmn_deltas.hip).  n = (win_length - 1) / 2, denom = n (n + 1)(2n + 1) / 3:
+ *        out[t] = (sum_{k = -n .. n} k x[idx(t + k)]) / denom
+ *      idx is the index map of torch.nn.functional.pad: TAC_DELTAS_REPLICATE (clamp), _CONSTANT (zero outside), _REFLECT (no edge
+ *      repeat, n < T) or _CIRCULAR (n <= T).  Each output is ONE fused multiply-add chain in ascending k and one division.  A
+ *      workgroup stages its tile and the 2n frames around it in the LDS: with stride_t == 1 lanes load along t; with stride_f == 1
+ *      (the transposed view of a (T, F) matrix) lanes load along f and the tile is turned in the LDS; the stores are along t either
+ *      way.  Every other layout takes the first form.  Bit-identical from run to run.
+ *      adjoint != 0 (_REPLICATE and _CONSTANT): x is grad_out and out the gradient w.r.t. the input: the taps negated over a
+ *      zero-padded row, and for _REPLICATE what the clamped reads sent to s = 0 and s = T - 1 (those two in float64).
+ *      tac_deltas_supported: TAC_OK; TAC_E_INVALID for win_length < 3, an unknown mode or a row too short for the mode;
+ *      TAC_E_UNSUPPORTED for n > 32 (win_length > 66) and for the adjoint of the other two modes.  Nothing is launched for those. */
+#define TAC_DELTAS_REPLICATE 0
+#define TAC_DELTAS_CONSTANT 1
+#define TAC_DELTAS_REFLECT 2
+#define TAC_DELTAS_CIRCULAR 3
+int tac_deltas_supported(int64_t n_frames, int32_t win_length, int32_t mode, int adjoint);
+int tac_deltas_f32(const float* x, int64_t rows, int64_t n_feats, int64_t n_frames, int64_t stride_r, int64_t stride_f,
+                   int64_t stride_t, int32_t win_length, int32_t mode, int adjoint, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,11 +16,12 @@ from .functional import (stft, istft, complex_norm, create_mel_filter, apply_fil
                          phase_vocoder, amplitude_to_db, db_to_amplitude, mu_law_encoding,
                          mu_law_decoding, hpss, create_dct, dct, resample, lfilter, biquad, lowpass_biquad,
                          highpass_biquad, bandpass_biquad, bandreject_biquad, allpass_biquad, equalizer_biquad,
-                         preemphasis, deemphasis, fftconvolve, convolve, kaldi_fbank)
+                         preemphasis, deemphasis, fftconvolve, convolve, kaldi_fbank, sliding_window_cmn,
+                         compute_deltas)
 from .layers import (STFT, ISTFT, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
                      MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis,
-                     FFTConvolve, Convolve, KaldiFbank)
+                     FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas)
 from . import distributed
 from . import kaldi
 

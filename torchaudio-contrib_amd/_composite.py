@@ -152,6 +152,118 @@ def fftconvolve(x, y, n_fft=0):
     return out.contiguous()
 
 
+def cmn_check(cmn_window, min_cmn_window):
+    """The ``ValueError`` cases of ``sliding_window_cmn``'s window arguments, shared by the functional and the layer"""
+    if cmn_window < 1:
+        raise ValueError('sliding_window_cmn: cmn_window must be at least 1, got %d' % cmn_window)
+    if min_cmn_window < 1:
+        raise ValueError('sliding_window_cmn: min_cmn_window must be at least 1, got %d' % min_cmn_window)
+
+
+def cmn_bounds(n_frames, cmn_window, min_cmn_window, center, device=None):
+    """(ws, we): int64 ``(T,)`` tensors, the window ``[ws, we)`` of every frame of ``sliding_window_cmn`` — the closed form of
+    Kaldi's step-by-step procedure (``cmn_bounds`` of csrc/cmn_deltas.hip)."""
+    # a window beyond the row, or a minimum beyond twice the row, gives the bounds of that cap: no int64 sum can overflow
+    cmn_window, min_cmn_window = min(cmn_window, max(n_frames, 1)), min(min_cmn_window, 2 * max(n_frames, 1))
+    t = torch.arange(n_frames, dtype=torch.int64, device=device)
+    if center:
+        ws = (t - cmn_window // 2).clamp(min=0).clamp(max=max(n_frames - cmn_window, 0))
+        we = (ws + cmn_window).clamp(max=n_frames)
+    else:
+        ws = (t - cmn_window).clamp(min=0)
+        we = (t + 1).clamp(min=min_cmn_window)
+        over = (we - n_frames).clamp(min=0)
+        ws = (ws - over).clamp(min=0)
+        we = we - over
+    return ws, we
+
+
+def sliding_window_cmn(x, cmn_window, min_cmn_window, center, norm_vars):
+    """torchaudio's ``functional.sliding_window_cmn`` over ``(…, T, F)``, all frames at once: the sums of every window are
+    differences of a float64 ``cumsum`` gathered at the closed-form bounds (no loop over frames, no running sum in the input's
+    dtype), the subtraction and the variance are float64 and the result is rounded to the input's dtype once.  The sums run over
+    the finite samples; a cumulative count of the non-finite ones makes exactly the frames whose window holds one NaN, as the
+    kernel does."""
+    n_frames = x.shape[-2]
+    if x.numel() == 0:
+        return torch.zeros_like(x, memory_format=torch.contiguous_format)
+    ws, we = cmn_bounds(n_frames, cmn_window, min_cmn_window, center, x.device)
+    wide = x.to(torch.float64)
+    finite = torch.isfinite(wide)
+    clean = torch.where(finite, wide, torch.zeros((), dtype=wide.dtype, device=x.device))
+
+    def window_sums(v):
+        c = TF.pad(v.cumsum(-2), (0, 0, 1, 0))
+        return c.index_select(-2, we) - c.index_select(-2, ws)
+
+    n = (we - ws).to(torch.float64).unsqueeze(-1)
+    mean = window_sums(clean) / n
+    out = clean - mean
+    if norm_vars:
+        # a window of one frame gives exactly 0: its variance (0) is masked BEFORE the power, so that the unselected branch
+        # does not send 0 * inf = NaN into the gradient
+        single = n == 1.0
+        var = window_sums(clean * clean) / n - mean * mean
+        var = torch.where(single, torch.ones((), dtype=wide.dtype, device=x.device), var)
+        out = torch.where(single, torch.zeros((), dtype=wide.dtype, device=x.device), out * var.pow(-0.5))
+    bad = window_sums((~finite).to(torch.int64)) > 0
+    out = torch.where(bad, torch.full((), float('nan'), dtype=wide.dtype, device=x.device), out)
+    return out.to(x.dtype).contiguous()
+
+
+DELTAS_MODES = ('replicate', 'constant', 'reflect', 'circular')
+
+
+def deltas_check_args(win_length, mode):
+    """The ``ValueError`` cases of ``compute_deltas`` that do not depend on the input, shared by the functional and the layer"""
+    if win_length < 3:
+        raise ValueError('compute_deltas: win_length must be at least 3, got %d' % win_length)
+    if mode not in DELTAS_MODES:
+        raise ValueError('compute_deltas: mode must be one of %s, got %r' % (', '.join(DELTAS_MODES), mode))
+
+
+def deltas_check(n_frames, win_length, mode):
+    """The ``ValueError`` cases of ``compute_deltas``, the same on every route; returns ``n = (win_length - 1) // 2``."""
+    deltas_check_args(win_length, mode)
+    n = (win_length - 1) // 2
+    if mode == 'reflect' and n >= n_frames:
+        raise ValueError("compute_deltas: mode='reflect' needs more than n = %d frames, got %d" % (n, n_frames))
+    if mode == 'circular' and n > n_frames:
+        raise ValueError("compute_deltas: mode='circular' needs at least n = %d frames, got %d" % (n, n_frames))
+    return n
+
+
+def deltas_index(n_frames, n, mode, device=None):
+    """(idx, inside): for output frame t and tap k = -n .. n the source frame of ``torch.nn.functional.pad``'s ``mode`` —
+    ``(T, 2n + 1)`` int64 — and whether the tap reads the row at all (False in the zero padding of ``'constant'``)"""
+    pos = torch.arange(n_frames, dtype=torch.int64, device=device).unsqueeze(-1) + \
+        torch.arange(-n, n + 1, dtype=torch.int64, device=device)
+    inside = (pos >= 0) & (pos < n_frames)
+    if mode == 'reflect':
+        idx = torch.where(pos < 0, -pos, torch.where(pos >= n_frames, 2 * (n_frames - 1) - pos, pos))
+    elif mode == 'circular':
+        idx = torch.remainder(pos, max(n_frames, 1))
+    else:
+        idx = pos.clamp(0, max(n_frames - 1, 0))
+    if mode != 'constant':
+        inside = torch.ones_like(inside)
+    return idx, inside
+
+
+def compute_deltas(x, win_length, mode):
+    """torchaudio's ``functional.compute_deltas`` over ``(…, F, T)`` as an index gather: ``sum_k k x[idx(t + k)] / denom`` with
+    ``idx`` the index map of ``pad``'s ``mode``, accumulated in float64 and rounded to the input's dtype once.  Contiguous."""
+    n_frames = x.shape[-1]
+    n = deltas_check(n_frames, win_length, mode)
+    if x.numel() == 0:
+        return torch.zeros_like(x, memory_format=torch.contiguous_format)
+    idx, inside = deltas_index(n_frames, n, mode, x.device)
+    taps = torch.arange(-n, n + 1, dtype=torch.float64, device=x.device) * inside.to(torch.float64)      # (T, 2n + 1)
+    gathered = x.to(torch.float64)[..., idx]                                                            # (…, F, T, 2n + 1)
+    out = (gathered * taps).sum(-1) / (n * (n + 1) * (2 * n + 1) / 3.0)
+    return out.to(x.dtype).contiguous()
+
+
 _kaldi_constants = {}
 
 

@@ -1187,6 +1187,74 @@ def kaldi_fbank(x, p, w, s, n, m):
     return out
 
 
+# ----------------------------------------------------------------------------- sliding CMN and deltas (csrc/cmn_deltas.hip)
+#: the pad modes of ``tac_deltas_f32`` in the header's numbering
+DELTAS_MODES = {'replicate': 0, 'constant': 1, 'reflect': 2, 'circular': 3}
+
+
+def _positive_strides(x):
+    return all(st > 0 for st, k in zip(x.stride(), x.shape) if k > 1)
+
+
+def sliding_cmn_covers(x):
+    """True where ``tac_sliding_cmn_f32`` reads ``x`` (…, T, F) where it lies: positive strides on every axis longer than one"""
+    return x.dim() >= 2 and _positive_strides(x)
+
+
+def sliding_cmn_chunk(rows, n_frames, n_feats, cmn_window, min_cmn_window):
+    """frames one thread of ``tac_sliding_cmn_f32`` walks at this shape (the library's own choice)"""
+    return int(_native.lib().tac_sliding_cmn_chunk(rows, n_frames, n_feats, cmn_window, min_cmn_window))
+
+
+def _rows3(x):
+    """``x`` (…, A, B) as (rows, A, B): a view where the leading dims collapse into one stride, a copy otherwise"""
+    rows = x.reshape((-1,) + tuple(x.shape[-2:]))
+    return rows if _positive_strides(rows) else rows.contiguous()
+
+
+def sliding_cmn_rows(x, cmn_window, min_cmn_window, center, norm_vars, adjoint=False):
+    """``(…, T, F) -> (…, T, F)``, dense, through ``tac_sliding_cmn_f32``: one launch on ``x`` where it lies (any positive
+    strides; the leading dims are copied only when no single row stride expresses them).  ``adjoint``: ``x`` is the gradient of
+    the output and the result the gradient of the input (``norm_vars`` off)."""
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        rows = _rows3(x)
+        with _native.on_device(x.device):
+            rc = _native.lib().tac_sliding_cmn_f32(
+                _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0), rows.stride(1), rows.stride(2),
+                cmn_window, min_cmn_window, int(bool(center)), int(bool(norm_vars)), int(bool(adjoint)), _native.ptr(out),
+                _native.stream_ptr(x.device))
+        _native.check(rc, 'tac_sliding_cmn_f32')
+        _count('tac_sliding_cmn_f32', out)
+    return out
+
+
+def deltas_supported(n_frames, win_length, mode, adjoint=False):
+    """True where ``tac_deltas_f32`` takes these arguments: the library's own answer (``tac_deltas_supported``: the widest
+    window, and for the adjoint the two modes whose gradient it has), so the cap is stated in csrc/cmn_deltas.hip alone"""
+    return _native.lib().tac_deltas_supported(n_frames, win_length, DELTAS_MODES[mode], int(bool(adjoint))) == _native.TAC_OK
+
+
+def deltas_covers(x, win_length, mode, adjoint=False):
+    """True where ``tac_deltas_f32`` takes this call on ``x`` where it lies: ``deltas_supported`` and positive strides"""
+    return deltas_supported(int(x.shape[-1]), win_length, mode, adjoint) and _positive_strides(x)
+
+
+def deltas_rows(x, win_length, mode, adjoint=False):
+    """``(…, F, T) -> (…, F, T)``, dense, through ``tac_deltas_f32``: one launch on ``x`` where it lies.  ``adjoint``: ``x`` is the
+    gradient of the output and the result the gradient of the input."""
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        rows = _rows3(x)
+        with _native.on_device(x.device):
+            rc = _native.lib().tac_deltas_f32(
+                _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0), rows.stride(1), rows.stride(2),
+                win_length, DELTAS_MODES[mode], int(bool(adjoint)), _native.ptr(out), _native.stream_ptr(x.device))
+        _native.check(rc, 'tac_deltas_f32')
+        _count('tac_deltas_f32', out)
+    return out
+
+
 # ----------------------------------------------------------------------------- complex pairs
 def is_dense(x):
     """True when x's elements tile one gap-free block of memory (in any dim order)."""

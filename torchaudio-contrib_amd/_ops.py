@@ -11,6 +11,8 @@ see them by name.
     tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
     tac_amd::resample           polyphase windowed-sinc resampling of the waveform (csrc/resample.hip)
     tac_amd::kaldi_fbank        Kaldi log mel filterbank features: framing, FFT, mel bank and log in one launch (csrc/kaldi_fbank.hip)
+    tac_amd::sliding_window_cmn sliding-window cepstral mean (and variance) normalisation over (…, T, F) (csrc/cmn_deltas.hip)
+    tac_amd::compute_deltas     delta coefficients along time over (…, F, T) (csrc/cmn_deltas.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -411,7 +413,25 @@ def _fftconvolve_hip_backward(saved, rest, needs, grads):
     return [H.fftconvolve(grads[0], y, n_fft, reverse=True, offset=m - 1, out_len=length), None]
 
 
-_HIP_BACKWARD = {'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+def _sliding_window_cmn_hip_backward(saved, rest, needs, grads):
+    cmn_window, min_cmn_window, center, norm_vars = rest
+    if grads[0] is None or not needs[0] or norm_vars:
+        return None                 # (the variance's gradient: the stock-torch route, announced)
+    g = grads[0] if H.sliding_cmn_covers(grads[0]) else grads[0].contiguous()      # (an expanded grad_out is copied)
+    # the frames whose window holds s form an interval: the same sliding sum, over g[t] / n(t)
+    return [H.sliding_cmn_rows(g, cmn_window, min_cmn_window, center, False, adjoint=True)]
+
+
+def _compute_deltas_hip_backward(saved, rest, needs, grads):
+    win_length, mode = rest
+    if grads[0] is None or not needs[0] or not H.deltas_supported(int(grads[0].shape[-1]), win_length, mode, adjoint=True):
+        return None                 # ('reflect' / 'circular', a window beyond the kernel's: the stock-torch route, announced)
+    g = grads[0] if H.deltas_covers(grads[0], win_length, mode, adjoint=True) else grads[0].contiguous()      # (an expanded grad_out)
+    return [H.deltas_rows(g, win_length, mode, adjoint=True)]
+
+
+_HIP_BACKWARD = {'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
+                 'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -748,6 +768,53 @@ def _kaldi_fbank_fake(wave, *args):
 
 
 _register('kaldi_fbank', '(Tensor wave, %s) -> Tensor' % K.SCHEMA_ARGS, _kaldi_fbank_cuda, C.kaldi_fbank, _kaldi_fbank_fake, 1)
+
+
+# ============================================================================= sliding_window_cmn, compute_deltas
+def _sliding_window_cmn_cuda(x, cmn_window, min_cmn_window, center, norm_vars):
+    if x.numel() == 0:
+        return torch.zeros_like(x, memory_format=torch.contiguous_format)       # an empty output: nothing is launched
+    reason = _hip_dtype(x)
+    if reason is None and not H.sliding_cmn_covers(x):
+        reason = 'non-positive strides'
+    if reason is not None:
+        _composite_route('sliding_window_cmn', reason)
+        return C.sliding_window_cmn(x, cmn_window, min_cmn_window, center, norm_vars)
+    out = H.sliding_cmn_rows(_f32(x), cmn_window, min_cmn_window, center, norm_vars)
+    return out if x.dtype == out.dtype else out.to(x.dtype)
+
+
+def _same_shape_fake(x, *args):
+    return x.new_empty(tuple(x.shape))
+
+
+_register('sliding_window_cmn', '(Tensor x, int cmn_window, int min_cmn_window, bool center, bool norm_vars) -> Tensor',
+          _sliding_window_cmn_cuda, C.sliding_window_cmn, _same_shape_fake, 1)
+
+
+def _compute_deltas_cuda(x, win_length, mode):
+    C.deltas_check(x.shape[-1], win_length, mode)
+    if x.numel() == 0:
+        return torch.zeros_like(x, memory_format=torch.contiguous_format)
+    reason = _hip_dtype(x)
+    if reason is None and not H.deltas_supported(int(x.shape[-1]), win_length, mode):
+        reason = 'win_length %d (beyond the widest window of the kernel)' % win_length
+    if reason is None and not H.deltas_covers(x, win_length, mode):
+        reason = 'non-positive strides'
+    if reason is not None:
+        _composite_route('compute_deltas', reason)
+        return C.compute_deltas(x, win_length, mode)
+    out = H.deltas_rows(_f32(x), win_length, mode)
+    return out if x.dtype == out.dtype else out.to(x.dtype)
+
+
+def _compute_deltas_fake(x, win_length, mode):
+    C.deltas_check(x.shape[-1], win_length, mode)
+    return x.new_empty(tuple(x.shape))
+
+
+_register('compute_deltas', '(Tensor x, int win_length, str mode) -> Tensor', _compute_deltas_cuda, C.compute_deltas,
+          _compute_deltas_fake, 1)
 
 
 # ============================================================================= lfilter

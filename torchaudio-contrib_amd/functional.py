@@ -17,6 +17,7 @@ import math
 
 import torch
 
+from . import _composite
 from . import _hip
 from . import _ops
 from . import _filters
@@ -26,7 +27,7 @@ from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'sliding_window_cmn', 'compute_deltas', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
 
 _call = _ops.call
@@ -274,6 +275,49 @@ def kaldi_fbank(waveforms, blackman_coeff=0.42, dither=0.0, energy_floor=1.0, fr
 
 #: the keywords ``kaldi_fbank`` takes behind the waveform
 _KALDI_KEYWORDS = kaldi_fbank.__code__.co_varnames[1:kaldi_fbank.__code__.co_argcount]
+
+
+def sliding_window_cmn(specgram, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False):
+    """``(…, T, F)`` → the same shape and dtype: torchaudio's ``functional.sliding_window_cmn`` (Kaldi's ``apply-cmvn-sliding``)
+    over the layout ``kaldi_fbank`` returns, time second to last.  Frame ``t`` loses the mean of its window ``[ws, we)``: with
+    ``center``, ``cmn_window`` frames around ``t`` held inside the row; otherwise the ``cmn_window`` frames before ``t`` and
+    ``t`` itself (``cmn_window + 1`` frames away from the ends, as in Kaldi), grown to ``min_cmn_window`` frames at the start of
+    the row.  ``norm_vars`` also divides by the window's standard deviation (0 where the window is one frame).  On a HIP device
+    float32 input with positive strides — a feature or time slice as it lies — is ONE launch (csrc/cmn_deltas.hip): float64
+    running sums per feature and time chunk, rounded to float32 once, where torchaudio's float32 running sums drift; its
+    gradient is the same kernel's adjoint mode without ``norm_vars``.  float64, non-positive strides and the gradient with
+    ``norm_vars`` take the vectorised float64 ``cumsum`` form in torch operators, announced; CPU tensors take it too.  Unlike
+    torchaudio, whose running sums stay poisoned to the end of the row, a NaN or an infinity reaches exactly the frames whose
+    window holds it (they are NaN) and nothing else."""
+    x = _tensor(specgram, 'specgram')
+    cmn_window, min_cmn_window = int(cmn_window), int(min_cmn_window)
+    _composite.cmn_check(cmn_window, min_cmn_window)
+    if x.dim() < 2:
+        raise ValueError('sliding_window_cmn: expected a tensor of shape (…, time, features), got %d dimension(s)' % x.dim())
+    if not x.is_floating_point():
+        raise RuntimeError('sliding_window_cmn: expected a floating-point tensor, got %s' % x.dtype)
+    return _call('sliding_window_cmn', x, cmn_window, min_cmn_window, bool(center), bool(norm_vars))
+
+
+def compute_deltas(specgram, win_length=5, mode='replicate'):
+    """``(…, F, T)`` → the same shape, contiguous: torchaudio's ``functional.compute_deltas``,
+    ``out[…, t] = sum_{k=-n..n} k x[…, idx(t + k)] / denom`` with ``n = (win_length - 1) // 2``, ``denom = n (n + 1)(2n + 1) / 3``
+    and ``idx`` the index map of ``torch.nn.functional.pad`` for ``mode``: ``'replicate'``, ``'constant'``, ``'reflect'`` (needs
+    ``n < T``) or ``'circular'`` (``n <= T``).  On a HIP device float32 input with positive strides and ``win_length <= 66`` is
+    ONE launch (csrc/cmn_deltas.hip) on the tensor where it lies — contiguous rows, or the transposed view ``feats.T`` of a
+    ``(T, F)`` Kaldi matrix, which is turned through the LDS; the gradient is the same kernel's adjoint mode for
+    ``'replicate'`` and ``'constant'``.  float64, non-positive strides, wider windows and the gradient of the other two modes
+    take an index gather in torch operators, announced; CPU tensors take it too."""
+    x = _tensor(specgram, 'specgram')
+    if x.dim() < 1:
+        raise ValueError('compute_deltas: expected a tensor of shape (…, features, time), got a scalar')
+    if not x.is_floating_point():
+        raise RuntimeError('compute_deltas: expected a floating-point tensor, got %s' % x.dtype)
+    win_length = int(win_length)
+    _composite.deltas_check(int(x.shape[-1]), win_length, mode)
+    if x.dim() == 1:
+        return _call('compute_deltas', x.unsqueeze(0), win_length, mode).squeeze(0)
+    return _call('compute_deltas', x, win_length, mode)
 
 
 _CONV_MODES = ('full', 'valid', 'same')

@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as F
+from . import _composite
 from . import _filters
 from . import _hip
 from . import _lazy
@@ -441,6 +442,40 @@ class KaldiFbank(_ModuleNoStateBuffers):
 
     def __repr__(self):
         return self.__class__.__name__ + '(' + ', '.join('{}={!r}'.format(k, v) for k, v in self.options.items()) + ')'
+
+
+class SlidingWindowCmn(_ModuleNoStateBuffers):
+    """``functional.sliding_window_cmn`` as a layer (torchaudio's ``transforms.SlidingWindowCmn``): ``(…, T, F)`` → the same
+    shape.  No buffers."""
+
+    def __init__(self, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False):
+        super(SlidingWindowCmn, self).__init__()
+        self.cmn_window, self.min_cmn_window = int(cmn_window), int(min_cmn_window)
+        self.center, self.norm_vars = bool(center), bool(norm_vars)
+        _composite.cmn_check(self.cmn_window, self.min_cmn_window)          # argument errors surface here, not in the first forward
+
+    def forward(self, specgram):
+        return F.sliding_window_cmn(specgram, self.cmn_window, self.min_cmn_window, self.center, self.norm_vars)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(cmn_window={}, min_cmn_window={}, center={}, norm_vars={})'.format(
+            self.cmn_window, self.min_cmn_window, self.center, self.norm_vars)
+
+
+class ComputeDeltas(_ModuleNoStateBuffers):
+    """``functional.compute_deltas`` as a layer (torchaudio's ``transforms.ComputeDeltas``): ``(…, F, T)`` → the same shape.
+    No buffers."""
+
+    def __init__(self, win_length=5, mode='replicate'):
+        super(ComputeDeltas, self).__init__()
+        self.win_length, self.mode = int(win_length), mode
+        _composite.deltas_check_args(self.win_length, mode)                 # argument errors surface here, not in the first forward
+
+    def forward(self, specgram):
+        return F.compute_deltas(specgram, self.win_length, self.mode)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(win_length={}, mode={!r})'.format(self.win_length, self.mode)
 
 
 class FFTConvolve(_ModuleNoStateBuffers):
