@@ -572,6 +572,26 @@ int tac_kaldi_fbank_f32(const float* x, int64_t rows, int64_t length, int64_t st
                         const int32_t* table, int32_t n_fft, int32_t win_length, int32_t shift, int32_t n_mels, int32_t w_total,
                         int32_t flags, float preemph, float energy_floor, float* out, void* stream);
 
+/* (18b) functional.kaldi_mfcc / kaldi_spectrogram (torchaudio.compliance.kaldi.mfcc / .spectrogram): epilogues of the launch of (18),
+ *      everything up to the power row P[k] = |rfft f|^2, k <= N/2, as there (same arguments, same flags, same eps).
+ *      tac_kaldi_spectrogram_f32: out: float[rows][T][N/2 + 1]; out[k] = log max(P[k], eps) for k = 1 .. N/2, the Nyquist bin
+ *      included; out[0] = e, the log energy of (18).  No bank.  TAC_KALDI_POWER, _LOG and _USE_ENERGY are implied, _HTK is ignored.
+ *      tac_kaldi_mfcc_f32: out: float[rows][T][n_ceps], 1 <= n_ceps <= n_mels.  L[b] = log max(sum_k bank[b][k] P[k], eps) (the row of
+ *      (18) with TAC_KALDI_LOG | TAC_KALDI_POWER, which are implied) stays in the LDS; C[c] = sum_b L[b] dct[b][c] is ONE fused
+ *      multiply-add chain over b ascending.  dct = DEVICE float[n_mels][n_ceps]: the caller's DCT-II matrix with the lifter (and
+ *      the sqrt 2 of HTK's C0) folded in.  With TAC_KALDI_USE_ENERGY C[0] := e; with TAC_KALDI_HTK the columns are stored as
+ *      [C1 .. C_{n_ceps - 1}, C0].  A NaN in L reaches every coefficient of its frame and no other frame.
+ *      The matrix shares the launch's 64 KB of LDS with the waves' areas, the window and the packed bank:
+ *      tac_kaldi_mfcc_table_limit(n_fft, n_mels, w_total) is the largest n_mels * n_ceps a launch takes (0: arguments outside (18));
+ *      beyond it TAC_E_UNSUPPORTED, nothing launched.  One writer per element, no atomics: bit-identical from run to run. */
+int64_t tac_kaldi_mfcc_table_limit(int32_t n_fft, int32_t n_mels, int32_t w_total);
+int tac_kaldi_mfcc_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* window, const float* weights,
+                       const int32_t* table, const float* dct, int32_t n_fft, int32_t win_length, int32_t shift, int32_t n_mels,
+                       int32_t w_total, int32_t n_ceps, int32_t flags, float preemph, float energy_floor, float* out, void* stream);
+int tac_kaldi_spectrogram_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* window, int32_t n_fft,
+                              int32_t win_length, int32_t shift, int32_t flags, float preemph, float energy_floor, float* out,
+                              void* stream);
+
 /* (19) functional.sliding_window_cmn (Kaldi's apply-cmvn-sliding): ONE launch over x[r*stride_r + t*stride_t + f*stride_f], r < rows,
  *      t < n_frames = T, f < n_feats = F (strides in elements, positive for every axis longer than one), out: float[rows][T][F], dense
  *      (csrc/cmn_deltas.hip).  W = cmn_window >= 1, M = min_cmn_window >= 1.  The window of frame t is [ws, we), n = we - ws:

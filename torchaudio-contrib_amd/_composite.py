@@ -268,34 +268,31 @@ _kaldi_constants = {}
 
 
 def _kaldi_tables(p, w, n, dtype, device):
-    """(window (W,), bank (bins, n // 2)) of ``_kaldi`` — built in float64, rounded once — cached per argument set"""
-    key = (p.window_type, p.blackman_coeff, w, n, p.num_mel_bins, p.sample_frequency, p.low_freq, p.high_freq, dtype, str(device))
+    """(window (W,), bank (bins, n // 2)) of ``_kaldi`` — built in float64, rounded once — cached per argument set; no bank for
+    ``SpectrogramParams``"""
+    bins = getattr(p, 'num_mel_bins', None)
+    band = (bins, p.sample_frequency, p.low_freq, p.high_freq) if bins is not None else None
+    key = (p.window_type, p.blackman_coeff, w, n, band, dtype, str(device))
     hit = _kaldi_constants.get(key)
     if hit is None:
         with torch.inference_mode(False):
             window = _kaldi.window64(p.window_type, w, p.blackman_coeff).to(dtype).to(device)
-            bank = _kaldi.mel_bank64(p.num_mel_bins, n, p.sample_frequency, p.low_freq, p.high_freq)[:, :-1]
-            bank = bank.to(dtype).to(device)
+            bank = None
+            if bins is not None:
+                bank = _kaldi.mel_bank64(bins, n, p.sample_frequency, p.low_freq, p.high_freq)[:, :-1]
+                bank = bank.to(dtype).to(device)
         if len(_kaldi_constants) > 32:
             _kaldi_constants.clear()
         hit = _kaldi_constants[key] = (window, bank)
     return hit
 
 
-def kaldi_fbank(wave, *args):
-    """torchaudio's ``compliance.kaldi.fbank`` over ``(…, time)`` in torch operators, step by step as ``_kaldi`` defines it:
+def _kaldi_spectrum(work, p, w, s, n, m, window):
+    """The steps ``kaldi_fbank``, ``kaldi_mfcc`` and ``kaldi_spectrogram`` share, on ``(…, time)`` with ``m >= 1`` frames:
     frames (an ``unfold`` view, or a gather through the mirrored index with ``snip_edges=False``), dither, mean removal (the
     sum accumulated in float64, rounded once), energy, pre-emphasis with the first sample replicated, window, ``rfft`` at ``N``
-    points, the bank over the bins below the last one, the floored logarithm, the energy column, the mean over frames."""
-    p = _kaldi.Params(*args)
-    w, s, n = _kaldi.check(p)
-    work = wave if wave.dtype in (torch.float32, torch.float64) else wave.float()
+    points.  Returns (``|rfft|`` (…, m, n // 2 + 1), the log energy (…, m) before its floor, the floor under the logarithms)."""
     length = work.shape[-1]
-    m = _kaldi.num_frames(length, w, s, p.snip_edges)
-    cols = p.num_mel_bins + (1 if p.use_energy else 0)
-    if m == 0 or work.numel() == 0:
-        return wave.new_zeros(tuple(wave.shape[:-1]) + (m, cols))
-    window, bank = _kaldi_tables(p, w, n, work.dtype, work.device)
     if p.snip_edges:
         frames = work.unfold(-1, w, s)
     else:
@@ -315,16 +312,83 @@ def kaldi_fbank(wave, *args):
     frames = frames * window
     if energy is None:
         energy = log_energy(frames)
-    spec = torch.fft.rfft(frames, n=n, dim=-1).abs()[..., :n // 2]
+    return torch.fft.rfft(frames, n=n, dim=-1).abs(), energy, floor
+
+
+def _kaldi_floored_energy(energy, p):
+    if p.energy_floor > 0.0:
+        energy = torch.maximum(energy, torch.tensor(math.log(p.energy_floor), dtype=energy.dtype, device=energy.device))
+    return energy
+
+
+def kaldi_fbank(wave, *args):
+    """torchaudio's ``compliance.kaldi.fbank`` over ``(…, time)`` in torch operators, step by step as ``_kaldi`` defines it:
+    the frames' spectra (``_kaldi_spectrum``), the bank over the bins below the last one, the floored logarithm, the energy
+    column, the mean over frames."""
+    p = _kaldi.Params(*args)
+    w, s, n = _kaldi.check(p)
+    work = wave if wave.dtype in (torch.float32, torch.float64) else wave.float()
+    length = work.shape[-1]
+    m = _kaldi.num_frames(length, w, s, p.snip_edges)
+    cols = p.num_mel_bins + (1 if p.use_energy else 0)
+    if m == 0 or work.numel() == 0:
+        return wave.new_zeros(tuple(wave.shape[:-1]) + (m, cols))
+    window, bank = _kaldi_tables(p, w, n, work.dtype, work.device)
+    spec, energy, floor = _kaldi_spectrum(work, p, w, s, n, m, window)
+    spec = spec[..., :n // 2]
     if p.use_power:
         spec = spec.pow(2.0)
     out = torch.matmul(spec, bank.t())
     if p.use_log_fbank:
         out = torch.maximum(out, floor).log()
     if p.use_energy:
-        if p.energy_floor > 0.0:
-            energy = torch.maximum(energy, torch.tensor(math.log(p.energy_floor), dtype=work.dtype, device=work.device))
+        energy = _kaldi_floored_energy(energy, p)
         out = torch.cat([out, energy.unsqueeze(-1)] if p.htk_compat else [energy.unsqueeze(-1), out], -1)
+    if p.subtract_mean:
+        out = out - out.mean(dim=-2, keepdim=True)
+    out = out.contiguous()
+    return out if out.dtype == wave.dtype else out.to(wave.dtype)
+
+
+def kaldi_mfcc(wave, *args):
+    """torchaudio's ``compliance.kaldi.mfcc`` over ``(…, time)`` in torch operators: the log-mel rows as ``kaldi_fbank`` makes
+    them, times ``_kaldi.mfcc_table64`` (DCT-II, lifter, HTK's sqrt 2), the energy in place of C0, the HTK column order, the
+    mean over frames."""
+    p = _kaldi.MfccParams(*args)
+    w, s, n = _kaldi.check(p, 'kaldi_mfcc')
+    work = wave if wave.dtype in (torch.float32, torch.float64) else wave.float()
+    m = _kaldi.num_frames(work.shape[-1], w, s, p.snip_edges)
+    if m == 0 or work.numel() == 0:
+        return wave.new_zeros(tuple(wave.shape[:-1]) + (m, p.num_ceps))
+    window, bank = _kaldi_tables(p, w, n, work.dtype, work.device)
+    spec, energy, floor = _kaldi_spectrum(work, p, w, s, n, m, window)
+    logmel = torch.maximum(torch.matmul(spec[..., :n // 2].pow(2.0), bank.t()), floor).log()
+    with torch.inference_mode(False):
+        table = _kaldi.mfcc_table64(p).to(work.dtype).to(work.device)
+    out = torch.matmul(logmel, table)
+    if p.use_energy:
+        out = torch.cat([_kaldi_floored_energy(energy, p).unsqueeze(-1), out[..., 1:]], -1)
+    if p.htk_compat:
+        out = torch.cat([out[..., 1:], out[..., :1]], -1)
+    if p.subtract_mean:
+        out = out - out.mean(dim=-2, keepdim=True)
+    out = out.contiguous()
+    return out if out.dtype == wave.dtype else out.to(wave.dtype)
+
+
+def kaldi_spectrogram(wave, *args):
+    """torchaudio's ``compliance.kaldi.spectrogram`` over ``(…, time)`` in torch operators: the floored logarithm of every bin
+    of the power spectrum, the Nyquist bin included, the log energy in place of the DC bin, the mean over frames."""
+    p = _kaldi.SpectrogramParams(*args)
+    w, s, n = _kaldi.check(p, 'kaldi_spectrogram')
+    work = wave if wave.dtype in (torch.float32, torch.float64) else wave.float()
+    m = _kaldi.num_frames(work.shape[-1], w, s, p.snip_edges)
+    if m == 0 or work.numel() == 0:
+        return wave.new_zeros(tuple(wave.shape[:-1]) + (m, n // 2 + 1))
+    window, _ = _kaldi_tables(p, w, n, work.dtype, work.device)
+    spec, energy, floor = _kaldi_spectrum(work, p, w, s, n, m, window)
+    out = torch.maximum(spec.pow(2.0), floor).log()
+    out = torch.cat([_kaldi_floored_energy(energy, p).unsqueeze(-1), out[..., 1:]], -1)
     if p.subtract_mean:
         out = out - out.mean(dim=-2, keepdim=True)
     out = out.contiguous()

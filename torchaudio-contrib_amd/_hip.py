@@ -1148,19 +1148,98 @@ _kaldi_tables = {}
 
 def _kaldi_device_tables(p, w, n, device):
     """(window float32 (W,), packed weights, int32 table (3, bins)) on ``device``: built in float64 on the host, rounded once,
-    cached per argument set and device"""
-    key = (p.window_type, p.blackman_coeff, w, n, p.num_mel_bins, p.sample_frequency, p.low_freq, p.high_freq, device)
+    cached per argument set and device.  ``SpectrogramParams`` have no bank: (window, None, None, 0)."""
+    bins = getattr(p, 'num_mel_bins', None)
+    band = (bins, p.sample_frequency, p.low_freq, p.high_freq) if bins is not None else None
+    key = (p.window_type, p.blackman_coeff, w, n, band, device)
     hit = _kaldi_tables.get(key)
     if hit is None:
         with torch.inference_mode(False):
             window = _kaldi.window64(p.window_type, w, p.blackman_coeff).to(torch.float32)
-            bank = _kaldi.mel_bank64(p.num_mel_bins, n, p.sample_frequency, p.low_freq, p.high_freq).to(torch.float32)
-            weights, table = _kaldi.packed_runs(bank)
-            hit = (window.to(device), weights.to(device), table.contiguous().to(device), int(weights.numel()))
+            if bins is None:
+                hit = (window.to(device), None, None, 0)
+            else:
+                bank = _kaldi.mel_bank64(bins, n, p.sample_frequency, p.low_freq, p.high_freq).to(torch.float32)
+                weights, table = _kaldi.packed_runs(bank)
+                hit = (window.to(device), weights.to(device), table.contiguous().to(device), int(weights.numel()))
         if len(_kaldi_tables) > 64:
             _kaldi_tables.clear()
         _kaldi_tables[key] = hit
     return hit
+
+
+def _kaldi_rows(x):
+    """``x`` (…, L) as (rows, L) for the kaldi launches: read where it lies when its leading dims collapse into one positive row
+    stride over unit-stride rows, copied otherwise"""
+    length = int(x.shape[-1])
+    rows = x.reshape(-1, length)
+    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+        rows = rows.contiguous()
+    return rows
+
+
+def _kaldi_flags(p):
+    return sum(bit for name, bit in _KALDI_FLAGS.items() if getattr(p, name, False))
+
+
+_kaldi_dct_tables = {}
+
+
+def _kaldi_dct_table(p, device):
+    """``_kaldi.mfcc_table64`` rounded to float32 once, (num_mel_bins, num_ceps) row-major on ``device``: the lanes of a frame
+    read consecutive words of one row"""
+    key = (p.num_mel_bins, p.num_ceps, p.cepstral_lifter, p.htk_compat and not p.use_energy, device)
+    hit = _kaldi_dct_tables.get(key)
+    if hit is None:
+        with torch.inference_mode(False):
+            hit = _kaldi.mfcc_table64(p).to(torch.float32).contiguous().to(device)
+        if len(_kaldi_dct_tables) > 64:
+            _kaldi_dct_tables.clear()
+        _kaldi_dct_tables[key] = hit
+    return hit
+
+
+def kaldi_mfcc_table_limit(p, w, n, device):
+    """``tac_kaldi_mfcc_table_limit``: the largest ``num_mel_bins * num_ceps`` the launch has LDS for beside this call's
+    window and packed bank — asked before launching, so that a larger table is routed, not refused"""
+    w_total = _kaldi_device_tables(p, w, n, device)[3]
+    return int(_native.lib().tac_kaldi_mfcc_table_limit(n, p.num_mel_bins, w_total))
+
+
+def kaldi_mfcc(x, p, w, s, n, m):
+    """``(…, L)`` float32 -> ``(…, m, num_ceps)`` through ``tac_kaldi_mfcc_f32``: one launch (``subtract_mean`` is the
+    caller's); rows as ``kaldi_fbank`` takes them."""
+    window, weights, table, w_total = _kaldi_device_tables(p, w, n, x.device)
+    dct = _kaldi_dct_table(p, x.device)
+    out = _empty(tuple(x.shape[:-1]) + (m, p.num_ceps), device=x.device)
+    if not out.numel():
+        return out
+    rows = _kaldi_rows(x)
+    with _native.on_device(x.device):
+        rc = _native.lib().tac_kaldi_mfcc_f32(
+            _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0), _native.ptr(window), _native.ptr(weights),
+            _native.ptr(table), _native.ptr(dct), n, w, s, p.num_mel_bins, w_total, p.num_ceps, _kaldi_flags(p),
+            p.preemphasis_coefficient, p.energy_floor, _native.ptr(out), _native.stream_ptr(x.device))
+    _native.check(rc, 'tac_kaldi_mfcc_f32')
+    _count('tac_kaldi_mfcc_f32', out)
+    return out
+
+
+def kaldi_spectrogram(x, p, w, s, n, m):
+    """``(…, L)`` float32 -> ``(…, m, n / 2 + 1)`` through ``tac_kaldi_spectrogram_f32``: one launch (``subtract_mean`` is the
+    caller's); rows as ``kaldi_fbank`` takes them."""
+    window = _kaldi_device_tables(p, w, n, x.device)[0]
+    out = _empty(tuple(x.shape[:-1]) + (m, n // 2 + 1), device=x.device)
+    if not out.numel():
+        return out
+    rows = _kaldi_rows(x)
+    with _native.on_device(x.device):
+        rc = _native.lib().tac_kaldi_spectrogram_f32(
+            _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0), _native.ptr(window), n, w, s, _kaldi_flags(p),
+            p.preemphasis_coefficient, p.energy_floor, _native.ptr(out), _native.stream_ptr(x.device))
+    _native.check(rc, 'tac_kaldi_spectrogram_f32')
+    _count('tac_kaldi_spectrogram_f32', out)
+    return out
 
 
 def kaldi_fbank(x, p, w, s, n, m):
@@ -1173,10 +1252,8 @@ def kaldi_fbank(x, p, w, s, n, m):
     out = _empty(tuple(x.shape[:-1]) + (m, cols), device=x.device)
     if not out.numel():
         return out
-    rows = x.reshape(-1, length)
-    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
-        rows = rows.contiguous()
-    flags = sum(bit for name, bit in _KALDI_FLAGS.items() if getattr(p, name))
+    rows = _kaldi_rows(x)
+    flags = _kaldi_flags(p)
     with _native.on_device(x.device):
         rc = _native.lib().tac_kaldi_fbank_f32(
             _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(window), _native.ptr(weights), _native.ptr(table),

@@ -42,6 +42,7 @@ EXPORTS = (
     'tac_spectral_mac_tile', 'tac_spectral_mac_f32', 'tac_fftconvolve_default_n_fft', 'tac_fftconvolve_supported',
     'tac_fftconvolve_spectra_workspace', 'tac_fftconvolve_spectra_f32', 'tac_fftconvolve_workspace', 'tac_fftconvolve_f32',
     'tac_fftconvolve_direct_f32', 'tac_kaldi_num_frames', 'tac_kaldi_fbank_f32',
+    'tac_kaldi_mfcc_table_limit', 'tac_kaldi_mfcc_f32', 'tac_kaldi_spectrogram_f32',
     'tac_sliding_cmn_chunk', 'tac_sliding_cmn_f32', 'tac_deltas_supported', 'tac_deltas_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
@@ -210,6 +211,10 @@ def lib():
         h.tac_kaldi_num_frames.restype = _I64
         h.tac_kaldi_num_frames.argtypes = [_I64, _I32, _I32, ctypes.c_int]
         h.tac_kaldi_fbank_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P]
+        h.tac_kaldi_mfcc_table_limit.restype = _I64
+        h.tac_kaldi_mfcc_table_limit.argtypes = [_I32, _I32, _I32]
+        h.tac_kaldi_mfcc_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P]
+        h.tac_kaldi_spectrogram_f32.argtypes = [_P, _I64, _I64, _I64, _P, _I32, _I32, _I32, _I32, _F, _F, _P, _P]
         h.tac_sliding_cmn_chunk.restype = _I64
         h.tac_sliding_cmn_chunk.argtypes = [_I64, _I64, _I64, _I64, _I64]
         h.tac_sliding_cmn_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, ctypes.c_int, ctypes.c_int,

@@ -11,6 +11,8 @@ see them by name.
     tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
     tac_amd::resample           polyphase windowed-sinc resampling of the waveform (csrc/resample.hip)
     tac_amd::kaldi_fbank        Kaldi log mel filterbank features: framing, FFT, mel bank and log in one launch (csrc/kaldi_fbank.hip)
+    tac_amd::kaldi_mfcc         Kaldi cepstra: the same launch with the DCT, lifter and energy substitution as its epilogue
+    tac_amd::kaldi_spectrogram  Kaldi log power spectrogram: the same launch, every bin's logarithm, the energy as column 0
     tac_amd::sliding_window_cmn sliding-window cepstral mean (and variance) normalisation over (…, T, F) (csrc/cmn_deltas.hip)
     tac_amd::compute_deltas     delta coefficients along time over (…, F, T) (csrc/cmn_deltas.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
@@ -734,6 +736,24 @@ def _kaldi_shape(wave, p):
     return tuple(wave.shape[:-1]) + (m, p.num_mel_bins + (1 if p.use_energy else 0))
 
 
+def _kaldi_reason(wave, p, w, n):
+    """why the launch of csrc/kaldi_fbank.hip does not take this call (any of the three parameter tuples), or None"""
+    reason = _hip_dtype(wave)
+    if reason is None and not p.round_to_power_of_two:
+        reason = 'round_to_power_of_two=False'
+    if reason is None and n not in H.KALDI_SIZES:
+        reason = 'a transform of %d points (the kernel takes %s)' % (n, ' / '.join(str(v) for v in H.KALDI_SIZES))
+    if reason is None and getattr(p, 'num_mel_bins', 0) > H.KALDI_MAX_BINS:
+        reason = '%d mel bins (the kernel takes up to %d)' % (p.num_mel_bins, H.KALDI_MAX_BINS)
+    if reason is None and p.dither != 0.0:
+        reason = 'dither != 0'
+    if reason is None and any(st <= 0 for st, k in zip(wave.stride(), wave.shape) if k > 1):
+        reason = 'non-positive strides'
+    if reason is None and not p.snip_edges and wave.shape[-1] < w:
+        reason = 'snip_edges=False on a waveform shorter than a frame'
+    return reason
+
+
 def _kaldi_fbank_cuda(wave, *args):
     p = K.Params(*args)
     w, s, n = K.check(p)
@@ -741,19 +761,7 @@ def _kaldi_fbank_cuda(wave, *args):
     m = K.num_frames(length, w, s, p.snip_edges)
     if m == 0 or wave.numel() == 0:
         return wave.new_zeros(_kaldi_shape(wave, p))            # an empty output: nothing is launched
-    reason = _hip_dtype(wave)
-    if reason is None and not p.round_to_power_of_two:
-        reason = 'round_to_power_of_two=False'
-    if reason is None and n not in H.KALDI_SIZES:
-        reason = 'a transform of %d points (the kernel takes %s)' % (n, ' / '.join(str(v) for v in H.KALDI_SIZES))
-    if reason is None and p.num_mel_bins > H.KALDI_MAX_BINS:
-        reason = '%d mel bins (the kernel takes up to %d)' % (p.num_mel_bins, H.KALDI_MAX_BINS)
-    if reason is None and p.dither != 0.0:
-        reason = 'dither != 0'
-    if reason is None and any(st <= 0 for st, k in zip(wave.stride(), wave.shape) if k > 1):
-        reason = 'non-positive strides'
-    if reason is None and not p.snip_edges and length < w:
-        reason = 'snip_edges=False on a waveform shorter than a frame'
+    reason = _kaldi_reason(wave, p, w, n)
     if reason is not None:
         _composite_route('kaldi_fbank', reason)
         return C.kaldi_fbank(wave, *args)
@@ -768,6 +776,72 @@ def _kaldi_fbank_fake(wave, *args):
 
 
 _register('kaldi_fbank', '(Tensor wave, %s) -> Tensor' % K.SCHEMA_ARGS, _kaldi_fbank_cuda, C.kaldi_fbank, _kaldi_fbank_fake, 1)
+
+
+# ============================================================================= kaldi_mfcc, kaldi_spectrogram
+def _kaldi_frames(wave, p):
+    w, s, n = K.sizes(p.sample_frequency, p.frame_length, p.frame_shift, p.round_to_power_of_two)
+    return K.num_frames(wave.shape[-1], w, s, p.snip_edges), n
+
+
+def _kaldi_mfcc_shape(wave, p):
+    return tuple(wave.shape[:-1]) + (_kaldi_frames(wave, p)[0], p.num_ceps)
+
+
+def _kaldi_spectrogram_shape(wave, p):
+    m, n = _kaldi_frames(wave, p)
+    return tuple(wave.shape[:-1]) + (m, n // 2 + 1)
+
+
+def _kaldi_mfcc_cuda(wave, *args):
+    p = K.MfccParams(*args)
+    w, s, n = K.check(p, 'kaldi_mfcc')
+    m = K.num_frames(wave.shape[-1], w, s, p.snip_edges)
+    if m == 0 or wave.numel() == 0:
+        return wave.new_zeros(_kaldi_mfcc_shape(wave, p))       # an empty output: nothing is launched
+    reason = _kaldi_reason(wave, p, w, n)
+    if reason is None:
+        limit = H.kaldi_mfcc_table_limit(p, w, n, wave.device)
+        if p.num_mel_bins * p.num_ceps > limit:
+            reason = 'a DCT table of %d x %d floats (the launch has room for %d)' % (p.num_mel_bins, p.num_ceps, limit)
+    if reason is not None:
+        _composite_route('kaldi_mfcc', reason)
+        return C.kaldi_mfcc(wave, *args)
+    out = H.kaldi_mfcc(_f32(wave), p, w, s, n, m)
+    if p.subtract_mean:
+        out = out - out.mean(dim=-2, keepdim=True)
+    return out if wave.dtype == out.dtype else out.to(wave.dtype)
+
+
+def _kaldi_mfcc_fake(wave, *args):
+    return wave.new_empty(_kaldi_mfcc_shape(wave, K.MfccParams(*args)))
+
+
+_register('kaldi_mfcc', '(Tensor wave, %s) -> Tensor' % K.MFCC_SCHEMA_ARGS, _kaldi_mfcc_cuda, C.kaldi_mfcc, _kaldi_mfcc_fake, 1)
+
+
+def _kaldi_spectrogram_cuda(wave, *args):
+    p = K.SpectrogramParams(*args)
+    w, s, n = K.check(p, 'kaldi_spectrogram')
+    m = K.num_frames(wave.shape[-1], w, s, p.snip_edges)
+    if m == 0 or wave.numel() == 0:
+        return wave.new_zeros(_kaldi_spectrogram_shape(wave, p))
+    reason = _kaldi_reason(wave, p, w, n)
+    if reason is not None:
+        _composite_route('kaldi_spectrogram', reason)
+        return C.kaldi_spectrogram(wave, *args)
+    out = H.kaldi_spectrogram(_f32(wave), p, w, s, n, m)
+    if p.subtract_mean:
+        out = out - out.mean(dim=-2, keepdim=True)
+    return out if wave.dtype == out.dtype else out.to(wave.dtype)
+
+
+def _kaldi_spectrogram_fake(wave, *args):
+    return wave.new_empty(_kaldi_spectrogram_shape(wave, K.SpectrogramParams(*args)))
+
+
+_register('kaldi_spectrogram', '(Tensor wave, %s) -> Tensor' % K.SPECTROGRAM_SCHEMA_ARGS, _kaldi_spectrogram_cuda,
+          C.kaldi_spectrogram, _kaldi_spectrogram_fake, 1)
 
 
 # ============================================================================= sliding_window_cmn, compute_deltas

@@ -20,6 +20,16 @@
 //                       intervals end below the Nyquist bin, which is never read.  log is logf (as the dB epilogue's log10f).
 // One writer per output element, no atomics: bit-identical from run to run.  A non-finite sample reaches exactly the frames
 // whose W samples contain it (the span is shared, the reads are per frame).
+//
+// kaldi.mfcc and kaldi.spectrogram are epilogues of the same launch (MODE below): everything up to the |X|^2 row is shared.
+//   spectrogram         the frame's lanes write log max(|X[k]|^2, eps) for k = 1 .. N/2 (the Nyquist bin included) and the log
+//                       energy as column 0: no bank, no bank tables.
+//   mfcc                the bands' logarithms go to the free half of the frame's own part of the area (the row takes N/2 + 1 of
+//                       its N + N/16 + 2 floats) instead of memory; after a fence lane t computes the coefficients c = t,
+//                       t + N/32, ..: each ONE fused multiply-add chain over b ascending against a table in the LDS,
+//                       table[b][c] = D[b][c] lift[c] (and sqrt 2 on c = 0 for HTK without energy), float64 on the host,
+//                       rounded once; the lanes of a frame read consecutive words of row b.  Energy substitution and the HTK
+//                       rotation are decided at the store.  A NaN band reaches every chain of its frame (NaN * 0 = NaN).
 #include <cmath>
 
 #include "host_common.hpp"
@@ -31,6 +41,8 @@ constexpr int KF_MAX_MELS = 128;
 constexpr int KF_MAX_WEIGHTS = 4096;             // floats of packed bank (a triangular bank has at most N of them)
 constexpr float KF_EPS = 1.1920928955078125e-07f;   // 2^-23
 constexpr float KF_LOG_EPS = -15.942385f;           // float32(log 2^-23): the floor's own value, not what logf makes of it
+
+enum { KF_FBANK = 0, KF_MFCC = 1, KF_SPECTROGRAM = 2 };      // the epilogue of the launch
 
 enum { KF_SNIP = TAC_KALDI_SNIP_EDGES, KF_DC = TAC_KALDI_REMOVE_DC, KF_RAW_ENERGY = TAC_KALDI_RAW_ENERGY, KF_USE_ENERGY = TAC_KALDI_USE_ENERGY,
        KF_HTK = TAC_KALDI_HTK, KF_LOG = TAC_KALDI_LOG, KF_POWER = TAC_KALDI_POWER };
@@ -44,6 +56,12 @@ struct KfArgs {
     int win_length, shift, n_mels, w_total, flags, first;     // first: start of frame 0 (0 or -(W/2 - S/2))
     float preemph, log_energy_floor;
     float* out;
+};
+
+// KF_MFCC only, and a kernel argument of its own behind the others: KfArgs and with it the fbank kernel's code stay as they were
+struct KfDct {
+    const float* table;       // [n_mels][n_ceps], lifter (and HTK's sqrt 2) folded in
+    int n_ceps;
 };
 
 template <int LPF>
@@ -66,9 +84,25 @@ __device__ __forceinline__ long long kf_mirror(long long j, long long n) {
     return j < 0 ? 0 : (j >= n ? n - 1 : j);
 }
 
-template <int NC>
+// CH coefficients of a frame's DCT at once: c0, c0 + LPF, ..; every chain runs over b ascending
+template <int CH, int LPF>
+__device__ __forceinline__ void kf_dct_chunk(const float* lrow, const float* dtab, int M, int nc, int c0, float (&acc)[4]) {
+    int col[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        col[j] = c0 + j * LPF < nc ? c0 + j * LPF : nc - 1;   // a lane past the last coefficient reads the last one
+        acc[j] = 0.0f;
+    }
+    for (int b = 0; b < M; ++b) {
+        const float l = lrow[b];
+#pragma unroll
+        for (int j = 0; j < CH; ++j) acc[j] = __builtin_fmaf(l, dtab[b * nc + col[j]], acc[j]);
+    }
+}
+
+template <int NC, int MODE>
 __global__ void __launch_bounds__(KF_WAVES * 64)
-kaldi_fbank_kernel(KfArgs a, Tables tb) {
+kaldi_fbank_kernel(KfArgs a, Tables tb, KfDct dct) {
     constexpr int E = 16;
     using F = WaveFft<NC, E>;
     constexpr int LPF = F::LPF, G = F::G, N = F::N;
@@ -91,7 +125,7 @@ kaldi_fbank_kernel(KfArgs a, Tables tb) {
     int* const boff = bnum + M;
 
     for (int i = threadIdx.x; i < N; i += KF_WAVES * 64) wins[i] = i < W ? a.window[i] : 0.0f;
-    for (int i = threadIdx.x; i < a.w_total; i += KF_WAVES * 64) wts[i] = a.weights[i];
+    for (int i = threadIdx.x; i < a.w_total; i += KF_WAVES * 64) wts[i] = a.weights[i];     // (KF_SPECTROGRAM: no bank, 0 and 0)
     for (int b = threadIdx.x; b < M; b += KF_WAVES * 64) {
         // clamped to what the row and the packed bank hold, whatever the table says: never the Nyquist bin, never past the weights
         int lo = a.table[b], n = a.table[M + b], off = a.table[2 * M + b];
@@ -103,6 +137,9 @@ kaldi_fbank_kernel(KfArgs a, Tables tb) {
         bnum[b] = n;
         boff[b] = off;
     }
+    float* const dtab = reinterpret_cast<float*>(boff + M);    // KF_MFCC: n_mels x n_ceps
+    if constexpr (MODE == KF_MFCC)
+        for (int i = threadIdx.x; i < M * dct.n_ceps; i += KF_WAVES * 64) dtab[i] = dct.table[i];
 
     cf tw[F::NTW];
     cf ptw[F::NPAIR];
@@ -226,6 +263,53 @@ kaldi_fbank_kernel(KfArgs a, Tables tb) {
             wave_lds_fence();
         }
 
+        if constexpr (MODE == KF_SPECTROGRAM) {
+            // ---- every bin's logarithm, the Nyquist bin srow[NC] included; the energy in place of the DC bin
+            if (live) {
+                float* const orow = a.out + (row * T + frame0 + sub) * (NC + 1);
+                for (int k = t; k <= NC; k += LPF) orow[k] = k == 0 ? energy : kf_log_floor(srow[k]);
+            }
+        } else if constexpr (MODE == KF_MFCC) {
+            // ---- the bank as below, its logarithms kept in the LDS: the half of the frame's part behind the row is free
+            static_assert(NC + 2 + KF_MAX_MELS <= 2 * F::PADDED, "the log-mel row does not fit behind the spectrum row");
+            float* const lrow = srow + NC + 2;
+            if (live) {
+                for (int b = t; b < M; b += LPF) {
+                    const int lo = blo[b], n = bnum[b];
+                    const float* const wb = wts + boff[b];
+                    float acc = 0.0f;
+                    for (int j = 0; j < n; ++j) acc = __builtin_fmaf(wb[j], srow[lo + j], acc);
+                    lrow[b] = kf_log_floor(acc);
+                }
+            }
+            wave_lds_fence();                                  // the frame's whole log-mel row is written
+            // ---- DCT: coefficient c = t, t + LPF, ..; the energy in place of C0; HTK: [C1 .. C_{n-1}, C0]
+            if (live) {
+                const int nc = dct.n_ceps;
+                float* const orow = a.out + (row * T + frame0 + sub) * nc;
+                const bool sub_e = (a.flags & KF_USE_ENERGY) != 0, htk = (a.flags & KF_HTK) != 0;
+                auto store = [&](int cc, float val) {
+                    if (cc < nc) orow[htk ? (cc == 0 ? nc - 1 : cc - 1) : cc] = (cc == 0 && sub_e) ? energy : val;
+                };
+                float acc[4];
+                int c0 = t;
+                for (; c0 - t + 3 * LPF < nc; c0 += 4 * LPF) {          // (uniform over the wave: t is taken out)
+                    kf_dct_chunk<4, LPF>(lrow, dtab, M, nc, c0, acc);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) store(c0 + j * LPF, acc[j]);
+                }
+                if (c0 - t + LPF < nc) {
+                    kf_dct_chunk<2, LPF>(lrow, dtab, M, nc, c0, acc);
+                    store(c0, acc[0]);
+                    store(c0 + LPF, acc[1]);
+                    c0 += 2 * LPF;
+                }
+                if (c0 - t < nc) {
+                    kf_dct_chunk<1, LPF>(lrow, dtab, M, nc, c0, acc);
+                    store(c0, acc[0]);
+                }
+            }
+        } else
         // ---- the bank: one chain per output element over its band's bins, ascending
         if (live) {
             float* const orow = a.out + (row * T + frame0 + sub) * C;
@@ -241,20 +325,27 @@ kaldi_fbank_kernel(KfArgs a, Tables tb) {
     }
 }
 
+// bytes of LDS of a launch without the DCT table: the waves' areas, the window, the packed bank and its table
 template <int NC>
-int kf_launch(const KfArgs& a, hipStream_t stream) {
+constexpr size_t kf_lds_bytes(int w_total, int n_mels) {
+    using F = WaveFft<NC, 16>;
+    constexpr int WAVE_SLOTS = ((F::G * F::PADDED + 1) / 2) * 2;
+    return (size_t)KF_WAVES * WAVE_SLOTS * sizeof(cf) + 4 * ((size_t)F::N + (size_t)w_total + 3 * (size_t)n_mels);
+}
+
+template <int NC, int MODE = KF_FBANK>
+int kf_launch(const KfArgs& a, hipStream_t stream, KfDct dct = KfDct()) {
     using F = WaveFft<NC, 16>;
     Tables tb;
     const int rc = get_tables(2 * NC, &tb);
     if (rc != TAC_OK) return rc;
-    constexpr int WAVE_SLOTS = ((F::G * F::PADDED + 1) / 2) * 2;
-    const size_t bytes = (size_t)KF_WAVES * WAVE_SLOTS * sizeof(cf) + 4 * ((size_t)F::N + (size_t)a.w_total + 3 * (size_t)a.n_mels);
+    const size_t bytes = kf_lds_bytes<NC>(a.w_total, a.n_mels) + (MODE == KF_MFCC ? 4 * (size_t)a.n_mels * (size_t)dct.n_ceps : 0);
     if (bytes > 64 * 1024) return TAC_E_UNSUPPORTED;
     const long long units = a.rows * ((a.n_frames + F::G - 1) / F::G);
     long long per_cu = (long long)(160 * 1024 / bytes);
     per_cu = per_cu > 2 ? 2 : per_cu;                          // the kernel's ~220 registers leave room for two waves per SIMD
     const long long blocks = persistent_blocks(units, KF_WAVES, (long long)device_cu_count() * per_cu);
-    return launch_kernel(kaldi_fbank_kernel<NC>, blocks, KF_WAVES * 64, bytes, stream, a, tb);
+    return launch_kernel(kaldi_fbank_kernel<NC, MODE>, blocks, KF_WAVES * 64, bytes, stream, a, tb, dct);
 }
 
 }  // namespace tac
@@ -303,6 +394,92 @@ int tac_kaldi_fbank_f32(const float* x, int64_t rows, int64_t length, int64_t st
     a.out = out;
     hipStream_t s = (hipStream_t)stream;
     return n_fft == 256 ? kf_launch<128>(a, s) : (n_fft == 512 ? kf_launch<256>(a, s) : kf_launch<512>(a, s));
+}
+
+int64_t tac_kaldi_mfcc_table_limit(int32_t n_fft, int32_t n_mels, int32_t w_total) {
+    using namespace tac;
+    if ((n_fft != 256 && n_fft != 512 && n_fft != 1024) || n_mels < 4 || n_mels > KF_MAX_MELS || w_total < 1 || w_total > KF_MAX_WEIGHTS)
+        return 0;
+    const size_t fixed = n_fft == 256 ? kf_lds_bytes<128>(w_total, n_mels)
+                                      : (n_fft == 512 ? kf_lds_bytes<256>(w_total, n_mels) : kf_lds_bytes<512>(w_total, n_mels));
+    return fixed >= 64 * 1024 ? 0 : (int64_t)((64 * 1024 - fixed) / 4);
+}
+
+// what the three entry points share: the checks on the rows and the framing, and the arguments derived from them
+static int kf_common_args(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* window, int32_t n_fft,
+                          int32_t win_length, int32_t shift, int32_t flags, float preemph, float energy_floor, float* out,
+                          tac::KfArgs* a) {
+    using namespace tac;
+    if (!x || !window || !out) return TAC_E_INVALID;
+    if (rows <= 0 || length <= 0 || win_length < 2 || shift < 1) return TAC_E_INVALID;
+    if (rows == 1) stride_r = 0;
+    if (rows > 1 && stride_r <= 0) return TAC_E_INVALID;
+    if (n_fft != 256 && n_fft != 512 && n_fft != 1024) return TAC_E_UNSUPPORTED;
+    if (win_length > n_fft) return TAC_E_UNSUPPORTED;
+    const bool snip = (flags & KF_SNIP) != 0;
+    if (!snip && length < win_length) return TAC_E_UNSUPPORTED;                 // (the mirror would leave the row)
+    if (length >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;
+    const int64_t frames = tac_kaldi_num_frames(length, win_length, shift, snip ? 1 : 0);
+    if (frames <= 0) return TAC_E_INVALID;
+    if (frames >= 0x7fffffffLL || rows >= (1LL << 40)) return TAC_E_UNSUPPORTED;
+    *a = KfArgs();
+    a->x = x;
+    a->stride_r = stride_r;
+    a->length = length;
+    a->rows = rows;
+    a->n_frames = frames;
+    a->window = window;
+    a->win_length = win_length;
+    a->shift = shift;
+    a->flags = flags;
+    a->first = snip ? 0 : -(win_length / 2 - shift / 2);
+    a->preemph = preemph;
+    a->log_energy_floor = energy_floor > 0.0f ? std::log(energy_floor) : -INFINITY;
+    a->out = out;
+    return TAC_OK;
+}
+
+int tac_kaldi_mfcc_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* window, const float* weights,
+                       const int32_t* table, const float* dct, int32_t n_fft, int32_t win_length, int32_t shift, int32_t n_mels,
+                       int32_t w_total, int32_t n_ceps, int32_t flags, float preemph, float energy_floor, float* out, void* stream) {
+    using namespace tac;
+    if (!weights || !table || !dct || w_total < 1 || n_ceps < 1) return TAC_E_INVALID;
+    if (n_mels < 4 || n_mels > KF_MAX_MELS || w_total > KF_MAX_WEIGHTS) return TAC_E_UNSUPPORTED;
+    if (n_ceps > n_mels) return TAC_E_INVALID;
+    KfArgs a;
+    // the log-mel row of the definition: logarithm of the power bank, whatever the caller's bits say
+    const int rc = kf_common_args(x, rows, length, stride_r, window, n_fft, win_length, shift, flags | KF_LOG | KF_POWER, preemph,
+                                  energy_floor, out, &a);
+    if (rc != TAC_OK) return rc;
+    if ((int64_t)n_mels * n_ceps > tac_kaldi_mfcc_table_limit(n_fft, n_mels, w_total)) return TAC_E_UNSUPPORTED;
+    a.weights = weights;
+    a.table = table;
+    a.n_mels = n_mels;
+    a.w_total = w_total;
+    KfDct d;
+    d.table = dct;
+    d.n_ceps = n_ceps;
+    hipStream_t s = (hipStream_t)stream;
+    return n_fft == 256 ? kf_launch<128, KF_MFCC>(a, s, d)
+                        : (n_fft == 512 ? kf_launch<256, KF_MFCC>(a, s, d) : kf_launch<512, KF_MFCC>(a, s, d));
+}
+
+int tac_kaldi_spectrogram_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* window, int32_t n_fft,
+                              int32_t win_length, int32_t shift, int32_t flags, float preemph, float energy_floor, float* out,
+                              void* stream) {
+    using namespace tac;
+    KfArgs a;
+    // log |X|^2 with the log energy as column 0: power, logarithm and energy are the definition, not options
+    const int rc = kf_common_args(x, rows, length, stride_r, window, n_fft, win_length, shift,
+                                  (flags | KF_LOG | KF_POWER | KF_USE_ENERGY) & ~KF_HTK, preemph, energy_floor, out, &a);
+    if (rc != TAC_OK) return rc;
+    a.weights = nullptr;                                        // no bank: nothing of it is read (w_total = n_mels = 0)
+    a.table = nullptr;
+    a.n_mels = 0;
+    a.w_total = 0;
+    hipStream_t s = (hipStream_t)stream;
+    return n_fft == 256 ? kf_launch<128, KF_SPECTROGRAM>(a, s)
+                        : (n_fft == 512 ? kf_launch<256, KF_SPECTROGRAM>(a, s) : kf_launch<512, KF_SPECTROGRAM>(a, s));
 }
 
 }  // extern "C"

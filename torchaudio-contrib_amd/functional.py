@@ -27,7 +27,7 @@ from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'sliding_window_cmn', 'compute_deltas', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
 
 _call = _ops.call
@@ -275,6 +275,64 @@ def kaldi_fbank(waveforms, blackman_coeff=0.42, dither=0.0, energy_floor=1.0, fr
 
 #: the keywords ``kaldi_fbank`` takes behind the waveform
 _KALDI_KEYWORDS = kaldi_fbank.__code__.co_varnames[1:kaldi_fbank.__code__.co_argcount]
+
+
+def _kaldi_waveform(waveforms, name):
+    x = _tensor(waveforms, 'waveforms')
+    if x.dim() < 1:
+        raise RuntimeError('%s: expected a tensor of shape (…, time), got a scalar' % name)
+    if not x.is_floating_point():
+        raise RuntimeError('%s: expected a floating-point waveform, got %s' % (name, x.dtype))
+    return x
+
+
+def kaldi_mfcc(waveforms, blackman_coeff=0.42, cepstral_lifter=22.0, dither=0.0, energy_floor=1.0, frame_length=25.0,
+               frame_shift=10.0, high_freq=0.0, htk_compat=False, low_freq=20.0, num_ceps=13, num_mel_bins=23,
+               preemphasis_coefficient=0.97, raw_energy=True, remove_dc_offset=True, round_to_power_of_two=True,
+               sample_frequency=16000.0, snip_edges=True, subtract_mean=False, use_energy=False, vtln_high=-500.0, vtln_low=100.0,
+               vtln_warp=1.0, window_type='povey'):
+    """``(…, time)`` → ``(…, frames, num_ceps)``: Kaldi's mel-frequency cepstral coefficients with the keywords and defaults of
+    ``torchaudio.compliance.kaldi.mfcc`` (``kaldi.mfcc`` is that function itself, for ``(channels, time)``), over any leading
+    dimensions.  The log-mel rows are those of ``kaldi_fbank`` (natural logarithm of the power bank); a row times the
+    orthonormal DCT-II gives ``C``, ``C[c] *= 1 + cepstral_lifter / 2 sin(pi c / cepstral_lifter)``, ``C[0]`` is the frame's log
+    energy with ``use_energy``, and ``htk_compat`` moves column 0 to the end (times sqrt 2 unless it is the energy).  The
+    definition is in ``_kaldi.py``.  On a HIP device float32 input is ONE launch from waveform rows to cepstra
+    (csrc/kaldi_fbank.hip, the DCT as the epilogue of the ``kaldi_fbank`` launch) under ``kaldi_fbank``'s conditions and while
+    the DCT table fits the launch's LDS beside the bank (about 5000 elements: 80 x 40 does, 80 x 80 does not); the rest, and
+    the backward pass, take torch operators, announced.  ``num_ceps > num_mel_bins`` is a ``ValueError``; ``vtln_warp != 1``
+    is not implemented."""
+    x = _kaldi_waveform(waveforms, 'kaldi_mfcc')
+    if vtln_warp != 1.0:
+        raise NotImplementedError('kaldi_mfcc: vtln_warp != 1 (vocal tract length normalisation) is not implemented')
+    p = _kaldi.MfccParams(float(blackman_coeff), float(cepstral_lifter), float(dither), float(energy_floor), float(frame_length),
+                          float(frame_shift), float(high_freq), bool(htk_compat), float(low_freq), int(num_ceps),
+                          int(num_mel_bins), float(preemphasis_coefficient), bool(raw_energy), bool(remove_dc_offset),
+                          bool(round_to_power_of_two), float(sample_frequency), bool(snip_edges), bool(subtract_mean),
+                          bool(use_energy), str(window_type))
+    _kaldi.check(p, 'kaldi_mfcc')
+    return _call('kaldi_mfcc', x, *p)
+
+
+def kaldi_spectrogram(waveforms, blackman_coeff=0.42, dither=0.0, energy_floor=1.0, frame_length=25.0, frame_shift=10.0,
+                      preemphasis_coefficient=0.97, raw_energy=True, remove_dc_offset=True, round_to_power_of_two=True,
+                      sample_frequency=16000.0, snip_edges=True, subtract_mean=False, window_type='povey'):
+    """``(…, time)`` → ``(…, frames, N / 2 + 1)``: Kaldi's log power spectrogram with the keywords and defaults of
+    ``torchaudio.compliance.kaldi.spectrogram`` (``kaldi.spectrogram`` is that function itself, for ``(channels, time)``), over
+    any leading dimensions.  Frames as in ``kaldi_fbank``; the output is ``log max(|rfft|^2, eps)`` of every bin, the Nyquist
+    bin included, with the frame's log energy (floored at ``log energy_floor``) in place of the DC bin.  On a HIP device float32
+    input is ONE launch (csrc/kaldi_fbank.hip, without the bank) under ``kaldi_fbank``'s conditions; the rest, and the backward
+    pass, take torch operators, announced."""
+    x = _kaldi_waveform(waveforms, 'kaldi_spectrogram')
+    p = _kaldi.SpectrogramParams(float(blackman_coeff), float(dither), float(energy_floor), float(frame_length),
+                                 float(frame_shift), float(preemphasis_coefficient), bool(raw_energy), bool(remove_dc_offset),
+                                 bool(round_to_power_of_two), float(sample_frequency), bool(snip_edges), bool(subtract_mean),
+                                 str(window_type))
+    _kaldi.check(p, 'kaldi_spectrogram')
+    return _call('kaldi_spectrogram', x, *p)
+
+
+_KALDI_MFCC_KEYWORDS = kaldi_mfcc.__code__.co_varnames[1:kaldi_mfcc.__code__.co_argcount]
+_KALDI_SPECTROGRAM_KEYWORDS = kaldi_spectrogram.__code__.co_varnames[1:kaldi_spectrogram.__code__.co_argcount]
 
 
 def sliding_window_cmn(specgram, cmn_window=600, min_cmn_window=100, center=False, norm_vars=False):

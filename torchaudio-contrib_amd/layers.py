@@ -444,6 +444,38 @@ class KaldiFbank(_ModuleNoStateBuffers):
         return self.__class__.__name__ + '(' + ', '.join('{}={!r}'.format(k, v) for k, v in self.options.items()) + ')'
 
 
+class _KaldiFeature(_ModuleNoStateBuffers):
+    """a ``functional.kaldi_*`` function as a layer: keywords checked and argument errors raised at construction"""
+    _function, _keywords = None, ()
+
+    def __init__(self, **kwargs):
+        super(_KaldiFeature, self).__init__()
+        unknown = sorted(set(kwargs) - set(self._keywords))
+        if unknown:
+            raise TypeError('%s: unexpected keyword(s) %s' % (self.__class__.__name__, ', '.join(unknown)))
+        self.options = dict(kwargs)
+        type(self)._function(torch.zeros(0), **self.options)   # argument errors surface here, not in the first forward
+
+    def forward(self, waveforms):
+        return type(self)._function(waveforms, **self.options)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(' + ', '.join('{}={!r}'.format(k, v) for k, v in self.options.items()) + ')'
+
+
+class KaldiMfcc(_KaldiFeature):
+    """``functional.kaldi_mfcc`` as a layer: ``(…, time)`` → ``(…, frames, num_ceps)``, with the keywords and defaults of
+    ``torchaudio.compliance.kaldi.mfcc`` (less ``channel`` and ``min_duration``, which belong to ``kaldi.mfcc``).  No buffers:
+    the window, the packed bank and the DCT table are cached per argument set and device."""
+    _function, _keywords = staticmethod(F.kaldi_mfcc), F._KALDI_MFCC_KEYWORDS
+
+
+class KaldiSpectrogram(_KaldiFeature):
+    """``functional.kaldi_spectrogram`` as a layer: ``(…, time)`` → ``(…, frames, N / 2 + 1)``, with the keywords and defaults
+    of ``torchaudio.compliance.kaldi.spectrogram`` (less ``channel`` and ``min_duration``).  No buffers."""
+    _function, _keywords = staticmethod(F.kaldi_spectrogram), F._KALDI_SPECTROGRAM_KEYWORDS
+
+
 class SlidingWindowCmn(_ModuleNoStateBuffers):
     """``functional.sliding_window_cmn`` as a layer (torchaudio's ``transforms.SlidingWindowCmn``): ``(…, T, F)`` → the same
     shape.  No buffers."""
