@@ -5,7 +5,8 @@ Reference and bound: tests/resample_rules.py — the float64 sum per output samp
 ``(K_n + 2) * 2^-24 * sum |h64| |x|``; every element is checked.  The lengths are the smallest that reach each path of the
 kernel: 1, 2, ``width``, ``orig - 1 / orig / orig + 1`` (less than one block of phases, exactly one, one and a sample), the input
 span of one tile of ``TILE`` = 1024 outputs minus one / exactly / plus one (the last output of a tile, the first of the next), and
-three tiles plus a remainder (a persistent workgroup's second round, the span's start at every alignment).  Rows 1 and 3; dense
+three tiles plus a remainder (every tile position of a row, the span's start at every alignment; at most 3 rows x 4 tiles = 12 units
+on a grid of 12 workgroups, so no workgroup takes a second unit here: tests/test_grid_wrap_gpu.py does that).  Rows 1 and 3; dense
 rows (16-byte loads), a padded row stride and a start one float into the allocation (float loads), a padded stride of four floats
 (16-byte loads across rows), and a (2, 3, L) batch.  A reference is computed once per (filter, length) and shared by the layouts."""
 import warnings
