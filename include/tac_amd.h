@@ -118,7 +118,20 @@ int tac_melspec_f32(const float* wave, const float* window, const tac_stft_desc*
  *      pieces in adjacent lanes; 12 steps instead of 18 for the standard 128-band bank.  seg_steps int32[3]; first / band /
  *      index int32[192]; weights float[weights_cap >= 256 * (L0 + L1 + L2)]; TAC_E_UNSUPPORTED when no segment triple fits.
  *      The kernel form that contracted this layout measured 3 - 5 % slower than the lane layout and is not shipped
- *      (tools/ablation/README.md); tests emulate its contraction on the plan. */
+ *      (tools/ablation/README.md); tests emulate its contraction on the plan.
+ *      n_fft = TAC_PACK_PAIRS_2048 (both pack functions; n_freqs = 1025, exactly 128 bands): the PAIR layout of the fft_length-2048
+ *      kernel, float32 samples only (tac_melspec_sparse_f32; the coded entry point answers TAC_E_INVALID).  Every lane runs three segments
+ *      of A, B, C four-tap steps: band l; band 64 + l (lanes >= 32: its first B quads); lanes >= 32 the next C quads of band 64 + l,
+ *      lanes < 32 the quads of band 96 + l behind those, whose sum the kernel hands to lane l + 32.  14 steps instead of 4 + 14 for
+ *      the standard 16 kHz bank.  wpack = float[A + B + C][64][4], desc = int32[3][64] first bins (multiples of four), followed by
+ *      the classic table of the same bank (weights at wpack + info[0], first bins at desc + 192) for the kernel forms that do not
+ *      contract pairs; wpack_cap >= 256 * (A + B + C + 20), desc_cap >= 320.  info_host = {256 (A + B + C), 3, 64 + 512, A + B + C,
+ *      A, B, C, steps of the classic slot 1}.  TAC_E_UNSUPPORTED for banks outside the instantiated shapes (4, 6, 4), (4, 7, 3),
+ *      (3, 7, 5), and for banks whose classic table is not the (4, 14) / (4, 16) one of the unrolled kernels: callers then pack with
+ *      n_fft = 2048.  The code means the pair layout since the revision that introduced melspec_stream3_kernel<..., PA, PC> (ABI version 5,
+ *      no symbol added); -2048 selected round 4's piece layout until round 5, and libraries between the two answer it with
+ *      TAC_E_UNSUPPORTED, which callers treat like any refused bank. */
+#define TAC_PACK_PAIRS_2048 (-2048)
 int tac_melbank_pack(const float* fb, int32_t n_freqs, int32_t n_mels, int32_t n_fft, float* wpack,
                      int32_t wpack_cap, int32_t* desc, int32_t desc_cap, int32_t* info_host, void* stream);
 /* ... the same tables without a device (round 6; n_fft = 256, 400, 512, 1024, 2048 or 4096): fb_host, wpack_host, desc_host are HOST buffers, nothing is launched

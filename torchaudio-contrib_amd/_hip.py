@@ -573,6 +573,23 @@ def _melbank_pack(fb, n_fft):
     return result
 
 
+# The fused fft_length-2048 float32 launches contract 128-band banks in the PAIR layout (csrc/melspec_sparse.hip pack_pairs: 14
+# steps per frame instead of 4 + 14 for the standard bank).  False: the classic lane layout — for same-process A/B runs and the test
+# that compares the two; packs are cached per selector, plans are not: call ``invalidate()`` after changing it.
+PAIR_LAYOUT = True
+PACK_PAIRS_2048 = -2048         # TAC_PACK_PAIRS_2048 (include/tac_amd.h): the one Python copy; tools take it from here
+
+
+def _fused_pack(fb, n_fft):
+    """``_melbank_pack`` for the forward float32 fused launch: the pair layout where the bank fits one of its shapes, else
+    (and for every other fft size) the classic pack.  The coded-input and backward kernels take the classic pack."""
+    if PAIR_LAYOUT and n_fft == 2048 and tuple(fb.shape) == (1025, 128):
+        pack = _melbank_pack(fb, PACK_PAIRS_2048)
+        if pack is not None:
+            return pack
+    return _melbank_pack(fb, n_fft)
+
+
 def _filterbank_plan(fb):
     """(device int32 plan, host ctypes copy): non-zero bin range per 16-band tile, computed by a device kernel.
     The plan rides on the filterbank tensor object itself (a module's constant buffer is scanned once — the only
@@ -668,7 +685,7 @@ def mel_plan(wave, window, fb, n_fft, hop, win_length, center, pad_mode, normali
     g = geometry(wave, n_fft, hop, win_length, center, pad_mode, normalized, onesided)
     if g.flatten or g.desc is None or fb.shape[0] != g.n_bins or _fused_mel_route(g, fb, power) != 'sparse':
         return None
-    wpack, dsc, info = _melbank_pack(fb, g.n_fft)
+    wpack, dsc, info = _fused_pack(fb, g.n_fft)
     p = MelPlan()
     p.fn = _native.lib().tac_melspec_sparse_f32
     p.window, p.fb, p.win_stamp, p.fb_stamp = window, fb, _stamp(window), _stamp(fb)
@@ -717,7 +734,7 @@ def melspectrogram(wave, window, fb, n_fft, hop, win_length, center, pad_mode, n
     src = _rows_of(wave, g)
     out = _empty(g.lead + (g.n_frames, n_mels), device=wave.device)
     if route == 'sparse':          # band-sparse contraction (the faster form for triangular banks)
-        wpack, desc, info = _melbank_pack(fb, g.n_fft)
+        wpack, desc, info = _fused_pack(fb, g.n_fft)
         with _native.on_device(wave.device):
             rc = _native.lib().tac_melspec_sparse_f32(
                 _native.ptr(src), _native.ptr(window), g.desc, float(power), _native.ptr(wpack), _native.ptr(desc),

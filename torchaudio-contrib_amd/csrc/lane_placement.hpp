@@ -69,4 +69,25 @@ inline std::vector<int> place_band_starts(int nslot, const int* steps, const std
     return start;
 }
 
+// LDS cycles of a frame's row reads for chosen first bins: per slot and sixteen-lane group, steps x the largest number of DIFFERENT quads
+// that share a bank group (what place_band_starts minimises per group; 4 x steps per slot is conflict-free)
+inline int row_read_cycles(int nslot, const int* steps, const std::vector<int>& first) {
+    static const int kGroup[2][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                                      {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31}};
+    int total = 0;
+    for (int s = 0; s < nslot; ++s)
+        for (int gi = 0; gi < 4; ++gi) {
+            std::vector<int> quads[16];
+            int worst = 1;
+            for (int i = 0; i < 16; ++i) {
+                const int q = first[s * 64 + kGroup[gi & 1][i] + 32 * (gi >> 1)] / 4;
+                std::vector<int>& v = quads[q & 15];
+                if (std::find(v.begin(), v.end(), q) == v.end()) v.push_back(q);
+                worst = std::max(worst, (int)v.size());
+            }
+            total += steps[s] * worst;
+        }
+    return total;
+}
+
 }  // namespace tac

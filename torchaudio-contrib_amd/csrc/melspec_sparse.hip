@@ -359,6 +359,43 @@ static int launch_stream(FrameGeom g, const Tables& tb, const SparseArgs& sm, co
     const long long total = g.rows * g.n_frames;
     if (total >= 0x7fffffffLL) return TAC_E_UNSUPPORTED;                  // 32-bit global frame numbers in-kernel
     if (g.length < 2 * NC) return TAC_E_UNSUPPORTED;                       // (its clamped sample requests need a whole frame)
+    if (info_host[2] & ST_PAIR_MARK) {                                    // pair layout (pack_pairs): its own instantiations of the twelve-wave kernel
+        int shape = -1;
+        for (int i = 0; i < ST_PAIR_SHAPES; ++i)
+            if (info_host[4] == ST_PAIR_SHAPE[i][0] && info_host[5] == ST_PAIR_SHAPE[i][1] && info_host[6] == ST_PAIR_SHAPE[i][2]) shape = i;
+        const int c1 = info_host[7];
+        if (FMT != FMT_F32 || NC != 1024 || shape < 0 || info_host[1] != 3 || sm.n_mels != 128 || info_host[0] != 256 * info_host[3] ||
+            (c1 != ST_FAST_STEPS1 && c1 != ST_FAST_STEPS1_SHORT))
+            return TAC_E_INVALID;
+        if constexpr (FMT == FMT_F32 && NC == 1024) {
+            static const bool rotation = getenv("TAC_STREAM2") != nullptr;
+            if (fft_pipe_mfma() || rotation) {    // the other kernel forms contract the classic table behind the pair table
+                const int32_t classic[8] = {256 * (ST_FAST_STEPS0 + c1), 2, 64, ST_FAST_STEPS0 + c1, ST_FAST_STEPS0, c1, 0, 0};
+                SparseArgs cm = sm;
+                cm.wpack = sm.wpack + info_host[0];
+                cm.desc = sm.desc + 192;
+                cm.wtot = classic[0];
+                cm.dstride = classic[1];
+                return launch_stream<NC, E, FMT>(g, tb, cm, classic, power, stream, samples, lut);
+            }
+            const size_t ldsp = stream3_lds_bytes<NC, E>(sm.wtot, S3_WAVES, false) + S3_TW2L_BYTES;
+            StreamArgs m{sm.wpack, sm.desc, 3, {info_host[4], info_host[5], info_host[6], 0}, sm.wtot,
+                         sm.n_mels, sm.db, sm.amin, sm.log10_ref, sm.out, total, samples, lut, 0, nullptr, 0};
+            const bool pow2 = (power == 2.0f);
+            void (*kp)(FrameGeom, Tables, StreamArgs);
+#define TAC_S3_PAIR(I) (pow2 ? melspec_stream3_kernel<NC, E, true, FMT, ST_PAIR_SHAPE[I][1] + ST_PAIR_SHAPE[I][2], S3_WAVES, ST_PAIR_SHAPE[I][0], ST_PAIR_SHAPE[I][2]> \
+                             : melspec_stream3_kernel<NC, E, false, FMT, ST_PAIR_SHAPE[I][1] + ST_PAIR_SHAPE[I][2], S3_WAVES, ST_PAIR_SHAPE[I][0], ST_PAIR_SHAPE[I][2]>)
+            kp = shape == 0 ? TAC_S3_PAIR(0) : (shape == 1 ? TAC_S3_PAIR(1) : TAC_S3_PAIR(2));
+#undef TAC_S3_PAIR
+            static_assert(ST_PAIR_SHAPES == 3, "one instantiation per shape");
+            const long long bp = persistent_blocks(total, S3_WAVES, device_cu_count());
+            m.chunk = (total + bp - 1) / bp;
+            m.probe = (g_clock_probe && g_clock_probe_pairs >= bp) ? g_clock_probe : nullptr;
+            set_last_route("melspec_stream3_kernel<%d, %d, %s, %d, %d, %d, %d, %d>", NC, E, pow2 ? "true" : "false", FMT,
+                           info_host[5] + info_host[6], S3_WAVES, info_host[4], info_host[6]);
+            return launch_kernel(kp, bp, S3_WAVES * 64, ldsp, stream, g, tb, m);
+        }
+    }
     const size_t lds_bytes = stream_lds_bytes<NC, E>(sm.wtot);
     if (info_host[1] < 1 || info_host[1] > ST_MAX_SLOTS) return TAC_E_UNSUPPORTED;
     if (FMT != FMT_F32) g.vec2_ok = coded_pairs_aligned(g, samples, FMT);
@@ -609,6 +646,156 @@ static int pack_lanes(const std::vector<float>& h, int n_freqs, int n_mels, floa
     return TAC_OK;
 }
 
+// Pair layout of the streaming kernel (TAC_PACK_PAIRS_2048; float32 samples, banks of exactly 128 bands): the classic table runs
+// 4 + 14 steps because ONE lane owns the widest band; here the light lanes 0 .. 31 contract the tail of the band that lane l + 32
+// owns and hand over one partial sum (a v_permlane32_swap), so every lane runs A + B + C steps:
+//   steps [0, A):         band l, whole                                                        -> value 0
+//   steps [A, A + B):     lanes < 32: band 64 + l, whole; lanes >= 32: the first B quads of band 64 + l
+//   steps [A + B, .. + C): lanes >= 32: the next C quads of band 64 + l; lanes < 32: the quads of band 96 + l behind those
+// value 1 of a lane is its B sum, plus for lanes >= 32 its own C sum and the C sum of lane l - 32: lane l still stores bands l and
+// 64 + l.  A cell is (band, first live bin, live bins); as in pack_lanes a cell's run may start earlier than its live bins (zero
+// weights in front: place_band_starts uses that slack against bank conflicts) and is shifted down where it would leave the row.
+// desc = int32[3][64] first bins; behind the pair table (weights at wpack + info[0], first bins at desc + 192) lies the CLASSIC
+// table of the same bank, for the kernel forms that do not know the pair layout (matrix pipe, two-frame rotation): a pack
+// serves every form the process may select later.  info = {256 (A + B + C), 3, 64 + ST_PAIR_MARK, A + B + C, A, B, C, steps of the
+// classic slot 1}.  TAC_E_UNSUPPORTED for banks that fit none of the instantiated shapes: the caller packs the classic layout.
+static int pack_pairs(const std::vector<float>& h, int n_freqs, int n_mels, float* wpack, int wpack_cap, int32_t* desc,
+                      int desc_cap, int32_t* info_host, hipStream_t stream, bool to_host = false) {
+    if (n_mels != 128 || n_freqs != 1025 || desc_cap < 192 + 128) return TAC_E_UNSUPPORTED;
+    const int limit = StreamCfg<1024, 16>::PROW;
+    std::vector<int> blo(n_mels, 0), bq(n_mels, 0), bend(n_mels, 0);         // per band: first bin (multiple of four), quads, end of the non-zero run
+    for (int m = 0; m < n_mels; ++m) {
+        int l0 = n_freqs, h0 = 0;
+        for (int f = 0; f < n_freqs; ++f)
+            if (h[(size_t)f * n_mels + m] != 0.0f) { l0 = f < l0 ? f : l0; h0 = f + 1; }
+        if (h0 > l0) {
+            blo[m] = l0 & ~3;
+            bend[m] = h0;
+            bq[m] = (h0 - blo[m] + 3) / 4;
+        }
+    }
+    int need_a = 0, need_b = 0, need_w = 0;
+    for (int m = 0; m < 64; ++m) need_a = std::max(need_a, bq[m]);
+    for (int m = 64; m < 96; ++m) need_b = std::max(need_b, bq[m]);
+    for (int m = 96; m < 128; ++m) need_w = std::max(need_w, bq[m]);
+    // Among the instantiated shapes that hold the bank in the fewest steps, the one whose row reads cost the fewest LDS cycles (the
+    // benchmark bank fits (4, 6, 4) and (4, 7, 3): with B = 7 the widest of bands 64 .. 95 has a step of slack, too)
+    int steps[3] = {0, 0, 0}, best_cycles = 0;
+    std::vector<int> best_first, best_lo, best_hi, best_band;
+    for (int i = 0; i < ST_PAIR_SHAPES; ++i) {
+        const int* shp = ST_PAIR_SHAPE[i];
+        if (need_a > shp[0] || need_b > shp[1] || need_w > shp[1] + 2 * shp[2]) continue;
+        if (!best_first.empty() && shp[0] + shp[1] + shp[2] > steps[0] + steps[1] + steps[2]) continue;
+        const int keep[3] = {steps[0], steps[1], steps[2]};
+        steps[0] = shp[0]; steps[1] = shp[1]; steps[2] = shp[2];
+        const int B = steps[1], C = steps[2];
+        // A split band has B + 2 C - quads steps to spare, and where its three pieces meet is free: each piece's run may start early (zero
+        // weights in front, or taps the piece before it already holds) as long as the three runs together cover the band.  The pieces are
+        // placed one after the other — place_band_starts sees, per cell, the quads the run MUST cover and takes the rest as slack against
+        // bank conflicts — and every tap goes to the first run that reaches it.
+        std::vector<int> band(192, 0), lo(192, 0), len(192, 0), first(192, 0);   // per cell (segment, lane): band, bins the run must cover, its first bin
+        std::vector<int> live_lo(192, 0), live_hi(192, 0);                       // bins whose weights the cell holds
+        auto must = [&](int c, int m, int q0, int q1) {                          // the run of cell c has to cover quads [q0, q1) of band m
+            band[c] = m;
+            lo[c] = blo[m] + 4 * q0;
+            len[c] = q1 > q0 ? std::min(bend[m], blo[m] + 4 * q1) - lo[c] : 0;
+            if (len[c] < 0) len[c] = 0;
+        };
+        auto place = [&](int c0, int c1) {                                       // places all cells, keeps those of [c0, c1): returns nothing
+            const std::vector<int> st = place_band_starts(3, steps, lo, len);
+            for (int c = c0; c < c1; ++c) {
+                first[c] = st[c];
+                const int n = steps[c / 64];
+                if (first[c] + 4 * n > limit) first[c] = (limit - 4 * n) & ~3;   // keep the padded run inside the row
+            }
+        };
+        auto end_quad = [&](int c) { return (first[c] + 4 * steps[c / 64] - blo[band[c]]) / 4; };   // first quad of its band behind cell c's run
+        for (int l = 0; l < 64; ++l) {
+            must(l, l, 0, bq[l]);
+            if (l < 32) must(64 + l, 64 + l, 0, bq[64 + l]);
+            else must(64 + l, 64 + l, 0, std::max(1, bq[64 + l] - 2 * C));     // (the two C runs take up to 2 C quads)
+            band[128 + l] = l >= 32 ? 64 + l : 96 + l;
+        }
+        place(0, 128);
+        for (int l = 32; l < 64; ++l) {                                          // second piece: from the end of the first to within C quads of the band's end
+            const int e1 = std::min(end_quad(64 + l), bq[64 + l]);
+            must(128 + l, 64 + l, e1, std::max(e1, bq[64 + l] - C));
+        }
+        place(160, 192);
+        for (int l = 0; l < 32; ++l) {                                           // third piece, in the light lane: the rest
+            const int m = 96 + l, e2 = std::min(std::max(end_quad(64 + 32 + l), end_quad(128 + 32 + l)), bq[m]);
+            must(128 + l, m, e2, bq[m]);
+        }
+        place(128, 160);
+        for (int l = 0; l < 64; ++l) {
+            live_lo[l] = blo[l];
+            live_hi[l] = bend[l];
+            live_lo[64 + l] = blo[64 + l];
+            live_hi[64 + l] = l < 32 ? bend[64 + l] : std::min(bend[64 + l], first[64 + l] + 4 * B);
+            if (l >= 32) {
+                const int up = 128 + l, down = 128 + l - 32;                    // the band's second and third piece
+                live_lo[up] = live_hi[64 + l];
+                live_hi[up] = std::max(live_lo[up], std::min(bend[64 + l], first[up] + 4 * C));
+                live_lo[down] = live_hi[up];
+                live_hi[down] = std::max(live_lo[down], bend[64 + l]);
+            }
+        }
+        const int cycles = row_read_cycles(3, steps, first);
+        if (best_first.empty() || cycles < best_cycles) {
+            best_cycles = cycles; best_first = first; best_lo = live_lo; best_hi = live_hi; best_band = band;
+        } else {
+            steps[0] = keep[0]; steps[1] = keep[1]; steps[2] = keep[2];
+        }
+    }
+    if (best_first.empty()) return TAC_E_UNSUPPORTED;
+    const int A = steps[0], B = steps[1], C = steps[2], total_steps = A + B + C;
+    const int wtot = 256 * total_steps;
+    std::vector<int> first = best_first, live_lo = best_lo, live_hi = best_hi, band = best_band, lo;
+    std::vector<float> wp((size_t)wtot, 0.0f);
+    int base = 0;
+    for (int s = 0; s < 3; ++s) {
+        for (int l = 0; l < 64; ++l) {
+            const int c = s * 64 + l;
+            if (live_hi[c] > first[c] + 4 * steps[s] || (live_hi[c] > live_lo[c] && live_lo[c] < first[c])) return TAC_E_UNSUPPORTED;   // (cannot happen: every run covers its bins)
+            for (int j = 0; j < steps[s]; ++j)
+                for (int u = 0; u < 4; ++u) {
+                    const int bin = first[c] + 4 * j + u;
+                    const bool live = bin >= live_lo[c] && bin < live_hi[c];
+                    wp[((size_t)(base + j) * 64 + l) * 4 + u] = live ? h[(size_t)bin * n_mels + band[c]] : 0.0f;
+                }
+        }
+        base += steps[s];
+    }
+    lo = first;
+    // the classic table behind it
+    int32_t classic[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (wtot >= wpack_cap) return TAC_E_UNSUPPORTED;
+    const int rc = pack_lanes(h, n_freqs, n_mels, wpack + wtot, wpack_cap - wtot, desc + 192, desc_cap - 192, classic, stream, to_host);
+    if (rc != TAC_OK) return rc;
+    // (the launcher hands the classic table only to the FAST kernel forms: a bank whose classic slot 1 needs more than ST_FAST_STEPS1
+    // steps — a widest band of 17 quads fits (3, 7, 5) — stays on the classic pack and the general kernel)
+    if (classic[1] != 2 || classic[2] != 64 || classic[4] != ST_FAST_STEPS0 ||
+        (classic[5] != ST_FAST_STEPS1 && classic[5] != ST_FAST_STEPS1_SHORT))
+        return TAC_E_UNSUPPORTED;
+    if (to_host) {
+        std::copy(wp.begin(), wp.end(), wpack);
+        std::copy(lo.begin(), lo.end(), desc);
+    } else {
+        TAC_HIP(hipMemcpyAsync(wpack, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        TAC_HIP(hipMemcpyAsync(desc, lo.data(), lo.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        TAC_HIP(hipStreamSynchronize(stream));
+    }
+    info_host[0] = wtot;
+    info_host[1] = 3;
+    info_host[2] = 64 + ST_PAIR_MARK;
+    info_host[3] = total_steps;
+    info_host[4] = A;
+    info_host[5] = B;
+    info_host[6] = C;
+    info_host[7] = classic[5];
+    return TAC_OK;
+}
+
 }  // namespace tac
 
 extern "C" {
@@ -635,6 +822,11 @@ int tac_melbank_pack_host(const float* fb_host, int32_t n_freqs, int32_t n_mels,
     using namespace tac;
     if (!fb_host || !wpack_host || !desc_host || !info_host || n_freqs <= 0 || n_mels <= 0) return TAC_E_INVALID;
     const bool lanes = n_fft == 256 || n_fft == 400 || n_fft == 512 || n_fft == 1024;
+    if (n_fft == TAC_PACK_PAIRS_2048) {
+        if (n_freqs != 1025) return TAC_E_UNSUPPORTED;
+        const std::vector<float> hp(fb_host, fb_host + (size_t)n_freqs * n_mels);
+        return pack_pairs(hp, n_freqs, n_mels, wpack_host, wpack_cap, desc_host, desc_cap, info_host, nullptr, true);
+    }
     if ((n_fft != 2048 && n_fft != 4096 && !lanes) || n_freqs != n_fft / 2 + 1) return TAC_E_UNSUPPORTED;
     const std::vector<float> h(fb_host, fb_host + (size_t)n_freqs * n_mels);
     if (n_fft == 400) return pack_n400(h, n_freqs, n_mels, wpack_host, wpack_cap, desc_host, desc_cap, info_host, nullptr, true);
@@ -647,7 +839,14 @@ int tac_melbank_pack(const float* fb, int32_t n_freqs, int32_t n_mels, int32_t n
                      int32_t wpack_cap, int32_t* desc, int32_t desc_cap, int32_t* info_host, void* stream) {
     using namespace tac;
     if (!fb || !wpack || !desc || !info_host || n_freqs <= 0 || n_mels <= 0) return TAC_E_INVALID;
-    if (n_fft < 0) return TAC_E_UNSUPPORTED;          // (round 4's piece layout, TAC_PACK_PIECES_2048: its kernel form is not shipped)
+    if (n_fft == TAC_PACK_PAIRS_2048) {               // the pair layout of the fft_length-2048 kernel (pack_pairs)
+        if (n_freqs != 1025) return TAC_E_UNSUPPORTED;
+        std::vector<float> hp((size_t)n_freqs * n_mels);
+        TAC_HIP(hipMemcpyAsync(hp.data(), fb, hp.size() * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        TAC_HIP(hipStreamSynchronize((hipStream_t)stream));
+        return pack_pairs(hp, n_freqs, n_mels, wpack, wpack_cap, desc, desc_cap, info_host, (hipStream_t)stream);
+    }
+    if (n_fft < 0) return TAC_E_UNSUPPORTED;
     // n_fft == 0: pack for the standalone filterbank kernel (32 lane groups, any number of bins)
     const int groups = n_fft == 0 ? FBS_WAVES * 4 : sparse_groups_for(n_fft);
     if (groups == 0 || (n_fft != 0 && n_freqs != n_fft / 2 + 1)) return TAC_E_UNSUPPORTED;
@@ -738,7 +937,7 @@ int tac_melspec_sparse_f32(const float* wave, const float* window, const tac_stf
                                 (hipStream_t)stream);
     }
     const bool lanes_pack = info_host[2] >= LM_MARK;                               // mel_lanes.hpp layout
-    if (!lanes_pack && (info_host[2] & ~(d->n_fft == 2048 ? ST_REV_MARK : 0)) != sparse_groups_for(d->n_fft)) return TAC_E_INVALID;   // pack built for another geometry
+    if (!lanes_pack && (info_host[2] & ~(d->n_fft == 2048 ? (ST_REV_MARK | ST_PAIR_MARK) : 0)) != sparse_groups_for(d->n_fft)) return TAC_E_INVALID;   // pack built for another geometry
     FrameGeom g;
     int64_t T = 0;
     int rc = make_geometry(wave, window, d, &g, &T);

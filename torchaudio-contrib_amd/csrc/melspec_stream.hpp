@@ -61,6 +61,11 @@ struct StreamArgs {
     int rev;               // cell 64 s + l is band n_mels - 1 - (64 s + l) (banks whose band count is not a multiple of 64: pack_lanes)
 };
 constexpr int ST_REV_MARK = 256;               // in info_host[2] of such a pack (below LM_MARK)
+// Pair layout of the 128-band banks (pack_pairs, melspec_sparse.hip; contracted by melspec_stream3_kernel<..., PA, PC>): every lane
+// runs A + B + C steps, lanes 0 .. 31 taking the tail of the band that lane l + 32 owns.  The instantiated (A, B, C), tried in this order
+constexpr int ST_PAIR_MARK = 512;              // in info_host[2] of such a pack
+constexpr int ST_PAIR_SHAPES = 3;
+constexpr int ST_PAIR_SHAPE[ST_PAIR_SHAPES][3] = {{4, 6, 4}, {4, 7, 3}, {3, 7, 5}};
 
 // sample formats of the frame load (tac_amd.h TAC_SAMPLES_*)
 // (FMT_*: host_common.hpp)

@@ -219,7 +219,10 @@ struct S3Setup {
 // a 128-band bank (what tac_melbank_pack produces for the standard mel banks): the contraction fully unrolled
 // FMT: sample format of the frame load (FMT_*): float32, int16 PCM, mu-law codes as uint8 / int64 (converted in registers)
 // WAVES: waves per workgroup (= per CU): 12, three per SIMD
-template <int NC, int E, bool POW2, int FMT, int FAST1, int WAVES>
+// PA, PC: 0, or the pair layout of a 128-band bank (pack_pairs, melspec_sparse.hip): segments of A = PA, B = FAST1 - PC and C = PC
+// steps with their own first bins; lanes 0 .. 31 spend segment C on the tail of the band that lane + 32 owns and hand its sum over
+// (tac_last_route prints <NC, E, POW2, FMT, B + C, WAVES, A, C>: "10, 12, 4, 4" is the shape (4, 6, 4))
+template <int NC, int E, bool POW2, int FMT, int FAST1, int WAVES, int PA = 0, int PC = 0>
 __global__ void __launch_bounds__(WAVES * 64, (WAVES + 3) / 4)
 melspec_stream3_kernel(FrameGeom g, Tables tb, StreamArgs m) {
     using C = StreamCfg<NC, E>;
@@ -493,7 +496,53 @@ melspec_stream3_kernel(FrameGeom g, Tables tb, StreamArgs m) {
         i = (int)__builtin_amdgcn_readfirstlane(ask);
         request(i);
         // ---- s4: filterbank contraction, dB, row store
-        if constexpr (FAST1 > 0) {
+        if constexpr (FAST1 > 0 && PC > 0) {
+            // pair layout: 14 (15) steps for the standard banks instead of 4 + 14 (4 + 16).  Segments A and B are read in one batch,
+            // segment C behind A's FMAs, as the classic form batches its slot 1
+            constexpr int SA = PA, SB = FAST1 - PC, SC = PC;
+            static_assert(SA > 0 && SB > 0 && FMT == FMT_F32, "three segments, float32 samples");
+            const int ci = cur < nloc ? cur : nloc - 1;
+            const f4* wp = reinterpret_cast<const f4*>(wlds) + lane;
+            const f4* p0 = reinterpret_cast<const f4*>(prow + lo_s[0]);
+            const f4* p1 = reinterpret_cast<const f4*>(prow + lo_s[1]);
+            const f4* p2 = reinterpret_cast<const f4*>(prow + lo_s[2]);
+            cf a0 = mkc(0.f, 0.f), a1 = mkc(0.f, 0.f), b0 = mkc(0.f, 0.f), b1 = mkc(0.f, 0.f), c0 = mkc(0.f, 0.f), c1 = mkc(0.f, 0.f);
+            f4 wa[SA], qa[SA], wb[SB], qb[SB];
+#pragma unroll
+            for (int u = 0; u < SA; ++u) {
+                wa[u] = wp[u * 64];
+                qa[u] = p0[u];
+            }
+#pragma unroll
+            for (int u = 0; u < SB; ++u) {
+                wb[u] = wp[(SA + u) * 64];
+                qb[u] = p1[u];
+            }
+#pragma unroll
+            for (int u = 0; u < SA; ++u) fma4(wa[u], qa[u], a0, a1);
+            f4 wc[SC], qc[SC];
+#pragma unroll
+            for (int u = 0; u < SC; ++u) {
+                wc[u] = wp[(SA + SB + u) * 64];
+                qc[u] = p2[u];
+            }
+#pragma unroll
+            for (int u = 0; u < SB; ++u) fma4(wb[u], qb[u], b0, b1);
+#pragma unroll
+            for (int u = 0; u < SC; ++u) fma4(wc[u], qc[u], c0, c1);
+            float v0 = (a0.x + a0.y) + (a1.x + a1.y);
+            const float sb = (b0.x + b0.y) + (b1.x + b1.y), sc = (c0.x + c0.y) + (c1.x + c1.y);
+            // lanes >= 32 receive the C sum of lane - 32 (rows {2, 3} of the first operand <- rows {0, 1} of the second); lanes < 32 keep the zero
+            const auto got = __builtin_amdgcn_permlane32_swap(0u, __float_as_uint(sc), false, false);
+            float v1 = (sb + (lane >= 32 ? sc : 0.0f)) + __uint_as_float(got[0]);
+            if (m.db) {
+                v0 = fast_db ? amp_to_db_fast(v0, m.amin, ten_log10_ref) : amp_to_db(v0, m.amin, m.log10_ref);
+                v1 = fast_db ? amp_to_db_fast(v1, m.amin, ten_log10_ref) : amp_to_db(v1, m.amin, m.log10_ref);
+            }
+            float* orow = m.out + (begin + place(ci)) * (long long)m.n_mels + lane;
+            orow[0] = v0;
+            orow[64] = v1;
+        } else if constexpr (FAST1 > 0) {
             const int ci = cur < nloc ? cur : nloc - 1;
             const f4* wp = reinterpret_cast<const f4*>(wlds) + lane;
             const f4* p0 = reinterpret_cast<const f4*>(prow + lo_s[0]);
