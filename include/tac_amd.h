@@ -646,6 +646,29 @@ int tac_deltas_supported(int64_t n_frames, int32_t win_length, int32_t mode, int
 int tac_deltas_f32(const float* x, int64_t rows, int64_t n_feats, int64_t n_frames, int64_t stride_r, int64_t stride_f,
                    int64_t stride_t, int32_t win_length, int32_t mode, int adjoint, float* out, void* stream);
 
+/* (21) SpecAugment's masks (functional.mask_along_axis / mask_along_axis_iid, TimeMasking, FrequencyMasking, SpecAugment): EVERY
+ *      mask of a call in ONE launch over x[r*stride_r + a*stride_a + b*stride_b], r < rows, a < n_a = A, b < n_b = B (strides in
+ *      elements, positive for every axis longer than one), out: float[rows][A][B], dense (csrc/specaug.hip).
+ *      spans = DEVICE int32[span_rows][k_a + k_b][2]; span_rows is rows, or 1 for one table shared by every row.  The first k_a
+ *      spans run along A, the other k_b along B; a span is [start, end), clamped to its axis by the kernel whatever the table
+ *      holds, and empty where end <= start.  spans may be NULL where k_a + k_b == 0 (a dense copy).
+ *        out[a][b] = fill      if an A-span of the row holds a or a B-span of the row holds b
+ *                  = x[a][b]   otherwise
+ *      fill = *value_ptr where value_ptr (DEVICE float) is given, else the immediate value.  The fill is selected, not multiplied
+ *      in, and a masked element is not loaded: a NaN under a mask does not reach the output.
+ *      Lanes run along b in 16-byte chunks where x has unit stride there, B % 4 == 0 and base and strides keep the chunks
+ *      aligned; in dwords otherwise.  Where x has its unit stride along a (the transposed view of a (T, F) matrix) a 64 x 64 tile
+ *      is loaded along a, turned in the LDS and stored along b.  A persistent grid of at most 32 workgroups per CU walks the units
+ *      (row, A-block, B-chunk); a unit's spans become bit masks in the LDS once per unit.  One writer per element, no atomics:
+ *      bit-identical from run to run.
+ *      tac_mask_spans_supported: TAC_OK; TAC_E_INVALID for a negative count; TAC_E_UNSUPPORTED for k_a + k_b > TAC_MASK_MAX_SPANS.
+ *      Nothing is launched for those. */
+#define TAC_MASK_MAX_SPANS 64
+int tac_mask_spans_supported(int32_t k_a, int32_t k_b);
+int tac_mask_spans_f32(const float* x, int64_t rows, int64_t n_a, int64_t n_b, int64_t stride_r, int64_t stride_a, int64_t stride_b,
+                       const int32_t* spans, int64_t span_rows, int32_t k_a, int32_t k_b, const float* value_ptr, float value,
+                       float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

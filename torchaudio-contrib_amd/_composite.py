@@ -267,6 +267,26 @@ def compute_deltas(x, win_length, mode):
 _kaldi_constants = {}
 
 
+def mask_spans(x, spans, k_a, value):
+    """SpecAugment's masks over ``(…, A, B)`` as sequential ``masked_fill``s: span ``s`` of ``spans`` (integer ``(R, k, 2)``, ``R`` 1 or
+    the number of leading indices; the first ``k_a`` along A, the rest along B) fills ``[start, end)`` of its axis with ``value``
+    (a number or a 0-dim tensor).  Returns a new contiguous tensor.  The CPU route of ``tac_amd::mask_spans`` and its announced
+    composite route; what csrc/specaug.hip does in one launch."""
+    lead = tuple(x.shape[:-2])
+    k = int(spans.shape[-2])
+    out = x.contiguous()
+    if k == 0 or x.numel() == 0:
+        return out.clone() if out is x else out
+    per_row = spans.reshape((-1, k, 2)).to(x.device)
+    per_row = per_row.reshape(lead + (k, 2)) if per_row.shape[0] != 1 or not lead else per_row.reshape((1,) * len(lead) + (k, 2))
+    index = (torch.arange(x.shape[-2], device=x.device).view(-1, 1), torch.arange(x.shape[-1], device=x.device).view(1, -1))
+    for s in range(k):
+        i = index[0 if s < k_a else 1]
+        start, end = per_row[..., s, 0, None, None], per_row[..., s, 1, None, None]
+        out = out.masked_fill((i >= start) & (i < end), value)
+    return out
+
+
 def _kaldi_tables(p, w, n, dtype, device):
     """(window (W,), bank (bins, n // 2)) of ``_kaldi`` — built in float64, rounded once — cached per argument set; no bank for
     ``SpectrogramParams``"""

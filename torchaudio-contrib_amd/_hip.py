@@ -1349,6 +1349,42 @@ def deltas_rows(x, win_length, mode, adjoint=False):
     return out
 
 
+# ----------------------------------------------------------------------------- SpecAugment's masks (csrc/specaug.hip)
+def mask_spans_supported(k_a, k_b):
+    """True where ``tac_mask_spans_f32`` takes ``k_a + k_b`` spans: the library's own answer (``tac_mask_spans_supported``), so the
+    cap is stated in csrc/specaug.hip and include/tac_amd.h alone"""
+    return _native.lib().tac_mask_spans_supported(k_a, k_b) == _native.TAC_OK
+
+
+def mask_spans_covers(x, k_a, k_b):
+    """True where ``tac_mask_spans_f32`` takes this call on ``x`` (…, A, B) where it lies: ``mask_spans_supported`` and positive
+    strides on every axis longer than one"""
+    return x.dim() >= 2 and mask_spans_supported(k_a, k_b) and _positive_strides(x)
+
+
+def mask_spans_rows(x, spans, k_a, value_t=None, value=0.0):
+    """``(…, A, B) -> (…, A, B)``, dense, through ``tac_mask_spans_f32``: every span of ``spans`` (int32 ``(R, k, 2)`` on ``x``'s
+    device, ``R`` 1 or the number of rows, the first ``k_a`` along A) filled in one launch on ``x`` where it lies.  The fill is
+    the 0-dim float32 device tensor ``value_t`` where given (read by the kernel: no host sync), else ``value``."""
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        rows = _rows3(x)
+        k = int(spans.shape[-2])
+        if k and (spans.dtype != torch.int32 or not spans.is_contiguous() or spans.device != x.device
+                  or spans.shape[0] not in (1, rows.shape[0])):
+            raise ValueError('mask_spans: spans must be a contiguous int32 (1 or %d, k, 2) tensor on %s' % (rows.shape[0], x.device))
+        if value_t is not None and (value_t.dtype != torch.float32 or value_t.numel() != 1 or value_t.device != x.device):
+            raise ValueError('mask_spans: the fill tensor must be one float32 element on %s' % x.device)
+        with _native.on_device(x.device):
+            rc = _native.lib().tac_mask_spans_f32(
+                _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0), rows.stride(1), rows.stride(2),
+                _native.ptr(spans) if k else None, int(spans.shape[0]) if k else 1, k_a, k - k_a,
+                None if value_t is None else _native.ptr(value_t), float(value), _native.ptr(out), _native.stream_ptr(x.device))
+        _native.check(rc, 'tac_mask_spans_f32')
+        _count('tac_mask_spans_f32', out)
+    return out
+
+
 # ----------------------------------------------------------------------------- complex pairs
 def is_dense(x):
     """True when x's elements tile one gap-free block of memory (in any dim order)."""

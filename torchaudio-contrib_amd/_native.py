@@ -44,6 +44,7 @@ EXPORTS = (
     'tac_fftconvolve_direct_f32', 'tac_kaldi_num_frames', 'tac_kaldi_fbank_f32',
     'tac_kaldi_mfcc_table_limit', 'tac_kaldi_mfcc_f32', 'tac_kaldi_spectrogram_f32',
     'tac_sliding_cmn_chunk', 'tac_sliding_cmn_f32', 'tac_deltas_supported', 'tac_deltas_f32',
+    'tac_mask_spans_supported', 'tac_mask_spans_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -221,6 +222,8 @@ def lib():
                                           ctypes.c_int, _P, _P]
         h.tac_deltas_supported.argtypes = [_I64, _I32, _I32, ctypes.c_int]
         h.tac_deltas_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, ctypes.c_int, _P, _P]
+        h.tac_mask_spans_supported.argtypes = [_I32, _I32]
+        h.tac_mask_spans_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I32, _I32, _P, _F, _P, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

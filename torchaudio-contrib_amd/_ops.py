@@ -15,6 +15,7 @@ see them by name.
     tac_amd::kaldi_spectrogram  Kaldi log power spectrogram: the same launch, every bin's logarithm, the energy as column 0
     tac_amd::sliding_window_cmn sliding-window cepstral mean (and variance) normalisation over (…, T, F) (csrc/cmn_deltas.hip)
     tac_amd::compute_deltas     delta coefficients along time over (…, F, T) (csrc/cmn_deltas.hip)
+    tac_amd::mask_spans         SpecAugment: every time and frequency mask of a call over (…, F, T) in one launch (csrc/specaug.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -432,7 +433,21 @@ def _compute_deltas_hip_backward(saved, rest, needs, grads):
     return [H.deltas_rows(g, win_length, mode, adjoint=True)]
 
 
+def _mask_spans_hip_backward(saved, rest, needs, grads):
+    """``saved``: the span table; ``needs``: (the input, a tensor fill).  The copy's adjoint is the copy: the same kernel on grad_out
+    with zeros under the masks; what it took out is the fill's share."""
+    (spans,) = saved
+    k_a = rest[0]
+    g = grads[0]
+    if g is None or not H.mask_spans_supported(k_a, int(spans.shape[-2]) - k_a):
+        return None                 # (more spans than the kernel takes: the stock-torch route, announced)
+    g = g if H.mask_spans_covers(g, k_a, int(spans.shape[-2]) - k_a) else g.contiguous()      # (an expanded grad_out is copied)
+    gx = H.mask_spans_rows(g, spans, k_a, None, 0.0)
+    return [gx if needs[0] else None, (g - gx).sum() if needs[1] else None]
+
+
 _HIP_BACKWARD = {'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
+                 'mask_spans': _mask_spans_hip_backward,
                  'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
@@ -889,6 +904,95 @@ def _compute_deltas_fake(x, win_length, mode):
 
 _register('compute_deltas', '(Tensor x, int win_length, str mode) -> Tensor', _compute_deltas_cuda, C.compute_deltas,
           _compute_deltas_fake, 1)
+
+
+# ============================================================================= mask_spans (SpecAugment)
+def _mask_spans_check(x, spans, k_a):
+    if x.dim() < 2:
+        raise ValueError('mask_spans: expected a tensor of shape (…, A, B), got %d dimension(s)' % x.dim())
+    if spans.dim() != 3 or spans.shape[-1] != 2 or not 0 <= k_a <= spans.shape[-2]:
+        raise ValueError('mask_spans: spans must be (R, k, 2) with 0 <= k_a <= k, got %r and k_a = %d' % (tuple(spans.shape), k_a))
+    rows = 1
+    for n in x.shape[:-2]:
+        rows *= n
+    if spans.shape[-2] and spans.shape[0] != 1 and spans.shape[0] != rows:
+        raise ValueError('mask_spans: spans hold %d rows, the input %d' % (spans.shape[0], rows))
+
+
+def _mask_spans_cuda(x, spans, k_a, value_t, value):
+    _mask_spans_check(x, spans, k_a)
+    if x.numel() == 0:
+        return torch.empty_like(x, memory_format=torch.contiguous_format)       # an empty output: nothing is launched
+    k_b = int(spans.shape[-2]) - k_a
+    reason = _hip_dtype(x)
+    if reason is None and not H.mask_spans_supported(k_a, k_b):
+        reason = '%d spans (beyond what one launch of the kernel takes)' % (k_a + k_b)
+    if reason is None and not H.mask_spans_covers(x, k_a, k_b):
+        reason = 'non-positive strides'
+    if reason is not None:
+        _composite_route('mask_spans', reason)
+        return C.mask_spans(x, spans, k_a, value if value_t is None else value_t)
+    if spans.dtype != torch.int32 or not spans.is_contiguous() or spans.device != x.device:
+        spans = spans.to(device=x.device, dtype=torch.int32).contiguous()
+    if value_t is not None:
+        value_t = value_t.to(device=x.device, dtype=torch.float32).reshape(())
+    out = H.mask_spans_rows(_f32(x), spans, k_a, value_t, value)
+    return out if x.dtype == out.dtype else out.to(x.dtype)
+
+
+def _mask_spans_cpu(x, spans, k_a, value_t, value):
+    _mask_spans_check(x, spans, k_a)
+    return C.mask_spans(x, spans, k_a, value if value_t is None else value_t)
+
+
+def _mask_spans_fake(x, spans, k_a, value_t, value):
+    _mask_spans_check(x, spans, k_a)
+    return x.new_empty(tuple(x.shape))
+
+
+def _register_mask_spans_autograd():
+    """Backward of ``tac_amd::mask_spans``, whose tensor arguments do not all come first.  The gradients depend on grad_out and the
+    span table alone: ``grad_x`` is grad_out with zeros under the masks, and the gradient of a tensor fill is the sum of grad_out
+    under them, ``(grad_out - grad_x).sum()``.  float32 on a HIP device: the kernel (``_HIP_BACKWARD``); everything else, and every
+    double backward, the same two expressions in torch operators — announced on a HIP device like every stock-torch route."""
+    hip_backward = _HIP_BACKWARD['mask_spans']
+
+    def setup_context(ctx, inputs, output):
+        x, spans, k_a, value_t, value = inputs
+        ctx.save_for_backward(spans)
+        ctx.rest = (k_a, value)
+        ctx.plain = _plain_hip_f32(x) and (value_t is None or _plain_hip_f32(value_t))
+        ctx.fill = None if value_t is None else (value_t.dtype, tuple(value_t.shape), value_t.device)
+
+    def backward(ctx, g):
+        (spans,) = ctx.saved_tensors
+        needs = (ctx.needs_input_grad[0], ctx.needs_input_grad[3] and ctx.fill is not None)
+        second_order = torch.is_grad_enabled()
+        why = 'double backward (create_graph=True)' if second_order else None
+        res = None
+        if why is None:
+            if ctx.plain and _plain_hip_f32(g):
+                with torch.no_grad():
+                    res = hip_backward((spans,), ctx.rest, needs, (g,))
+                why = 'this gradient has no gfx950 kernel'
+            else:
+                why = _hip_dtype(g) or 'tensor subclass'
+        if res is None:
+            if g.is_cuda:
+                _composite_route('mask_spans', 'backward: ' + why)
+            gx = C.mask_spans(g, spans, ctx.rest[0], 0.0)
+            res = [gx if needs[0] else None, (g - gx).sum() if needs[1] else None]
+        gx, gv = res
+        if gv is not None:
+            gv = gv.to(device=ctx.fill[2], dtype=ctx.fill[0]).reshape(ctx.fill[1])
+        return gx, None, None, gv, None
+
+    torch.library.register_autograd('%s::mask_spans' % NS, backward, setup_context=setup_context, lib=_lib)
+
+
+_register('mask_spans', '(Tensor x, Tensor spans, int k_a, Tensor? value_t, float value) -> Tensor', _mask_spans_cuda, _mask_spans_cpu,
+          _mask_spans_fake, 2, differentiable=False)
+_register_mask_spans_autograd()
 
 
 # ============================================================================= lfilter

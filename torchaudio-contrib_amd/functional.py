@@ -23,11 +23,12 @@ from . import _ops
 from . import _filters
 from . import _kaldi
 from . import _resample
+from . import _specaug
 from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
 
 _call = _ops.call
@@ -376,6 +377,28 @@ def compute_deltas(specgram, win_length=5, mode='replicate'):
     if x.dim() == 1:
         return _call('compute_deltas', x.unsqueeze(0), win_length, mode).squeeze(0)
     return _call('compute_deltas', x, win_length, mode)
+
+
+def mask_along_axis_iid(specgrams, mask_param, mask_value, axis, p=1.0):
+    """``(…, freq, time)`` with at least three dimensions → a new contiguous tensor of the same shape and dtype: torchaudio's
+    ``functional.mask_along_axis_iid``.  Every leading index gets a span of its own on ``axis`` (``dim - 2``: frequency, ``dim - 1``:
+    time): ``value = rand(lead) * mask_param``, ``min_value = rand(lead) * (n - value)``, and ``[int(min_value), int(min_value) +
+    int(value))`` is set to ``mask_value`` (a number or a 0-dim tensor).  ``p < 1`` bounds ``mask_param`` by ``int(n * p)``; a
+    ``mask_param`` below 1 returns the input itself.  The draws are torch's, on the input's device, and nothing waits for them: on a
+    HIP device float32 input (float16 / bfloat16 widened) with positive strides is ONE launch (csrc/specaug.hip) that reads the
+    spans on the device.  float64, integer dtypes and non-positive strides take sequential ``masked_fill``s in torch operators,
+    announced; CPU tensors take them too."""
+    x = _tensor(specgrams, 'specgrams')
+    return _specaug.mask_along_axis_iid(x, int(mask_param), mask_value, axis, float(p))
+
+
+def mask_along_axis(specgram, mask_param, mask_value, axis, p=1.0):
+    """``(…, freq, time)`` with at least two dimensions → a new contiguous tensor of the same shape and dtype: torchaudio's
+    ``functional.mask_along_axis``.  One span, drawn like ``mask_along_axis_iid``'s but with ``torch.rand(1)`` of the CPU generator,
+    is shared by every leading index; ``ValueError`` if it comes out ``mask_param`` wide or wider.  The routes are those of
+    ``mask_along_axis_iid``."""
+    x = _tensor(specgram, 'specgram')
+    return _specaug.mask_along_axis(x, int(mask_param), mask_value, axis, float(p))
 
 
 _CONV_MODES = ('full', 'valid', 'same')

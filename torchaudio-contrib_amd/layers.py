@@ -19,6 +19,7 @@ from . import _hip
 from . import _lazy
 from . import _ops
 from . import _resample
+from . import _specaug
 from ._lazy import DeferredSpectral, DeferredWave, can_defer, can_defer_codes, lazy_fusion_enabled, realize
 
 
@@ -508,6 +509,70 @@ class ComputeDeltas(_ModuleNoStateBuffers):
 
     def __repr__(self):
         return self.__class__.__name__ + '(win_length={}, mode={!r})'.format(self.win_length, self.mode)
+
+
+class _AxisMasking(_ModuleNoStateBuffers):
+    """One mask along the time or the frequency axis of ``(…, freq, time)`` (torchaudio's ``transforms._AxisMasking``): a span per
+    leading index with ``iid_masks`` on an input of three or more dimensions, one shared span otherwise.  No buffers."""
+    _from_end = 1                      # the axis, counted from the end
+
+    def __init__(self, mask_param, iid_masks=False, p=1.0):
+        super(_AxisMasking, self).__init__()
+        self.mask_param, self.iid_masks, self.p = int(mask_param), bool(iid_masks), float(p)
+        _specaug.check_p(self.__class__.__name__, self.p)                   # argument errors surface here, not in the first forward
+
+    def forward(self, specgram, mask_value=0.0):
+        x = realize(specgram)
+        name = self.__class__.__name__
+        if self.iid_masks and x.dim() >= 3:
+            return _specaug.mask_along_axis_iid(x, self.mask_param, mask_value, x.dim() - self._from_end, self.p, name)
+        return _specaug.mask_along_axis(x, self.mask_param, mask_value, x.dim() - self._from_end, self.p, name)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(mask_param={}, iid_masks={}, p={})'.format(self.mask_param, self.iid_masks, self.p)
+
+
+class TimeMasking(_AxisMasking):
+    """torchaudio's ``transforms.TimeMasking``: ``forward(specgram, mask_value=0.0)`` masks up to ``time_mask_param`` frames (at most
+    the share ``p`` of them) of ``(…, freq, time)``: one launch on a HIP device (``functional.mask_along_axis[_iid]``)."""
+    _from_end = 1
+
+    def __init__(self, time_mask_param, iid_masks=False, p=1.0):
+        super(TimeMasking, self).__init__(time_mask_param, iid_masks, p)
+
+
+class FrequencyMasking(_AxisMasking):
+    """torchaudio's ``transforms.FrequencyMasking``: ``forward(specgram, mask_value=0.0)`` masks up to ``freq_mask_param`` bins of
+    ``(…, freq, time)``: one launch on a HIP device."""
+    _from_end = 2
+
+    def __init__(self, freq_mask_param, iid_masks=False):
+        super(FrequencyMasking, self).__init__(freq_mask_param, iid_masks, 1.0)
+
+
+class SpecAugment(_ModuleNoStateBuffers):
+    """torchaudio's ``transforms.SpecAugment`` over ``(…, freq, time)``: ``n_time_masks`` time masks of up to ``time_mask_param`` frames
+    (at most the share ``p`` of them), then ``n_freq_masks`` frequency masks of up to ``freq_mask_param`` bins, filled with 0
+    (``zero_masking``) or with the input's mean, taken once before any mask; a span per leading index with ``iid_masks`` on three
+    or more dimensions.  The draws are made in the order of the sequential ``mask_along_axis[_iid]`` calls, so a generator state
+    gives what those give; ALL masks are then applied by one ``tac_amd::mask_spans`` call — on a HIP device one launch
+    (csrc/specaug.hip) beside torch's ``mean``, whose result the kernel reads on the device.  No buffers."""
+
+    def __init__(self, n_time_masks, time_mask_param, n_freq_masks, freq_mask_param, iid_masks=True, p=1.0, zero_masking=False):
+        super(SpecAugment, self).__init__()
+        self.n_time_masks, self.time_mask_param = int(n_time_masks), int(time_mask_param)
+        self.n_freq_masks, self.freq_mask_param = int(n_freq_masks), int(freq_mask_param)
+        self.iid_masks, self.p, self.zero_masking = bool(iid_masks), float(p), bool(zero_masking)
+        _specaug.check_p('SpecAugment', self.p)
+
+    def forward(self, specgram):
+        return _specaug.spec_augment(realize(specgram), self.n_time_masks, self.time_mask_param, self.n_freq_masks,
+                                     self.freq_mask_param, self.iid_masks, self.p, self.zero_masking)
+
+    def __repr__(self):
+        return ('SpecAugment(n_time_masks={}, time_mask_param={}, n_freq_masks={}, freq_mask_param={}, iid_masks={}, p={}, '
+                'zero_masking={})').format(self.n_time_masks, self.time_mask_param, self.n_freq_masks, self.freq_mask_param,
+                                           self.iid_masks, self.p, self.zero_masking)
 
 
 class FFTConvolve(_ModuleNoStateBuffers):
