@@ -669,6 +669,40 @@ int tac_mask_spans_f32(const float* x, int64_t rows, int64_t n_a, int64_t n_b, i
                        const int32_t* spans, int64_t span_rows, int32_t k_a, int32_t k_b, const float* value_ptr, float value,
                        float* out, void* stream);
 
+/* (22) functional.add_noise / AddNoise: noise mixed into a waveform at a signal-to-noise ratio, and its gradient
+ *      (csrc/add_noise.hip).  Row r = o * rows_inner + i (r < rows, rows_inner divides rows) of waveform starts at
+ *      o * w_stride_o + i * w_stride_r and sample t lies t * w_stride_t behind it; noise likewise (strides in floats: the time
+ *      strides positive, the others >= 0 — one noise row may serve every row, or one per batch entry its rows_inner channels);
+ *      out: float[rows][length], dense.
+ *      snr = DEVICE float[snr_rows], lengths = DEVICE int32 / int64 (lengths_i64) [length_rows] or NULL (every row whole); snr_rows
+ *      and length_rows are rows or 1.  With m_t = t < lengths[r] (clamped to [0, length]):
+ *        E_s = sum_t (waveform_t m_t)^2,  E_n = sum_t (noise_t m_t)^2,  scale = sqrt(E_s / E_n) 10^(-snr / 20)     in float64
+ *        out_t = fma((float)scale, noise_t, waveform_t)   for every t < length
+ *      Samples at or behind lengths[r] are not loaded by the sums; E_s = 0 gives scale 0, E_n = 0 inf, both NaN.  Three launches on
+ *      the stream, no host wait: per-tile float64 partial sums (a tile = tac_add_noise_tile() samples of a row, a persistent grid
+ *      of at most 32 workgroups per CU), a wave per row that sums them in a fixed order, and the mix over the same tiles.  No
+ *      atomics: bit-identical from run to run.  16-byte accesses where unit time strides, bases, the other strides and length % 4
+ *      allow.
+ *      work: DEVICE scratch of tac_add_noise_work_bytes(rows, length) bytes, 8-byte aligned (0 for sizes the kernels do not take:
+ *      rows * tiles beyond 2^31 - 1, for which the launchers return TAC_E_UNSUPPORTED); nothing in it has to be initialised.
+ *      tac_add_noise_grad_f32: with d = sum_t grad_out_t noise_t over all t,
+ *        grad_waveform_t = grad_out_t + (scale / E_s) d waveform_t m_t
+ *        grad_noise_t    = scale grad_out_t - (scale / E_n) d noise_t m_t
+ *        grad_snr        = -(ln 10 / 20) scale d                 float[rows]
+ *      by the same three launches in adjoint mode (both tensor gradients in one pass, dense over rows); each of the three may be
+ *      NULL. */
+int64_t tac_add_noise_tile(void);
+int64_t tac_add_noise_work_bytes(int64_t rows, int64_t length);
+int tac_add_noise_f32(const float* waveform, int64_t w_stride_o, int64_t w_stride_r, int64_t w_stride_t, const float* noise,
+                      int64_t n_stride_o, int64_t n_stride_r, int64_t n_stride_t, int64_t rows, int64_t rows_inner, int64_t length,
+                      const float* snr, int64_t snr_rows, const void* lengths, int64_t length_rows, int32_t lengths_i64, void* work,
+                      float* out, void* stream);
+int tac_add_noise_grad_f32(const float* grad_out, int64_t g_stride_o, int64_t g_stride_r, int64_t g_stride_t, const float* waveform,
+                           int64_t w_stride_o, int64_t w_stride_r, int64_t w_stride_t, const float* noise, int64_t n_stride_o,
+                           int64_t n_stride_r, int64_t n_stride_t, int64_t rows, int64_t rows_inner, int64_t length, const float* snr,
+                           int64_t snr_rows, const void* lengths, int64_t length_rows, int32_t lengths_i64, void* work,
+                           float* grad_waveform, float* grad_noise, float* grad_snr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

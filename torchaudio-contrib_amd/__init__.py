@@ -17,12 +17,14 @@ from .functional import (stft, istft, complex_norm, create_mel_filter, apply_fil
                          mu_law_decoding, hpss, create_dct, dct, resample, lfilter, biquad, lowpass_biquad,
                          highpass_biquad, bandpass_biquad, bandreject_biquad, allpass_biquad, equalizer_biquad,
                          preemphasis, deemphasis, fftconvolve, convolve, kaldi_fbank, sliding_window_cmn,
-                         compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid)
+                         compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid,
+                         add_noise, speed)
 from .layers import (STFT, ISTFT, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
                      MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis,
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,
-                     KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment)
+                     KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment,
+                     AddNoise, Speed, SpeedPerturbation)
 from . import distributed
 from . import kaldi
 

@@ -1,0 +1,48 @@
+"""Waveform augmentation: the argument checks of ``add_noise`` and the rate arithmetic of ``speed`` (torchaudio's
+``functional.add_noise`` / ``functional.speed``), the one place the functionals and the layers get them from.
+
+``add_noise`` is ONE ``tac_amd::add_noise`` op: the signal-to-noise ratio and the lengths stay tensors and are read by the kernels on
+the device.  ``speed`` has no kernel of its own: it is ``tac_amd::resample`` at the reduced pair ``int(factor * orig_freq) :
+int(orig_freq)`` — 9:10, 11:10, 19:20, 21:20 for the usual perturbation factors — and the new lengths are torch operators on the
+lengths' device; nothing waits for the host.
+"""
+import math
+
+import torch
+
+from . import _ops
+
+
+def add_noise(waveform, noise, snr, lengths=None, name='add_noise'):
+    """the checks of torchaudio's ``add_noise`` (``ValueError``), then one ``tac_amd::add_noise`` call"""
+    for what, t in (('waveform', waveform), ('noise', noise), ('snr', snr)) + ((('lengths', lengths),) if lengths is not None else ()):
+        if not torch.is_tensor(t):
+            raise TypeError('%s: %s must be a torch.Tensor, got %s' % (name, what, type(t).__name__))
+    if not (waveform.dim() - 1 == noise.dim() - 1 == snr.dim() and (lengths is None or lengths.dim() == snr.dim())) or waveform.dim() < 1:
+        raise ValueError("%s: input leading dimensions don't match: waveform %r, noise %r, snr %r%s"
+                         % (name, tuple(waveform.shape), tuple(noise.shape), tuple(snr.shape),
+                            '' if lengths is None else ', lengths %r' % (tuple(lengths.shape),)))
+    if waveform.shape[-1] != noise.shape[-1]:
+        raise ValueError('%s: length dimensions of waveform and noise don\'t match (got %d and %d)'
+                         % (name, waveform.shape[-1], noise.shape[-1]))
+    return _ops.call('add_noise', waveform, noise, snr, lengths)
+
+
+def speed_rates(orig_freq, factor, name='speed'):
+    """``(source, target)``: ``int(factor * orig_freq)`` and ``int(orig_freq)`` divided by their gcd — the rates ``resample`` is called
+    with; ``ValueError`` for a factor that is not positive or that leaves no source rate"""
+    if not factor > 0:
+        raise ValueError('%s: factor must be positive, got %r' % (name, factor))
+    source, target = int(factor * orig_freq), int(orig_freq)
+    if source <= 0 or target <= 0:
+        raise ValueError('%s: factor %r at orig_freq %r leaves no sample rate (int(factor * orig_freq) = %d)' % (name, factor, orig_freq, source))
+    gcd = math.gcd(source, target)
+    return source // gcd, target // gcd
+
+
+def speed_lengths(lengths, source, target):
+    """the valid lengths after ``resample(source -> target)``: ``ceil(lengths * target / source)`` in the dtype of ``lengths``, by
+    torch operators where ``lengths`` lies"""
+    if lengths is None:
+        return None
+    return torch.ceil(lengths * target / source).to(lengths.dtype)

@@ -287,6 +287,24 @@ def mask_spans(x, spans, k_a, value):
     return out
 
 
+def add_noise(waveform, noise, snr, lengths=None):
+    """torchaudio's ``functional.add_noise`` in torch operators, in the inputs' dtype: with ``m_t = t < lengths`` (all ones without
+    ``lengths``), ``E_s = sum_t (waveform_t m_t)^2``, ``E_n = sum_t (noise_t m_t)^2``, ``scale = 10 ** ((10 (log10 E_s - log10 E_n) - snr) /
+    20)`` and ``out = waveform + scale * noise`` at EVERY sample.  Leading dimensions broadcast.  The masked samples are selected out
+    (``torch.where``), as the kernel leaves them unread: a NaN behind a row's length does not reach its scale.  The CPU
+    route of ``tac_amd::add_noise`` and its announced composite route; what csrc/add_noise.hip does in three launches."""
+    if lengths is not None:
+        mask = torch.arange(waveform.shape[-1], device=waveform.device) < lengths.unsqueeze(-1)
+        masked_waveform = torch.where(mask, waveform, torch.zeros((), dtype=waveform.dtype, device=waveform.device))
+        masked_noise = torch.where(mask, noise, torch.zeros((), dtype=noise.dtype, device=noise.device))
+    else:
+        masked_waveform, masked_noise = waveform, noise
+    energy_signal = (masked_waveform * masked_waveform).sum(-1)
+    energy_noise = (masked_noise * masked_noise).sum(-1)
+    scale = 10 ** ((10 * (torch.log10(energy_signal) - torch.log10(energy_noise)) - snr) / 20)
+    return (waveform + scale.unsqueeze(-1) * noise).contiguous()
+
+
 def _kaldi_tables(p, w, n, dtype, device):
     """(window (W,), bank (bins, n // 2)) of ``_kaldi`` — built in float64, rounded once — cached per argument set; no bank for
     ``SpectrogramParams``"""

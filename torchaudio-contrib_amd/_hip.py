@@ -1385,6 +1385,133 @@ def mask_spans_rows(x, spans, k_a, value_t=None, value=0.0):
     return out
 
 
+# ----------------------------------------------------------------------------- add_noise (csrc/add_noise.hip)
+#: samples of one row per unit of ``tac_add_noise_f32`` (csrc/add_noise.hip: AN_TILE)
+ADD_NOISE_TILE = 4096
+
+
+def _add_noise_rows_of(lead):
+    rows = 1
+    for n in lead:
+        rows *= int(n)
+    return rows
+
+
+def _add_noise_groups(x, lead):
+    """``x`` (…, L) broadcast to ``lead + (L,)`` and read where it lies: its time stride and the ``(size, stride)`` pairs of the
+    leading dimensions longer than one (a stride of 0 where ``x`` is broadcast)"""
+    length = int(x.shape[-1])
+    view = x.expand(tuple(lead) + (length,))
+    return (view.stride(-1) if length > 1 else 1), [(int(n), int(s)) for n, s in zip(view.shape[:-1], view.stride()[:-1]) if n > 1]
+
+
+def _collapse(dims):
+    """the one stride that walks ``dims`` in row-major order, or None"""
+    for (_, s_out), (n_in, s_in) in zip(dims[:-1], dims[1:]):
+        if s_out != s_in * n_in:
+            return None
+    return dims[-1][1] if dims else 0
+
+
+def _add_noise_plan(lead, operands):
+    """How ``tac_add_noise_f32`` walks the rows of these (…, L) operands: ``(rows_inner, [(outer stride, row stride, time stride)])`` with
+    row ``o * rows_inner + i`` of an operand at ``o * outer + i * row`` — the leading dimensions split at ONE place, the same for every
+    operand, into two runs of one stride each (dense batches, padded rows, every second row, one noise row for all rows, one noise
+    row per batch entry for its channels) — or the reason (a string) why the kernels do not read them where they lie"""
+    found = [_add_noise_groups(x, lead) for x in operands]
+    if any(st <= 0 for st, _ in found):
+        return 'non-positive time strides'
+    rows, length = _add_noise_rows_of(lead), int(operands[0].shape[-1])
+    if rows and length and int(_native.lib().tac_add_noise_work_bytes(rows, length)) <= 0:
+        return 'more tiles of %d samples than one launch takes' % ADD_NOISE_TILE
+    count = len(found[0][1])
+    for split in range(count + 1):
+        strides = [(_collapse(dims[:split]), _collapse(dims[split:]), st) for st, dims in found]
+        if all(so is not None and sr is not None for so, sr, _ in strides):
+            inner = 1
+            for n, _ in found[0][1][split:]:
+                inner *= n
+            return inner, strides
+    return 'leading dimensions that do not collapse to two strides'
+
+
+def add_noise_reason(lead, *operands):
+    """None where ``tac_add_noise_f32`` / ``tac_add_noise_grad_f32`` read these (…, L) operands where they lie, else the reason"""
+    plan = _add_noise_plan(lead, operands)
+    return plan if isinstance(plan, str) else None
+
+
+def add_noise_covers(lead, *operands):
+    return add_noise_reason(lead, *operands) is None
+
+
+def _add_noise_table(t, lead, dtype=None):
+    """``t`` broadcast to ``lead`` as the kernel's table: ``(tensor, entries)`` with one entry where ``t`` holds one, else one per row"""
+    if dtype is not None and t.dtype != dtype:
+        t = t.to(dtype)
+    if t.numel() == 1:
+        return t.reshape(1), 1
+    flat = t.expand(tuple(lead)).reshape(-1)
+    return (flat if flat.is_contiguous() else flat.contiguous()), flat.shape[0]
+
+
+def _add_noise_args(operands, snr, lengths, lead):
+    """the arguments of either entry from the operands (``grad_out`` first where there is one) up to the scratch, and the tensors
+    that have to outlive the call"""
+    length = int(operands[0].shape[-1])
+    rows = _add_noise_rows_of(lead)
+    inner, strides = _add_noise_plan(lead, operands)
+    snr_t, snr_rows = _add_noise_table(snr, lead, torch.float32)
+    if lengths is None:
+        len_t, len_rows, len_i64 = None, 1, 0
+    else:
+        if lengths.dtype not in (torch.int32, torch.int64):       # t < lengths  <=>  t < ceil(lengths)
+            lengths = (lengths.ceil() if lengths.is_floating_point() else lengths).clamp(-1, length).to(torch.int64)
+        len_t, len_rows = _add_noise_table(lengths, lead)
+        len_i64 = int(len_t.dtype == torch.int64)
+    work = torch.empty((int(_native.lib().tac_add_noise_work_bytes(rows, length)) // 8,), dtype=torch.float64, device=operands[0].device)
+    args = []
+    for x, (so, sr, st) in zip(operands, strides):
+        args += [_native.ptr(x), so, sr, st]
+    args += [rows, inner, length, _native.ptr(snr_t), snr_rows, None if len_t is None else _native.ptr(len_t), len_rows, len_i64,
+             _native.ptr(work)]
+    return args, (snr_t, len_t, work)
+
+
+def add_noise_rows(waveform, noise, snr, lengths, lead):
+    """``waveform``, ``noise`` (…, L) float32, ``snr`` and ``lengths`` (…), all broadcast to the leading shape ``lead``: ``lead + (L,)``,
+    dense, through ``tac_add_noise_f32`` — one entry, three launches on the current stream, the operands read where they lie
+    (``add_noise_covers``), ``snr`` and ``lengths`` read on the device.  The float64 scratch comes from torch's allocator."""
+    out = _empty(tuple(lead) + (int(waveform.shape[-1]),), device=waveform.device)
+    if out.numel():
+        args, keep = _add_noise_args((waveform, noise), snr, lengths, lead)
+        with _native.on_device(waveform.device):
+            rc = _native.lib().tac_add_noise_f32(*args, _native.ptr(out), _native.stream_ptr(waveform.device))
+        _native.check(rc, 'tac_add_noise_f32')
+        _count('tac_add_noise_f32', out)
+    return out
+
+
+def add_noise_grad_rows(grad_out, waveform, noise, snr, lengths, lead, needs):
+    """The gradients of ``add_noise_rows`` w.r.t. (waveform, noise, snr) where ``needs`` asks for them, each over the broadcast
+    shape (``lead + (L,)``, ``lead``): one ``tac_add_noise_grad_f32`` entry — the same three launches in adjoint mode, both tensor
+    gradients written in one pass."""
+    shape = tuple(lead) + (int(waveform.shape[-1]),)
+    dev = waveform.device
+    gw = _empty(shape, device=dev) if needs[0] else None
+    gn = _empty(shape, device=dev) if needs[1] else None
+    gs = _empty(tuple(lead), device=dev) if needs[2] else None
+    if grad_out.numel() and any(needs):
+        args, keep = _add_noise_args((grad_out, waveform, noise), snr, lengths, lead)
+        with _native.on_device(dev):
+            rc = _native.lib().tac_add_noise_grad_f32(
+                *args, None if gw is None else _native.ptr(gw), None if gn is None else _native.ptr(gn),
+                None if gs is None else _native.ptr(gs), _native.stream_ptr(dev))
+        _native.check(rc, 'tac_add_noise_grad_f32')
+        _count('tac_add_noise_grad_f32', gw, gn, gs)
+    return gw, gn, gs
+
+
 # ----------------------------------------------------------------------------- complex pairs
 def is_dense(x):
     """True when x's elements tile one gap-free block of memory (in any dim order)."""

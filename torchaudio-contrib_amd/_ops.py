@@ -16,6 +16,7 @@ see them by name.
     tac_amd::sliding_window_cmn sliding-window cepstral mean (and variance) normalisation over (…, T, F) (csrc/cmn_deltas.hip)
     tac_amd::compute_deltas     delta coefficients along time over (…, F, T) (csrc/cmn_deltas.hip)
     tac_amd::mask_spans         SpecAugment: every time and frequency mask of a call over (…, F, T) in one launch (csrc/specaug.hip)
+    tac_amd::add_noise          noise mixed into (…, L) at a signal-to-noise ratio, under a length mask (csrc/add_noise.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -446,8 +447,31 @@ def _mask_spans_hip_backward(saved, rest, needs, grads):
     return [gx if needs[0] else None, (g - gx).sum() if needs[1] else None]
 
 
+def _add_noise_lead(waveform, noise, snr, lengths):
+    shapes = [tuple(waveform.shape[:-1]), tuple(noise.shape[:-1]), tuple(snr.shape)]
+    if lengths is not None:
+        shapes.append(tuple(lengths.shape))
+    return tuple(torch.broadcast_shapes(*shapes))
+
+
+def _add_noise_hip_backward(saved, rest, needs, grads):
+    """``saved``: (waveform, noise, snr); ``rest``: (lengths,).  One ``tac_add_noise_grad_f32`` entry recomputes the float64 sums and
+    writes the gradients over the broadcast shape; torch's ``sum`` then folds those of broadcast operands."""
+    waveform, noise, snr = saved
+    lengths = rest[0]
+    g = grads[0]
+    if g is None:
+        return None
+    lead = _add_noise_lead(waveform, noise, snr, lengths)
+    if not H.add_noise_covers(lead, waveform, noise):
+        return None                 # (the layouts the forward announced: the stock-torch route, announced again)
+    g = g if H.add_noise_covers(lead, g, waveform, noise) else g.contiguous()      # (one split of the rows has to serve all three)
+    got = H.add_noise_grad_rows(g, waveform, noise, snr, lengths, lead, needs)
+    return [None if t is None else t.sum_to_size(ref.shape) for t, ref in zip(got, saved)]
+
+
 _HIP_BACKWARD = {'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
-                 'mask_spans': _mask_spans_hip_backward,
+                 'mask_spans': _mask_spans_hip_backward, 'add_noise': _add_noise_hip_backward,
                  'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
@@ -993,6 +1017,58 @@ def _register_mask_spans_autograd():
 _register('mask_spans', '(Tensor x, Tensor spans, int k_a, Tensor? value_t, float value) -> Tensor', _mask_spans_cuda, _mask_spans_cpu,
           _mask_spans_fake, 2, differentiable=False)
 _register_mask_spans_autograd()
+
+
+# ============================================================================= add_noise
+def _add_noise_check(waveform, noise, snr, lengths):
+    if not (waveform.dim() - 1 == noise.dim() - 1 == snr.dim() and (lengths is None or lengths.dim() == snr.dim())) or waveform.dim() < 1:
+        raise ValueError("add_noise: the leading dimensions of waveform %r, noise %r, snr %r%s don't match"
+                         % (tuple(waveform.shape), tuple(noise.shape), tuple(snr.shape),
+                            '' if lengths is None else ' and lengths %r' % (tuple(lengths.shape),)))
+    if waveform.shape[-1] != noise.shape[-1]:
+        raise ValueError('add_noise: waveform and noise differ in length (%d and %d)' % (waveform.shape[-1], noise.shape[-1]))
+    try:
+        return _add_noise_lead(waveform, noise, snr, lengths)
+    except RuntimeError as exc:
+        raise ValueError('add_noise: the leading dimensions do not broadcast (%s)' % exc)
+
+
+def _add_noise_snr(snr, dtype):
+    """``snr`` in the dtype of the operands: the result has ``result_type(waveform, noise)`` on every route, the fake one included"""
+    return snr if snr.dtype == dtype or not dtype.is_floating_point else snr.to(dtype)
+
+
+def _add_noise_cuda(waveform, noise, snr, lengths):
+    lead = _add_noise_check(waveform, noise, snr, lengths)
+    _same_device('add_noise', waveform, noise, snr, *(() if lengths is None else (lengths,)))
+    shape = lead + (int(waveform.shape[-1]),)
+    dtype = torch.result_type(waveform, noise)
+    snr = _add_noise_snr(snr, dtype)
+    if 0 in shape:
+        return torch.empty(shape, dtype=dtype, device=waveform.device)          # an empty output: nothing is launched
+    reason = _hip_dtype(waveform, noise, snr)
+    if reason is None:
+        wave32, noise32 = _f32(waveform), _f32(noise)
+        reason = H.add_noise_reason(lead, wave32, noise32)
+    if reason is not None:
+        _composite_route('add_noise', reason)
+        return C.add_noise(waveform, noise, snr, lengths)
+    out = H.add_noise_rows(wave32, noise32, snr, lengths, lead)
+    return out if dtype == out.dtype else out.to(dtype)
+
+
+def _add_noise_fake(waveform, noise, snr, lengths):
+    lead = _add_noise_check(waveform, noise, snr, lengths)
+    return waveform.new_empty(lead + (waveform.shape[-1],), dtype=torch.result_type(waveform, noise))
+
+
+def _add_noise_cpu(waveform, noise, snr, lengths):
+    _add_noise_check(waveform, noise, snr, lengths)
+    return C.add_noise(waveform, noise, _add_noise_snr(snr, torch.result_type(waveform, noise)), lengths)
+
+
+_register('add_noise', '(Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths) -> Tensor', _add_noise_cuda, _add_noise_cpu,
+          _add_noise_fake, 3)
 
 
 # ============================================================================= lfilter

@@ -24,11 +24,12 @@ from . import _filters
 from . import _kaldi
 from . import _resample
 from . import _specaug
+from . import _augment
 from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
 
 _call = _ops.call
@@ -399,6 +400,29 @@ def mask_along_axis(specgram, mask_param, mask_value, axis, p=1.0):
     ``mask_along_axis_iid``."""
     x = _tensor(specgram, 'specgram')
     return _specaug.mask_along_axis(x, int(mask_param), mask_value, axis, float(p))
+
+
+def add_noise(waveform, noise, snr, lengths=None):
+    """``waveform`` (…, L), ``noise`` (…, L), ``snr`` (…) in dB, ``lengths`` (…) or None → (…, L): torchaudio's ``functional.add_noise``.
+    With ``m_t = t < lengths`` (every sample without ``lengths``; more than L: the whole row, 0 or less: none of it), ``E_s = sum_t
+    (waveform_t m_t)^2`` and ``E_n`` likewise, ``out = waveform + sqrt(E_s / E_n) 10^(-snr / 20) noise`` at every sample, masked or not.
+    The operands have the same number of leading dimensions and equal L (``ValueError`` otherwise), and the leading dimensions
+    broadcast: one noise row may serve every channel, one ``snr`` every row.  On a HIP device float32 input (float16 / bfloat16
+    widened) is one entry of three launches (csrc/add_noise.hip): float64 sums in a fixed order, ``scale`` rounded to float32 once,
+    one fused multiply-add per output, ``snr`` and ``lengths`` read on the device; samples behind ``lengths`` are not read by the
+    sums.  All three float32 gradients are the same kernels in adjoint mode.  float64, non-positive time strides and leading
+    dimensions that two strides do not walk take torch operators, announced; CPU tensors take them too."""
+    return _augment.add_noise(_tensor(waveform, 'waveform'), _tensor(noise, 'noise'), snr, lengths)
+
+
+def speed(waveform, orig_freq, factor, lengths=None):
+    """``(…, L)`` → ``((…, ceil(L * target / source)), out_lengths)``: torchaudio's ``functional.speed`` — the waveform played
+    ``factor`` times faster, i.e. ``resample(waveform, source, target)`` with ``source = int(factor * orig_freq)`` and ``target =
+    int(orig_freq)`` divided by their gcd (0.9 at 16 kHz: 9:10), on the ``resample`` kernel (one launch; equal rates return the
+    input).  ``out_lengths`` is None without ``lengths``, else ``ceil(lengths * target / source)`` in the dtype of ``lengths``,
+    computed where ``lengths`` lies.  ``ValueError`` for ``factor <= 0`` or ``int(factor * orig_freq) == 0``."""
+    source, target = _augment.speed_rates(orig_freq, factor)
+    return resample(waveform, source, target), _augment.speed_lengths(lengths, source, target)
 
 
 _CONV_MODES = ('full', 'valid', 'same')

@@ -20,6 +20,7 @@ from . import _lazy
 from . import _ops
 from . import _resample
 from . import _specaug
+from . import _augment
 from ._lazy import DeferredSpectral, DeferredWave, can_defer, can_defer_codes, lazy_fusion_enabled, realize
 
 
@@ -573,6 +574,53 @@ class SpecAugment(_ModuleNoStateBuffers):
         return ('SpecAugment(n_time_masks={}, time_mask_param={}, n_freq_masks={}, freq_mask_param={}, iid_masks={}, p={}, '
                 'zero_masking={})').format(self.n_time_masks, self.time_mask_param, self.n_freq_masks, self.freq_mask_param,
                                            self.iid_masks, self.p, self.zero_masking)
+
+
+class AddNoise(_ModuleNoStateBuffers):
+    """``functional.add_noise`` as a layer (torchaudio's ``transforms.AddNoise``): ``forward(waveform, noise, snr, lengths=None)``.  No
+    buffers."""
+
+    def forward(self, waveform, noise, snr, lengths=None):
+        return _augment.add_noise(realize(waveform), realize(noise), snr, lengths, 'AddNoise')
+
+
+class Speed(_ModuleNoStateBuffers):
+    """``functional.speed`` as a layer (torchaudio's ``transforms.Speed``): ``forward(waveform, lengths=None)`` returns ``(waveform
+    played factor times faster, its valid lengths or None)``.  It holds the ``Resample`` layer of the reduced pair ``int(factor *
+    orig_freq) : int(orig_freq)``, whose bank is built once, here."""
+
+    def __init__(self, orig_freq, factor):
+        super(Speed, self).__init__()
+        self.orig_freq, self.factor = orig_freq, factor
+        self.source_sample_rate, self.target_sample_rate = _augment.speed_rates(orig_freq, factor, 'Speed')
+        self.resampler = Resample(orig_freq=self.source_sample_rate, new_freq=self.target_sample_rate)
+
+    def forward(self, waveform, lengths=None):
+        return self.resampler(waveform), _augment.speed_lengths(lengths, self.source_sample_rate, self.target_sample_rate)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(orig_freq={}, factor={})'.format(self.orig_freq, self.factor)
+
+
+class SpeedPerturbation(_ModuleNoStateBuffers):
+    """torchaudio's ``transforms.SpeedPerturbation``: ``forward(waveform, lengths=None)`` draws one of ``factors`` —
+    ``int(torch.randint(len(factors), ()))`` from the CPU generator, once per call and before anything else, also where the factor
+    drawn is 1.0 — and applies that ``Speed``."""
+
+    def __init__(self, orig_freq, factors):
+        super(SpeedPerturbation, self).__init__()
+        factors = list(factors)
+        if not factors:
+            raise ValueError('SpeedPerturbation: factors must not be empty')
+        self.orig_freq, self.factors = orig_freq, factors
+        self.speeders = nn.ModuleList([Speed(orig_freq, factor) for factor in factors])
+
+    def forward(self, waveform, lengths=None):
+        index = int(torch.randint(len(self.speeders), ()))
+        return self.speeders[index](waveform, lengths)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(orig_freq={}, factors={})'.format(self.orig_freq, self.factors)
 
 
 class FFTConvolve(_ModuleNoStateBuffers):
