@@ -703,6 +703,27 @@ int tac_add_noise_grad_f32(const float* grad_out, int64_t g_stride_o, int64_t g_
                            int64_t snr_rows, const void* lengths, int64_t length_rows, int32_t lengths_i64, void* work,
                            float* grad_waveform, float* grad_noise, float* grad_snr, void* stream);
 
+/* (23) functional.loudness / Loudness: ITU-R BS.1770-4 gated loudness in LKFS (csrc/loudness.hip).  waveform: `entries` batch entries
+ *      of `channels` (1 .. 5) rows of `length` samples, unit time stride; channel c of entry e starts at e * stride_b + c * stride_c
+ *      (strides in floats, positive where the count exceeds 1).  coeffs = HOST double[12]: b[3], a[3] of the K-weighting's shelf,
+ *      then b[3], a[3] of its high-pass (a[0] != 0; normalised here).  gate and step are the block length and hop in samples; the
+ *      kernels take gate == 4 * step with step >= 16 (TAC_E_UNSUPPORTED otherwise) and length >= gate (TAC_E_SHORT_INPUT).  With nb =
+ *      (length - gate) / step + 1 blocks:
+ *        w = clip(highpass(clip(shelf(x))))           float64 recursions, each clipped to [-1, 1] in float64, never stored
+ *        E[c][k] = sum of w^2 over [k step, k step + gate) / gate,   l_k = -0.691 + 10 log10 sum_c g_c E[c][k],  g = (1, 1, 1, 1.41, 1.41)
+ *        out[e] = the level of the mean E over the blocks with l_k > -70 and l_k > (the level of the mean over l_k > -70) - 10
+ *      all in float64, rounded to float32 once; NaN where no block is left.  Two launches on the stream, no host wait: a workgroup
+ *      per row walks it in tiles of tac_loudness_tile() samples (state, and the sum of a bin of `step` samples that a tile boundary
+ *      cuts, carried from tile to tile; a persistent grid of one workgroup per CU) and writes the row's nb + 3 bin sums; a wave per
+ *      entry gates and reduces.  No atomics, one writer per element: bit-identical from run to run.  Samples behind the last block are
+ *      not read.
+ *      work: DEVICE scratch of tac_loudness_work_bytes(entries, channels, length, gate, step) bytes, 8-byte aligned (0 for what the
+ *      kernels do not take); nothing in it has to be initialised, every double of it is written.  out: float[entries]. */
+int64_t tac_loudness_tile(void);
+int64_t tac_loudness_work_bytes(int64_t entries, int32_t channels, int64_t length, int64_t gate, int64_t step);
+int tac_loudness_f32(const float* waveform, int64_t entries, int32_t channels, int64_t length, int64_t stride_b, int64_t stride_c,
+                     int64_t gate, int64_t step, const double* coeffs, void* work, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ import math
 import torch
 import torch.nn.functional as TF
 
+from . import _filters
 from . import _kaldi
 
 TWO_PI = 2.0 * math.pi
@@ -141,6 +142,33 @@ def lfilter(wave, a_coeffs, b_coeffs, clamp):
     if clamp:
         y = y.clamp(-1.0, 1.0)
     return y.reshape(wave.shape)
+
+
+def loudness(waveform, sample_rate):
+    """torchaudio's ``functional.loudness`` (ITU-R BS.1770-4) in torch operators, in the input's dtype: ``(…, channels, time)`` →
+    ``(…)``.  The K-weighting is this package's ``treble_biquad`` and ``highpass_biquad`` (``lfilter`` above, each clipped to [-1, 1]
+    and rounded to the input's dtype), then the mean square of blocks of ``gate`` samples every ``step``, the weighted sum over
+    the channels, and the two gates: ``l_k > -70`` and ``l_k >`` the level of the mean over those blocks ``- 10``.  A gated block is
+    multiplied by 0, so a NaN block makes its entry NaN; no block left gives 0 / 0 = NaN.  The CPU route of ``tac_amd::loudness``
+    and its announced composite route; what csrc/loudness.hip does in two launches."""
+    gate, step = _filters.loudness_blocks(sample_rate)
+    w = waveform
+    for b, a in _filters.k_weighting(sample_rate):
+        w = lfilter(w, _filters.host_tensor(a), _filters.host_tensor(b), True)
+    energy = torch.square(w).unfold(-1, gate, step).mean(-1)                                    # (…, C, nb)
+    g = torch.tensor(_filters.LOUDNESS_WEIGHTS[:energy.shape[-2]], dtype=energy.dtype, device=energy.device)
+
+    def level(e):
+        return -0.691 + 10.0 * torch.log10((g * e).sum(-1))
+
+    def gated(keep):
+        return (keep.unsqueeze(-2) * energy).sum(-1) / torch.count_nonzero(keep, dim=-1).unsqueeze(-1)
+
+    l = -0.691 + 10.0 * torch.log10((g.unsqueeze(-1) * energy).sum(-2))                          # (…, nb)
+    keep = l > -70.0
+    gamma = level(gated(keep)) - 10.0
+    keep = keep & (l > gamma.unsqueeze(-1))
+    return level(gated(keep))
 
 
 def fftconvolve(x, y, n_fft=0):

@@ -71,6 +71,68 @@ def equalizer(sample_rate, center_freq, gain, Q=0.707):
     return (1.0 + alpha * A, -2.0 * c, 1.0 - alpha * A), (1.0 + alpha / A, -2.0 * c, 1.0 - alpha / A)
 
 
+def _shelf_terms(sample_rate, gain, central_freq, Q):
+    w0, alpha = _w0_alpha(sample_rate, central_freq, Q)
+    A = math.exp(float(gain) / 40.0 * math.log(10.0))
+    c = math.cos(w0)
+    return A, 2.0 * math.sqrt(A) * alpha, (A - 1.0) * c, (A + 1.0) * c
+
+
+def treble(sample_rate, gain, central_freq=3000, Q=0.707):
+    """High shelf of ``gain`` dB (torchaudio's ``treble_biquad``): with ``A = exp(gain / 40 ln 10)``, ``t1 = 2 sqrt(A) alpha``,
+    ``t2 = (A - 1) cos w0``, ``t3 = (A + 1) cos w0``: ``b = (A ((A + 1) + t2 + t1), -2 A ((A - 1) + t3), A ((A + 1) + t2 - t1))``,
+    ``a = ((A + 1) - t2 + t1, 2 ((A - 1) - t3), (A + 1) - t2 - t1)``."""
+    A, t1, t2, t3 = _shelf_terms(sample_rate, gain, central_freq, Q)
+    return ((A * ((A + 1.0) + t2 + t1), -2.0 * A * ((A - 1.0) + t3), A * ((A + 1.0) + t2 - t1)),
+            ((A + 1.0) - t2 + t1, 2.0 * ((A - 1.0) - t3), (A + 1.0) - t2 - t1))
+
+
+def bass(sample_rate, gain, central_freq=100, Q=0.707):
+    """Low shelf of ``gain`` dB (torchaudio's ``bass_biquad``), the mirror image of ``treble``: ``b = (A ((A + 1) - t2 + t1),
+    2 A ((A - 1) - t3), A ((A + 1) - t2 - t1))``, ``a = ((A + 1) + t2 + t1, -2 ((A - 1) + t3), (A + 1) + t2 - t1)``."""
+    A, t1, t2, t3 = _shelf_terms(sample_rate, gain, central_freq, Q)
+    return ((A * ((A + 1.0) - t2 + t1), 2.0 * A * ((A - 1.0) - t3), A * ((A + 1.0) - t2 - t1)),
+            ((A + 1.0) + t2 + t1, -2.0 * ((A - 1.0) + t3), (A + 1.0) + t2 - t1))
+
+
+#: the channel weights of ITU-R BS.1770-4 (left, right, centre, left surround, right surround) as torchaudio has them
+LOUDNESS_WEIGHTS = (1.0, 1.0, 1.0, 1.41, 1.41)
+
+
+def loudness_blocks(sample_rate):
+    """``(gate, step)``: the block of 400 ms and its hop of a quarter of it in samples, each by Python's ``round`` as torchaudio's
+    ``loudness`` takes them"""
+    gate = int(round(0.4 * sample_rate))
+    return gate, int(round(gate * 0.25))
+
+
+def k_weighting(sample_rate):
+    """``((b, a), (b, a))``: the two biquads in front of the loudness measurement, torchaudio's ``treble_biquad(4 dB, 1500 Hz,
+    Q = 1 / sqrt 2)`` and ``highpass_biquad(38 Hz, Q = 0.5)``"""
+    return treble(sample_rate, 4.0, 1500.0, 1.0 / math.sqrt(2.0)), highpass(sample_rate, 38.0, 0.5)
+
+
+def loudness_check(waveform, sample_rate, name='loudness'):
+    """The checks of ``loudness`` (``ValueError``), before anything touches a device; returns ``(gate, step)``"""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate <= 0:
+        raise ValueError('%s: sample_rate must be a positive int, got %r' % (name, sample_rate))
+    if waveform.dim() < 2:
+        raise ValueError('%s: expected a waveform of shape (..., channels, time), got shape %s' % (name, tuple(waveform.shape)))
+    if waveform.size(-2) > 5:
+        raise ValueError('Only up to 5 channels are supported.')
+    if waveform.size(-2) < 1:
+        raise ValueError('%s: the waveform has no channel (shape %s)' % (name, tuple(waveform.shape)))
+    if not waveform.is_floating_point():
+        raise ValueError('%s: expected a floating-point waveform, got %s' % (name, waveform.dtype))
+    gate, step = loudness_blocks(sample_rate)
+    if gate < 1 or step < 1:
+        raise ValueError('%s: sample_rate %d leaves no block (400 ms are %d samples, the hop %d)' % (name, sample_rate, gate, step))
+    if waveform.size(-1) < gate:
+        raise ValueError('%s: the waveform has %d samples, shorter than one block of 400 ms (%d samples at %d Hz)'
+                         % (name, waveform.size(-1), gate, sample_rate))
+    return gate, step
+
+
 _tensors = {}
 
 

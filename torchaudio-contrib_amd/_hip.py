@@ -1003,6 +1003,45 @@ def lfilter_rows(x, b, a, clamp, reverse=False):
     return out
 
 
+# ----------------------------------------------------------------------------- loudness (csrc/loudness.hip)
+#: samples of one row per tile of ``tac_loudness_f32`` (csrc/loudness.hip: LO_TILE), checked against the library's own value at the
+#: first launch, and the shortest hop its bins take (LO_C: at most one bin edge in a lane's chunk)
+LOUDNESS_TILE = 16384
+LOUDNESS_MIN_STEP = 16
+_loudness_tile_checked = False
+
+
+def loudness_entries(x, stages, gate, step):
+    """``(…, C, L) -> (…)`` through ``tac_loudness_f32``: one entry, two launches on the current stream.  ``stages``: the two
+    ``(b, a)`` of the K-weighting as tuples of Python floats.  ``x`` is read where it lies when its leading dimensions collapse
+    into one positive stride beside a positive channel stride over unit-stride rows; it is copied otherwise.  The float64 bins
+    come from torch's allocator."""
+    global _loudness_tile_checked
+    lead, (channels, length) = tuple(x.shape[:-2]), x.shape[-2:]
+    rows = x.unsqueeze(0) if x.dim() == 2 else x.reshape(-1, channels, length)
+    entries = rows.shape[0]
+    if (length > 1 and rows.stride(2) != 1) or (entries > 1 and rows.stride(0) <= 0) or (channels > 1 and rows.stride(1) <= 0):
+        rows = rows.contiguous()
+    h = _native.lib()
+    if not _loudness_tile_checked:
+        if h.tac_loudness_tile() != LOUDNESS_TILE:
+            raise RuntimeError('libtac_amd.so walks %d samples per tile, _hip.LOUDNESS_TILE says %d' % (h.tac_loudness_tile(), LOUDNESS_TILE))
+        _loudness_tile_checked = True
+    need = int(h.tac_loudness_work_bytes(entries, channels, length, gate, step))
+    if need <= 0:
+        raise RuntimeError('tac_loudness_f32 does not take %d entries of %d channels and %d samples at gate %d, step %d'
+                           % (entries, channels, length, gate, step))
+    out = _empty((entries,), device=x.device)
+    work = _empty((need // 8,), dtype=torch.float64, device=x.device)
+    coeffs = (ctypes.c_double * 12)(*[v for b, a in stages for v in tuple(b) + tuple(a)])
+    with _native.on_device(x.device):
+        rc = h.tac_loudness_f32(_native.ptr(rows), entries, channels, length, rows.stride(0), rows.stride(1), gate, step, coeffs,
+                                _native.ptr(work), _native.ptr(out), _native.stream_ptr(x.device))
+    _native.check(rc, 'tac_loudness_f32')
+    _count('tac_loudness_f32', out, work)
+    return out.reshape(lead)
+
+
 # ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
 #: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
 FFTCONV_SIZES = (2048, 4096, 8192)

@@ -46,6 +46,7 @@ EXPORTS = (
     'tac_sliding_cmn_chunk', 'tac_sliding_cmn_f32', 'tac_deltas_supported', 'tac_deltas_f32',
     'tac_mask_spans_supported', 'tac_mask_spans_f32',
     'tac_add_noise_tile', 'tac_add_noise_work_bytes', 'tac_add_noise_f32', 'tac_add_noise_grad_f32',
+    'tac_loudness_tile', 'tac_loudness_work_bytes', 'tac_loudness_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -232,6 +233,11 @@ def lib():
         h.tac_add_noise_f32.argtypes = [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _P]
         h.tac_add_noise_grad_f32.argtypes = [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P,
                                              _I64, _I32, _P, _P, _P, _P, _P]
+        h.tac_loudness_tile.restype = _I64
+        h.tac_loudness_tile.argtypes = []
+        h.tac_loudness_work_bytes.restype = _I64
+        h.tac_loudness_work_bytes.argtypes = [_I64, _I32, _I64, _I64, _I64]
+        h.tac_loudness_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

@@ -17,6 +17,7 @@ see them by name.
     tac_amd::compute_deltas     delta coefficients along time over (…, F, T) (csrc/cmn_deltas.hip)
     tac_amd::mask_spans         SpecAugment: every time and frequency mask of a call over (…, F, T) in one launch (csrc/specaug.hip)
     tac_amd::add_noise          noise mixed into (…, L) at a signal-to-noise ratio, under a length mask (csrc/add_noise.hip)
+    tac_amd::loudness           ITU-R BS.1770-4 gated loudness of (…, channels, L): K-weighting, blocks and gates (csrc/loudness.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -41,6 +42,7 @@ import torch
 from torch.library import Library
 
 from . import _composite as C
+from . import _filters as FL
 from . import _hip as H
 from . import _hip64 as H64
 from . import _kaldi as K
@@ -1069,6 +1071,46 @@ def _add_noise_cpu(waveform, noise, snr, lengths):
 
 _register('add_noise', '(Tensor waveform, Tensor noise, Tensor snr, Tensor? lengths) -> Tensor', _add_noise_cuda, _add_noise_cpu,
           _add_noise_fake, 3)
+
+
+# ============================================================================= loudness
+def loudness_reason(waveform, gate, step):
+    """why the two launches of csrc/loudness.hip do not take this call, or None"""
+    reason = _hip_dtype(waveform)
+    if reason is None and any(st <= 0 for st, n in zip(waveform.stride(), waveform.shape) if n > 1):
+        reason = 'non-positive strides'
+    if reason is None and gate != 4 * step:
+        reason = 'a sample rate whose block of %d samples is not four hops of %d' % (gate, step)
+    if reason is None and step < H.LOUDNESS_MIN_STEP:
+        reason = 'a hop of %d samples (the kernel takes %d or more)' % (step, H.LOUDNESS_MIN_STEP)
+    return reason
+
+
+def _loudness_cuda(waveform, sample_rate):
+    gate, step = FL.loudness_check(waveform, sample_rate)
+    if 0 in waveform.shape[:-2]:
+        return waveform.new_empty(tuple(waveform.shape[:-2]))       # an empty batch: nothing is launched
+    reason = loudness_reason(waveform, gate, step)
+    if reason is not None:
+        _composite_route('loudness', reason)
+        return C.loudness(waveform, sample_rate)
+    out = H.loudness_entries(_f32(waveform), FL.k_weighting(sample_rate), gate, step)
+    return out if waveform.dtype == out.dtype else out.to(waveform.dtype)
+
+
+def _loudness_cpu(waveform, sample_rate):
+    FL.loudness_check(waveform, sample_rate)
+    if 0 in waveform.shape[:-2]:
+        return waveform.new_empty(tuple(waveform.shape[:-2]))
+    return C.loudness(waveform, sample_rate)
+
+
+def _loudness_fake(waveform, sample_rate):
+    return waveform.new_empty(tuple(waveform.shape[:-2]))
+
+
+# (no gradient kernel: the backward pass re-evaluates the definition with torch operators, announced, as kaldi_fbank's does)
+_register('loudness', '(Tensor waveform, int sample_rate) -> Tensor', _loudness_cuda, _loudness_cpu, _loudness_fake, 1)
 
 
 # ============================================================================= lfilter

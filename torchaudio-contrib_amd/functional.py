@@ -30,7 +30,7 @@ from ._lazy import realize as _realize
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
-           'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis']
+           'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness']
 
 _call = _ops.call
 
@@ -550,6 +550,39 @@ def equalizer_biquad(waveforms, sample_rate, center_freq, gain, Q=0.707):
     """Peaking equalizer of ``gain`` dB at ``center_freq``: with ``A = 10^(gain / 40)``, ``b = (1 + alpha A, -2 cos w0,
     1 - alpha A)``, ``a = (1 + alpha / A, -2 cos w0, 1 - alpha / A)``."""
     return _design(waveforms, _filters.equalizer(sample_rate, center_freq, gain, Q))
+
+
+def treble_biquad(waveforms, sample_rate, gain, central_freq=3000, Q=0.707):
+    """High shelf (torchaudio's ``functional.treble_biquad``): ``gain`` dB above ``central_freq``.  With ``A = exp(gain / 40 ln 10)``,
+    ``t1 = 2 sqrt(A) alpha``, ``t2 = (A - 1) cos w0`` and ``t3 = (A + 1) cos w0``: ``b = (A ((A + 1) + t2 + t1), -2 A ((A - 1) + t3),
+    A ((A + 1) + t2 - t1))``, ``a = ((A + 1) - t2 + t1, 2 ((A - 1) - t3), (A + 1) - t2 - t1)``.  One ``lfilter`` launch."""
+    return _design(waveforms, _filters.treble(sample_rate, gain, central_freq, Q))
+
+
+def bass_biquad(waveforms, sample_rate, gain, central_freq=100, Q=0.707):
+    """Low shelf (torchaudio's ``functional.bass_biquad``): ``gain`` dB below ``central_freq``; ``b = (A ((A + 1) - t2 + t1),
+    2 A ((A - 1) - t3), A ((A + 1) - t2 - t1))``, ``a = ((A + 1) + t2 + t1, -2 ((A - 1) + t3), (A + 1) + t2 - t1)`` with the terms of
+    ``treble_biquad``.  One ``lfilter`` launch."""
+    return _design(waveforms, _filters.bass(sample_rate, gain, central_freq, Q))
+
+
+def loudness(waveform, sample_rate):
+    """``(…, channels, time)`` → ``(…)``: torchaudio's ``functional.loudness``, the gated loudness of ITU-R BS.1770-4 in LKFS.  The
+    waveform passes the K-weighting (``treble_biquad(4 dB, 1500 Hz, Q = 1 / sqrt 2)``, then ``highpass_biquad(38 Hz, Q = 0.5)``, each
+    clipped to [-1, 1]); the mean square of blocks of ``gate = round(0.4 sample_rate)`` samples every ``step = round(gate / 4)`` is
+    summed over the channels with the weights (1, 1, 1, 1.41, 1.41) into ``l_k = -0.691 + 10 log10(.)``; blocks at or below -70 and
+    blocks at or below the level of the remaining blocks' mean minus 10 are dropped, and the level of the mean of what is left is
+    returned — NaN when nothing is left (silence).  ``ValueError`` for fewer than two dimensions, more than five channels, a
+    non-floating dtype, a ``sample_rate`` that is not a positive int and a waveform shorter than one block.
+
+    float32 on a HIP device (float16 / bfloat16 widened) is one entry of two launches (csrc/loudness.hip): the waveform is read
+    once, both recursions, the clips, the squares and every sum are float64 and stay on chip, the gates run in a wave per entry,
+    and the result is the float64 value rounded once.  float64, non-positive strides, a rate whose block is not four hops (11025 Hz:
+    4410 and 1102) or whose hop is below 16 samples, and the backward pass take ``_composite.loudness`` (also the CPU path),
+    announced with ``CompositeRouteWarning`` on a device."""
+    x = _tensor(waveform, 'waveform')
+    _filters.loudness_check(x, sample_rate)
+    return _call('loudness', x, sample_rate)
 
 
 def preemphasis(waveforms, coeff=0.97):

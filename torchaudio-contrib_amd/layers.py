@@ -584,6 +584,23 @@ class AddNoise(_ModuleNoStateBuffers):
         return _augment.add_noise(realize(waveform), realize(noise), snr, lengths, 'AddNoise')
 
 
+class Loudness(_ModuleNoStateBuffers):
+    """``functional.loudness`` as a layer (torchaudio's ``transforms.Loudness``): ``forward(waveform)`` maps ``(…, channels, time)``
+    to the ``(…)`` loudness in LKFS at ``sample_rate``.  No buffers."""
+
+    def __init__(self, sample_rate):
+        super(Loudness, self).__init__()
+        if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate <= 0:
+            raise ValueError('Loudness: sample_rate must be a positive int, got %r' % (sample_rate,))
+        self.sample_rate = sample_rate
+
+    def forward(self, waveform):
+        return F.loudness(waveform, self.sample_rate)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sample_rate={})'.format(self.sample_rate)
+
+
 class Speed(_ModuleNoStateBuffers):
     """``functional.speed`` as a layer (torchaudio's ``transforms.Speed``): ``forward(waveform, lengths=None)`` returns ``(waveform
     played factor times faster, its valid lengths or None)``.  It holds the ``Resample`` layer of the reduced pair ``int(factor *
