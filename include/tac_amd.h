@@ -724,6 +724,32 @@ int64_t tac_loudness_work_bytes(int64_t entries, int32_t channels, int64_t lengt
 int tac_loudness_f32(const float* waveform, int64_t entries, int32_t channels, int64_t length, int64_t stride_b, int64_t stride_c,
                      int64_t gate, int64_t step, const double* coeffs, void* work, float* out, void* stream);
 
+/* (24) functional.detect_pitch_frequency / PitchFrequency: torchaudio's NCCF pitch (csrc/pitch.hip).  waveform: n0 * n1 rows of `time`
+ *      samples; row r starts at (r / n1) * stride_0 + (r % n1) * stride_1 and its samples are stride_t apart (strides in floats,
+ *      positive where the count exceeds 1; any alignment).  With F = frame, L = max_lag, N = ceil(time / F) frames and the row
+ *      continued by zeros:
+ *        nccf[t][l] = (s1 . s2) / (1e-9 + |s1|)^2 / (1e-9 + |s2|)^2,  s1 = x[tF : tF + F], s2 = x[tF + l : tF + l + F],  l = 1 .. L
+ *        lag[t] = ch if nccf[t][ch] > 0.99 nccf[t][cb] else cb,  cb / ch the first arg-max over l in [lag_min + 1, L] / [lag_min + 1, L / 2]
+ *        out[k] = sample_rate / lower median of padded[k : k + win_length],  padded = (win_length - 1) / 2 copies of lag[0], then lag
+ *      with N + (win_length - 1) / 2 - win_length + 1 outputs a row (TAC_E_SHORT_INPUT if that is below 1).  lag_min >= 1 and
+ *      lag_min < L / 2 (TAC_E_INVALID otherwise).  Products and their sums are float32 in a fixed order, the energies of s2 come from
+ *      a float64 prefix of squares; the (frames, lags) matrix stays in registers and the LDS.  A frame whose F + L samples hold a NaN
+ *      or Inf gets some lag in [lag_min + 1, L]; no other frame is touched by it.  An all-zero frame gets lag_min + 1.
+ *      tac_pitch_lags_f32 is the first launch alone (lags: int32[n0 * n1][N]), tac_pitch_smooth_i32 the second (win_length 1 ..
+ *      tac_pitch_max_win(), TAC_E_UNSUPPORTED beyond), tac_pitch_frequency_f32 both on the stream: no host wait, no atomics, one
+ *      writer per element, bit-identical from run to run.  `lags` is DEVICE scratch of n0 * n1 * N int32 there, all of it written.
+ *      tac_pitch_plan: the frames a workgroup of the first launch takes together (*group) and its LDS bytes, or TAC_E_UNSUPPORTED
+ *      where the F + L samples of a single frame do not fit the LDS plan (64 KB); the launchers return the same. */
+int32_t tac_pitch_max_win(void);
+int tac_pitch_plan(int64_t n_frames, int32_t frame, int32_t max_lag, int32_t* group, int32_t* lds_bytes);
+int tac_pitch_lags_f32(const float* waveform, int64_t n0, int64_t n1, int64_t time, int64_t stride_0, int64_t stride_1, int64_t stride_t,
+                       int32_t frame, int32_t max_lag, int32_t lag_min, int32_t* lags, void* stream);
+int tac_pitch_smooth_i32(const int32_t* lags, int64_t rows, int64_t n_frames, int32_t win_length, int32_t sample_rate, float* out,
+                         void* stream);
+int tac_pitch_frequency_f32(const float* waveform, int64_t n0, int64_t n1, int64_t time, int64_t stride_0, int64_t stride_1,
+                            int64_t stride_t, int32_t sample_rate, int32_t frame, int32_t max_lag, int32_t lag_min, int32_t win_length,
+                            int32_t* lags, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ import torch.nn.functional as TF
 
 from . import _filters
 from . import _kaldi
+from . import _pitch
 
 TWO_PI = 2.0 * math.pi
 
@@ -169,6 +170,49 @@ def loudness(waveform, sample_rate):
     gamma = level(gated(keep)) - 10.0
     keep = keep & (l > gamma.unsqueeze(-1))
     return level(gated(keep))
+
+
+def pitch_nccf(waveform, geo):
+    """``(rows, time)`` → ``(rows, n_frames, max_lag)``: column ``c`` holds lag ``c + 1``.  The loop over the lags of torchaudio's
+    ``_compute_nccf``: ``(s1 . s2) / (1e-9 + |s1|)^2 / (1e-9 + |s2|)^2`` — both energies, not their roots."""
+    frame, n_frames = geo.frame, geo.n_frames
+    x = TF.pad(waveform, (0, geo.max_lag + n_frames * frame - waveform.shape[-1]))
+    columns = []
+    for lag in range(1, geo.max_lag + 1):
+        s1 = x[..., :-lag].unfold(-1, frame, frame)[..., :n_frames, :]
+        s2 = x[..., lag:].unfold(-1, frame, frame)[..., :n_frames, :]
+        columns.append(((s1 * s2).sum(-1) / (1e-9 + torch.linalg.vector_norm(s1, ord=2, dim=-1)).pow(2)
+                        / (1e-9 + torch.linalg.vector_norm(s2, ord=2, dim=-1)).pow(2)).unsqueeze(-1))
+    return torch.cat(columns, -1)
+
+
+def pitch_lags(nccf, geo):
+    """``(rows, n_frames, max_lag)`` → int64 ``(rows, n_frames)``: the lag of the best column from ``lag_min`` on, or of the best
+    one below ``half`` where that one exceeds 0.99 of it"""
+    best = torch.max(nccf[..., geo.lag_min:], -1)
+    low = torch.max(nccf[..., geo.lag_min:geo.half], -1)
+    take = low[0] > 0.99 * best[0]
+    return take * low[1] + ~take * best[1] + (geo.lag_min + 1)
+
+
+def pitch_smooth(lags, win_length, sample_rate):
+    """``(rows, n_frames)`` integer lags → float32 ``(rows, n_frames + pad - win_length + 1)``: the lower median over ``win_length``
+    lags behind ``pad = (win_length - 1) // 2`` copies of the first one, then ``float32(sample_rate) / float32(lag)``"""
+    pad = (win_length - 1) // 2
+    if pad:
+        lags = torch.cat([lags[..., :1].expand(lags.shape[:-1] + (pad,)), lags], -1)
+    values = torch.median(lags.unfold(-1, win_length, 1), -1)[0]
+    return torch.tensor(float(sample_rate), dtype=torch.float32, device=lags.device) / values.to(torch.float32)
+
+
+def detect_pitch_frequency(waveform, sample_rate, frame_time=1e-2, win_length=30, freq_low=85, freq_high=3400):
+    """torchaudio's ``functional.detect_pitch_frequency`` in torch operators: ``(…, time)`` → float32 ``(…, n_out)``.  The NCCF is
+    formed in the input's dtype, lag by lag; the result is float32 whatever the input.  The CPU route of
+    ``tac_amd::detect_pitch_frequency`` and its announced composite route; what csrc/pitch.hip does in two launches."""
+    geo = _pitch.check(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+    rows = waveform.reshape(-1, waveform.shape[-1])
+    freq = pitch_smooth(pitch_lags(pitch_nccf(rows, geo), geo), win_length, sample_rate)
+    return freq.reshape(tuple(waveform.shape[:-1]) + (geo.n_out,))
 
 
 def fftconvolve(x, y, n_fft=0):

@@ -1042,6 +1042,89 @@ def loudness_entries(x, stages, gate, step):
     return out.reshape(lead)
 
 
+# ----------------------------------------------------------------------------- detect_pitch_frequency (csrc/pitch.hip)
+#: the longest median window ``tac_pitch_smooth_i32`` takes (csrc/pitch.hip: PT_MAX_WIN), checked against the library at the first use
+PITCH_MAX_WIN = 64
+_pitch_win_checked = False
+
+
+def pitch_plan(n_frames, frame, max_lag):
+    """``(G, LDS bytes)``: the frames one workgroup of ``tac_pitch_lags_f32`` takes together and what it stages them in, or None
+    where the ``frame + max_lag`` samples of a single frame are beyond its LDS plan"""
+    global _pitch_win_checked
+    h = _native.lib()
+    if not _pitch_win_checked:
+        if h.tac_pitch_max_win() != PITCH_MAX_WIN:
+            raise RuntimeError('libtac_amd.so takes median windows up to %d, _hip.PITCH_MAX_WIN says %d' % (h.tac_pitch_max_win(), PITCH_MAX_WIN))
+        _pitch_win_checked = True
+    group, nbytes = ctypes.c_int32(0), ctypes.c_int32(0)
+    if h.tac_pitch_plan(n_frames, frame, max_lag, ctypes.byref(group), ctypes.byref(nbytes)) != 0:
+        return None
+    return group.value, nbytes.value
+
+
+def _pitch_rows(x):
+    """``(…, time)`` as ``(n0, n1, time)`` read where it lies: a view when the leading dimensions collapse into two positive strides
+    beside a positive time stride, a contiguous copy otherwise"""
+    time = x.shape[-1]
+    if x.dim() == 1:
+        rows = x.reshape(1, 1, time)
+    elif x.dim() == 2:
+        rows = x.unsqueeze(0)
+    else:
+        rows = x.reshape(-1, x.shape[-2], time)          # (a view where the strides allow it, else torch copies)
+    if any(st <= 0 for st, n in zip(rows.stride(), rows.shape) if n > 1):
+        rows = rows.contiguous()
+    return rows
+
+
+def pitch_lags(x, frame, max_lag, lag_min):
+    """``(…, time)`` float32 → int32 ``(…, ceil(time / frame))``: the first launch of csrc/pitch.hip alone, ``tac_pitch_lags_f32``"""
+    rows = _pitch_rows(x)
+    n0, n1, time = rows.shape
+    n_frames = -(-time // frame)
+    lags = _empty((n0 * n1, n_frames), dtype=torch.int32, device=x.device)
+    with _native.on_device(x.device):
+        rc = _native.lib().tac_pitch_lags_f32(_native.ptr(rows), n0, n1, time, rows.stride(0), rows.stride(1), rows.stride(2), frame,
+                                              max_lag, lag_min, _native.ptr(lags), _native.stream_ptr(x.device))
+    _native.check(rc, 'tac_pitch_lags_f32')
+    _count('tac_pitch_lags_f32', lags)
+    return lags.reshape(tuple(x.shape[:-1]) + (n_frames,))
+
+
+def pitch_smooth(lags, win_length, sample_rate):
+    """int32 ``(…, n_frames)`` → float32 ``(…, n_frames + (win_length - 1) // 2 - win_length + 1)``: the second launch alone,
+    ``tac_pitch_smooth_i32`` — the lower median over ``win_length`` lags behind copies of the first, then ``sample_rate / lag``"""
+    n_frames = lags.shape[-1]
+    rows = lags.reshape(-1, n_frames).contiguous()
+    n_out = n_frames + (win_length - 1) // 2 - win_length + 1
+    out = _empty((rows.shape[0], max(n_out, 0)), device=lags.device)
+    with _native.on_device(lags.device):
+        rc = _native.lib().tac_pitch_smooth_i32(_native.ptr(rows), rows.shape[0], n_frames, win_length, sample_rate, _native.ptr(out),
+                                                _native.stream_ptr(lags.device))
+    _native.check(rc, 'tac_pitch_smooth_i32')
+    _count('tac_pitch_smooth_i32', out)
+    return out.reshape(tuple(lags.shape[:-1]) + (n_out,))
+
+
+def pitch_frequency(x, sample_rate, frame, max_lag, lag_min, win_length):
+    """``(…, time)`` float32 → float32 ``(…, n_out)`` through ``tac_pitch_frequency_f32``: one entry, two launches on the current
+    stream.  The int32 lags between them come from torch's allocator."""
+    rows = _pitch_rows(x)
+    n0, n1, time = rows.shape
+    n_frames = -(-time // frame)
+    n_out = n_frames + (win_length - 1) // 2 - win_length + 1
+    lags = _empty((n0 * n1, n_frames), dtype=torch.int32, device=x.device)
+    out = _empty((n0 * n1, n_out), device=x.device)
+    with _native.on_device(x.device):
+        rc = _native.lib().tac_pitch_frequency_f32(_native.ptr(rows), n0, n1, time, rows.stride(0), rows.stride(1), rows.stride(2),
+                                                   sample_rate, frame, max_lag, lag_min, win_length, _native.ptr(lags), _native.ptr(out),
+                                                   _native.stream_ptr(x.device))
+    _native.check(rc, 'tac_pitch_frequency_f32')
+    _count('tac_pitch_frequency_f32', out, lags)
+    return out.reshape(tuple(x.shape[:-1]) + (n_out,))
+
+
 # ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
 #: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
 FFTCONV_SIZES = (2048, 4096, 8192)

@@ -47,6 +47,7 @@ EXPORTS = (
     'tac_mask_spans_supported', 'tac_mask_spans_f32',
     'tac_add_noise_tile', 'tac_add_noise_work_bytes', 'tac_add_noise_f32', 'tac_add_noise_grad_f32',
     'tac_loudness_tile', 'tac_loudness_work_bytes', 'tac_loudness_f32',
+    'tac_pitch_max_win', 'tac_pitch_plan', 'tac_pitch_lags_f32', 'tac_pitch_smooth_i32', 'tac_pitch_frequency_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -238,6 +239,12 @@ def lib():
         h.tac_loudness_work_bytes.restype = _I64
         h.tac_loudness_work_bytes.argtypes = [_I64, _I32, _I64, _I64, _I64]
         h.tac_loudness_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]
+        h.tac_pitch_max_win.restype = _I32
+        h.tac_pitch_max_win.argtypes = []
+        h.tac_pitch_plan.argtypes = [_I64, _I32, _I32, _P, _P]
+        h.tac_pitch_lags_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P]
+        h.tac_pitch_smooth_i32.argtypes = [_P, _I64, _I64, _I32, _I32, _P, _P]
+        h.tac_pitch_frequency_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

@@ -18,6 +18,7 @@ see them by name.
     tac_amd::mask_spans         SpecAugment: every time and frequency mask of a call over (…, F, T) in one launch (csrc/specaug.hip)
     tac_amd::add_noise          noise mixed into (…, L) at a signal-to-noise ratio, under a length mask (csrc/add_noise.hip)
     tac_amd::loudness           ITU-R BS.1770-4 gated loudness of (…, channels, L): K-weighting, blocks and gates (csrc/loudness.hip)
+    tac_amd::detect_pitch_frequency   NCCF pitch of (…, L): correlations, peak choice and median in two launches (csrc/pitch.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -46,6 +47,7 @@ from . import _filters as FL
 from . import _hip as H
 from . import _hip64 as H64
 from . import _kaldi as K
+from . import _pitch as PT
 from . import _resample as RS
 
 NS = 'tac_amd'
@@ -1111,6 +1113,50 @@ def _loudness_fake(waveform, sample_rate):
 
 # (no gradient kernel: the backward pass re-evaluates the definition with torch operators, announced, as kaldi_fbank's does)
 _register('loudness', '(Tensor waveform, int sample_rate) -> Tensor', _loudness_cuda, _loudness_cpu, _loudness_fake, 1)
+
+
+# ============================================================================= detect_pitch_frequency
+def pitch_reason(waveform, sample_rate, frame_time=1e-2, win_length=30, freq_low=85, freq_high=3400):
+    """why the two launches of csrc/pitch.hip do not take this call, or None"""
+    geo = PT.check(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+    reason = _hip_dtype(waveform)
+    if reason is None and any(st <= 0 for st, n in zip(waveform.stride(), waveform.shape) if n > 1):
+        reason = 'non-positive strides'
+    if reason is None and (sample_rate >= 2 ** 31 or waveform.shape[-1] >= 2 ** 40):
+        reason = 'a sample rate of %d over %d samples (beyond the launch\'s int32 rate and lags)' % (sample_rate, waveform.shape[-1])
+    if reason is None and win_length > H.PITCH_MAX_WIN:
+        reason = 'a median window of %d lags (the kernel takes %d or fewer)' % (win_length, H.PITCH_MAX_WIN)
+    if reason is None and H.pitch_plan(geo.n_frames, geo.frame, geo.max_lag) is None:
+        reason = 'frames of %d samples and %d lags (beyond the LDS plan of the correlation launch)' % (geo.frame, geo.max_lag)
+    return reason
+
+
+def _pitch_cuda(waveform, sample_rate, frame_time, win_length, freq_low, freq_high):
+    geo = PT.check(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+    if 0 in waveform.shape[:-1]:
+        return waveform.new_empty(tuple(waveform.shape[:-1]) + (geo.n_out,), dtype=torch.float32)     # nothing is launched
+    reason = pitch_reason(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+    if reason is not None:
+        _composite_route('detect_pitch_frequency', reason)
+        return C.detect_pitch_frequency(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+    return H.pitch_frequency(_f32(waveform), int(sample_rate), geo.frame, geo.max_lag, geo.lag_min, win_length)
+
+
+def _pitch_cpu(waveform, sample_rate, frame_time, win_length, freq_low, freq_high):
+    geo = PT.check(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+    if 0 in waveform.shape[:-1]:
+        return waveform.new_empty(tuple(waveform.shape[:-1]) + (geo.n_out,), dtype=torch.float32)
+    return C.detect_pitch_frequency(waveform, sample_rate, frame_time, win_length, freq_low, freq_high)
+
+
+def _pitch_fake(waveform, sample_rate, frame_time, win_length, freq_low, freq_high):
+    geo = PT.geometry(waveform.shape[-1], sample_rate, frame_time, win_length, freq_low, freq_high)
+    return waveform.new_empty(tuple(waveform.shape[:-1]) + (geo.n_out,), dtype=torch.float32)
+
+
+# (no autograd: the result is piecewise constant in the waveform and carries no gradient, as torchaudio's carries none)
+_register('detect_pitch_frequency', '(Tensor waveform, int sample_rate, float frame_time, int win_length, float freq_low, '
+          'float freq_high) -> Tensor', _pitch_cuda, _pitch_cpu, _pitch_fake, 1, differentiable=False)
 
 
 # ============================================================================= lfilter

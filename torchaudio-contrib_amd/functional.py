@@ -22,6 +22,7 @@ from . import _hip
 from . import _ops
 from . import _filters
 from . import _kaldi
+from . import _pitch
 from . import _resample
 from . import _specaug
 from . import _augment
@@ -30,7 +31,7 @@ from ._lazy import realize as _realize
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
-           'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness']
+           'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency']
 
 _call = _ops.call
 
@@ -583,6 +584,34 @@ def loudness(waveform, sample_rate):
     x = _tensor(waveform, 'waveform')
     _filters.loudness_check(x, sample_rate)
     return _call('loudness', x, sample_rate)
+
+
+def detect_pitch_frequency(waveform, sample_rate, frame_time=1e-2, win_length=30, freq_low=85, freq_high=3400):
+    """``(…, time)`` → float32 ``(…, n_out)``: torchaudio's ``functional.detect_pitch_frequency``, the pitch in Hz from the normalised
+    cross-correlation function and a median over time.  With ``L = ceil(sample_rate / freq_low)`` lags, frames of ``F =
+    ceil(sample_rate frame_time)`` samples, ``N = ceil(time / F)`` of them and the row continued by ``L + N F - time`` zeros:
+    ``nccf[t, l] = (s1 . s2) / (1e-9 + |s1|)^2 / (1e-9 + |s2|)^2`` for ``s1 = x[tF : tF + F]``, ``s2 = x[tF + l : tF + l + F]``, ``l
+    = 1 … L`` (both energies, not their roots: the reference's form).  In columns ``c = l - 1`` the frame's lag is the first arg-max
+    over ``[lag_min, L // 2)`` if its value exceeds 0.99 of the maximum over ``[lag_min, L)``, and the first arg-max of that range
+    otherwise, ``lag_min = ceil(sample_rate / freq_high)``; an all-zero frame gets ``lag_min + 1``.  The lags get ``(win_length - 1)
+    // 2`` copies of the first in front, ``out`` is ``float32(sample_rate) / float32(lower median of win_length lags)`` and ``n_out
+    = N + (win_length - 1) // 2 - win_length + 1`` (``N - 15`` at the default).  The result is float32 for every input dtype and
+    carries no gradient.
+
+    ``ValueError``, before anything touches a device, for an empty search range (``lag_min >= L // 2``: ``freq_high=170`` at 16
+    kHz), fewer frames than a window takes, ``win_length < 1``, a non-positive ``sample_rate``, ``frame_time``, ``freq_low`` or
+    ``freq_high``, and a tensor without a time axis.
+
+    float32 on a HIP device (float16 / bfloat16 widened) is one entry of two launches (csrc/pitch.hip): the correlations are float32
+    sums in a fixed order formed in the LDS, the ``(frames, lags)`` matrix is never stored, and the median and the division are the
+    second launch.  A frame whose ``F + L`` samples hold a NaN or Inf gets some lag in ``[lag_min + 1, L]`` — which one is not
+    pinned, on any route — and every frame whose samples hold none is unaffected.  float64, non-positive or expanded strides,
+    ``F`` / ``L`` beyond the launch's LDS plan and ``win_length`` above 64 take ``_composite.detect_pitch_frequency`` (also the CPU
+    path), announced with ``CompositeRouteWarning`` on a device."""
+    x = _tensor(waveform, 'waveform')
+    _pitch.check(x, sample_rate, frame_time, win_length, freq_low, freq_high)
+    # (detached: the op is registered without autograd and its result is piecewise constant)
+    return _call('detect_pitch_frequency', x.detach(), sample_rate, float(frame_time), win_length, float(freq_low), float(freq_high))
 
 
 def preemphasis(waveforms, coeff=0.97):

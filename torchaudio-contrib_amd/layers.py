@@ -18,6 +18,7 @@ from . import _filters
 from . import _hip
 from . import _lazy
 from . import _ops
+from . import _pitch
 from . import _resample
 from . import _specaug
 from . import _augment
@@ -599,6 +600,24 @@ class Loudness(_ModuleNoStateBuffers):
 
     def __repr__(self):
         return self.__class__.__name__ + '(sample_rate={})'.format(self.sample_rate)
+
+
+class PitchFrequency(_ModuleNoStateBuffers):
+    """``functional.detect_pitch_frequency`` as a layer: ``forward(waveform)`` maps ``(…, time)`` to the float32 ``(…, n_out)`` pitch
+    in Hz.  No buffers."""
+
+    def __init__(self, sample_rate, frame_time=1e-2, win_length=30, freq_low=85, freq_high=3400):
+        super(PitchFrequency, self).__init__()
+        _pitch.geometry(2 ** 40, sample_rate, frame_time, win_length, freq_low, freq_high)    # (every error but a short waveform's)
+        self.sample_rate, self.frame_time, self.win_length = sample_rate, frame_time, win_length
+        self.freq_low, self.freq_high = freq_low, freq_high
+
+    def forward(self, waveform):
+        return F.detect_pitch_frequency(waveform, self.sample_rate, self.frame_time, self.win_length, self.freq_low, self.freq_high)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sample_rate={}, frame_time={}, win_length={}, freq_low={}, freq_high={})'.format(
+            self.sample_rate, self.frame_time, self.win_length, self.freq_low, self.freq_high)
 
 
 class Speed(_ModuleNoStateBuffers):
