@@ -750,6 +750,52 @@ int tac_pitch_frequency_f32(const float* waveform, int64_t n0, int64_t n1, int64
                             int64_t stride_t, int32_t sample_rate, int32_t frame, int32_t max_lag, int32_t lag_min, int32_t win_length,
                             int32_t* lags, float* out, void* stream);
 
+/* (25) functional.psd / mvdr_weights_souden / apply_beamforming and the MVDR layer: torchaudio's mask-based Souden MVDR beamformer
+ *      (csrc/beamform.hip).  spec: complex pairs X[b][c][f][t][2] of `batch` entries, `channels` (2 .. 8), `bins` and `frames`, read
+ *      where they lie: the four strides are in floats, positive and even, the pair itself contiguous and the base 8-byte aligned
+ *      (TAC_E_INVALID otherwise).  A lane owns one system g = b * bins + f; frame-major spectrograms (stride_f = 2) load coalesced.
+ *      Masks are real [b][f][t] with three positive strides in floats: a unit time stride is staged through the LDS, any other is
+ *      read directly.
+ *
+ *      tac_psd_f32: psd[g][c][e] = sum_t m'[t] X[c][t] conj(X[e][t]), m' = 1 (mask_a NULL), m (normalize 0) or m / (sum_t m + eps).
+ *      n_psd 2 forms a second PSD in the same pass over spec, from mask_b, or from 1 - mask_a where `complement` is set (mask_b
+ *      ignored).  Time is cut into `chunks` pieces of 64 frames (tac_psd_plan: the cut depends on `frames` alone, so a system's
+ *      result does not depend on the rest of the batch); launch 1 leaves per piece
+ *      float32 sums part[n_psd][chunks][channels^2][batch * bins] and float64 mask sums msum[n_psd][chunks][batch * bins] — both
+ *      DEVICE scratch, all of it written — and launch 2 adds the pieces in ascending order in float64, normalises in float64,
+ *      rounds once and stores both triangles from one value (Hermitian to the bit; imaginary diagonal +0).  No atomics; bit-identical
+ *      from run to run.  psd_a / psd_b: float32 [batch * bins][channels][channels][2].
+ *
+ *      tac_mvdr_weights_souden_f32: per system, in float64 from the float32 PSDs: psd_n += (diag_eps * Re tr psd_n + 1e-8) I where
+ *      diagonal_loading; N = psd_n^-1 psd_s by elimination with partial pivoting; W = N / (tr N + eps); w = W[:, ref_channel], or
+ *      w = sum_c W[:, c] u[c] with u = ref_vector[b * ref_stride_b + c] (float32 on the DEVICE) where ref_vector is not NULL.
+ *      Rounded to float32 once: weights[batch * bins][channels][2].
+ *
+ *      tac_apply_beamforming_f32: out[b][f][t] = sum_c conj(w[g][c]) X[b][c][f][t], one fused multiply-add chain over c; out is
+ *      pairs with strides out_b / out_f / out_t in floats (frame-major: out_f = 2, out_t = 2 * bins).
+ *
+ *      tac_mvdr_souden_f32: launch 1 of tac_psd_f32 with two masks (normalize on, eps = psd_eps), the weights launch reading the
+ *      pieces (it sums them exactly as launch 2 would), then the apply launch: three launches on the stream, no host wait, the
+ *      same bits as the three entries called one after the other.  `weights` is an output too. */
+int tac_psd_plan(int64_t frames, int32_t* chunk_frames, int32_t* chunks);
+int32_t tac_beamform_grid(int32_t which, int32_t cus);   /* most workgroups of launch `which` (0 psd, 1 apply) on `cus` CUs (<= 0: this device's) */
+int tac_psd_f32(const float* spec, int64_t batch, int32_t channels, int64_t bins, int64_t frames, int64_t stride_b, int64_t stride_c,
+                int64_t stride_f, int64_t stride_t, const float* mask_a, int64_t a_stride_b, int64_t a_stride_f, int64_t a_stride_t,
+                const float* mask_b, int64_t b_stride_b, int64_t b_stride_f, int64_t b_stride_t, int32_t n_psd, int32_t complement,
+                int32_t normalize, double eps, int32_t chunks, float* part, double* msum, float* psd_a, float* psd_b, void* stream);
+int tac_mvdr_weights_souden_f32(const float* psd_s, const float* psd_n, int64_t batch, int64_t bins, int32_t channels,
+                                const float* ref_vector, int64_t ref_stride_b, int32_t ref_channel, int32_t diagonal_loading,
+                                double diag_eps, double eps, float* weights, void* stream);
+int tac_apply_beamforming_f32(const float* weights, const float* spec, int64_t batch, int32_t channels, int64_t bins, int64_t frames,
+                              int64_t stride_b, int64_t stride_c, int64_t stride_f, int64_t stride_t, float* out, int64_t out_b,
+                              int64_t out_f, int64_t out_t, void* stream);
+int tac_mvdr_souden_f32(const float* spec, int64_t batch, int32_t channels, int64_t bins, int64_t frames, int64_t stride_b,
+                        int64_t stride_c, int64_t stride_f, int64_t stride_t, const float* mask_s, int64_t s_stride_b,
+                        int64_t s_stride_f, int64_t s_stride_t, const float* mask_n, int64_t n_stride_b, int64_t n_stride_f,
+                        int64_t n_stride_t, double psd_eps, const float* ref_vector, int64_t ref_stride_b, int32_t ref_channel,
+                        int32_t diagonal_loading, double diag_eps, double eps, int32_t chunks, float* part, double* msum,
+                        float* weights, float* out, int64_t out_b, int64_t out_f, int64_t out_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

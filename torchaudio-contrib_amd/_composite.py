@@ -26,6 +26,7 @@ import torch.nn.functional as TF
 from . import _filters
 from . import _kaldi
 from . import _pitch
+from . import _beamform
 
 TWO_PI = 2.0 * math.pi
 
@@ -213,6 +214,58 @@ def detect_pitch_frequency(waveform, sample_rate, frame_time=1e-2, win_length=30
     rows = waveform.reshape(-1, waveform.shape[-1])
     freq = pitch_smooth(pitch_lags(pitch_nccf(rows, geo), geo), win_length, sample_rate)
     return freq.reshape(tuple(waveform.shape[:-1]) + (geo.n_out,))
+
+
+def _complex(t):
+    """pairs ``(…, 2)`` as a complex tensor: a view where the strides allow one (the frame-major views do)"""
+    ok = t.stride(-1) == 1 and all(st % 2 == 0 for st, n in zip(t.stride()[:-1], t.shape[:-1]) if n > 1)
+    return torch.view_as_complex(t if ok else t.contiguous())
+
+
+def psd(specgram, mask, normalize=True, eps=1e-10):
+    """torchaudio's ``functional.psd`` in torch operators, on pairs: ``(…, C, F, T, 2)`` → ``(…, F, C, C, 2)``.  The literal form:
+    an einsum that materialises ``(…, F, T, C, C)``, the (normalised) mask applied to it, then the sum over time.  ``mask``:
+    ``(…, F, T)`` or ``_beamform.none``."""
+    x = _complex(specgram).transpose(-3, -2)                                   # (…, F, C, T)
+    outer = torch.einsum('...ct,...et->...tce', x, x.conj())
+    if not _beamform.absent(mask):
+        if normalize:
+            mask = mask / (mask.sum(dim=-1, keepdim=True) + eps)
+        outer = outer * mask[..., None, None]
+    return torch.view_as_real(outer.sum(dim=-3))
+
+
+def mvdr_weights_souden(psd_s, psd_n, ref_vector, ref_channel, diagonal_loading=True, diag_eps=1e-7, eps=1e-8):
+    """torchaudio's ``functional.mvdr_weights_souden`` on pairs: two ``(…, F, C, C, 2)`` → ``(…, F, C, 2)``.  ``ref_vector``: real
+    ``(…, C)`` / ``(C,)`` or ``_beamform.none`` (then column ``ref_channel``)."""
+    s, n = _complex(psd_s), _complex(psd_n)
+    if diagonal_loading:
+        trace = n.diagonal(dim1=-1, dim2=-2).sum(-1).real[..., None, None]
+        n = n + (trace * diag_eps + 1e-8) * torch.eye(n.shape[-1], dtype=n.dtype, device=n.device)
+    numerator = torch.linalg.solve(n, s)
+    ws = numerator / (numerator.diagonal(dim1=-1, dim2=-2).sum(-1)[..., None, None] + eps)
+    if _beamform.absent(ref_vector):
+        w = ws[..., :, ref_channel]
+    else:
+        w = torch.einsum('...fec,...c->...fe', ws, ref_vector.to(ws.dtype))
+    return torch.view_as_real(w.contiguous())
+
+
+def apply_beamforming(weights, specgram):
+    """torchaudio's ``functional.apply_beamforming`` on pairs: ``(…, F, C, 2)`` and ``(…, C, F, T, 2)`` → ``(…, F, T, 2)``, returned
+    as the frame-major view the kernels return"""
+    y = torch.einsum('...fc,...cft->...ft', _complex(weights).conj(), _complex(specgram))
+    return torch.view_as_real(y.transpose(-2, -1).contiguous()).transpose(-3, -2)
+
+
+def mvdr_souden(specgram, mask_s, mask_n, ref_vector, ref_channel, diagonal_loading=True, diag_eps=1e-7, eps=1e-8, psd_eps=1e-15):
+    """the ``MVDR`` layer at ``solution='ref_channel'``: two normalised PSDs (``mask_n`` absent: ``1 - mask_s``), Souden weights,
+    the weights applied"""
+    if _beamform.absent(mask_n):
+        mask_n = 1 - mask_s
+    w = mvdr_weights_souden(psd(specgram, mask_s, True, psd_eps), psd(specgram, mask_n, True, psd_eps), ref_vector, ref_channel,
+                            diagonal_loading, diag_eps, eps)
+    return apply_beamforming(w, specgram)
 
 
 def fftconvolve(x, y, n_fft=0):

@@ -1125,6 +1125,164 @@ def pitch_frequency(x, sample_rate, frame, max_lag, lag_min, win_length):
     return out.reshape(tuple(x.shape[:-1]) + (n_out,))
 
 
+# ----------------------------------------------------------------------------- psd / mvdr_weights_souden / apply_beamforming (csrc/beamform.hip)
+#: how the last calls got their spectrograms: read where they lay (frame-major views, channel slices, any 8-byte aligned pairs whose
+#: bins run faster than their frames), or copied into the frame-major layout first
+beamform_layout = {'in_place': 0, 'copied': 0}
+
+
+def _bf_spec(spec):
+    """``(…, C, F, T, 2)`` float32 → ``(B, C, F, T, 2)`` for the kernels: a view where the leading dimensions collapse into one
+    stride, the pairs are contiguous and 8-byte aligned, every stride is even and positive and the bins run faster than the
+    frames; a frame-major copy otherwise"""
+    tail = tuple(spec.shape[-4:])
+    x5 = None
+    if spec.stride(-1) == 1:
+        if spec.dim() == 4:
+            x5 = spec.unsqueeze(0)
+        elif spec.dim() == 5:
+            x5 = spec
+        else:
+            try:
+                x5 = spec.view((-1,) + tail)
+            except RuntimeError:
+                x5 = None
+    if x5 is not None:
+        ok = x5.data_ptr() % 8 == 0 and all(st > 0 and st % 2 == 0 for st, n in zip(x5.stride()[:4], x5.shape[:4]) if n > 1)
+        if ok and tail[1] > 1 and tail[2] > 1 and x5.stride(2) > x5.stride(3):
+            ok = False                                                  # time runs faster than the bins: lanes along f would not coalesce
+        if not ok:
+            x5 = None
+    if x5 is None:
+        beamform_layout['copied'] += 1                                  # (clone: ``contiguous()`` would keep a misaligned frame-major tensor)
+        return spec.reshape((-1,) + tail).transpose(2, 3).clone(memory_format=torch.contiguous_format).transpose(2, 3)
+    beamform_layout['in_place'] += 1
+    return x5
+
+
+def _bf_mask(mask, F, T):
+    """``(…, F, T)`` float32 → ``(B, F, T)`` read where it lies (a copy where the leading dimensions do not collapse)"""
+    m = mask.reshape(-1, F, T)
+    if any(st <= 0 for st, n in zip(m.stride(), m.shape) if n > 1):
+        m = m.contiguous()
+    return m
+
+
+def _bf_mask_args(m):
+    return (None, 0, 0, 0) if m is None else (_native.ptr(m), m.stride(0), m.stride(1), m.stride(2))
+
+
+def psd_chunks(frames):
+    """the pieces ``tac_psd_plan`` cuts ``frames`` into: a function of the frame count alone"""
+    chunks = ctypes.c_int32(0)
+    _native.check(_native.lib().tac_psd_plan(frames, None, ctypes.byref(chunks)), 'tac_psd_plan')
+    return chunks.value
+
+
+def _bf_scratch(n_psd, chunks, C, G, device):
+    """the pieces of the PSD launch: float32 sums and float64 mask sums, all of it written by the launch"""
+    return _empty((n_psd, chunks, C * C, G), device=device), _empty((n_psd, chunks, G), dtype=torch.float64, device=device)
+
+
+def psd(spec, mask_a=None, mask_b=None, complement=False, normalize=True, eps=1e-10):
+    """``(…, C, F, T, 2)`` float32 → ``(…, F, C, C, 2)`` through ``tac_psd_f32``: one entry of two launches.  With ``mask_b`` or
+    ``complement`` (the second mask is ``1 - mask_a``, formed in the kernel) BOTH PSDs come from one pass over ``spec`` and a pair
+    is returned."""
+    lead, (C, F, T) = tuple(spec.shape[:-4]), spec.shape[-4:-1]
+    x = _bf_spec(spec)
+    B = x.shape[0]
+    n_psd = 2 if (mask_b is not None or complement) else 1
+    ma = None if mask_a is None else _bf_mask(mask_a, F, T)
+    mb = None if mask_b is None else _bf_mask(mask_b, F, T)
+    chunks = psd_chunks(T)
+    part, msum = _bf_scratch(n_psd, chunks, C, B * F, spec.device)
+    out = [_empty((B * F, C, C, 2), device=spec.device) for _ in range(n_psd)]
+    with _native.on_device(spec.device):
+        rc = _native.lib().tac_psd_f32(_native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                                       *_bf_mask_args(ma), *_bf_mask_args(mb), n_psd, 1 if complement else 0, 1 if normalize else 0,
+                                       float(eps), chunks, _native.ptr(part), _native.ptr(msum), _native.ptr(out[0]),
+                                       _native.ptr(out[1]) if n_psd == 2 else None, _native.stream_ptr(spec.device))
+    _native.check(rc, 'tac_psd_f32')
+    _count('tac_psd_f32', part, msum, *out)
+    out = [o.reshape(lead + (F, C, C, 2)) for o in out]
+    return tuple(out) if n_psd == 2 else out[0]
+
+
+def _bf_ref(ref_vector, lead, C):
+    """the reference vector for the kernels: ``(pointer, batch stride, tensor kept alive)``"""
+    if ref_vector is None:
+        return None, 0, None
+    u = ref_vector.to(torch.float32)
+    if u.dim() == 1:
+        u = u.contiguous()
+        return _native.ptr(u), 0, u
+    u = u.reshape(-1, C).contiguous()
+    return _native.ptr(u), C, u
+
+
+def mvdr_weights_souden(psd_s, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    """two ``(…, F, C, C, 2)`` float32 → ``(…, F, C, 2)`` through ``tac_mvdr_weights_souden_f32``: one launch, float64 on chip"""
+    lead, F, C = tuple(psd_s.shape[:-4]), psd_s.shape[-4], psd_s.shape[-2]
+    s, n = psd_s.reshape(-1, F, C, C, 2).contiguous(), psd_n.reshape(-1, F, C, C, 2).contiguous()
+    B = s.shape[0]
+    ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
+    out = _empty((B * F, C, 2), device=psd_s.device)
+    with _native.on_device(psd_s.device):
+        rc = _native.lib().tac_mvdr_weights_souden_f32(_native.ptr(s), _native.ptr(n), B, F, C, ref_ptr, ref_stride, ref_channel,
+                                                       1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(out),
+                                                       _native.stream_ptr(psd_s.device))
+    _native.check(rc, 'tac_mvdr_weights_souden_f32')
+    _count('tac_mvdr_weights_souden_f32', out)
+    return out.reshape(lead + (F, C, 2))
+
+
+def _bf_out(lead, B, F, T, device):
+    """the frame-major output: ``(B, T, F, 2)`` storage, and its logical ``(…, F, T, 2)`` view"""
+    store = _empty((B, T, F, 2), device=device)
+    return store, store.view(lead + (T, F, 2)).transpose(-3, -2)
+
+
+def apply_beamforming(weights, spec):
+    """``(…, F, C, 2)`` and ``(…, C, F, T, 2)`` float32 → the frame-major view ``(…, F, T, 2)`` through ``tac_apply_beamforming_f32``"""
+    lead, (C, F, T) = tuple(spec.shape[:-4]), spec.shape[-4:-1]
+    x = _bf_spec(spec)
+    B = x.shape[0]
+    w = weights.reshape(B * F, C, 2).contiguous()
+    store, out = _bf_out(lead, B, F, T, spec.device)
+    with _native.on_device(spec.device):
+        rc = _native.lib().tac_apply_beamforming_f32(_native.ptr(w), _native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2),
+                                                     x.stride(3), _native.ptr(store), T * F * 2, 2, F * 2,
+                                                     _native.stream_ptr(spec.device))
+    _native.check(rc, 'tac_apply_beamforming_f32')
+    _count('tac_apply_beamforming_f32', store)
+    return out
+
+
+def mvdr_souden(spec, mask_s, mask_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps, psd_eps):
+    """``MVDR`` at ``solution='ref_channel'`` through ``tac_mvdr_souden_f32``: ONE entry of three launches on the current stream —
+    both normalised PSDs from one pass over ``spec`` (``mask_n`` None: ``1 - mask_s`` formed in the kernel), the float64 solve,
+    the weights applied.  Returns ``(frame-major view (…, F, T, 2), weights (…, F, C, 2))``."""
+    lead, (C, F, T) = tuple(spec.shape[:-4]), spec.shape[-4:-1]
+    x = _bf_spec(spec)
+    B = x.shape[0]
+    ms = _bf_mask(mask_s, F, T)
+    mn = None if mask_n is None else _bf_mask(mask_n, F, T)
+    chunks = psd_chunks(T)
+    part, msum = _bf_scratch(2, chunks, C, B * F, spec.device)
+    ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
+    w = _empty((B * F, C, 2), device=spec.device)
+    store, out = _bf_out(lead, B, F, T, spec.device)
+    with _native.on_device(spec.device):
+        rc = _native.lib().tac_mvdr_souden_f32(_native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                                               *_bf_mask_args(ms), *_bf_mask_args(mn), float(psd_eps), ref_ptr, ref_stride, ref_channel,
+                                               1 if diagonal_loading else 0, float(diag_eps), float(eps), chunks, _native.ptr(part),
+                                               _native.ptr(msum), _native.ptr(w), _native.ptr(store), T * F * 2, 2, F * 2,
+                                               _native.stream_ptr(spec.device))
+    _native.check(rc, 'tac_mvdr_souden_f32')
+    _count('tac_mvdr_souden_f32', part, msum, w, store)
+    return out, w.reshape(lead + (F, C, 2))
+
+
 # ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
 #: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
 FFTCONV_SIZES = (2048, 4096, 8192)

@@ -19,6 +19,7 @@ see them by name.
     tac_amd::add_noise          noise mixed into (…, L) at a signal-to-noise ratio, under a length mask (csrc/add_noise.hip)
     tac_amd::loudness           ITU-R BS.1770-4 gated loudness of (…, channels, L): K-weighting, blocks and gates (csrc/loudness.hip)
     tac_amd::detect_pitch_frequency   NCCF pitch of (…, L): correlations, peak choice and median in two launches (csrc/pitch.hip)
+    tac_amd::psd, mvdr_weights_souden, apply_beamforming, mvdr_souden   mask-based MVDR beamforming over (…, C, F, T) (csrc/beamform.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -48,6 +49,7 @@ from . import _hip as H
 from . import _hip64 as H64
 from . import _kaldi as K
 from . import _pitch as PT
+from . import _beamform as BF
 from . import _resample as RS
 
 NS = 'tac_amd'
@@ -1157,6 +1159,118 @@ def _pitch_fake(waveform, sample_rate, frame_time, win_length, freq_low, freq_hi
 # (no autograd: the result is piecewise constant in the waveform and carries no gradient, as torchaudio's carries none)
 _register('detect_pitch_frequency', '(Tensor waveform, int sample_rate, float frame_time, int win_length, float freq_low, '
           'float freq_high) -> Tensor', _pitch_cuda, _pitch_cpu, _pitch_fake, 1, differentiable=False)
+
+
+# ============================================================================= psd, mvdr_weights_souden, apply_beamforming, mvdr_souden
+# Complex values are trailing-2 pairs here; an absent mask / reference vector is the empty tensor BF.none(like).
+def beamform_reason(channels, *tensors):
+    """why the kernels of csrc/beamform.hip do not take these tensors, or None"""
+    tensors = [t for t in tensors if not BF.absent(t)]
+    reason = _hip_dtype(*tensors)
+    if reason is None and not BF.MIN_CHANNELS <= channels <= BF.MAX_CHANNELS:
+        reason = '%d channels (the kernels take %d to %d)' % (channels, BF.MIN_CHANNELS, BF.MAX_CHANNELS)
+    if reason is None and any(st <= 0 for t in tensors for st, n in zip(t.stride(), t.shape) if n > 1):
+        reason = 'expanded or non-positive strides'
+    return reason
+
+
+def _bf_opt(t):
+    return None if BF.absent(t) else _f32(t)
+
+
+def _psd_shape(spec):
+    lead, ch, F, T = BF.spec_shape(spec)
+    return lead + (F, ch, ch, 2)
+
+
+def _psd_cuda(spec, mask, normalize, eps):
+    _same_device('psd', spec, mask)
+    lead, ch, F, T = BF.spec_shape(spec)
+    if 0 in spec.shape:
+        return spec.new_zeros(_psd_shape(spec), dtype=_out_dtype(spec))               # nothing is launched
+    reason = beamform_reason(ch, spec, mask)
+    if reason is not None:
+        _composite_route('psd', reason)
+        return C.psd(spec, mask, normalize, eps)
+    return H.psd(_f32(spec), _bf_opt(mask), normalize=normalize, eps=eps)
+
+
+def _psd_fake(spec, mask, normalize, eps):
+    return spec.new_empty(_psd_shape(spec), dtype=_out_dtype(spec))
+
+
+_register('psd', '(Tensor specgram, Tensor mask, bool normalize, float eps) -> Tensor', _psd_cuda, C.psd, _psd_fake, 2)
+
+
+def _weights_shape(psd_s):
+    lead, F, ch = BF.psd_shape(psd_s)
+    return lead + (F, ch, 2)
+
+
+def _weights_cuda(psd_s, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    _same_device('mvdr_weights_souden', psd_s, psd_n, ref_vector)
+    lead, F, ch = BF.psd_shape(psd_s)
+    if 0 in psd_s.shape:
+        return psd_s.new_zeros(_weights_shape(psd_s), dtype=_out_dtype(psd_s))
+    reason = beamform_reason(ch, psd_s, psd_n)
+    if reason is None and not BF.absent(ref_vector) and any(st < 0 for st in ref_vector.stride()):
+        reason = 'expanded or non-positive strides'
+    if reason is not None:
+        _composite_route('mvdr_weights_souden', reason)
+        return C.mvdr_weights_souden(psd_s, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps)
+    return H.mvdr_weights_souden(_f32(psd_s), _f32(psd_n), None if BF.absent(ref_vector) else ref_vector, ref_channel,
+                                 diagonal_loading, diag_eps, eps)
+
+
+def _weights_fake(psd_s, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    return psd_s.new_empty(_weights_shape(psd_s), dtype=_out_dtype(psd_s))
+
+
+_register('mvdr_weights_souden', '(Tensor psd_s, Tensor psd_n, Tensor ref_vector, int ref_channel, bool diagonal_loading, '
+          'float diag_eps, float eps) -> Tensor', _weights_cuda, C.mvdr_weights_souden, _weights_fake, 3)
+
+
+def _apply_beamforming_cuda(weights, spec):
+    _same_device('apply_beamforming', weights, spec)
+    lead, ch, F, T = BF.spec_shape(spec)
+    if 0 in spec.shape:
+        return _swapped(lead, (T, F, 2), _out_dtype(spec), spec.device, -3, -2).zero_()
+    reason = beamform_reason(ch, weights, spec)
+    if reason is not None:
+        _composite_route('apply_beamforming', reason)
+        return C.apply_beamforming(weights, spec)
+    return H.apply_beamforming(_f32(weights), _f32(spec))
+
+
+def _apply_beamforming_fake(weights, spec):
+    lead, ch, F, T = BF.spec_shape(spec)
+    return _swapped(lead, (T, F, 2), _out_dtype(spec), spec.device, -3, -2)
+
+
+_register('apply_beamforming', '(Tensor beamform_weights, Tensor specgram) -> Tensor', _apply_beamforming_cuda, C.apply_beamforming,
+          _apply_beamforming_fake, 2)
+
+
+def _mvdr_souden_cuda(spec, mask_s, mask_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps, psd_eps):
+    _same_device('mvdr_souden', spec, mask_s, mask_n, ref_vector)
+    lead, ch, F, T = BF.spec_shape(spec)
+    if 0 in spec.shape:
+        return _swapped(lead, (T, F, 2), _out_dtype(spec), spec.device, -3, -2).zero_()
+    reason = beamform_reason(ch, spec, mask_s, mask_n)
+    if reason is not None:
+        _composite_route('mvdr_souden', reason)
+        return C.mvdr_souden(spec, mask_s, mask_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps, psd_eps)
+    return H.mvdr_souden(_f32(spec), _f32(mask_s), _bf_opt(mask_n), None if BF.absent(ref_vector) else ref_vector, ref_channel,
+                         diagonal_loading, diag_eps, eps, psd_eps)[0]
+
+
+def _mvdr_souden_fake(spec, mask_s, mask_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps, psd_eps):
+    lead, ch, F, T = BF.spec_shape(spec)
+    return _swapped(lead, (T, F, 2), _out_dtype(spec), spec.device, -3, -2)
+
+
+_register('mvdr_souden', '(Tensor specgram, Tensor mask_s, Tensor mask_n, Tensor ref_vector, int ref_channel, bool diagonal_loading, '
+          'float diag_eps, float eps, float psd_eps) -> Tensor', _mvdr_souden_cuda, C.mvdr_souden, _mvdr_souden_fake, 4)
 
 
 # ============================================================================= lfilter

@@ -23,6 +23,7 @@ from . import _ops
 from . import _filters
 from . import _kaldi
 from . import _pitch
+from . import _beamform
 from . import _resample
 from . import _specaug
 from . import _augment
@@ -31,7 +32,8 @@ from ._lazy import realize as _realize
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
-           'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency']
+           'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
+           'psd', 'mvdr_weights_souden', 'apply_beamforming']
 
 _call = _ops.call
 
@@ -612,6 +614,54 @@ def detect_pitch_frequency(waveform, sample_rate, frame_time=1e-2, win_length=30
     _pitch.check(x, sample_rate, frame_time, win_length, freq_low, freq_high)
     # (detached: the op is registered without autograd and its result is piecewise constant)
     return _call('detect_pitch_frequency', x.detach(), sample_rate, float(frame_time), win_length, float(freq_low), float(freq_high))
+
+
+def psd(specgram, mask=None, normalize=True, eps=1e-10):
+    """``(…, channel, freq, time)`` complex → ``(…, freq, channel, channel)``: torchaudio's ``functional.psd``, the power spectral
+    density matrix ``Φ[f, c, e] = Σ_t m'[f, t] X[c, f, t] conj(X[e, f, t])`` with ``m' = 1`` without a mask, ``m`` with
+    ``normalize=False`` and ``m / (Σ_t m + eps)`` otherwise.  ``mask`` is real ``(…, freq, time)``; ``ValueError`` when its shape
+    does not match.  ``specgram`` is ``complex64`` (``complex64`` comes back) or the project's trailing-``2`` pairs (pairs come back).
+
+    float32 on a HIP device with 2 to 8 channels is one entry of two launches (csrc/beamform.hip): lanes run along the bins, a lane
+    keeps the Hermitian triangle of one (batch entry, bin) in registers over a piece of the frames, and the pieces are added in a
+    fixed order in float64 — no ``(…, freq, time, channel, channel)`` tensor, no atomics, the same bits every run, Hermitian to the
+    bit.  The frame-major views ``stft`` and ``phase_vocoder`` return are read in place.  float64, other channel counts, expanded or
+    non-positive strides and the backward pass take ``_composite.psd`` (also the CPU path), announced with
+    ``CompositeRouteWarning`` on a device."""
+    x, was_complex = _beamform.pairs(specgram, 'specgram')
+    _beamform.spec_shape(x)
+    if mask is None:
+        mask = _beamform.none(x)
+    else:
+        _beamform.check_mask(mask, x)
+    return _beamform.unpairs(_call('psd', x, mask, bool(normalize), float(eps)), was_complex)
+
+
+def mvdr_weights_souden(psd_s, psd_n, reference_channel, diagonal_loading=True, diag_eps=1e-7, eps=1e-8):
+    """two ``(…, freq, channel, channel)`` complex PSDs → ``(…, freq, channel)`` MVDR weights by Souden's solution (torchaudio's
+    ``functional.mvdr_weights_souden``): with loading ``Φn ← Φn + (diag_eps Re tr Φn + 1e-8) I``; ``N = Φn⁻¹ Φs`` by a solve;
+    ``W = N / (tr N + eps)``; ``w = W[:, r]`` for an int ``r``, ``w = Σ_c W[:, c] u[c]`` for a real tensor ``u`` of shape
+    ``(…, channel)`` or ``(channel,)``.
+
+    float32 on a HIP device with 2 to 8 channels is one launch with a lane per (batch entry, bin): loading, elimination with partial
+    pivoting, the complex trace, the division and the contraction run in float64 on chip from the float32 PSDs, and the result is
+    rounded once.  ``u`` is read on the device."""
+    s, was_complex = _beamform.pairs(psd_s, 'psd_s')
+    n, _ = _beamform.pairs(psd_n, 'psd_n')
+    lead, n_bins, n_ch, u, r = _beamform.check_weights_args(s, n, reference_channel)
+    out = _call('mvdr_weights_souden', s, n, _beamform.none(s) if u is None else u, r, bool(diagonal_loading), float(diag_eps),
+                float(eps))
+    return _beamform.unpairs(out, was_complex)
+
+
+def apply_beamforming(beamform_weights, specgram):
+    """``(…, freq, channel)`` weights and a ``(…, channel, freq, time)`` spectrogram → ``(…, freq, time)``: ``Y[f, t] = Σ_c
+    conj(w[f, c]) X[c, f, t]`` (torchaudio's ``functional.apply_beamforming``).  On a HIP device the result is the frame-major view
+    ``istft`` reads without a copy; each ``X`` element is read once and each output written once."""
+    w, _ = _beamform.pairs(beamform_weights, 'beamform_weights')
+    x, was_complex = _beamform.pairs(specgram, 'specgram')
+    _beamform.check_apply(w, x)
+    return _beamform.unpairs(_call('apply_beamforming', w, x), was_complex)
 
 
 def preemphasis(waveforms, coeff=0.97):

@@ -19,6 +19,7 @@ from . import _hip
 from . import _lazy
 from . import _ops
 from . import _pitch
+from . import _beamform
 from . import _resample
 from . import _specaug
 from . import _augment
@@ -618,6 +619,76 @@ class PitchFrequency(_ModuleNoStateBuffers):
     def __repr__(self):
         return self.__class__.__name__ + '(sample_rate={}, frame_time={}, win_length={}, freq_low={}, freq_high={})'.format(
             self.sample_rate, self.frame_time, self.win_length, self.freq_low, self.freq_high)
+
+
+class PSD(_ModuleNoStateBuffers):
+    """``functional.psd`` as a layer (torchaudio's ``transforms.PSD``): ``forward(specgram, mask=None)`` maps ``(…, channel, freq,
+    time)`` to ``(…, freq, channel, channel)``.  With ``multi_mask`` the mask is ``(…, channel, freq, time)`` and is averaged over
+    the channels first.  No buffers."""
+
+    def __init__(self, multi_mask=False, normalize=True, eps=1e-15):
+        super(PSD, self).__init__()
+        self.multi_mask, self.normalize, self.eps = bool(multi_mask), bool(normalize), float(eps)
+
+    def forward(self, specgram, mask=None):
+        if mask is not None and self.multi_mask:
+            _beamform.check_mask(mask, _beamform.pairs(specgram, 'specgram')[0], multi=True)
+            mask = mask.mean(dim=-3)
+        return F.psd(specgram, mask, self.normalize, self.eps)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(multi_mask={}, normalize={}, eps={})'.format(self.multi_mask, self.normalize, self.eps)
+
+
+class SoudenMVDR(_ModuleNoStateBuffers):
+    """torchaudio's ``transforms.SoudenMVDR``: ``forward(specgram, psd_s, psd_n, reference_channel, diagonal_loading=True,
+    diag_eps=1e-7, eps=1e-8)`` computes the Souden weights from the two PSDs and applies them: ``(…, channel, freq, time)`` →
+    ``(…, freq, time)``.  Two launches on a HIP device.  No buffers."""
+
+    def forward(self, specgram, psd_s, psd_n, reference_channel, diagonal_loading=True, diag_eps=1e-7, eps=1e-8):
+        w = F.mvdr_weights_souden(psd_s, psd_n, reference_channel, diagonal_loading, diag_eps, eps)
+        return F.apply_beamforming(w, specgram)
+
+
+class MVDR(_ModuleNoStateBuffers):
+    """torchaudio's mask-based ``transforms.MVDR`` at ``solution='ref_channel'``: ``forward(specgram, mask_s, mask_n=None)`` maps a
+    ``(…, channel, freq, time)`` spectrogram and real ``(…, freq, time)`` masks (``(…, channel, freq, time)`` with ``multi_mask``,
+    averaged over the channels) to the enhanced ``(…, freq, time)``; ``mask_n=None`` means ``1 - mask_s``.  The PSDs are those of
+    ``PSD(multi_mask, normalize=True, eps=1e-15)``, the weights Souden's at ``ref_channel``.  On a HIP device one entry of three
+    launches: both PSDs from ONE pass over the spectrogram (the complement formed in the kernel), the float64 solve, the weights
+    applied; the result is the frame-major view ``istft`` reads in place.  ``solution='stv_evd'`` / ``'stv_power'`` and
+    ``online=True`` raise ``NotImplementedError``.  No buffers."""
+
+    def __init__(self, ref_channel=0, solution='ref_channel', multi_mask=False, diag_loading=True, diag_eps=1e-7, online=False):
+        super(MVDR, self).__init__()
+        if solution != 'ref_channel':
+            raise NotImplementedError('MVDR: solution=%r is not implemented (only \'ref_channel\', Souden\'s, is)' % (solution,))
+        if online:
+            raise NotImplementedError('MVDR: online=True is not implemented')
+        if isinstance(ref_channel, bool) or not isinstance(ref_channel, int):
+            raise TypeError('MVDR: ref_channel must be an int, got %s' % type(ref_channel).__name__)
+        self.ref_channel, self.solution, self.multi_mask = ref_channel, solution, bool(multi_mask)
+        self.diag_loading, self.diag_eps, self.online = bool(diag_loading), float(diag_eps), False
+
+    def forward(self, specgram, mask_s, mask_n=None):
+        x, was_complex = _beamform.pairs(specgram, 'specgram')
+        lead, n_ch, n_bins, n_frames = _beamform.spec_shape(x)
+        if not -n_ch <= self.ref_channel < n_ch:
+            raise ValueError('MVDR: ref_channel %d is out of range for %d channels' % (self.ref_channel, n_ch))
+        masks = []
+        for name, mask in (('mask_s', mask_s), ('mask_n', mask_n)):
+            if mask is None and name == 'mask_n':
+                masks.append(_beamform.none(x))
+                continue
+            _beamform.check_mask(mask, x, name, multi=self.multi_mask)
+            masks.append(mask.mean(dim=-3) if self.multi_mask else mask)
+        out = _ops.call('mvdr_souden', x, masks[0], masks[1], _beamform.none(x), self.ref_channel % n_ch, self.diag_loading,
+                        self.diag_eps, 1e-8, 1e-15)
+        return _beamform.unpairs(out, was_complex)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(ref_channel={}, solution={!r}, multi_mask={}, diag_loading={}, diag_eps={})'.format(
+            self.ref_channel, self.solution, self.multi_mask, self.diag_loading, self.diag_eps)
 
 
 class Speed(_ModuleNoStateBuffers):
