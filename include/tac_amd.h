@@ -796,6 +796,41 @@ int tac_mvdr_souden_f32(const float* spec, int64_t batch, int32_t channels, int6
                         int32_t diagonal_loading, double diag_eps, double eps, int32_t chunks, float* part, double* msum,
                         float* weights, float* out, int64_t out_b, int64_t out_f, int64_t out_t, void* stream);
 
+/* (26) functional.rtf_evd / rtf_power / mvdr_weights_rtf and the RTFMVDR layer: the relative-transfer-function (steering vector)
+ *      half of torchaudio's beamforming (csrc/beamform.hip).  Systems, PSDs, weights, ref_vector / ref_stride_b / ref_channel,
+ *      diagonal loading and the channel counts (2 .. 8) are those of (25); an RTF is float32 [batch * bins][channels][2].  Every
+ *      entry below is ONE launch: float32 in, float64 on chip, one rounding per output.  A system's result depends on that system
+ *      alone (the same bits whatever else is in the batch, and from run to run); non-finite input ends in NaNs for its system only.
+ *      tac_rtf_power_f32 and tac_mvdr_weights_rtf_f32 take 16 systems a workgroup with a lane per system, as the Souden weights do.
+ *
+ *      tac_rtf_evd_f32: the eigenvector of the largest eigenvalue of the Hermitian psd_s (its lower triangle is read, the imaginary
+ *      diagonal ignored), by Jacobi rotations in round-robin order, a group of 2, 4 or 8 lanes per system with a row of the matrix
+ *      and of the eigenvectors per lane — at most 16 sweeps, left once the off-diagonal Frobenius norm is below 1e-16 of the
+ *      diagonal's — at unit 2-norm, with the phase that makes the component of largest modulus (lowest index on a tie) real and
+ *      positive (its imaginary part is +0).  Needs no spectral gap: psd_s = 0 or I gives the first unit vector.
+ *
+ *      tac_rtf_power_f32: psd_n loaded where diagonal_loading; phi = psd_n^-1 psd_s by elimination with partial pivoting;
+ *      r = phi[:, ref_channel] or phi u; n_iter >= 2: n_iter - 2 times r <- phi r, then r <- psd_s r; n_iter == 1: r <- psd_n r with
+ *      the loaded psd_n.  Not normalised.  n_iter < 1: TAC_E_INVALID; above tac_rtf_power_max_iter() (64): TAC_E_UNSUPPORTED.
+ *
+ *      tac_mvdr_weights_rtf_f32: a = psd_n^-1 rtf with the loaded psd_n; w = a / (Re rtf^H a + eps); then w *= conj(rtf[ref_channel]),
+ *      or w *= sum_c conj(rtf[c]) u[c] where ref_vector is not NULL; ref_channel < 0 without a vector: no scaling.
+ *
+ *      tac_rtf_mvdr_f32: the launch of tac_mvdr_weights_rtf_f32, then the apply launch of (25) on spec: two launches on the stream,
+ *      the bits of the two entries called one after the other.  `weights` is an output too. */
+int32_t tac_rtf_power_max_iter(void);
+int tac_rtf_evd_f32(const float* psd_s, int64_t batch, int64_t bins, int32_t channels, float* rtf, void* stream);
+int tac_rtf_power_f32(const float* psd_s, const float* psd_n, int64_t batch, int64_t bins, int32_t channels, const float* ref_vector,
+                      int64_t ref_stride_b, int32_t ref_channel, int32_t n_iter, int32_t diagonal_loading, double diag_eps, float* rtf,
+                      void* stream);
+int tac_mvdr_weights_rtf_f32(const float* rtf, const float* psd_n, int64_t batch, int64_t bins, int32_t channels,
+                             const float* ref_vector, int64_t ref_stride_b, int32_t ref_channel, int32_t diagonal_loading,
+                             double diag_eps, double eps, float* weights, void* stream);
+int tac_rtf_mvdr_f32(const float* spec, int64_t batch, int32_t channels, int64_t bins, int64_t frames, int64_t stride_b,
+                     int64_t stride_c, int64_t stride_f, int64_t stride_t, const float* rtf, const float* psd_n,
+                     const float* ref_vector, int64_t ref_stride_b, int32_t ref_channel, int32_t diagonal_loading, double diag_eps,
+                     double eps, float* weights, float* out, int64_t out_b, int64_t out_f, int64_t out_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

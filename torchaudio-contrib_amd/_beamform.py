@@ -1,4 +1,5 @@
-"""Argument checks and shapes of ``psd`` / ``mvdr_weights_souden`` / ``apply_beamforming`` (host arithmetic only; shared by
+"""Argument checks and shapes of ``psd`` / ``mvdr_weights_souden`` / ``apply_beamforming`` and of ``rtf_evd`` / ``rtf_power`` /
+``mvdr_weights_rtf``, whose RTFs are ``(…, F, C, 2)`` like the weights (host arithmetic only; shared by
 ``functional``, ``layers``, ``_ops``, ``_composite`` and ``_hip``).
 
 Complex values travel as the project's trailing-``2`` pairs below ``functional``: a spectrogram is ``(…, C, F, T, 2)``, a PSD
@@ -76,6 +77,27 @@ def check_weights_args(psd_s, psd_n, reference_channel):
     if not -C <= reference_channel < C:
         raise ValueError('reference_channel %d is out of range for %d channels' % (reference_channel, C))
     return lead, F, C, None, reference_channel % C
+
+
+def check_n_iter(n_iter):
+    """``ValueError`` for ``n_iter <= 0``, ``TypeError`` for a non-int"""
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int):
+        raise TypeError('n_iter must be an int, got %s' % type(n_iter).__name__)
+    if n_iter <= 0:
+        raise ValueError('n_iter must be positive, got %d' % n_iter)
+    return n_iter
+
+
+def check_rtf_weights_args(rtf, psd_n, reference_channel):
+    """``(lead, F, C, ref_vector or None, ref_channel)`` for an RTF ``(…, F, C, 2)`` and a PSD ``(…, F, C, C, 2)``, both in pairs;
+    ``reference_channel`` may be None (``ref_channel`` is then -1: no scaling), else as in ``check_weights_args``"""
+    lead, F, C = psd_shape(psd_n, 'psd_n')
+    if rtf.dim() < 3 or tuple(rtf.shape) != lead + (F, C, 2):
+        raise ValueError('rtf must be %s complex for a psd_n of %s, got pairs of shape %s'
+                         % (lead + (F, C), lead + (F, C, C), tuple(rtf.shape)))
+    if reference_channel is None:
+        return lead, F, C, None, -1
+    return check_weights_args(psd_n, psd_n, reference_channel)
 
 
 def check_apply(weights, spec):

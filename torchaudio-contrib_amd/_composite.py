@@ -268,6 +268,71 @@ def mvdr_souden(specgram, mask_s, mask_n, ref_vector, ref_channel, diagonal_load
     return apply_beamforming(w, specgram)
 
 
+def _loaded(n, diag_eps):
+    trace = n.diagonal(dim1=-1, dim2=-2).sum(-1).real[..., None, None]
+    return n + (trace * diag_eps + 1e-8) * torch.eye(n.shape[-1], dtype=n.dtype, device=n.device)
+
+
+def lead_phase(v):
+    """the phase convention of ``rtf_evd`` on a complex ``(…, C)`` vector: the component of largest modulus (lowest index on a tie)
+    made real and positive, its imaginary part exactly zero"""
+    mag = v.abs()
+    lead = mag.argmax(dim=-1, keepdim=True)                                   # (the first of equal maxima)
+    h = torch.gather(v, -1, lead)
+    v = v * (h.conj() / torch.gather(mag, -1, lead))
+    fixed = torch.view_as_real(v).clone()
+    fixed[..., 1].scatter_(-1, lead, 0.0)
+    return torch.view_as_complex(fixed)
+
+
+def rtf_evd(psd_s):
+    """torchaudio's ``functional.rtf_evd`` on pairs: ``(…, F, C, C, 2)`` → ``(…, F, C, 2)``, the eigenvector of the largest
+    eigenvalue by ``torch.linalg.eigh`` (unit 2-norm), then ``lead_phase``"""
+    _, v = torch.linalg.eigh(_complex(psd_s))
+    return torch.view_as_real(lead_phase(v[..., -1]))
+
+
+def rtf_power(psd_s, psd_n, ref_vector, ref_channel, n_iter=3, diagonal_loading=True, diag_eps=1e-7):
+    """torchaudio's ``functional.rtf_power`` on pairs: two ``(…, F, C, C, 2)`` → ``(…, F, C, 2)``"""
+    s, n = _complex(psd_s), _complex(psd_n)
+    if diagonal_loading:
+        n = _loaded(n, diag_eps)
+    phi = torch.linalg.solve(n, s)
+    if _beamform.absent(ref_vector):
+        r = phi[..., ref_channel]
+    else:
+        r = torch.einsum('...fec,...c->...fe', phi, ref_vector.to(phi.dtype))
+    r = r.unsqueeze(-1)
+    if n_iter >= 2:
+        for _ in range(n_iter - 2):
+            r = torch.matmul(phi, r)
+        r = torch.matmul(s, r)
+    else:
+        r = torch.matmul(n, r)
+    return torch.view_as_real(r.squeeze(-1).contiguous())
+
+
+def mvdr_weights_rtf(rtf, psd_n, ref_vector, ref_channel, diagonal_loading=True, diag_eps=1e-7, eps=1e-8):
+    """torchaudio's ``functional.mvdr_weights_rtf`` on pairs: ``(…, F, C, 2)`` and ``(…, F, C, C, 2)`` → ``(…, F, C, 2)``.
+    ``ref_vector`` absent and ``ref_channel`` -1: no reference scaling."""
+    d, n = _complex(rtf), _complex(psd_n)
+    if diagonal_loading:
+        n = _loaded(n, diag_eps)
+    numerator = torch.linalg.solve(n, d.unsqueeze(-1)).squeeze(-1)
+    denominator = torch.einsum('...d,...d->...', d.conj(), numerator)
+    w = numerator / (denominator.real.unsqueeze(-1) + eps)
+    if not _beamform.absent(ref_vector):
+        w = w * torch.einsum('...c,...c->...', d.conj(), ref_vector.to(d.dtype)[..., None, :]).unsqueeze(-1)
+    elif ref_channel >= 0:
+        w = w * d[..., ref_channel].conj().unsqueeze(-1)
+    return torch.view_as_real(w.contiguous())
+
+
+def rtf_mvdr(specgram, rtf, psd_n, ref_vector, ref_channel, diagonal_loading=True, diag_eps=1e-7, eps=1e-8):
+    """the ``RTFMVDR`` layer: the RTF weights, applied"""
+    return apply_beamforming(mvdr_weights_rtf(rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps), specgram)
+
+
 def fftconvolve(x, y, n_fft=0):
     """torchaudio's ``functional.fftconvolve`` in ``'full'`` mode: the one-shot form, ``irfft(rfft(x, n) * rfft(y, n), n)`` at
     ``n = L + M - 1`` along the last dimension, the leading dimensions broadcast.  ``n_fft`` (the partition size of the gfx950

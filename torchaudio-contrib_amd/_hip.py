@@ -1283,6 +1283,80 @@ def mvdr_souden(spec, mask_s, mask_n, ref_vector, ref_channel, diagonal_loading,
     return out, w.reshape(lead + (F, C, 2))
 
 
+# ----------------------------------------------------------------------------- rtf_evd / rtf_power / mvdr_weights_rtf (csrc/beamform.hip)
+def rtf_power_max_iter():
+    """the most ``n_iter`` ``tac_rtf_power_f32`` takes"""
+    return _native.lib().tac_rtf_power_max_iter()
+
+
+def rtf_evd(psd_s):
+    """``(…, F, C, C, 2)`` float32 → ``(…, F, C, 2)`` through ``tac_rtf_evd_f32``: one launch, cyclic Jacobi in float64 on chip; unit
+    norm, the component of largest modulus real and positive"""
+    lead, F, C = tuple(psd_s.shape[:-4]), psd_s.shape[-4], psd_s.shape[-2]
+    s = psd_s.reshape(-1, F, C, C, 2).contiguous()
+    B = s.shape[0]
+    out = _empty((B * F, C, 2), device=psd_s.device)
+    with _native.on_device(psd_s.device):
+        rc = _native.lib().tac_rtf_evd_f32(_native.ptr(s), B, F, C, _native.ptr(out), _native.stream_ptr(psd_s.device))
+    _native.check(rc, 'tac_rtf_evd_f32')
+    _count('tac_rtf_evd_f32', out)
+    return out.reshape(lead + (F, C, 2))
+
+
+def rtf_power(psd_s, psd_n, ref_vector, ref_channel, n_iter, diagonal_loading, diag_eps):
+    """two ``(…, F, C, C, 2)`` float32 → ``(…, F, C, 2)`` through ``tac_rtf_power_f32``: one launch, the solve and every product in
+    float64 on chip"""
+    lead, F, C = tuple(psd_s.shape[:-4]), psd_s.shape[-4], psd_s.shape[-2]
+    s, n = psd_s.reshape(-1, F, C, C, 2).contiguous(), psd_n.reshape(-1, F, C, C, 2).contiguous()
+    B = s.shape[0]
+    ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
+    out = _empty((B * F, C, 2), device=psd_s.device)
+    with _native.on_device(psd_s.device):
+        rc = _native.lib().tac_rtf_power_f32(_native.ptr(s), _native.ptr(n), B, F, C, ref_ptr, ref_stride, ref_channel, n_iter,
+                                             1 if diagonal_loading else 0, float(diag_eps), _native.ptr(out),
+                                             _native.stream_ptr(psd_s.device))
+    _native.check(rc, 'tac_rtf_power_f32')
+    _count('tac_rtf_power_f32', out)
+    return out.reshape(lead + (F, C, 2))
+
+
+def mvdr_weights_rtf(rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    """``(…, F, C, 2)`` and ``(…, F, C, C, 2)`` float32 → ``(…, F, C, 2)`` through ``tac_mvdr_weights_rtf_f32``: one launch.
+    ``ref_channel`` -1 without a vector: no reference scaling."""
+    lead, F, C = tuple(psd_n.shape[:-4]), psd_n.shape[-4], psd_n.shape[-2]
+    d, n = rtf.reshape(-1, F, C, 2).contiguous(), psd_n.reshape(-1, F, C, C, 2).contiguous()
+    B = n.shape[0]
+    ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
+    out = _empty((B * F, C, 2), device=psd_n.device)
+    with _native.on_device(psd_n.device):
+        rc = _native.lib().tac_mvdr_weights_rtf_f32(_native.ptr(d), _native.ptr(n), B, F, C, ref_ptr, ref_stride, ref_channel,
+                                                    1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(out),
+                                                    _native.stream_ptr(psd_n.device))
+    _native.check(rc, 'tac_mvdr_weights_rtf_f32')
+    _count('tac_mvdr_weights_rtf_f32', out)
+    return out.reshape(lead + (F, C, 2))
+
+
+def rtf_mvdr(spec, rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    """``RTFMVDR`` through ``tac_rtf_mvdr_f32``: ONE entry of two launches on the current stream — the RTF weights, the weights
+    applied.  Returns ``(frame-major view (…, F, T, 2), weights (…, F, C, 2))``."""
+    lead, (C, F, T) = tuple(spec.shape[:-4]), spec.shape[-4:-1]
+    x = _bf_spec(spec)
+    B = x.shape[0]
+    d, n = rtf.reshape(B, F, C, 2).contiguous(), psd_n.reshape(B, F, C, C, 2).contiguous()
+    ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
+    w = _empty((B * F, C, 2), device=spec.device)
+    store, out = _bf_out(lead, B, F, T, spec.device)
+    with _native.on_device(spec.device):
+        rc = _native.lib().tac_rtf_mvdr_f32(_native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
+                                            _native.ptr(d), _native.ptr(n), ref_ptr, ref_stride, ref_channel,
+                                            1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(w),
+                                            _native.ptr(store), T * F * 2, 2, F * 2, _native.stream_ptr(spec.device))
+    _native.check(rc, 'tac_rtf_mvdr_f32')
+    _count('tac_rtf_mvdr_f32', w, store)
+    return out, w.reshape(lead + (F, C, 2))
+
+
 # ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
 #: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
 FFTCONV_SIZES = (2048, 4096, 8192)

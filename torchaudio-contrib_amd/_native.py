@@ -49,6 +49,7 @@ EXPORTS = (
     'tac_loudness_tile', 'tac_loudness_work_bytes', 'tac_loudness_f32',
     'tac_pitch_max_win', 'tac_pitch_plan', 'tac_pitch_lags_f32', 'tac_pitch_smooth_i32', 'tac_pitch_frequency_f32',
     'tac_psd_plan', 'tac_beamform_grid', 'tac_psd_f32', 'tac_mvdr_weights_souden_f32', 'tac_apply_beamforming_f32', 'tac_mvdr_souden_f32',
+    'tac_rtf_power_max_iter', 'tac_rtf_evd_f32', 'tac_rtf_power_f32', 'tac_mvdr_weights_rtf_f32', 'tac_rtf_mvdr_f32',
 )
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
@@ -256,6 +257,12 @@ def lib():
         h.tac_apply_beamforming_f32.argtypes = [_P, _P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P]
         h.tac_mvdr_souden_f32.argtypes = (_spec + _mask + _mask + [_D, _P, _I64, _I32, _I32, _D, _D, _I32, _P, _P, _P, _P,
                                                                     _I64, _I64, _I64, _P])
+        h.tac_rtf_power_max_iter.restype = _I32
+        h.tac_rtf_power_max_iter.argtypes = []
+        h.tac_rtf_evd_f32.argtypes = [_P, _I64, _I64, _I32, _P, _P]
+        h.tac_rtf_power_f32.argtypes = [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32, _D, _P, _P]
+        h.tac_mvdr_weights_rtf_f32.argtypes = [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _D, _D, _P, _P]
+        h.tac_rtf_mvdr_f32.argtypes = _spec + [_P, _P, _P, _I64, _I32, _I32, _D, _D, _P, _P, _I64, _I64, _I64, _P]
         for name in EXPORTS:
             fn = getattr(h, name)
             if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code

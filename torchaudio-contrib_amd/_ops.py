@@ -20,6 +20,7 @@ see them by name.
     tac_amd::loudness           ITU-R BS.1770-4 gated loudness of (…, channels, L): K-weighting, blocks and gates (csrc/loudness.hip)
     tac_amd::detect_pitch_frequency   NCCF pitch of (…, L): correlations, peak choice and median in two launches (csrc/pitch.hip)
     tac_amd::psd, mvdr_weights_souden, apply_beamforming, mvdr_souden   mask-based MVDR beamforming over (…, C, F, T) (csrc/beamform.hip)
+    tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -1271,6 +1272,97 @@ def _mvdr_souden_fake(spec, mask_s, mask_n, ref_vector, ref_channel, diagonal_lo
 
 _register('mvdr_souden', '(Tensor specgram, Tensor mask_s, Tensor mask_n, Tensor ref_vector, int ref_channel, bool diagonal_loading, '
           'float diag_eps, float eps, float psd_eps) -> Tensor', _mvdr_souden_cuda, C.mvdr_souden, _mvdr_souden_fake, 4)
+
+
+# ============================================================================= rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr
+def _ref_reason(reason, ref_vector):
+    if reason is None and not BF.absent(ref_vector) and any(st < 0 for st in ref_vector.stride()):
+        reason = 'expanded or non-positive strides'
+    return reason
+
+
+def _rtf_evd_cuda(psd_s):
+    lead, F, ch = BF.psd_shape(psd_s)
+    if 0 in psd_s.shape:
+        return psd_s.new_zeros(_weights_shape(psd_s), dtype=_out_dtype(psd_s))
+    reason = beamform_reason(ch, psd_s)
+    if reason is not None:
+        _composite_route('rtf_evd', reason)
+        return C.rtf_evd(psd_s)
+    return H.rtf_evd(_f32(psd_s))
+
+
+def _rtf_evd_fake(psd_s):
+    return psd_s.new_empty(_weights_shape(psd_s), dtype=_out_dtype(psd_s))
+
+
+_register('rtf_evd', '(Tensor psd_s) -> Tensor', _rtf_evd_cuda, C.rtf_evd, _rtf_evd_fake, 1)
+
+
+def _rtf_power_cuda(psd_s, psd_n, ref_vector, ref_channel, n_iter, diagonal_loading, diag_eps):
+    _same_device('rtf_power', psd_s, psd_n, ref_vector)
+    lead, F, ch = BF.psd_shape(psd_s)
+    if 0 in psd_s.shape:
+        return psd_s.new_zeros(_weights_shape(psd_s), dtype=_out_dtype(psd_s))
+    reason = _ref_reason(beamform_reason(ch, psd_s, psd_n), ref_vector)
+    if reason is None and n_iter > H.rtf_power_max_iter():
+        reason = 'n_iter %d (the kernel takes up to %d)' % (n_iter, H.rtf_power_max_iter())
+    if reason is not None:
+        _composite_route('rtf_power', reason)
+        return C.rtf_power(psd_s, psd_n, ref_vector, ref_channel, n_iter, diagonal_loading, diag_eps)
+    return H.rtf_power(_f32(psd_s), _f32(psd_n), None if BF.absent(ref_vector) else ref_vector, ref_channel, n_iter,
+                       diagonal_loading, diag_eps)
+
+
+def _rtf_power_fake(psd_s, psd_n, ref_vector, ref_channel, n_iter, diagonal_loading, diag_eps):
+    return psd_s.new_empty(_weights_shape(psd_s), dtype=_out_dtype(psd_s))
+
+
+_register('rtf_power', '(Tensor psd_s, Tensor psd_n, Tensor ref_vector, int ref_channel, int n_iter, bool diagonal_loading, '
+          'float diag_eps) -> Tensor', _rtf_power_cuda, C.rtf_power, _rtf_power_fake, 3)
+
+
+def _weights_rtf_cuda(rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    _same_device('mvdr_weights_rtf', rtf, psd_n, ref_vector)
+    lead, F, ch = BF.psd_shape(psd_n)
+    if 0 in psd_n.shape:
+        return rtf.new_zeros(tuple(rtf.shape), dtype=_out_dtype(rtf))
+    reason = _ref_reason(beamform_reason(ch, rtf, psd_n), ref_vector)
+    if reason is not None:
+        _composite_route('mvdr_weights_rtf', reason)
+        return C.mvdr_weights_rtf(rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps)
+    return H.mvdr_weights_rtf(_f32(rtf), _f32(psd_n), None if BF.absent(ref_vector) else ref_vector, ref_channel, diagonal_loading,
+                              diag_eps, eps)
+
+
+def _weights_rtf_fake(rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    return rtf.new_empty(tuple(rtf.shape), dtype=_out_dtype(rtf))
+
+
+_register('mvdr_weights_rtf', '(Tensor rtf, Tensor psd_n, Tensor ref_vector, int ref_channel, bool diagonal_loading, float diag_eps, '
+          'float eps) -> Tensor', _weights_rtf_cuda, C.mvdr_weights_rtf, _weights_rtf_fake, 3)
+
+
+def _rtf_mvdr_cuda(spec, rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    _same_device('rtf_mvdr', spec, rtf, psd_n, ref_vector)
+    lead, ch, F, T = BF.spec_shape(spec)
+    if 0 in spec.shape:
+        return _swapped(lead, (T, F, 2), _out_dtype(spec), spec.device, -3, -2).zero_()
+    reason = _ref_reason(beamform_reason(ch, spec, rtf, psd_n), ref_vector)
+    if reason is not None:
+        _composite_route('rtf_mvdr', reason)
+        return C.rtf_mvdr(spec, rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps)
+    return H.rtf_mvdr(_f32(spec), _f32(rtf), _f32(psd_n), None if BF.absent(ref_vector) else ref_vector, ref_channel,
+                      diagonal_loading, diag_eps, eps)[0]
+
+
+def _rtf_mvdr_fake(spec, rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_eps, eps):
+    lead, ch, F, T = BF.spec_shape(spec)
+    return _swapped(lead, (T, F, 2), _out_dtype(spec), spec.device, -3, -2)
+
+
+_register('rtf_mvdr', '(Tensor specgram, Tensor rtf, Tensor psd_n, Tensor ref_vector, int ref_channel, bool diagonal_loading, '
+          'float diag_eps, float eps) -> Tensor', _rtf_mvdr_cuda, C.rtf_mvdr, _rtf_mvdr_fake, 4)
 
 
 # ============================================================================= lfilter

@@ -3,7 +3,7 @@
 // A spectrogram is complex pairs X[b][c][f][t][2] with C = 2 .. 8 channels, read where it lies (four strides in floats).  A SYSTEM is
 // one (batch entry, bin): g = b F + f, G = B F of them.  Lanes run along g, so with the frame-major layout the STFT kernels write
 // (bins of a frame contiguous) a wave's 64 loads of one channel and frame are 512 contiguous bytes, and a lane reduces over time in
-// its own registers: no cross-lane step anywhere in this file.
+// its own registers: no cross-lane step in any of the Souden launches.
 //
 // Launch 1, psd_partial_kernel<C, NM>.  A wave takes 64 systems over one piece of 64 frames — the cut depends on nothing but the
 // frame count, so a system's sums do not depend on what else is in the batch — and keeps, per PSD, the Hermitian triangle of
@@ -23,7 +23,15 @@
 //
 // apply_kernel<C>.  A wave takes 64 systems over 32 frames, the C conjugated weights in registers: out = sum_c conj(w[c]) X[c] as one
 // fused multiply-add chain per component; every X element is read once, every output written once, as an 8-byte pair.
+//
+// rtf_evd_kernel<C>, rtf_power_kernel<C>, mvdr_weights_rtf_kernel<C>: the steering-vector (RTF) half, one launch each, float32 in,
+// float64 on chip, one rounding per output, a system's result a function of that system alone.  rtf_power and mvdr_weights_rtf
+// share the layout and the elimination of mvdr_weights_kernel; rtf_evd is Jacobi with a group of lanes per system, rows in
+// registers and shuffles inside the group — the only cross-lane steps of this file.  tac_rtf_mvdr_f32 is mvdr_weights_rtf_kernel
+// followed by apply_kernel.
 #include <math.h>
+
+#include <utility>
 
 #include "host_common.hpp"
 
@@ -425,6 +433,395 @@ apply_kernel(const ApplyArgs A) {
     }
 }
 
+// ----------------------------------------------------------------------------- rtf_evd / rtf_power / mvdr_weights_rtf
+// rtf_power and mvdr_weights_rtf keep the layout of mvdr_weights_kernel: BF_WS systems a workgroup, an LDS matrix of C rows and W
+// complex float64 columns per system, element-major and system-minor, filled by all 256 lanes, then a lane per system.  rtf_evd, two
+// orders of magnitude more arithmetic, gives a system a group of lanes instead (below).
+#define RT_M(i, j, r, s) L[((((i) * W) + (j)) * 2 + (r)) * BF_WS + (s)]
+
+constexpr int BF_EVD_SWEEPS = 16;      // most Jacobi sweeps; the convergence test only leaves earlier
+constexpr int BF_MAX_ITER = 64;        // most n_iter of rtf_power
+
+// columns [col0, col0 + C) of the systems [g0, g0 + BF_WS) from a float32 [G][C][C][2] tensor; called by the whole workgroup
+template <int C, int W>
+__device__ __forceinline__ void rt_fill(double* L, const float* src, int col0, long long g0, long long G, int tid) {
+    constexpr int CC = C * C;
+    for (int idx = tid; idx < BF_WS * CC; idx += BF_THREADS) {
+        const int s = idx / CC, ij = idx - s * CC, i = ij / C, j = ij - i * C;
+        if (g0 + s < G) {
+            const float2 v = *reinterpret_cast<const float2*>(src + ((g0 + s) * CC + ij) * 2);
+            RT_M(i, col0 + j, 0, s) = (double)v.x, RT_M(i, col0 + j, 1, s) = (double)v.y;
+        }
+    }
+}
+
+// columns [0, C) += (diag_eps Re tr + 1e-8) I; returns what was added
+template <int C, int W>
+__device__ __forceinline__ double rt_load(double* L, int s, double diag_eps) {
+    double tr = 0.0;
+    for (int i = 0; i < C; ++i) tr += RT_M(i, i, 0, s);
+    const double load = diag_eps * tr + 1e-8;
+    for (int i = 0; i < C; ++i) RT_M(i, i, 0, s) += load;
+    return load;
+}
+
+// columns [C, C + NR) become M^-1 times themselves, M the columns [0, C): elimination with partial pivoting (pivot: largest |re| +
+// |im|) and back substitution, the steps of mvdr_weights_kernel; columns from C + NR on are left alone
+template <int C, int W, int NR>
+__device__ __forceinline__ void rt_solve(double* L, int s) {
+    constexpr int EW = C + NR;
+#pragma unroll 1
+    for (int k = 0; k < C; ++k) {
+        int piv = k;
+        double best = fabs(RT_M(k, k, 0, s)) + fabs(RT_M(k, k, 1, s));
+        for (int i = k + 1; i < C; ++i) {
+            const double v = fabs(RT_M(i, k, 0, s)) + fabs(RT_M(i, k, 1, s));
+            if (v > best) best = v, piv = i;
+        }
+        if (piv != k)
+            for (int j = k; j < EW; ++j) {
+                const double r0 = RT_M(k, j, 0, s), i0 = RT_M(k, j, 1, s);
+                RT_M(k, j, 0, s) = RT_M(piv, j, 0, s), RT_M(k, j, 1, s) = RT_M(piv, j, 1, s);
+                RT_M(piv, j, 0, s) = r0, RT_M(piv, j, 1, s) = i0;
+            }
+        const double pr = RT_M(k, k, 0, s), pi = RT_M(k, k, 1, s), den = pr * pr + pi * pi;
+        for (int i = k + 1; i < C; ++i) {
+            const double ar = RT_M(i, k, 0, s), ai = RT_M(i, k, 1, s);
+            const double fr = (ar * pr + ai * pi) / den, fi = (ai * pr - ar * pi) / den;
+            for (int j = k + 1; j < EW; ++j) {
+                const double r = RT_M(k, j, 0, s), q = RT_M(k, j, 1, s);
+                RT_M(i, j, 0, s) -= fr * r - fi * q;
+                RT_M(i, j, 1, s) -= fr * q + fi * r;
+            }
+        }
+    }
+#pragma unroll 1
+    for (int c = C; c < EW; ++c)
+        for (int i = C - 1; i >= 0; --i) {
+            double sr = RT_M(i, c, 0, s), si = RT_M(i, c, 1, s);
+            for (int j = i + 1; j < C; ++j) {
+                const double ar = RT_M(i, j, 0, s), ai = RT_M(i, j, 1, s), xr = RT_M(j, c, 0, s), xi = RT_M(j, c, 1, s);
+                sr -= ar * xr - ai * xi;
+                si -= ar * xi + ai * xr;
+            }
+            const double pr = RT_M(i, i, 0, s), pi = RT_M(i, i, 1, s), den = pr * pr + pi * pi;
+            RT_M(i, c, 0, s) = (sr * pr + si * pi) / den;
+            RT_M(i, c, 1, s) = (si * pr - sr * pi) / den;
+        }
+}
+
+// rtf_evd: Jacobi on the Hermitian matrix (its lower triangle is the data, as LAPACK's 'L') in float64, a GROUP of lanes per system:
+// lane i of a group of GL (2, 4 or 8) keeps row i of A and of V in registers, no LDS.  A rotation (p, q) with A[p][q] = b w, |w| = 1,
+// is J = D R, D = diag(.., conj(w) at q, ..), R the real rotation that annihilates b; A <- J^H A J, V <- V J.  The N - 1 steps of a
+// round-robin schedule over N = C rounded up to even hold N / 2 disjoint rotations each (pairs with the dummy index of an odd C are
+// skipped), all applied at once: the lane that owns row p forms the rotation from its own A[p][q] and diagonal and the partner's
+// diagonal, every lane gets the parameters of every pair by shuffles and rotates columns p, q of its rows of A and V, then the
+// lanes of a pair exchange their rows of A and mix them, and the 2 x 2 block is set in closed form.  The diagonal is kept in `diag`
+// (the slot A[i][i] of the row is never read).  Sums over a group are xor butterflies: an addition commutes, so every lane of the
+// group holds the same bits and the group leaves the sweeps together.  No spectral gap is needed: an exactly diagonal A (zero,
+// identity) leaves at once with V = I.  A NaN fails every comparison, so the sweeps end at once, and the 0 * input sum added to every
+// output turns the whole system, and only it, into NaNs.  Every access to a row is a value select on a compile-time index, so the
+// rows stay in registers.  (The form with a lane per system and [A | V] in the LDS, cyclic by rows, gave the same bounds and took
+// 4.4 x as long at (16, 8, 257, 1000) and 4.0 x at (8, 8, 2049, 2813): DESIGN 3.22.)
+constexpr int rr_n(int C) { return (C + 1) & ~1; }
+constexpr int rr_lanes(int C) { return C <= 2 ? 2 : (C <= 4 ? 4 : 8); }
+constexpr int rr_p(int n, int r, int m) { return m == 0 ? n - 1 : (r + m) % (n - 1); }
+constexpr int rr_q(int n, int r, int m) { return m == 0 ? r : (r - m + n - 1) % (n - 1); }
+
+template <int N>
+struct EvdRow {
+    double ar[N], ai[N], vr[N], vi[N], diag;
+};
+template <int H>
+struct EvdRot {
+    double c[H], sn[H], wr[H], wi[H];
+};
+
+template <int GL>
+__device__ __forceinline__ double group_sum(double x) {
+#pragma unroll
+    for (int d = 1; d < GL; d <<= 1) x += __shfl_xor(x, d, GL);
+    return x;
+}
+
+// the largest value over the group and the lowest lane index that holds it
+template <int GL>
+__device__ __forceinline__ void group_top(double& x, int& at) {
+#pragma unroll
+    for (int d = 1; d < GL; d <<= 1) {
+        const double y = __shfl_xor(x, d, GL);
+        const int o = __shfl_xor(at, d, GL);
+        if (y > x || (y == x && o < at)) x = y, at = o;
+    }
+}
+
+template <int C, int N, int P, int Q>
+__device__ __forceinline__ void evd_role(const EvdRow<N>& S, int i, int& partner, bool& is_p, double& pr, double& pi) {
+    if constexpr (P < C && Q < C) {
+        const double qr = S.ar[Q], qi = S.ai[Q];                     // (read by every lane, then selected: no pointer is selected)
+        const bool p = i == P;
+        partner = p ? Q : (i == Q ? P : partner);
+        is_p = is_p || p, pr = p ? qr : pr, pi = p ? qi : pi;
+    }
+}
+
+template <int C, int N, int GL, int M, int P, int Q>
+__device__ __forceinline__ void evd_columns(EvdRow<N>& S, EvdRot<N / 2>& R, int i, double c, double sn, double wr, double wi,
+                                            double& my_c, double& my_sn, double& my_wr, double& my_wi) {
+    if constexpr (P < C && Q < C) {
+        R.c[M] = __shfl(c, P, GL), R.sn[M] = __shfl(sn, P, GL), R.wr[M] = __shfl(wr, P, GL), R.wi[M] = __shfl(wi, P, GL);
+        const bool mine = i == P || i == Q;
+        my_c = mine ? R.c[M] : my_c, my_sn = mine ? R.sn[M] : my_sn, my_wr = mine ? R.wr[M] : my_wr, my_wi = mine ? R.wi[M] : my_wi;
+        const double ar = R.sn[M] * R.wr[M], ai = -R.sn[M] * R.wi[M], br = R.c[M] * R.wr[M], bi = -R.c[M] * R.wi[M];
+        {
+            const double xr = S.ar[P], xi = S.ai[P], yr = S.ar[Q], yi = S.ai[Q];
+            S.ar[P] = R.c[M] * xr - (ar * yr - ai * yi), S.ai[P] = R.c[M] * xi - (ar * yi + ai * yr);
+            S.ar[Q] = R.sn[M] * xr + (br * yr - bi * yi), S.ai[Q] = R.sn[M] * xi + (br * yi + bi * yr);
+        }
+        {
+            const double xr = S.vr[P], xi = S.vi[P], yr = S.vr[Q], yi = S.vi[Q];
+            S.vr[P] = R.c[M] * xr - (ar * yr - ai * yi), S.vi[P] = R.c[M] * xi - (ar * yi + ai * yr);
+            S.vr[Q] = R.sn[M] * xr + (br * yr - bi * yi), S.vi[Q] = R.sn[M] * xi + (br * yi + bi * yr);
+        }
+    }
+}
+
+template <int C, int N, int P, int Q>
+__device__ __forceinline__ void evd_clear(EvdRow<N>& S, int i) {
+    if constexpr (P < C && Q < C) {
+        S.ar[Q] = i == P ? 0.0 : S.ar[Q], S.ai[Q] = i == P ? 0.0 : S.ai[Q];
+        S.ar[P] = i == Q ? 0.0 : S.ar[P], S.ai[P] = i == Q ? 0.0 : S.ai[P];
+    }
+}
+
+template <int C, int N, int GL, int R, int... M>
+__device__ __forceinline__ void evd_step(EvdRow<N>& S, int i, std::integer_sequence<int, M...>) {
+    int partner = i;
+    bool is_p = false;
+    double pr = 0.0, pi = 0.0;
+    (evd_role<C, N, rr_p(N, R, M), rr_q(N, R, M)>(S, i, partner, is_p, pr, pi), ...);
+    const double other = __shfl(S.diag, partner, GL);
+    const double b = sqrt(pr * pr + pi * pi);
+    const bool rot = is_p && b > 0.0;
+    const double theta = (other - S.diag) / (2.0 * b);
+    const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+    const double c1 = 1.0 / sqrt(t * t + 1.0);
+    const double c = rot ? c1 : 1.0, sn = rot ? t * c1 : 0.0, wr = rot ? pr / b : 1.0, wi = rot ? pi / b : 0.0, tb = rot ? t * b : 0.0;
+    EvdRot<N / 2> rots;
+    double my_c = 1.0, my_sn = 0.0, my_wr = 1.0, my_wi = 0.0;
+    (evd_columns<C, N, GL, M, rr_p(N, R, M), rr_q(N, R, M)>(S, rots, i, c, sn, wr, wi, my_c, my_sn, my_wr, my_wi), ...);
+    // rows: p' = c p - sn w q, q' = sn p + c w q; a lane without a pair keeps its row (1 * mine + 0 * mine)
+    const bool paired = partner != i;
+    const double alr = !paired ? 1.0 : (is_p ? my_c : my_c * my_wr), ali = (!paired || is_p) ? 0.0 : my_c * my_wi;
+    const double ber = !paired ? 0.0 : (is_p ? -my_sn * my_wr : my_sn), bei = (paired && is_p) ? -my_sn * my_wi : 0.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const double orr = __shfl(S.ar[j], partner, GL), oi = __shfl(S.ai[j], partner, GL);
+        const double mr = S.ar[j], mi = S.ai[j];
+        S.ar[j] = (alr * mr - ali * mi) + (ber * orr - bei * oi);
+        S.ai[j] = (alr * mi + ali * mr) + (ber * oi + bei * orr);
+    }
+    const double tb_other = __shfl(tb, partner, GL);
+    S.diag = is_p ? S.diag - tb : S.diag + (paired ? tb_other : 0.0);
+    (evd_clear<C, N, rr_p(N, R, M), rr_q(N, R, M)>(S, i), ...);
+}
+
+template <int C, int N, int GL, int... R>
+__device__ __forceinline__ void evd_sweep(EvdRow<N>& S, int i, std::integer_sequence<int, R...>) {
+    (evd_step<C, N, GL, R>(S, i, std::make_integer_sequence<int, N / 2>{}), ...);
+}
+
+template <int C>
+__global__ void __launch_bounds__(BF_THREADS)
+rtf_evd_kernel(const float* psd, long long G, float* out) {
+    constexpr int N = rr_n(C), GL = rr_lanes(C), SPW = BF_THREADS / GL;
+    const int i = threadIdx.x % GL, sub = threadIdx.x / GL;
+    const long long tiles = (G + SPW - 1) / SPW;
+    for (long long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
+        const long long g = tl * SPW + sub;
+        if (g >= G) continue;                                       // (a whole group at once)
+        EvdRow<N> S;
+        double poison = 0.0;
+        S.diag = 0.0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            float2 v = make_float2(0.0f, 0.0f);                     // the lower triangle is the data: A[i][j] = conj(A[j][i]) above it
+            if (j < C && i < C) v = *reinterpret_cast<const float2*>(psd + ((g * C + (j <= i ? i : j)) * C + (j <= i ? j : i)) * 2);
+            S.diag = j == i ? (double)v.x : S.diag;
+            S.ar[j] = j == i ? 0.0 : (double)v.x, S.ai[j] = j == i ? 0.0 : (j < i ? (double)v.y : -(double)v.y);
+            S.vr[j] = j == i ? 1.0 : 0.0, S.vi[j] = 0.0;
+            poison += 0.0 * (double)v.x + 0.0 * (double)v.y;
+        }
+        poison = group_sum<GL>(poison);
+#pragma unroll 1
+        for (int sweep = 0; sweep < BF_EVD_SWEEPS; ++sweep) {
+            double off = 0.0;
+#pragma unroll
+            for (int j = 0; j < C; ++j) off += j == i ? 0.0 : S.ar[j] * S.ar[j] + S.ai[j] * S.ai[j];
+            off = group_sum<GL>(off);
+            const double dg = group_sum<GL>(S.diag * S.diag);
+            if (!(off > 2e-32 * dg)) break;                          // converged, or a NaN (off counts both triangles)
+            evd_sweep<C, N, GL>(S, i, std::make_integer_sequence<int, N - 1>{});
+        }
+        double lam = i < C ? S.diag : -INFINITY;
+        int top = i;
+        group_top<GL>(lam, top);
+        double vr = 0.0, vi = 0.0;
+#pragma unroll
+        for (int j = 0; j < C; ++j) vr = j == top ? S.vr[j] : vr, vi = j == top ? S.vi[j] : vi;
+        double big = i < C ? vr * vr + vi * vi : -1.0;
+        const double nrm = group_sum<GL>(i < C ? big : 0.0);
+        int lead = i;
+        group_top<GL>(big, lead);
+        const double hr = __shfl(vr, lead, GL), hi = __shfl(vi, lead, GL);
+        const double scale = 1.0 / (sqrt(nrm) * sqrt(big));
+        if (i < C) {
+            const double re = (vr * hr + vi * hi) * scale, im = i == lead ? 0.0 : (vi * hr - vr * hi) * scale;
+            *reinterpret_cast<float2*>(out + (g * C + i) * 2) = make_float2((float)(re + poison), (float)(im + poison));
+        }
+    }
+}
+
+struct RtfPowerArgs {
+    const float* psd_s;          // [G][C][C][2]
+    const float* psd_n;
+    long long G, F;
+    const float* ref;            // u[b * ref_sb + c], or null: ref_channel
+    long long ref_sb;
+    int ref_channel, loading, n_iter;
+    double diag_eps;
+    float* rtf;                  // [G][C][2]
+};
+
+// rtf_power: [psd_n | psd_s | K] with K = psd_s (n_iter >= 2) or the loaded psd_n (n_iter == 1), which the elimination leaves alone
+template <int C>
+__global__ void __launch_bounds__(BF_THREADS)
+rtf_power_kernel(const RtfPowerArgs A) {
+    extern __shared__ __align__(16) unsigned char bf_lds[];
+    double* L = reinterpret_cast<double*>(bf_lds);                  // [C][3 C][2][BF_WS]
+    constexpr int W = 3 * C;
+    const int tid = threadIdx.x;
+    const long long tiles = (A.G + BF_WS - 1) / BF_WS;
+    for (long long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
+        const long long g0 = tl * BF_WS;
+        rt_fill<C, W>(L, A.psd_n, 0, g0, A.G, tid);
+        rt_fill<C, W>(L, A.psd_s, C, g0, A.G, tid);
+        rt_fill<C, W>(L, A.n_iter >= 2 ? A.psd_s : A.psd_n, 2 * C, g0, A.G, tid);
+        __syncthreads();
+        const long long g = g0 + tid;
+        if (tid < BF_WS && g < A.G) {
+            const int s = tid;
+            if (A.loading) {
+                const double load = rt_load<C, W>(L, s, A.diag_eps);
+                if (A.n_iter < 2)
+                    for (int i = 0; i < C; ++i) RT_M(i, 2 * C + i, 0, s) += load;
+            }
+            rt_solve<C, W, C>(L, s);                                 // columns [C, 2 C): phi = psd_n^-1 psd_s
+            double rr[C], ri[C], nr[C], ni[C];
+            const float* u = A.ref ? A.ref + (g / A.F) * A.ref_sb : nullptr;
+#pragma unroll
+            for (int i = 0; i < C; ++i) {
+                if (u) {
+                    double ar = 0.0, ai = 0.0;
+                    for (int c = 0; c < C; ++c) {
+                        const double uc = (double)u[c];
+                        ar += RT_M(i, C + c, 0, s) * uc, ai += RT_M(i, C + c, 1, s) * uc;
+                    }
+                    rr[i] = ar, ri[i] = ai;
+                } else {
+                    rr[i] = RT_M(i, C + A.ref_channel, 0, s), ri[i] = RT_M(i, C + A.ref_channel, 1, s);
+                }
+            }
+#pragma unroll 1
+            for (int it = 0; it <= BF_MAX_ITER; ++it) {              // n_iter - 2 products with phi, then the one with K
+                const bool last = it >= A.n_iter - 2;
+                const int col = last ? 2 * C : C;
+#pragma unroll
+                for (int i = 0; i < C; ++i) {
+                    double ar = 0.0, ai = 0.0;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const double mr = RT_M(i, col + c, 0, s), mi = RT_M(i, col + c, 1, s);
+                        ar += mr * rr[c] - mi * ri[c];
+                        ai += mr * ri[c] + mi * rr[c];
+                    }
+                    nr[i] = ar, ni[i] = ai;
+                }
+#pragma unroll
+                for (int i = 0; i < C; ++i) rr[i] = nr[i], ri[i] = ni[i];
+                if (last) break;
+            }
+            float* o = A.rtf + g * C * 2;
+#pragma unroll
+            for (int i = 0; i < C; ++i) o[2 * i] = (float)rr[i], o[2 * i + 1] = (float)ri[i];
+        }
+        __syncthreads();
+    }
+}
+
+struct RtfWeightArgs {
+    const float* rtf;            // [G][C][2]
+    const float* psd_n;          // [G][C][C][2]
+    long long G, F;
+    const float* ref;            // u[b * ref_sb + c], or null: ref_channel (< 0: no scaling)
+    long long ref_sb;
+    int ref_channel, loading;
+    double diag_eps, eps;
+    float* w;                    // [G][C][2]
+};
+
+// mvdr_weights_rtf: [psd_n | d | d]; the first copy of d becomes a = psd_n^-1 d, w = a / (Re d^H a + eps), times conj(d[ref]) or
+// sum_c conj(d_c) u_c
+template <int C>
+__global__ void __launch_bounds__(BF_THREADS)
+mvdr_weights_rtf_kernel(const RtfWeightArgs A) {
+    extern __shared__ __align__(16) unsigned char bf_lds[];
+    double* L = reinterpret_cast<double*>(bf_lds);                  // [C][C + 2][2][BF_WS]
+    constexpr int W = C + 2;
+    const int tid = threadIdx.x;
+    const long long tiles = (A.G + BF_WS - 1) / BF_WS;
+    for (long long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
+        const long long g0 = tl * BF_WS;
+        rt_fill<C, W>(L, A.psd_n, 0, g0, A.G, tid);
+        for (int idx = tid; idx < BF_WS * C; idx += BF_THREADS) {
+            const int s = idx / C, i = idx - s * C;
+            if (g0 + s < A.G) {
+                const float2 v = *reinterpret_cast<const float2*>(A.rtf + ((g0 + s) * C + i) * 2);
+                RT_M(i, C, 0, s) = (double)v.x, RT_M(i, C, 1, s) = (double)v.y;
+                RT_M(i, C + 1, 0, s) = (double)v.x, RT_M(i, C + 1, 1, s) = (double)v.y;
+            }
+        }
+        __syncthreads();
+        const long long g = g0 + tid;
+        if (tid < BF_WS && g < A.G) {
+            const int s = tid;
+            if (A.loading) rt_load<C, W>(L, s, A.diag_eps);
+            rt_solve<C, W, 1>(L, s);
+            double q = A.eps;                                        // Re d^H a + eps
+            for (int c = 0; c < C; ++c) q += RT_M(c, C + 1, 0, s) * RT_M(c, C, 0, s) + RT_M(c, C + 1, 1, s) * RT_M(c, C, 1, s);
+            double sr = 1.0, si = 0.0;
+            bool scaled = true;
+            if (A.ref) {
+                const float* u = A.ref + (g / A.F) * A.ref_sb;
+                double ur = 0.0, ui = 0.0;
+                for (int c = 0; c < C; ++c) ur += RT_M(c, C + 1, 0, s) * (double)u[c], ui += RT_M(c, C + 1, 1, s) * (double)u[c];
+                sr = ur, si = -ui;
+            } else if (A.ref_channel >= 0) {
+                sr = RT_M(A.ref_channel, C + 1, 0, s), si = -RT_M(A.ref_channel, C + 1, 1, s);
+            } else {
+                scaled = false;
+            }
+            float* o = A.w + g * C * 2;
+            for (int i = 0; i < C; ++i) {
+                const double wr = RT_M(i, C, 0, s) / q, wi = RT_M(i, C, 1, s) / q;
+                o[2 * i] = (float)(scaled ? wr * sr - wi * si : wr), o[2 * i + 1] = (float)(scaled ? wr * si + wi * sr : wi);
+            }
+        }
+        __syncthreads();
+    }
+}
+#undef RT_M
+
 // ----------------------------------------------------------------------------- host side
 inline bool bf_stride_ok(long long n, long long& stride, bool pairs) {
     if (n == 1) { stride = 0; return true; }
@@ -538,9 +935,98 @@ inline int apply_launch(const float* weights, const SpecRef& x, int channels, lo
 #undef BF_CALL
 }
 
+inline bool rt_aligned(const void* a, const void* b) {
+    return a && b && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7) == 0;
+}
+
+// a workgroup per BF_WS systems with `columns` complex float64 columns a row in the LDS
+inline long long rt_blocks(long long G) { return persistent_blocks((G + BF_WS - 1) / BF_WS, 1, bf_grid(1, 0)); }
+inline size_t rt_lds(int channels, int columns) { return (size_t)channels * columns * 2 * BF_WS * sizeof(double); }
+
+inline int rtf_weights_launch(int channels, const RtfWeightArgs& A, hipStream_t stream) {
+#define BF_CALL(C) launch_kernel(mvdr_weights_rtf_kernel<C>, rt_blocks(A.G), BF_THREADS, rt_lds(C, C + 2), stream, A)
+    BF_BY_CHANNELS(channels, BF_CALL)
+#undef BF_CALL
+}
+
+// as weights_check, with ref_channel < 0 (and no vector) for "no reference"
+inline int rtf_weights_args(const float* rtf, const float* psd_n, long long batch, long long bins, int channels, const float* ref_vector,
+                            long long ref_sb, int ref_channel, int loading, double diag_eps, double eps, float* weights,
+                            RtfWeightArgs* A) {
+    const int rc = weights_check(batch, bins, channels, ref_vector, ref_sb, ref_channel < 0 ? 0 : ref_channel);
+    if (rc != TAC_OK) return rc;
+    if (!rt_aligned(rtf, psd_n) || !rt_aligned(weights, weights)) return TAC_E_INVALID;
+    A->rtf = rtf, A->psd_n = psd_n, A->G = batch * bins, A->F = bins;
+    A->ref = ref_vector, A->ref_sb = ref_sb, A->ref_channel = ref_channel < 0 ? -1 : ref_channel, A->loading = loading ? 1 : 0;
+    A->diag_eps = diag_eps, A->eps = eps, A->w = weights;
+    return TAC_OK;
+}
+
 }  // namespace tac
 
 extern "C" {
+
+int tac_rtf_evd_f32(const float* psd_s, int64_t batch, int64_t bins, int32_t channels, float* rtf, void* stream) {
+    using namespace tac;
+    long long ref_sb = 0;
+    const int rc = weights_check(batch, bins, channels, nullptr, ref_sb, 0);
+    if (rc != TAC_OK) return rc;
+    if (!rt_aligned(psd_s, rtf)) return TAC_E_INVALID;
+    const long long G = batch * bins;
+#define BF_CALL(C)                                                                                                        \
+    launch_kernel(rtf_evd_kernel<C>, persistent_blocks((G * rr_lanes(C) + BF_THREADS - 1) / BF_THREADS, 1, bf_grid(1, 0)), \
+                  BF_THREADS, 0, (hipStream_t)stream, psd_s, G, rtf)
+    BF_BY_CHANNELS(channels, BF_CALL)
+#undef BF_CALL
+}
+
+int32_t tac_rtf_power_max_iter(void) { return tac::BF_MAX_ITER; }
+
+int tac_rtf_power_f32(const float* psd_s, const float* psd_n, int64_t batch, int64_t bins, int32_t channels, const float* ref_vector,
+                      int64_t ref_stride_b, int32_t ref_channel, int32_t n_iter, int32_t diagonal_loading, double diag_eps, float* rtf,
+                      void* stream) {
+    using namespace tac;
+    long long ref_sb = ref_stride_b;
+    const int rc = weights_check(batch, bins, channels, ref_vector, ref_sb, ref_channel);
+    if (rc != TAC_OK) return rc;
+    if (n_iter < 1 || !rt_aligned(psd_s, psd_n) || !rt_aligned(rtf, rtf)) return TAC_E_INVALID;
+    if (n_iter > BF_MAX_ITER) return TAC_E_UNSUPPORTED;
+    RtfPowerArgs A;
+    A.psd_s = psd_s, A.psd_n = psd_n, A.G = batch * bins, A.F = bins;
+    A.ref = ref_vector, A.ref_sb = ref_sb, A.ref_channel = ref_channel, A.loading = diagonal_loading ? 1 : 0, A.n_iter = n_iter;
+    A.diag_eps = diag_eps, A.rtf = rtf;
+#define BF_CALL(C) launch_kernel(rtf_power_kernel<C>, rt_blocks(A.G), BF_THREADS, rt_lds(C, 3 * C), (hipStream_t)stream, A)
+    BF_BY_CHANNELS(channels, BF_CALL)
+#undef BF_CALL
+}
+
+int tac_mvdr_weights_rtf_f32(const float* rtf, const float* psd_n, int64_t batch, int64_t bins, int32_t channels,
+                             const float* ref_vector, int64_t ref_stride_b, int32_t ref_channel, int32_t diagonal_loading,
+                             double diag_eps, double eps, float* weights, void* stream) {
+    using namespace tac;
+    RtfWeightArgs A;
+    const int rc = rtf_weights_args(rtf, psd_n, batch, bins, channels, ref_vector, ref_stride_b, ref_channel, diagonal_loading,
+                                    diag_eps, eps, weights, &A);
+    if (rc != TAC_OK) return rc;
+    return rtf_weights_launch(channels, A, (hipStream_t)stream);
+}
+
+int tac_rtf_mvdr_f32(const float* spec, int64_t batch, int32_t channels, int64_t bins, int64_t frames, int64_t stride_b,
+                     int64_t stride_c, int64_t stride_f, int64_t stride_t, const float* rtf, const float* psd_n,
+                     const float* ref_vector, int64_t ref_stride_b, int32_t ref_channel, int32_t diagonal_loading, double diag_eps,
+                     double eps, float* weights, float* out, int64_t out_b, int64_t out_f, int64_t out_t, void* stream) {
+    using namespace tac;
+    SpecRef x;
+    int rc = bf_spec(spec, batch, channels, bins, frames, stride_b, stride_c, stride_f, stride_t, &x);
+    if (rc != TAC_OK) return rc;
+    RtfWeightArgs A;
+    if ((rc = rtf_weights_args(rtf, psd_n, batch, bins, channels, ref_vector, ref_stride_b, ref_channel, diagonal_loading, diag_eps,
+                               eps, weights, &A)) != TAC_OK)
+        return rc;
+    if (!out) return TAC_E_INVALID;
+    if ((rc = rtf_weights_launch(channels, A, (hipStream_t)stream)) != TAC_OK) return rc;
+    return apply_launch(weights, x, channels, batch, bins, frames, out, out_b, out_f, out_t, (hipStream_t)stream);
+}
 
 int tac_psd_plan(int64_t frames, int32_t* chunk_frames, int32_t* chunks) {
     int len = 0, n = 0;

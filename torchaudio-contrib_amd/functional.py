@@ -33,7 +33,7 @@ __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterba
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
-           'psd', 'mvdr_weights_souden', 'apply_beamforming']
+           'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf']
 
 _call = _ops.call
 
@@ -662,6 +662,54 @@ def apply_beamforming(beamform_weights, specgram):
     x, was_complex = _beamform.pairs(specgram, 'specgram')
     _beamform.check_apply(w, x)
     return _beamform.unpairs(_call('apply_beamforming', w, x), was_complex)
+
+
+def rtf_evd(psd_s):
+    """``(…, freq, channel, channel)`` complex Hermitian PSD → ``(…, freq, channel)``: the relative transfer function (steering
+    vector) as the eigenvector of the largest eigenvalue, at unit 2-norm (torchaudio's ``functional.rtf_evd``).
+
+    Any unit phase of an eigenvector is an eigenvector, and the eigen-solvers do not agree on the one they return.  This package
+    fixes it on every route: the component of largest modulus (the lowest index on a tie) is real and positive, its imaginary part
+    exactly zero.  ``mvdr_weights_rtf`` with a reference does not depend on the phase.
+
+    float32 on a HIP device with 2 to 8 channels is one launch with a lane per (batch entry, bin): cyclic Jacobi on the Hermitian
+    matrix in float64 on chip (the lower triangle is read), which needs no spectral gap — a zero, identity or rank-one PSD gives a
+    finite unit vector — rounded once.  Other inputs take ``torch.linalg.eigh`` and the same convention (``_composite.rtf_evd``)."""
+    s, was_complex = _beamform.pairs(psd_s, 'psd_s')
+    _beamform.psd_shape(s, 'psd_s')
+    return _beamform.unpairs(_call('rtf_evd', s), was_complex)
+
+
+def rtf_power(psd_s, psd_n, reference_channel, n_iter=3, diagonal_loading=True, diag_eps=1e-7):
+    """two ``(…, freq, channel, channel)`` complex PSDs → ``(…, freq, channel)``: the relative transfer function by the power
+    method (torchaudio's ``functional.rtf_power``).  With loading ``Φn ← Φn + (diag_eps Re tr Φn + 1e-8) I``; ``φ = Φn⁻¹ Φs`` by a
+    solve; ``r = φ[:, ref]`` for an int, ``φ u`` for a real tensor ``u`` of shape ``(…, channel)`` or ``(channel,)``; for ``n_iter >=
+    2``, ``r ← φ r`` ``n_iter - 2`` times and then ``r ← Φs r``; for ``n_iter == 1``, ``r ← Φn r`` with the loaded ``Φn``.  Not
+    normalised.  ``ValueError`` for ``n_iter <= 0``.
+
+    float32 on a HIP device with 2 to 8 channels and ``n_iter <= 64`` is one launch: the solve and every product in float64 on
+    chip from the float32 PSDs, rounded once."""
+    s, was_complex = _beamform.pairs(psd_s, 'psd_s')
+    n, _ = _beamform.pairs(psd_n, 'psd_n')
+    n_iter = _beamform.check_n_iter(n_iter)
+    lead, n_bins, n_ch, u, r = _beamform.check_weights_args(s, n, reference_channel)
+    out = _call('rtf_power', s, n, _beamform.none(s) if u is None else u, r, n_iter, bool(diagonal_loading), float(diag_eps))
+    return _beamform.unpairs(out, was_complex)
+
+
+def mvdr_weights_rtf(rtf, psd_n, reference_channel=None, diagonal_loading=True, diag_eps=1e-7, eps=1e-8):
+    """a ``(…, freq, channel)`` relative transfer function ``d`` and a ``(…, freq, channel, channel)`` noise PSD → ``(…, freq,
+    channel)`` MVDR weights (torchaudio's ``functional.mvdr_weights_rtf``): with loading ``Φn ← Φn + (diag_eps Re tr Φn + 1e-8) I``;
+    ``a = Φn⁻¹ d``; ``w = a / (Re(dᴴ a) + eps)``; then ``w ← w conj(d[ref])`` for an int reference, ``w ← w Σ_c conj(d_c) u_c`` for
+    a real tensor ``u``, nothing for ``None``.
+
+    float32 on a HIP device with 2 to 8 channels is one launch, float64 on chip, rounded once."""
+    d, was_complex = _beamform.pairs(rtf, 'rtf')
+    n, _ = _beamform.pairs(psd_n, 'psd_n')
+    lead, n_bins, n_ch, u, r = _beamform.check_rtf_weights_args(d, n, reference_channel)
+    out = _call('mvdr_weights_rtf', d, n, _beamform.none(d) if u is None else u, r, bool(diagonal_loading), float(diag_eps),
+                float(eps))
+    return _beamform.unpairs(out, was_complex)
 
 
 def preemphasis(waveforms, coeff=0.97):

@@ -650,6 +650,25 @@ class SoudenMVDR(_ModuleNoStateBuffers):
         return F.apply_beamforming(w, specgram)
 
 
+class RTFMVDR(_ModuleNoStateBuffers):
+    """torchaudio's ``transforms.RTFMVDR``: ``forward(specgram, rtf, psd_n, reference_channel, diagonal_loading=True, diag_eps=1e-7,
+    eps=1e-8)`` computes ``functional.mvdr_weights_rtf`` from the relative transfer function and the noise PSD and applies the
+    weights: ``(…, channel, freq, time)`` → ``(…, freq, time)``.  On a HIP device ONE entry of two launches, the result the
+    frame-major view ``istft`` reads in place.  ``PSD → rtf_evd / rtf_power → RTFMVDR`` is the steering-vector beamformer.  No
+    buffers."""
+
+    def forward(self, specgram, rtf, psd_n, reference_channel, diagonal_loading=True, diag_eps=1e-7, eps=1e-8):
+        x, was_complex = _beamform.pairs(specgram, 'specgram')
+        d, _ = _beamform.pairs(rtf, 'rtf')
+        n, _ = _beamform.pairs(psd_n, 'psd_n')
+        lead, n_ch, n_bins, n_frames = _beamform.spec_shape(x)
+        _beamform.check_apply(d, x)
+        _, _, _, u, r = _beamform.check_rtf_weights_args(d, n, reference_channel)
+        out = _ops.call('rtf_mvdr', x, d, n, _beamform.none(x) if u is None else u, r, bool(diagonal_loading), float(diag_eps),
+                        float(eps))
+        return _beamform.unpairs(out, was_complex)
+
+
 class MVDR(_ModuleNoStateBuffers):
     """torchaudio's mask-based ``transforms.MVDR`` at ``solution='ref_channel'``: ``forward(specgram, mask_s, mask_n=None)`` maps a
     ``(…, channel, freq, time)`` spectrogram and real ``(…, freq, time)`` masks (``(…, channel, freq, time)`` with ``multi_mask``,
