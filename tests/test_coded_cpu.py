@@ -3,8 +3,6 @@ of ``melspectrogram`` (int16 PCM) and ``melspectrogram_mulaw`` (uint8 / int64 co
 tests/test_coded_gpu.py included.  The keep conditions of the dB rule and the silent-frame conditions are properties of the inputs
 and the bounds, not of a kernel: they are established here, on the reference route, before a kernel is held to them.  Also: what the
 default run of the generator covers, and its narrowing rules against the host-side packer of the fused kernels' bank tables."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -73,9 +71,6 @@ def test_narrowing_rules_are_the_packers(tac):
     bank the generator can draw: the rule says yes exactly where the packer accepts the bank in the layout the coded kernels read
     (at 1024 the packer also builds wider tables, of up to 20 steps, which only the float32 kernels are instantiated for)."""
     h = tac._native.lib()
-    h.tac_melbank_pack_host.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                        ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
-    h.tac_melbank_pack_host.restype = ctypes.c_int
     yes = no = 0
     for n in R.SIZES:
         for rate in R.SAMPLE_RATES:

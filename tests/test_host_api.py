@@ -1030,3 +1030,39 @@ def test_planned_chain_falls_back_on_cpu(tac):
     y = fast(x)
     assert type(y) is torch.Tensor and torch.equal(y, model(x))
     assert type(torch.nn.Sequential(*tac.Melspectrogram(num_mels=32, sample_rate=16000, fft_length=512, hop_length=256))(x)) is torch.Tensor
+
+
+@pytest.mark.gpu
+def test_launch_helper_counts_refuses_and_hands_back(tac):
+    """``_hip._launch``, the one road from Python to a kernel: a launch is counted once and its output checked for poison; a refused
+    call raises under the entry point's name and counts nothing; a refusal the caller accepts comes back as the code.  Both
+    refusals are argument checks at the top of their entry points: no kernel runs on those paths."""
+    H, N = tac._hip, tac._native
+    assert torch.cuda.is_available(), 'this test needs the MI355X'
+    dev = torch.device('cuda', torch.cuda.current_device())
+    z = (torch.rand(8, 2, generator=torch.Generator().manual_seed(0)) * 2 - 1).to(dev)
+    H.set_poison_outputs(True)
+    try:
+        H.poison_report()
+        out = H._empty((8,), device=dev)
+        before = dict(H.launches)
+        assert H._launch('tac_complex_norm_f32', dev, (out,), N.ptr(z), 8, 1.0, N.ptr(out)) == N.TAC_OK
+        assert H.launches['tac_complex_norm_f32'] == before.get('tac_complex_norm_f32', 0) + 1
+        assert H.poison_report() == {}
+        want = torch.linalg.vector_norm(z.cpu(), dim=-1)
+        assert float((out.cpu() - want).abs().max()) <= 1e-6
+
+        counted = dict(H.launches)
+        with pytest.raises(RuntimeError, match=r'^tac_complex_norm_f32: '):
+            H._launch('tac_complex_norm_f32', dev, (out,), N.ptr(z), -1, 1.0, N.ptr(out))
+        assert H.launches == counted
+
+        x, mat, rows = torch.zeros(1, 257, 1, device=dev), torch.zeros(257, 1, device=dev), H._empty((1, 1, 1), device=dev)
+        args = (N.ptr(x), 1, 257, 1, 257, 1, 1, N.ptr(mat), 1, N.ptr(rows))
+        assert H._launch('tac_dct_rows_f32', dev, (rows,), *args, accept=(N.TAC_E_UNSUPPORTED,)) == N.TAC_E_UNSUPPORTED
+        assert H.launches == counted
+        with pytest.raises(NotImplementedError, match=r'^tac_dct_rows_f32: '):
+            H._launch('tac_dct_rows_f32', dev, (rows,), *args)
+        assert H.launches == counted and H.poison_report() == {}
+    finally:
+        H.set_poison_outputs(False)

@@ -30,6 +30,23 @@ def _count(name, *filled):
     check_written(name, *filled)
 
 
+#: ``accept`` of the launches whose caller takes another route when the entry point declines the call
+_DECLINED = (_native.TAC_E_UNSUPPORTED,)
+
+
+def _launch(name, dev, filled, *args, accept=()):
+    """One launch of the entry point ``name`` on ``dev``'s current stream (the last argument of every entry point), checked and
+    counted.  ``filled``: the tensors (or slices) it fills, checked for poison while that is on.  A return code in ``accept``
+    (``TAC_E_UNSUPPORTED`` where the caller then takes another route) is handed back as it is, and nothing is counted."""
+    with _native.on_device(dev):
+        rc = getattr(_native.lib(), name)(*args, _native.stream_ptr(dev))
+    if rc in accept:
+        return rc
+    _native.check(rc, name)
+    _count(name, *filled)
+    return _native.TAC_OK
+
+
 # ----------------------------------------------------------------------------- constant-table caches
 # Everything derived from a window / filterbank (packed weights, tile plans, transposes, adjoint tables, DFT matrices)
 # is cached ON the tensor object and stamped with what identifies its contents cheaply: the version counter (every
@@ -270,12 +287,8 @@ def _stft_dft(wave, window, g):
     x = x.contiguous()
     mat = _dft_matrix(window, g.n_fft, g.win_length, g.onesided, g.normalized)
     out = _empty(g.stft_shape, device=x.device)
-    with _native.on_device(x.device):
-        rc = _native.lib().tac_apply_filterbank_f32(
-            _native.ptr(x), x.shape[0], g.n_fft, g.n_frames, x.stride(0), 1, g.hop,
-            _native.ptr(mat), None, 2 * g.n_bins, _native.ptr(out), _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_apply_filterbank_f32 (DFT matrix)')
-    _count('tac_apply_filterbank_f32', out)
+    _launch('tac_apply_filterbank_f32', x.device, (out,), _native.ptr(x), x.shape[0], g.n_fft, g.n_frames, x.stride(0), 1, g.hop,
+            _native.ptr(mat), None, 2 * g.n_bins, _native.ptr(out))
     return out.transpose(-3, -2)
 
 
@@ -285,11 +298,7 @@ def stft(wave, window, n_fft, hop, win_length, center, pad_mode, normalized, one
         return _stft_dft(wave, window, g)
     src = _rows_of(wave, g)
     out = _empty(g.stft_shape, device=wave.device)
-    with _native.on_device(wave.device):
-        rc = _native.lib().tac_stft_f32(_native.ptr(src), _native.ptr(window), g.desc, _native.ptr(out),
-                                        _native.stream_ptr(wave.device))
-    _native.check(rc, 'tac_stft_f32')
-    _count('tac_stft_f32', out)
+    _launch('tac_stft_f32', wave.device, (out,), _native.ptr(src), _native.ptr(window), g.desc, _native.ptr(out))
     return out.transpose(-3, -2)
 
 
@@ -300,12 +309,8 @@ def spectrogram(wave, window, n_fft, hop, win_length, center, pad_mode, normaliz
         return amplitude_to_db(mag, ref, amin) if db else mag
     src = _rows_of(wave, g)
     out = _empty(g.spec_shape, device=wave.device)
-    with _native.on_device(wave.device):
-        rc = _native.lib().tac_spectrogram_f32(
-            _native.ptr(src), _native.ptr(window), g.desc, float(power), 1 if db else 0, float(ref), float(amin),
-            _native.ptr(out), _native.stream_ptr(wave.device))
-    _native.check(rc, 'tac_spectrogram_f32')
-    _count('tac_spectrogram_f32', out)
+    _launch('tac_spectrogram_f32', wave.device, (out,), _native.ptr(src), _native.ptr(window), g.desc, float(power),
+            1 if db else 0, float(ref), float(amin), _native.ptr(out))
     return out.transpose(-2, -1)
 
 
@@ -349,11 +354,7 @@ def istft_envelope(window, n_fft, hop, win_length, center, n_frames, kept):
         with torch.inference_mode(False):
             inv_env = torch.empty(n_pos, dtype=torch.float32, device=window.device)
         desc = _istft_desc(1, 1, 1, n_fft, hop, win_length, center, False)
-        with _native.on_device(window.device):
-            rc = _native.lib().tac_istft_envelope_f32(_native.ptr(window), desc, n_frames, _native.ptr(inv_env),
-                                                      None, _native.stream_ptr(window.device))
-        _native.check(rc, 'tac_istft_envelope_f32')
-        launches['tac_istft_envelope_f32'] = launches.get('tac_istft_envelope_f32', 0) + 1
+        _launch('tac_istft_envelope_f32', window.device, (), _native.ptr(window), desc, n_frames, _native.ptr(inv_env), None)
         if len(cache[1]) > 64:
             cache[1].clear()
         entry = cache[1][key] = (inv_env, set())
@@ -401,21 +402,14 @@ def istft(spec, window, n_fft, hop, win_length, center, normalized, length, rout
     if need < 0:
         _native.check(need, 'tac_istft_workspace')
 
-    def launch(work, nbytes):
-        with _native.on_device(spec.device):
-            return _native.lib().tac_istft_f32(_native.ptr(rows), rows.stride(0), rows.stride(1), n_frames, _native.ptr(window),
-                                               _native.ptr(inv_env), desc, None if work is None else _native.ptr(work), nbytes,
-                                               _native.ptr(out), _native.stream_ptr(spec.device))
-
+    head = (_native.ptr(rows), rows.stride(0), rows.stride(1), n_frames, _native.ptr(window), _native.ptr(inv_env), desc)
     rc = _native.TAC_E_UNSUPPORTED
     if need == 0 and route != 'general':
-        rc = launch(None, 0)
+        rc = _launch('tac_istft_f32', spec.device, (out,), *head, None, 0, _native.ptr(out), accept=_DECLINED)
     if rc == _native.TAC_E_UNSUPPORTED:                                 # (the general route takes any geometry and alignment)
         need = n_rows * n_frames * n_fft * 4
         work = torch.empty(need // 4, dtype=torch.float32, device=spec.device)      # scratch: every frame is written before it is read
-        rc = launch(work, need)
-    _native.check(rc, 'tac_istft_f32')
-    _count('tac_istft_f32', out)
+        _launch('tac_istft_f32', spec.device, (out,), *head, _native.ptr(work), need, _native.ptr(out))
     return out
 
 
@@ -432,21 +426,14 @@ def istft_backward(grad_out, window, n_fft, hop, win_length, center, normalized,
     n_rows, n_pos, n_bins = int(go.shape[0]), hop * (n_frames - 1) + n_fft, n_fft // 2 + 1
     padded = _empty((n_rows, n_pos), device=go.device)
     gspec = _empty(lead + (n_frames, n_bins, 2), device=go.device)
-    with _native.on_device(go.device):
-        stream = _native.stream_ptr(go.device)
-        rc = _native.lib().tac_istft_grad_input_f32(
-            _native.ptr(go), out_len, _native.ptr(inv_env),
-            _istft_desc(n_rows, out_len, out_len, n_fft, hop, win_length, center, normalized), n_frames, _native.ptr(padded), stream)
-        _native.check(rc, 'tac_istft_grad_input_f32')
-        _count('tac_istft_grad_input_f32', padded)
+    dev = go.device
+    with _native.on_device(dev):
+        _launch('tac_istft_grad_input_f32', dev, (padded,), _native.ptr(go), out_len, _native.ptr(inv_env),
+                _istft_desc(n_rows, out_len, out_len, n_fft, hop, win_length, center, normalized), n_frames, _native.ptr(padded))
         fwd = _native.StftDesc(rows=n_rows, length=n_pos, row_stride=n_pos, n_fft=n_fft, hop=hop, win_length=win_length, center=0,
                                pad_mode=0, normalized=0, onesided=1, reserved=0)
-        rc = _native.lib().tac_stft_f32(_native.ptr(padded), _native.ptr(window), fwd, _native.ptr(gspec), stream)
-        _native.check(rc, 'tac_stft_f32')
-        _count('tac_stft_f32', gspec)
-        rc = _native.lib().tac_istft_grad_bins_f32(_native.ptr(gspec), n_rows * n_frames, n_fft, 1 if normalized else 0, stream)
-        _native.check(rc, 'tac_istft_grad_bins_f32')
-        _count('tac_istft_grad_bins_f32', gspec)
+        _launch('tac_stft_f32', dev, (gspec,), _native.ptr(padded), _native.ptr(window), fwd, _native.ptr(gspec))
+        _launch('tac_istft_grad_bins_f32', dev, (gspec,), _native.ptr(gspec), n_rows * n_frames, n_fft, 1 if normalized else 0)
     return gspec.transpose(-3, -2)
 
 
@@ -735,26 +722,17 @@ def melspectrogram(wave, window, fb, n_fft, hop, win_length, center, pad_mode, n
     out = _empty(g.lead + (g.n_frames, n_mels), device=wave.device)
     if route == 'sparse':          # band-sparse contraction (the faster form for triangular banks)
         wpack, desc, info = _fused_pack(fb, g.n_fft)
-        with _native.on_device(wave.device):
-            rc = _native.lib().tac_melspec_sparse_f32(
-                _native.ptr(src), _native.ptr(window), g.desc, float(power), _native.ptr(wpack), _native.ptr(desc),
-                ctypes.cast(info, ctypes.c_void_p), n_mels, 1 if db else 0, float(ref), float(amin),
-                _native.ptr(out), _native.stream_ptr(wave.device))
+        rc = _launch('tac_melspec_sparse_f32', wave.device, (out,), _native.ptr(src), _native.ptr(window), g.desc, float(power),
+                     _native.ptr(wpack), _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), n_mels, 1 if db else 0,
+                     float(ref), float(amin), _native.ptr(out), accept=_DECLINED)
         if rc == _native.TAC_E_UNSUPPORTED:         # a geometry the fused kernel of this size declines: the two-kernel chain
             spec = spectrogram(wave, window, n_fft, hop, win_length, center, pad_mode, normalized, onesided, power,
                                False, 1.0, 1e-7)
             return apply_filterbank(spec, fb, db=(ref, amin) if db else None)
-        _native.check(rc, 'tac_melspec_sparse_f32')
-        _count('tac_melspec_sparse_f32', out)
         return out.transpose(-2, -1)
     _, plan_host = _filterbank_plan(fb)
-    with _native.on_device(wave.device):
-        rc = _native.lib().tac_melspec_f32(
-            _native.ptr(src), _native.ptr(window), g.desc, float(power), _native.ptr(fb),
-            ctypes.cast(plan_host, ctypes.c_void_p), n_mels, 1 if db else 0, float(ref), float(amin),
-            _native.ptr(out), _native.stream_ptr(wave.device))
-    _native.check(rc, 'tac_melspec_f32')
-    _count('tac_melspec_f32', out)
+    _launch('tac_melspec_f32', wave.device, (out,), _native.ptr(src), _native.ptr(window), g.desc, float(power), _native.ptr(fb),
+            ctypes.cast(plan_host, ctypes.c_void_p), n_mels, 1 if db else 0, float(ref), float(amin), _native.ptr(out))
     return out.transpose(-2, -1)
 
 
@@ -774,31 +752,19 @@ def apply_filterbank(spec, fb, allow_sparse=True, db=None):
         pack = _melbank_pack(fb, 0) if (allow_sparse and rows.stride(1) == 1 and MEL_PATH != 'mfma') else None
         if pack is not None:
             wpack, desc, info = pack
-            with _native.on_device(spec.device):
-                if db is None:
-                    name = 'tac_apply_filterbank_sparse_f32'
-                    rc = _native.lib().tac_apply_filterbank_sparse_f32(
-                        _native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0) if rows.shape[0] > 1 else 0,
-                        rows.stride(2), _native.ptr(wpack), _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), n_mels,
-                        _native.ptr(out), _native.stream_ptr(spec.device))
-                else:
-                    name = 'tac_apply_filterbank_sparse_db_f32'
-                    rc = _native.lib().tac_apply_filterbank_sparse_db_f32(
-                        _native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0) if rows.shape[0] > 1 else 0,
-                        rows.stride(2), _native.ptr(wpack), _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), n_mels,
-                        1, float(db[0]), float(db[1]), _native.ptr(out), _native.stream_ptr(spec.device))
+            head = (_native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0) if rows.shape[0] > 1 else 0, rows.stride(2),
+                    _native.ptr(wpack), _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), n_mels)
+            if db is None:
+                rc = _launch('tac_apply_filterbank_sparse_f32', spec.device, (out,), *head, _native.ptr(out),
+                             accept=_DECLINED)
+            else:
+                rc = _launch('tac_apply_filterbank_sparse_db_f32', spec.device, (out,), *head, 1, float(db[0]), float(db[1]),
+                             _native.ptr(out), accept=_DECLINED)
             if rc != _native.TAC_E_UNSUPPORTED:
-                _native.check(rc, name)
-                _count(name, out)
                 return out.transpose(-2, -1)
         plan, _ = _filterbank_plan(fb)
-        with _native.on_device(spec.device):
-            rc = _native.lib().tac_apply_filterbank_f32(
-                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0), rows.stride(1),
-                rows.stride(2), _native.ptr(fb), _native.ptr(plan), n_mels, _native.ptr(out),
-                _native.stream_ptr(spec.device))
-        _native.check(rc, 'tac_apply_filterbank_f32')
-        _count('tac_apply_filterbank_f32', out)
+        _launch('tac_apply_filterbank_f32', spec.device, (out,), _native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0),
+                rows.stride(1), rows.stride(2), _native.ptr(fb), _native.ptr(plan), n_mels, _native.ptr(out))
     out = out.transpose(-2, -1)
     return out if db is None else amplitude_to_db(out, db[0], db[1])
 
@@ -845,12 +811,8 @@ def dct_rows(x, mat, transposed=False):
         rows = x.reshape(-1, n_in, n_frames)            # a view wherever the leading dims collapse into one stride
         if any(st <= 0 for st, n in zip(rows.stride(), rows.shape) if n > 1):
             rows = rows.contiguous()                    # (expanded / flipped axes: the kernel takes positive strides)
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_dct_rows_f32(
-                _native.ptr(rows), rows.shape[0], n_in, n_frames, rows.stride(0), rows.stride(1), rows.stride(2),
-                _native.ptr(m), n_out, _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_dct_rows_f32')
-        _count('tac_dct_rows_f32', out)
+        _launch('tac_dct_rows_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], n_in, n_frames, rows.stride(0), rows.stride(1),
+                rows.stride(2), _native.ptr(m), n_out, _native.ptr(out))
     return out.transpose(-2, -1)
 
 
@@ -917,12 +879,8 @@ def polyphase(x, key, n_out, adjoint=False):
         rows = x.reshape(-1, length)
         if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
             rows = rows.contiguous()
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_polyphase_f32(
-                _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(taps), _native.ptr(table), b.phases, b.K,
-                run_min, b.step, off_min, off_max, n_out, _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_polyphase_f32')
-        _count('tac_polyphase_f32', out)
+        _launch('tac_polyphase_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(taps),
+                _native.ptr(table), b.phases, b.K, run_min, b.step, off_min, off_max, n_out, _native.ptr(out))
     return out
 
 
@@ -995,11 +953,8 @@ def lfilter_rows(x, b, a, clamp, reverse=False):
         if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
             rows = rows.contiguous()
         cb, ca = _lfilter_arrays(b, a)
-        with _native.on_device(x.device):
-            rc = h.tac_lfilter_f32(_native.ptr(rows), rows.shape[0], length, rows.stride(0), cb, ca, len(a), int(bool(clamp)),
-                                   int(bool(reverse)), _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_lfilter_f32')
-        _count('tac_lfilter_f32', out)
+        _launch('tac_lfilter_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0), cb, ca, len(a),
+                int(bool(clamp)), int(bool(reverse)), _native.ptr(out))
     return out
 
 
@@ -1034,11 +989,8 @@ def loudness_entries(x, stages, gate, step):
     out = _empty((entries,), device=x.device)
     work = _empty((need // 8,), dtype=torch.float64, device=x.device)
     coeffs = (ctypes.c_double * 12)(*[v for b, a in stages for v in tuple(b) + tuple(a)])
-    with _native.on_device(x.device):
-        rc = h.tac_loudness_f32(_native.ptr(rows), entries, channels, length, rows.stride(0), rows.stride(1), gate, step, coeffs,
-                                _native.ptr(work), _native.ptr(out), _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_loudness_f32')
-    _count('tac_loudness_f32', out, work)
+    _launch('tac_loudness_f32', x.device, (out, work), _native.ptr(rows), entries, channels, length, rows.stride(0), rows.stride(1),
+            gate, step, coeffs, _native.ptr(work), _native.ptr(out))
     return out.reshape(lead)
 
 
@@ -1084,11 +1036,8 @@ def pitch_lags(x, frame, max_lag, lag_min):
     n0, n1, time = rows.shape
     n_frames = -(-time // frame)
     lags = _empty((n0 * n1, n_frames), dtype=torch.int32, device=x.device)
-    with _native.on_device(x.device):
-        rc = _native.lib().tac_pitch_lags_f32(_native.ptr(rows), n0, n1, time, rows.stride(0), rows.stride(1), rows.stride(2), frame,
-                                              max_lag, lag_min, _native.ptr(lags), _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_pitch_lags_f32')
-    _count('tac_pitch_lags_f32', lags)
+    _launch('tac_pitch_lags_f32', x.device, (lags,), _native.ptr(rows), n0, n1, time, rows.stride(0), rows.stride(1), rows.stride(2),
+            frame, max_lag, lag_min, _native.ptr(lags))
     return lags.reshape(tuple(x.shape[:-1]) + (n_frames,))
 
 
@@ -1099,11 +1048,8 @@ def pitch_smooth(lags, win_length, sample_rate):
     rows = lags.reshape(-1, n_frames).contiguous()
     n_out = n_frames + (win_length - 1) // 2 - win_length + 1
     out = _empty((rows.shape[0], max(n_out, 0)), device=lags.device)
-    with _native.on_device(lags.device):
-        rc = _native.lib().tac_pitch_smooth_i32(_native.ptr(rows), rows.shape[0], n_frames, win_length, sample_rate, _native.ptr(out),
-                                                _native.stream_ptr(lags.device))
-    _native.check(rc, 'tac_pitch_smooth_i32')
-    _count('tac_pitch_smooth_i32', out)
+    _launch('tac_pitch_smooth_i32', lags.device, (out,), _native.ptr(rows), rows.shape[0], n_frames, win_length, sample_rate,
+            _native.ptr(out))
     return out.reshape(tuple(lags.shape[:-1]) + (n_out,))
 
 
@@ -1116,12 +1062,8 @@ def pitch_frequency(x, sample_rate, frame, max_lag, lag_min, win_length):
     n_out = n_frames + (win_length - 1) // 2 - win_length + 1
     lags = _empty((n0 * n1, n_frames), dtype=torch.int32, device=x.device)
     out = _empty((n0 * n1, n_out), device=x.device)
-    with _native.on_device(x.device):
-        rc = _native.lib().tac_pitch_frequency_f32(_native.ptr(rows), n0, n1, time, rows.stride(0), rows.stride(1), rows.stride(2),
-                                                   sample_rate, frame, max_lag, lag_min, win_length, _native.ptr(lags), _native.ptr(out),
-                                                   _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_pitch_frequency_f32')
-    _count('tac_pitch_frequency_f32', out, lags)
+    _launch('tac_pitch_frequency_f32', x.device, (out, lags), _native.ptr(rows), n0, n1, time, rows.stride(0), rows.stride(1),
+            rows.stride(2), sample_rate, frame, max_lag, lag_min, win_length, _native.ptr(lags), _native.ptr(out))
     return out.reshape(tuple(x.shape[:-1]) + (n_out,))
 
 
@@ -1197,13 +1139,9 @@ def psd(spec, mask_a=None, mask_b=None, complement=False, normalize=True, eps=1e
     chunks = psd_chunks(T)
     part, msum = _bf_scratch(n_psd, chunks, C, B * F, spec.device)
     out = [_empty((B * F, C, C, 2), device=spec.device) for _ in range(n_psd)]
-    with _native.on_device(spec.device):
-        rc = _native.lib().tac_psd_f32(_native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
-                                       *_bf_mask_args(ma), *_bf_mask_args(mb), n_psd, 1 if complement else 0, 1 if normalize else 0,
-                                       float(eps), chunks, _native.ptr(part), _native.ptr(msum), _native.ptr(out[0]),
-                                       _native.ptr(out[1]) if n_psd == 2 else None, _native.stream_ptr(spec.device))
-    _native.check(rc, 'tac_psd_f32')
-    _count('tac_psd_f32', part, msum, *out)
+    _launch('tac_psd_f32', spec.device, (part, msum, *out), _native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2),
+            x.stride(3), *_bf_mask_args(ma), *_bf_mask_args(mb), n_psd, 1 if complement else 0, 1 if normalize else 0, float(eps),
+            chunks, _native.ptr(part), _native.ptr(msum), _native.ptr(out[0]), _native.ptr(out[1]) if n_psd == 2 else None)
     out = [o.reshape(lead + (F, C, C, 2)) for o in out]
     return tuple(out) if n_psd == 2 else out[0]
 
@@ -1227,12 +1165,8 @@ def mvdr_weights_souden(psd_s, psd_n, ref_vector, ref_channel, diagonal_loading,
     B = s.shape[0]
     ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
     out = _empty((B * F, C, 2), device=psd_s.device)
-    with _native.on_device(psd_s.device):
-        rc = _native.lib().tac_mvdr_weights_souden_f32(_native.ptr(s), _native.ptr(n), B, F, C, ref_ptr, ref_stride, ref_channel,
-                                                       1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(out),
-                                                       _native.stream_ptr(psd_s.device))
-    _native.check(rc, 'tac_mvdr_weights_souden_f32')
-    _count('tac_mvdr_weights_souden_f32', out)
+    _launch('tac_mvdr_weights_souden_f32', psd_s.device, (out,), _native.ptr(s), _native.ptr(n), B, F, C, ref_ptr, ref_stride,
+            ref_channel, 1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(out))
     return out.reshape(lead + (F, C, 2))
 
 
@@ -1249,12 +1183,8 @@ def apply_beamforming(weights, spec):
     B = x.shape[0]
     w = weights.reshape(B * F, C, 2).contiguous()
     store, out = _bf_out(lead, B, F, T, spec.device)
-    with _native.on_device(spec.device):
-        rc = _native.lib().tac_apply_beamforming_f32(_native.ptr(w), _native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2),
-                                                     x.stride(3), _native.ptr(store), T * F * 2, 2, F * 2,
-                                                     _native.stream_ptr(spec.device))
-    _native.check(rc, 'tac_apply_beamforming_f32')
-    _count('tac_apply_beamforming_f32', store)
+    _launch('tac_apply_beamforming_f32', spec.device, (store,), _native.ptr(w), _native.ptr(x), B, C, F, T, x.stride(0), x.stride(1),
+            x.stride(2), x.stride(3), _native.ptr(store), T * F * 2, 2, F * 2)
     return out
 
 
@@ -1272,14 +1202,10 @@ def mvdr_souden(spec, mask_s, mask_n, ref_vector, ref_channel, diagonal_loading,
     ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
     w = _empty((B * F, C, 2), device=spec.device)
     store, out = _bf_out(lead, B, F, T, spec.device)
-    with _native.on_device(spec.device):
-        rc = _native.lib().tac_mvdr_souden_f32(_native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
-                                               *_bf_mask_args(ms), *_bf_mask_args(mn), float(psd_eps), ref_ptr, ref_stride, ref_channel,
-                                               1 if diagonal_loading else 0, float(diag_eps), float(eps), chunks, _native.ptr(part),
-                                               _native.ptr(msum), _native.ptr(w), _native.ptr(store), T * F * 2, 2, F * 2,
-                                               _native.stream_ptr(spec.device))
-    _native.check(rc, 'tac_mvdr_souden_f32')
-    _count('tac_mvdr_souden_f32', part, msum, w, store)
+    _launch('tac_mvdr_souden_f32', spec.device, (part, msum, w, store), _native.ptr(x), B, C, F, T, x.stride(0), x.stride(1),
+            x.stride(2), x.stride(3), *_bf_mask_args(ms), *_bf_mask_args(mn), float(psd_eps), ref_ptr, ref_stride, ref_channel,
+            1 if diagonal_loading else 0, float(diag_eps), float(eps), chunks, _native.ptr(part), _native.ptr(msum), _native.ptr(w),
+            _native.ptr(store), T * F * 2, 2, F * 2)
     return out, w.reshape(lead + (F, C, 2))
 
 
@@ -1296,10 +1222,7 @@ def rtf_evd(psd_s):
     s = psd_s.reshape(-1, F, C, C, 2).contiguous()
     B = s.shape[0]
     out = _empty((B * F, C, 2), device=psd_s.device)
-    with _native.on_device(psd_s.device):
-        rc = _native.lib().tac_rtf_evd_f32(_native.ptr(s), B, F, C, _native.ptr(out), _native.stream_ptr(psd_s.device))
-    _native.check(rc, 'tac_rtf_evd_f32')
-    _count('tac_rtf_evd_f32', out)
+    _launch('tac_rtf_evd_f32', psd_s.device, (out,), _native.ptr(s), B, F, C, _native.ptr(out))
     return out.reshape(lead + (F, C, 2))
 
 
@@ -1311,12 +1234,8 @@ def rtf_power(psd_s, psd_n, ref_vector, ref_channel, n_iter, diagonal_loading, d
     B = s.shape[0]
     ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
     out = _empty((B * F, C, 2), device=psd_s.device)
-    with _native.on_device(psd_s.device):
-        rc = _native.lib().tac_rtf_power_f32(_native.ptr(s), _native.ptr(n), B, F, C, ref_ptr, ref_stride, ref_channel, n_iter,
-                                             1 if diagonal_loading else 0, float(diag_eps), _native.ptr(out),
-                                             _native.stream_ptr(psd_s.device))
-    _native.check(rc, 'tac_rtf_power_f32')
-    _count('tac_rtf_power_f32', out)
+    _launch('tac_rtf_power_f32', psd_s.device, (out,), _native.ptr(s), _native.ptr(n), B, F, C, ref_ptr, ref_stride, ref_channel,
+            n_iter, 1 if diagonal_loading else 0, float(diag_eps), _native.ptr(out))
     return out.reshape(lead + (F, C, 2))
 
 
@@ -1328,12 +1247,8 @@ def mvdr_weights_rtf(rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag
     B = n.shape[0]
     ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
     out = _empty((B * F, C, 2), device=psd_n.device)
-    with _native.on_device(psd_n.device):
-        rc = _native.lib().tac_mvdr_weights_rtf_f32(_native.ptr(d), _native.ptr(n), B, F, C, ref_ptr, ref_stride, ref_channel,
-                                                    1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(out),
-                                                    _native.stream_ptr(psd_n.device))
-    _native.check(rc, 'tac_mvdr_weights_rtf_f32')
-    _count('tac_mvdr_weights_rtf_f32', out)
+    _launch('tac_mvdr_weights_rtf_f32', psd_n.device, (out,), _native.ptr(d), _native.ptr(n), B, F, C, ref_ptr, ref_stride,
+            ref_channel, 1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(out))
     return out.reshape(lead + (F, C, 2))
 
 
@@ -1347,13 +1262,9 @@ def rtf_mvdr(spec, rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_e
     ref_ptr, ref_stride, keep = _bf_ref(ref_vector, lead, C)
     w = _empty((B * F, C, 2), device=spec.device)
     store, out = _bf_out(lead, B, F, T, spec.device)
-    with _native.on_device(spec.device):
-        rc = _native.lib().tac_rtf_mvdr_f32(_native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2), x.stride(3),
-                                            _native.ptr(d), _native.ptr(n), ref_ptr, ref_stride, ref_channel,
-                                            1 if diagonal_loading else 0, float(diag_eps), float(eps), _native.ptr(w),
-                                            _native.ptr(store), T * F * 2, 2, F * 2, _native.stream_ptr(spec.device))
-    _native.check(rc, 'tac_rtf_mvdr_f32')
-    _count('tac_rtf_mvdr_f32', w, store)
+    _launch('tac_rtf_mvdr_f32', spec.device, (w, store), _native.ptr(x), B, C, F, T, x.stride(0), x.stride(1), x.stride(2),
+            x.stride(3), _native.ptr(d), _native.ptr(n), ref_ptr, ref_stride, ref_channel, 1 if diagonal_loading else 0,
+            float(diag_eps), float(eps), _native.ptr(w), _native.ptr(store), T * F * 2, 2, F * 2)
     return out, w.reshape(lead + (F, C, 2))
 
 
@@ -1414,17 +1325,13 @@ def _conv_spectra(y, n_fft, reverse):
     def build():
         rows = _conv_kernel_rows(y)
         h_rows, m = int(rows.shape[0]), int(rows.shape[1])
-        h = _native.lib()
-        need = int(h.tac_fftconvolve_spectra_workspace(h_rows, m, n_fft))
+        need = int(_native.lib().tac_fftconvolve_spectra_workspace(h_rows, m, n_fft))
         if need < 0:
             _native.check(need, 'tac_fftconvolve_spectra_workspace')
         work = torch.empty(need // 4, dtype=torch.float32, device=y.device)      # scratch: written before it is read
         out = _empty((h_rows, -(-m // (n_fft // 2)), n_fft // 2 + 1, 2), device=y.device)
-        with _native.on_device(y.device):
-            rc = h.tac_fftconvolve_spectra_f32(_native.ptr(rows), h_rows, m, rows.stride(0), n_fft, int(bool(reverse)),
-                                               _native.ptr(work), need, _native.ptr(out), _native.stream_ptr(y.device))
-        _native.check(rc, 'tac_fftconvolve_spectra_f32')
-        _count('tac_fftconvolve_spectra_f32', out)
+        _launch('tac_fftconvolve_spectra_f32', y.device, (out,), _native.ptr(rows), h_rows, m, rows.stride(0), n_fft,
+                int(bool(reverse)), _native.ptr(work), need, _native.ptr(out))
         return out
     return cached_on(y, '_tac_conv', ('spectra', n_fft, bool(reverse)), build)
 
@@ -1479,27 +1386,21 @@ def fftconvolve(x, y, n_fft=0, reverse=False, offset=0, out_len=None):
         rows = rows.contiguous()
     n_rows = int(rows.shape[0])
     hrow = _conv_row_map(y, lead)
-    h = _native.lib()
     route = fftconvolve_route(m, hrow is None, n_fft)
     with _native.on_device(x.device):
-        stream = _native.stream_ptr(x.device)
         if route == 'direct':
             bank, table = _conv_direct_bank(y, reverse, offset)
-            rc = h.tac_fftconvolve_direct_f32(_native.ptr(rows), n_rows, length, rows.stride(0), _native.ptr(bank),
-                                              _native.ptr(table), m, offset, out_len, _native.ptr(out), stream)
-            _native.check(rc, 'tac_fftconvolve_direct_f32')
-            _count('tac_fftconvolve_direct_f32', out)
+            _launch('tac_fftconvolve_direct_f32', x.device, (out,), _native.ptr(rows), n_rows, length, rows.stride(0),
+                    _native.ptr(bank), _native.ptr(table), m, offset, out_len, _native.ptr(out))
             return out
         spectra = _conv_spectra(y, route, reverse)
-        need = int(h.tac_fftconvolve_workspace(n_rows, length, m, route, offset, out_len))
+        need = int(_native.lib().tac_fftconvolve_workspace(n_rows, length, m, route, offset, out_len))
         if need < 0:
             _native.check(need, 'tac_fftconvolve_workspace')
         work = torch.empty(need // 4, dtype=torch.float32, device=x.device)      # scratch: every area is written before it is read
-        rc = h.tac_fftconvolve_f32(_native.ptr(rows), n_rows, length, rows.stride(0), _native.ptr(spectra),
-                                   None if hrow is None else _native.ptr(hrow), int(spectra.shape[0]), m, route, 0, offset,
-                                   out_len, _native.ptr(work), need, _native.ptr(out), out_len, stream)
-    _native.check(rc, 'tac_fftconvolve_f32')
-    _count('tac_fftconvolve_f32', out)
+        _launch('tac_fftconvolve_f32', x.device, (out,), _native.ptr(rows), n_rows, length, rows.stride(0), _native.ptr(spectra),
+                None if hrow is None else _native.ptr(hrow), int(spectra.shape[0]), m, route, 0, offset, out_len, _native.ptr(work),
+                need, _native.ptr(out), out_len)
     return out
 
 
@@ -1586,13 +1487,9 @@ def kaldi_mfcc(x, p, w, s, n, m):
     if not out.numel():
         return out
     rows = _kaldi_rows(x)
-    with _native.on_device(x.device):
-        rc = _native.lib().tac_kaldi_mfcc_f32(
-            _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0), _native.ptr(window), _native.ptr(weights),
-            _native.ptr(table), _native.ptr(dct), n, w, s, p.num_mel_bins, w_total, p.num_ceps, _kaldi_flags(p),
-            p.preemphasis_coefficient, p.energy_floor, _native.ptr(out), _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_kaldi_mfcc_f32')
-    _count('tac_kaldi_mfcc_f32', out)
+    _launch('tac_kaldi_mfcc_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0),
+            _native.ptr(window), _native.ptr(weights), _native.ptr(table), _native.ptr(dct), n, w, s, p.num_mel_bins, w_total,
+            p.num_ceps, _kaldi_flags(p), p.preemphasis_coefficient, p.energy_floor, _native.ptr(out))
     return out
 
 
@@ -1604,12 +1501,8 @@ def kaldi_spectrogram(x, p, w, s, n, m):
     if not out.numel():
         return out
     rows = _kaldi_rows(x)
-    with _native.on_device(x.device):
-        rc = _native.lib().tac_kaldi_spectrogram_f32(
-            _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0), _native.ptr(window), n, w, s, _kaldi_flags(p),
-            p.preemphasis_coefficient, p.energy_floor, _native.ptr(out), _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_kaldi_spectrogram_f32')
-    _count('tac_kaldi_spectrogram_f32', out)
+    _launch('tac_kaldi_spectrogram_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0),
+            _native.ptr(window), n, w, s, _kaldi_flags(p), p.preemphasis_coefficient, p.energy_floor, _native.ptr(out))
     return out
 
 
@@ -1624,14 +1517,9 @@ def kaldi_fbank(x, p, w, s, n, m):
     if not out.numel():
         return out
     rows = _kaldi_rows(x)
-    flags = _kaldi_flags(p)
-    with _native.on_device(x.device):
-        rc = _native.lib().tac_kaldi_fbank_f32(
-            _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(window), _native.ptr(weights), _native.ptr(table),
-            n, w, s, p.num_mel_bins, w_total, flags, p.preemphasis_coefficient, p.energy_floor, _native.ptr(out),
-            _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_kaldi_fbank_f32')
-    _count('tac_kaldi_fbank_f32', out)
+    _launch('tac_kaldi_fbank_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(window),
+            _native.ptr(weights), _native.ptr(table), n, w, s, p.num_mel_bins, w_total, _kaldi_flags(p), p.preemphasis_coefficient,
+            p.energy_floor, _native.ptr(out))
     return out
 
 
@@ -1667,13 +1555,9 @@ def sliding_cmn_rows(x, cmn_window, min_cmn_window, center, norm_vars, adjoint=F
     out = _empty(tuple(x.shape), device=x.device)
     if out.numel():
         rows = _rows3(x)
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_sliding_cmn_f32(
-                _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0), rows.stride(1), rows.stride(2),
-                cmn_window, min_cmn_window, int(bool(center)), int(bool(norm_vars)), int(bool(adjoint)), _native.ptr(out),
-                _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_sliding_cmn_f32')
-        _count('tac_sliding_cmn_f32', out)
+        _launch('tac_sliding_cmn_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2],
+                rows.stride(0), rows.stride(1), rows.stride(2), cmn_window, min_cmn_window, int(bool(center)), int(bool(norm_vars)),
+                int(bool(adjoint)), _native.ptr(out))
     return out
 
 
@@ -1694,12 +1578,8 @@ def deltas_rows(x, win_length, mode, adjoint=False):
     out = _empty(tuple(x.shape), device=x.device)
     if out.numel():
         rows = _rows3(x)
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_deltas_f32(
-                _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0), rows.stride(1), rows.stride(2),
-                win_length, DELTAS_MODES[mode], int(bool(adjoint)), _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_deltas_f32')
-        _count('tac_deltas_f32', out)
+        _launch('tac_deltas_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0),
+                rows.stride(1), rows.stride(2), win_length, DELTAS_MODES[mode], int(bool(adjoint)), _native.ptr(out))
     return out
 
 
@@ -1729,13 +1609,9 @@ def mask_spans_rows(x, spans, k_a, value_t=None, value=0.0):
             raise ValueError('mask_spans: spans must be a contiguous int32 (1 or %d, k, 2) tensor on %s' % (rows.shape[0], x.device))
         if value_t is not None and (value_t.dtype != torch.float32 or value_t.numel() != 1 or value_t.device != x.device):
             raise ValueError('mask_spans: the fill tensor must be one float32 element on %s' % x.device)
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_mask_spans_f32(
-                _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0), rows.stride(1), rows.stride(2),
-                _native.ptr(spans) if k else None, int(spans.shape[0]) if k else 1, k_a, k - k_a,
-                None if value_t is None else _native.ptr(value_t), float(value), _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_mask_spans_f32')
-        _count('tac_mask_spans_f32', out)
+        _launch('tac_mask_spans_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], rows.shape[1], rows.shape[2], rows.stride(0),
+                rows.stride(1), rows.stride(2), _native.ptr(spans) if k else None, int(spans.shape[0]) if k else 1, k_a, k - k_a,
+                None if value_t is None else _native.ptr(value_t), float(value), _native.ptr(out))
     return out
 
 
@@ -1839,10 +1715,7 @@ def add_noise_rows(waveform, noise, snr, lengths, lead):
     out = _empty(tuple(lead) + (int(waveform.shape[-1]),), device=waveform.device)
     if out.numel():
         args, keep = _add_noise_args((waveform, noise), snr, lengths, lead)
-        with _native.on_device(waveform.device):
-            rc = _native.lib().tac_add_noise_f32(*args, _native.ptr(out), _native.stream_ptr(waveform.device))
-        _native.check(rc, 'tac_add_noise_f32')
-        _count('tac_add_noise_f32', out)
+        _launch('tac_add_noise_f32', waveform.device, (out,), *args, _native.ptr(out))
     return out
 
 
@@ -1857,12 +1730,8 @@ def add_noise_grad_rows(grad_out, waveform, noise, snr, lengths, lead, needs):
     gs = _empty(tuple(lead), device=dev) if needs[2] else None
     if grad_out.numel() and any(needs):
         args, keep = _add_noise_args((grad_out, waveform, noise), snr, lengths, lead)
-        with _native.on_device(dev):
-            rc = _native.lib().tac_add_noise_grad_f32(
-                *args, None if gw is None else _native.ptr(gw), None if gn is None else _native.ptr(gn),
-                None if gs is None else _native.ptr(gs), _native.stream_ptr(dev))
-        _native.check(rc, 'tac_add_noise_grad_f32')
-        _count('tac_add_noise_grad_f32', gw, gn, gs)
+        _launch('tac_add_noise_grad_f32', dev, (gw, gn, gs), *args, None if gw is None else _native.ptr(gw),
+                None if gn is None else _native.ptr(gn), None if gs is None else _native.ptr(gs))
     return gw, gn, gs
 
 
@@ -1896,11 +1765,7 @@ def complex_norm(z, power):
     out = _pair_output(z)
     n = out.numel()
     if n:
-        with _native.on_device(z.device):
-            rc = _native.lib().tac_complex_norm_f32(_native.ptr(z), n, float(power), _native.ptr(out),
-                                                    _native.stream_ptr(z.device))
-        _native.check(rc, 'tac_complex_norm_f32')
-        _count('tac_complex_norm_f32', out)
+        _launch('tac_complex_norm_f32', z.device, (out,), _native.ptr(z), n, float(power), _native.ptr(out))
     return out
 
 
@@ -1908,11 +1773,7 @@ def angle(z):
     z = _pairs(z)
     phase = _pair_output(z)
     if phase.numel():
-        with _native.on_device(z.device):
-            rc = _native.lib().tac_magphase_f32(_native.ptr(z), phase.numel(), 1.0, None, _native.ptr(phase),
-                                                _native.stream_ptr(z.device))
-        _native.check(rc, 'tac_magphase_f32')
-        _count('tac_magphase_f32', phase)
+        _launch('tac_magphase_f32', z.device, (phase,), _native.ptr(z), phase.numel(), 1.0, None, _native.ptr(phase))
     return phase
 
 
@@ -1920,11 +1781,8 @@ def magphase(z, power):
     z = _pairs(z)
     mag, phase = _pair_output(z), _pair_output(z)
     if phase.numel():
-        with _native.on_device(z.device):
-            rc = _native.lib().tac_magphase_f32(_native.ptr(z), phase.numel(), float(power), _native.ptr(mag),
-                                                _native.ptr(phase), _native.stream_ptr(z.device))
-        _native.check(rc, 'tac_magphase_f32')
-        _count('tac_magphase_f32', mag, phase)
+        _launch('tac_magphase_f32', z.device, (mag, phase), _native.ptr(z), phase.numel(), float(power), _native.ptr(mag),
+                _native.ptr(phase))
     return mag, phase
 
 
@@ -1967,13 +1825,9 @@ def phase_vocoder(spec, rate, phase_advance):
     out = _empty(lead + (n_out, n_freqs, 2), dtype=dtype, device=spec.device)
     if out.numel() and n_frames:
         name = 'tac_phase_vocoder_f64' if dtype == torch.float64 else 'tac_phase_vocoder_f32'
-        with _native.on_device(spec.device):
-            rc = getattr(_native.lib(), name)(
-                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0) if rows.shape[0] > 1 else 0,
-                rows.stride(1), rows.stride(2), _native.ptr(pa), _native.ptr(idx0), _native.ptr(idx1),
-                _native.ptr(alpha), n_out, _native.ptr(out), _native.stream_ptr(spec.device))
-        _native.check(rc, name)
-        _count(name, out)
+        _launch(name, spec.device, (out,), _native.ptr(rows), rows.shape[0], n_freqs, n_frames,
+                rows.stride(0) if rows.shape[0] > 1 else 0, rows.stride(1), rows.stride(2), _native.ptr(pa), _native.ptr(idx0),
+                _native.ptr(idx1), _native.ptr(alpha), n_out, _native.ptr(out))
     return out.transpose(-3, -2)
 
 
@@ -1993,13 +1847,9 @@ def phase_vocoder_backward(spec, rate, grad_out):
     go.transpose(-3, -2).copy_(grad_out)
     gs = torch.zeros(lead + (n_frames, n_freqs, 2), dtype=torch.float32, device=spec.device)    # the kernel accumulates into it
     if go.numel() and n_frames:
-        with _native.on_device(spec.device):
-            rc = _native.lib().tac_phase_vocoder_backward_f32(
-                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0) if rows.shape[0] > 1 else 0,
-                rows.stride(1), rows.stride(2), _native.ptr(idx0), _native.ptr(idx1), _native.ptr(alpha), n_out,
-                _native.ptr(go), _native.ptr(gs), _native.stream_ptr(spec.device))
-        _native.check(rc, 'tac_phase_vocoder_backward_f32')
-        _count('tac_phase_vocoder_backward_f32')
+        _launch('tac_phase_vocoder_backward_f32', spec.device, (), _native.ptr(rows), rows.shape[0], n_freqs, n_frames,
+                rows.stride(0) if rows.shape[0] > 1 else 0, rows.stride(1), rows.stride(2), _native.ptr(idx0), _native.ptr(idx1),
+                _native.ptr(alpha), n_out, _native.ptr(go), _native.ptr(gs))
     return gs.transpose(-3, -2)
 
 
@@ -2064,13 +1914,9 @@ def stretch_norm(mag, rate, power, db, ref, amin):
         rows = _magnitude_rows(mag)
         stride_r, stride_t = _stretch_strides(rows)
         flags = torch.empty(rows.shape[0], dtype=torch.int32, device=mag.device)       # the kernels' workspace: one word per row
-        with _native.on_device(mag.device):
-            rc = _native.lib().tac_stretch_norm_f32(
-                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t, _native.ptr(idx0), _native.ptr(alpha),
-                n_out, float(power), 1 if db else 0, float(ref), float(amin), _native.ptr(out), _native.ptr(flags),
-                _native.stream_ptr(mag.device))
-        _native.check(rc, 'tac_stretch_norm_f32')
-        _count('tac_stretch_norm_f32', out)
+        _launch('tac_stretch_norm_f32', mag.device, (out,), _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t,
+                _native.ptr(idx0), _native.ptr(alpha), n_out, float(power), 1 if db else 0, float(ref), float(amin), _native.ptr(out),
+                _native.ptr(flags))
     return out.transpose(-2, -1)
 
 
@@ -2092,14 +1938,11 @@ def stretch_mel(mag, fb, rate, power, db, ref, amin):
         stride_r, stride_t = _stretch_strides(rows)
         out = _empty(lead + (n_out, n_mels), device=mag.device)
         flags = torch.empty(rows.shape[0], dtype=torch.int32, device=mag.device)
-        with _native.on_device(mag.device):
-            rc = _native.lib().tac_stretch_mel_f32(
-                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t, _native.ptr(idx0), _native.ptr(alpha),
-                n_out, float(power), _native.ptr(wpack), _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), n_mels,
-                1 if db else 0, float(ref), float(amin), _native.ptr(out), _native.ptr(flags), _native.stream_ptr(mag.device))
+        rc = _launch('tac_stretch_mel_f32', mag.device, (out,), _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t,
+                     _native.ptr(idx0), _native.ptr(alpha), n_out, float(power), _native.ptr(wpack), _native.ptr(desc),
+                     ctypes.cast(info, ctypes.c_void_p), n_mels, 1 if db else 0, float(ref), float(amin), _native.ptr(out),
+                     _native.ptr(flags), accept=_DECLINED)
         if rc != _native.TAC_E_UNSUPPORTED:
-            _native.check(rc, 'tac_stretch_mel_f32')
-            _count('tac_stretch_mel_f32', out)
             return out.transpose(-2, -1)
     spec = stretch_norm(mag, rate, power, False, 1.0, 1e-7)
     return apply_filterbank(spec, fb, db=(ref, amin) if db else None)
@@ -2118,34 +1961,27 @@ def stretch_norm_backward(mag, rate, power, grad_out):
         stride_r, stride_t = _stretch_strides(rows)
         go = torch.empty(lead + (n_out, n_freqs), dtype=torch.float32, device=mag.device)          # frame-major, dense
         go.transpose(-2, -1).copy_(grad_out)
-        with _native.on_device(mag.device):
-            rc = _native.lib().tac_stretch_norm_backward_f32(
-                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r, stride_t, _native.ptr(idx0), _native.ptr(alpha),
-                _native.ptr(bounds), n_out, float(power), _native.ptr(go), _native.ptr(gm), _native.stream_ptr(mag.device))
-        _native.check(rc, 'tac_stretch_norm_backward_f32')
-        _count('tac_stretch_norm_backward_f32', gm)
+        _launch('tac_stretch_norm_backward_f32', mag.device, (gm,), _native.ptr(rows), rows.shape[0], n_freqs, n_frames, stride_r,
+                stride_t, _native.ptr(idx0), _native.ptr(alpha), _native.ptr(bounds), n_out, float(power), _native.ptr(go),
+                _native.ptr(gm))
     return gm.transpose(-2, -1)
 
 
 # ----------------------------------------------------------------------------- elementwise
-def _unary(x, name, launch):
+def _unary(x, name, *params):
     x = x if is_dense(x) else x.contiguous()
     out = _empty_like(x)
     if x.numel():
-        with _native.on_device(x.device):
-            rc = launch(_native.lib(), _native.ptr(x), x.numel(), _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, name)
-        _count(name, out)
+        _launch(name, x.device, (out,), _native.ptr(x), x.numel(), *params, _native.ptr(out))
     return out
 
 
 def amplitude_to_db(x, ref, amin):
-    return _unary(x, 'tac_amplitude_to_db_f32',
-                  lambda h, p, n, o, s: h.tac_amplitude_to_db_f32(p, n, float(ref), float(amin), o, s))
+    return _unary(x, 'tac_amplitude_to_db_f32', float(ref), float(amin))
 
 
 def db_to_amplitude(x, ref):
-    return _unary(x, 'tac_db_to_amplitude_f32', lambda h, p, n, o, s: h.tac_db_to_amplitude_f32(p, n, float(ref), o, s))
+    return _unary(x, 'tac_db_to_amplitude_f32', float(ref))
 
 
 _mulaw_consts = {}
@@ -2173,11 +2009,8 @@ def mu_law_encoding(x, n_quantize):
             thr_ptr = _native.ptr(thr)
         else:
             thr_ptr, n_pos, n_neg, zero = None, 0, 0, 0
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_mulaw_encode_f32_i64(_native.ptr(x), x.numel(), n_quantize, thr_ptr, n_pos, n_neg,
-                                                        zero, _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_mulaw_encode_f32_i64')
-        _count('tac_mulaw_encode_f32_i64', out)
+        _launch('tac_mulaw_encode_f32_i64', x.device, (out,), _native.ptr(x), x.numel(), n_quantize, thr_ptr, n_pos, n_neg, zero,
+                _native.ptr(out))
     return out
 
 
@@ -2187,11 +2020,8 @@ def mu_law_decoding_int(codes, n_quantize):
     out = _empty(codes.shape, device=codes.device)
     if codes.numel():
         lut_ptr = _native.ptr(_mulaw_tables(codes.device)[4]) if n_quantize == 256 else None
-        with _native.on_device(codes.device):
-            rc = _native.lib().tac_mulaw_decode_i64_f32(_native.ptr(codes), codes.numel(), n_quantize, lut_ptr,
-                                                        _native.ptr(out), _native.stream_ptr(codes.device))
-        _native.check(rc, 'tac_mulaw_decode_i64_f32')
-        _count('tac_mulaw_decode_i64_f32', out)
+        _launch('tac_mulaw_decode_i64_f32', codes.device, (out,), _native.ptr(codes), codes.numel(), n_quantize, lut_ptr,
+                _native.ptr(out))
     return out
 
 
@@ -2200,9 +2030,7 @@ def mu_law_decoding_float(codes, n_quantize):
     table (bit-exact, what reference tests/test_functional.py:182-193 bit-compares), everything else from the
     closed form."""
     lut = _mulaw_tables(codes.device)[4] if n_quantize == 256 else None
-    return _unary(codes, 'tac_mulaw_decode_f32_f32',
-                  lambda h, p, n, o, s: h.tac_mulaw_decode_f32_f32(p, n, n_quantize,
-                                                                   None if lut is None else _native.ptr(lut), o, s))
+    return _unary(codes, 'tac_mulaw_decode_f32_f32', n_quantize, None if lut is None else _native.ptr(lut))
 
 
 def mu_law_encoding_f64(x, n_quantize):
@@ -2210,11 +2038,7 @@ def mu_law_encoding_f64(x, n_quantize):
     x = x if x.is_contiguous() else x.contiguous()
     out = _empty(x.shape, dtype=torch.int64, device=x.device)
     if x.numel():
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_mulaw_encode_f64_i64(_native.ptr(x), x.numel(), n_quantize, _native.ptr(out),
-                                                        _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_mulaw_encode_f64_i64')
-        _count('tac_mulaw_encode_f64_i64', out)
+        _launch('tac_mulaw_encode_f64_i64', x.device, (out,), _native.ptr(x), x.numel(), n_quantize, _native.ptr(out))
     return out
 
 
@@ -2223,11 +2047,8 @@ def mu_law_decoding_f64(codes, n_quantize):
     codes = codes if codes.is_contiguous() else codes.contiguous()
     out = _empty(codes.shape, dtype=torch.float64, device=codes.device)
     if codes.numel():
-        with _native.on_device(codes.device):
-            rc = _native.lib().tac_mulaw_decode_f64(_native.ptr(codes), 1 if codes.dtype == torch.int64 else 0, codes.numel(),
-                                                    n_quantize, _native.ptr(out), _native.stream_ptr(codes.device))
-        _native.check(rc, 'tac_mulaw_decode_f64')
-        _count('tac_mulaw_decode_f64', out)
+        _launch('tac_mulaw_decode_f64', codes.device, (out,), _native.ptr(codes), 1 if codes.dtype == torch.int64 else 0,
+                codes.numel(), n_quantize, _native.ptr(out))
     return out
 
 
@@ -2284,13 +2105,9 @@ def apply_filterbank_backward(grad_out, fb):
         if gm.dtype != torch.float32:
             gm = gm.float()
         out = _empty(tuple(gm.shape[:-1]) + (n_freqs,), device=gm.device)
-        with _native.on_device(gm.device):
-            rc = _native.lib().tac_apply_filterbank_adjoint_f32(_native.ptr(gm), gm.numel() // n_mels, n_mels,
-                                                                _native.ptr(table), n_freqs, _native.ptr(out),
-                                                                _native.stream_ptr(gm.device))
+        rc = _launch('tac_apply_filterbank_adjoint_f32', gm.device, (out,), _native.ptr(gm), gm.numel() // n_mels, n_mels,
+                     _native.ptr(table), n_freqs, _native.ptr(out), accept=_DECLINED)
         if rc != _native.TAC_E_UNSUPPORTED:
-            _native.check(rc, 'tac_apply_filterbank_adjoint_f32')
-            _count('tac_apply_filterbank_adjoint_f32', out)
             return out.transpose(-2, -1)
     return apply_filterbank(grad_out, transposed_bank(fb), allow_sparse=False)
 
@@ -2329,16 +2146,10 @@ def _melspectrogram_backward_ola(grad_mel, wave, window, fb, n_fft, hop, win_len
         gm = gm.float()
     out = _empty(tuple(wave.shape), device=wave.device)
     work = _empty(max(int(need), 4) // 4, device=wave.device)          # (scratch: poisoned, not checked)
-    with _native.on_device(wave.device):
-        rc = _native.lib().tac_melspectrogram_backward_ola_f32(
-            _native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc, _native.ptr(gm), n_mels, _native.ptr(table),
-            n_freqs, float(power), _native.ptr(work), int(need), _native.ptr(out), g.length,
-            _native.stream_ptr(wave.device))
-    if rc == _native.TAC_E_UNSUPPORTED:
-        return None
-    _native.check(rc, 'tac_melspectrogram_backward_ola_f32')
-    _count('tac_melspectrogram_backward_ola_f32', out)
-    return out
+    rc = _launch('tac_melspectrogram_backward_ola_f32', wave.device, (out,), _native.ptr(_rows_of(wave, g)), _native.ptr(window),
+                 g.desc, _native.ptr(gm), n_mels, _native.ptr(table), n_freqs, float(power), _native.ptr(work), int(need),
+                 _native.ptr(out), g.length, accept=_DECLINED)
+    return None if rc == _native.TAC_E_UNSUPPORTED else out
 
 
 def _melspectrogram_backward_fused_n400(grad_mel, wave, window, fb, hop, win_length, center, pad_mode, normalized, power):
@@ -2361,17 +2172,12 @@ def _melspectrogram_backward_fused_n400(grad_mel, wave, window, fb, hop, win_len
                             center=1 if center else 0, pad_mode=_native.PAD_MODES[pad_mode],
                             normalized=1 if normalized else 0, onesided=1, reserved=0)
     with _native.on_device(wave.device):
-        rc = _native.lib().tac_melspectrogram_backward_f32(
-            _native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc, _native.ptr(gm), n_mels, _native.ptr(table), n_freqs,
-            float(power), _native.ptr(frames), _native.stream_ptr(wave.device))
+        rc = _launch('tac_melspectrogram_backward_f32', wave.device, (frames,), _native.ptr(_rows_of(wave, g)), _native.ptr(window),
+                     g.desc, _native.ptr(gm), n_mels, _native.ptr(table), n_freqs, float(power), _native.ptr(frames),
+                     accept=_DECLINED)
         if rc == _native.TAC_E_UNSUPPORTED:
             return None
-        _native.check(rc, 'tac_melspectrogram_backward_f32')
-        _count('tac_melspectrogram_backward_f32', frames)
-        rc = _native.lib().tac_overlap_add_f32(_native.ptr(frames), desc, _native.ptr(out), g.length,
-                                               _native.stream_ptr(wave.device))
-        _native.check(rc, 'tac_overlap_add_f32')
-        _count('tac_overlap_add_f32', out)
+        _launch('tac_overlap_add_f32', wave.device, (out,), _native.ptr(frames), desc, _native.ptr(out), g.length)
     return out
 
 
@@ -2401,39 +2207,26 @@ def stft_backward(grad_spec, wave, window, n_fft, hop, win_length, center, pad_m
         need = _native.lib().tac_spectrogram_backward_ola_workspace(g.desc)
         if need >= 0:
             work = _empty(max(int(need), 4) // 4, device=wave.device)  # (scratch: poisoned, not checked)
-            with _native.on_device(wave.device):
-                rc = _native.lib().tac_spectrogram_backward_ola_f32(
-                    _native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc, _native.ptr(gn), float(power),
-                    _native.ptr(work), int(need), _native.ptr(out), g.length, _native.stream_ptr(wave.device))
+            rc = _launch('tac_spectrogram_backward_ola_f32', wave.device, (out,), _native.ptr(_rows_of(wave, g)), _native.ptr(window),
+                         g.desc, _native.ptr(gn), float(power), _native.ptr(work), int(need), _native.ptr(out), g.length,
+                         accept=_DECLINED)
             if rc != _native.TAC_E_UNSUPPORTED:
-                _native.check(rc, 'tac_spectrogram_backward_ola_f32')
-                _count('tac_spectrogram_backward_ola_f32', out)
                 return out
     frames = _empty((g.rows, g.n_frames, n_fft), device=wave.device)
     desc = _native.StftDesc(rows=g.rows, length=g.length, row_stride=g.length, n_fft=n_fft, hop=hop,
                             win_length=win_length, center=1 if center else 0, pad_mode=_native.PAD_MODES[pad_mode],
                             normalized=1 if normalized else 0, onesided=1, reserved=0)
-    with _native.on_device(wave.device):
+    dev = wave.device
+    with _native.on_device(dev):
         if gn is None:
-            rc = _native.lib().tac_stft_backward_f32(_native.ptr(gs), _native.ptr(window), desc, _native.ptr(frames),
-                                                     _native.stream_ptr(wave.device))
-            _native.check(rc, 'tac_stft_backward_f32')
-            _count('tac_stft_backward_f32', frames)
+            _launch('tac_stft_backward_f32', dev, (frames,), _native.ptr(gs), _native.ptr(window), desc, _native.ptr(frames))
         elif gs is None:
-            rc = _native.lib().tac_spectrogram_backward_f32(_native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc,
-                                                            _native.ptr(gn), float(power), _native.ptr(frames),
-                                                            _native.stream_ptr(wave.device))
-            _native.check(rc, 'tac_spectrogram_backward_f32')
-            _count('tac_spectrogram_backward_f32', frames)
+            _launch('tac_spectrogram_backward_f32', dev, (frames,), _native.ptr(_rows_of(wave, g)), _native.ptr(window), g.desc,
+                    _native.ptr(gn), float(power), _native.ptr(frames))
         else:
-            rc = _native.lib().tac_stft_norm_backward_f32(_native.ptr(gs), _native.ptr(gn), float(power), _native.ptr(window),
-                                                          desc, _native.ptr(frames), _native.stream_ptr(wave.device))
-            _native.check(rc, 'tac_stft_norm_backward_f32')
-            _count('tac_stft_norm_backward_f32', frames)
-        rc = _native.lib().tac_overlap_add_f32(_native.ptr(frames), desc, _native.ptr(out), g.length,
-                                               _native.stream_ptr(wave.device))
-        _native.check(rc, 'tac_overlap_add_f32')
-        _count('tac_overlap_add_f32', out)
+            _launch('tac_stft_norm_backward_f32', dev, (frames,), _native.ptr(gs), _native.ptr(gn), float(power),
+                    _native.ptr(window), desc, _native.ptr(frames))
+        _launch('tac_overlap_add_f32', dev, (out,), _native.ptr(frames), desc, _native.ptr(out), g.length)
     return out
 
 
@@ -2449,22 +2242,14 @@ def fold_twosided(grad, n_fft, width):
     lead = tuple(grad.shape[:-2]) if width == 2 else tuple(grad.shape[:-1])
     out = _empty(lead + ((n_bins, 2) if width == 2 else (n_bins,)), device=grad.device)
     frames = out.numel() // (n_bins * width)
-    with _native.on_device(grad.device):
-        rc = _native.lib().tac_fold_twosided_f32(_native.ptr(grad), frames, n_fft, width, _native.ptr(out),
-                                                 _native.stream_ptr(grad.device))
-    _native.check(rc, 'tac_fold_twosided_f32')
-    _count('tac_fold_twosided_f32', out)
+    _launch('tac_fold_twosided_f32', grad.device, (out,), _native.ptr(grad), frames, n_fft, width, _native.ptr(out))
     return out
 
 
 def sum_slabs(x):
     """(S, ...) -> (...): the slabs added up in order (deterministic)."""
     out = _empty(tuple(x.shape[1:]), device=x.device)
-    with _native.on_device(x.device):
-        rc = _native.lib().tac_sum_slabs_f32(_native.ptr(x), x.shape[0], out.numel(), _native.ptr(out),
-                                             _native.stream_ptr(x.device))
-    _native.check(rc, 'tac_sum_slabs_f32')
-    _count('tac_sum_slabs_f32', out)
+    _launch('tac_sum_slabs_f32', x.device, (out,), _native.ptr(x), x.shape[0], out.numel(), _native.ptr(out))
     return out
 
 
@@ -2507,18 +2292,13 @@ def _frame_gradients(gs, window, g):
     frames = _empty((g.rows, g.n_frames, g.n_fft), device=gs.device)
     with _native.on_device(gs.device):
         if fft_kernel_size(g.n_fft) or g.mixed_radix or smooth_fft_size(g.n_fft) or g.n_fft == 8192:
-            rc = _native.lib().tac_stft_backward_f32(_native.ptr(gs), _native.ptr(window), _desc(g, onesided=1),
-                                                     _native.ptr(frames), _native.stream_ptr(gs.device))
-            _native.check(rc, 'tac_stft_backward_f32')
-            _count('tac_stft_backward_f32', frames)
+            _launch('tac_stft_backward_f32', gs.device, (frames,), _native.ptr(gs), _native.ptr(window), _desc(g, onesided=1),
+                    _native.ptr(frames))
         else:
             n_cols = 2 * (g.n_fft // 2 + 1)
             mat_t = _dft_matrix_t(window, g.n_fft, g.win_length, g.normalized)
-            rc = _native.lib().tac_apply_filterbank_f32(
-                _native.ptr(gs), g.rows, n_cols, g.n_frames, g.n_frames * n_cols, 1, n_cols, _native.ptr(mat_t), None,
-                g.n_fft, _native.ptr(frames), _native.stream_ptr(gs.device))
-            _native.check(rc, 'tac_apply_filterbank_f32 (DFT matrix, adjoint)')
-            _count('tac_apply_filterbank_f32', frames)
+            _launch('tac_apply_filterbank_f32', gs.device, (frames,), _native.ptr(gs), g.rows, n_cols, g.n_frames,
+                    g.n_frames * n_cols, 1, n_cols, _native.ptr(mat_t), None, g.n_fft, _native.ptr(frames))
     return frames
 
 
@@ -2537,11 +2317,7 @@ def stft_backward_general(grad_spec, wave, window, n_fft, hop, win_length, cente
     if need_wave:
         frames = _frame_gradients(gs, window, g)
         grad_wave = _empty(tuple(wave.shape), device=dev)
-        with _native.on_device(dev):
-            rc = _native.lib().tac_overlap_add_f32(_native.ptr(frames), _desc(g), _native.ptr(grad_wave), g.length,
-                                                   _native.stream_ptr(dev))
-        _native.check(rc, 'tac_overlap_add_f32')
-        _count('tac_overlap_add_f32', grad_wave)
+        _launch('tac_overlap_add_f32', dev, (grad_wave,), _native.ptr(frames), _desc(g), _native.ptr(grad_wave), g.length)
         del frames
     if need_window:
         unwindowed = _frame_gradients(gs, _ones_window(dev, win_length), g)
@@ -2551,11 +2327,7 @@ def stft_backward_general(grad_spec, wave, window, n_fft, hop, win_length, cente
         if n_part < 0:
             _native.check(n_part, 'tac_window_grad_partials')
         partial = _empty((n_part, n_fft), device=dev)
-        with _native.on_device(dev):
-            rc = _native.lib().tac_window_grad_f32(_native.ptr(unwindowed), _native.ptr(src), desc, _native.ptr(partial),
-                                                   n_part, _native.stream_ptr(dev))
-        _native.check(rc, 'tac_window_grad_f32')
-        _count('tac_window_grad_f32', partial)
+        _launch('tac_window_grad_f32', dev, (partial,), _native.ptr(unwindowed), _native.ptr(src), desc, _native.ptr(partial), n_part)
         off = (n_fft - win_length) // 2
         grad_window = sum_slabs(partial)[off:off + win_length]
     return grad_wave, grad_window
@@ -2575,11 +2347,8 @@ def filterbank_grad(spec, grad_out):
     out = _empty((n_freqs, n_mels), device=sp.device)
     if total == 0:
         return out.zero_()
-    with _native.on_device(sp.device):
-        rc = _native.lib().tac_apply_filterbank_f32(_native.ptr(sp), 1, total, n_freqs, 0, n_freqs, 1, _native.ptr(gm), None,
-                                                    n_mels, _native.ptr(out), _native.stream_ptr(sp.device))
-    _native.check(rc, 'tac_apply_filterbank_f32 (filterbank gradient)')
-    _count('tac_apply_filterbank_f32', out)
+    _launch('tac_apply_filterbank_f32', sp.device, (out,), _native.ptr(sp), 1, total, n_freqs, 0, n_freqs, 1, _native.ptr(gm), None,
+            n_mels, _native.ptr(out))
     return out
 
 
@@ -2608,11 +2377,7 @@ def complex_norm_backward(z, grad_out, power):
     gz = _empty_strided(z.shape, z.stride(), device=z.device)
     n = go.numel()
     if n:
-        with _native.on_device(z.device):
-            rc = _native.lib().tac_complex_norm_backward_f32(_native.ptr(z), _native.ptr(go), n, float(power),
-                                                             _native.ptr(gz), _native.stream_ptr(z.device))
-        _native.check(rc, 'tac_complex_norm_backward_f32')
-        _count('tac_complex_norm_backward_f32', gz)
+        _launch('tac_complex_norm_backward_f32', z.device, (gz,), _native.ptr(z), _native.ptr(go), n, float(power), _native.ptr(gz))
     return gz
 
 
@@ -2632,12 +2397,8 @@ def magphase_backward(z, grad_mag, grad_phase, power):
     gz = _empty_strided(z.shape, z.stride(), device=z.device)
     n = z.numel() // 2
     if n:
-        with _native.on_device(z.device):
-            rc = _native.lib().tac_magphase_backward_f32(_native.ptr(z), None if gm is None else _native.ptr(gm),
-                                                         None if gp is None else _native.ptr(gp), n, float(power),
-                                                         _native.ptr(gz), _native.stream_ptr(z.device))
-        _native.check(rc, 'tac_magphase_backward_f32')
-        _count('tac_magphase_backward_f32', gz)
+        _launch('tac_magphase_backward_f32', z.device, (gz,), _native.ptr(z), None if gm is None else _native.ptr(gm),
+                None if gp is None else _native.ptr(gp), n, float(power), _native.ptr(gz))
     return gz
 
 
@@ -2650,11 +2411,8 @@ def db_to_amplitude_backward(x, grad_out, ref):
         go.copy_(grad_out)
     gx = _empty_like(x)
     if x.numel():
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_db_to_amplitude_backward_f32(_native.ptr(x), _native.ptr(go), x.numel(), float(ref),
-                                                                _native.ptr(gx), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_db_to_amplitude_backward_f32')
-        _count('tac_db_to_amplitude_backward_f32', gx)
+        _launch('tac_db_to_amplitude_backward_f32', x.device, (gx,), _native.ptr(x), _native.ptr(go), x.numel(), float(ref),
+                _native.ptr(gx))
     return gx
 
 
@@ -2667,11 +2425,8 @@ def amplitude_to_db_backward(x, grad_out, amin):
         go.copy_(grad_out)
     gx = _empty_like(x)
     if x.numel():
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_amplitude_to_db_backward_f32(_native.ptr(x), _native.ptr(go), x.numel(), float(amin),
-                                                                _native.ptr(gx), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_amplitude_to_db_backward_f32')
-        _count('tac_amplitude_to_db_backward_f32', gx)
+        _launch('tac_amplitude_to_db_backward_f32', x.device, (gx,), _native.ptr(x), _native.ptr(go), x.numel(), float(amin),
+                _native.ptr(gx))
     return gx
 
 
@@ -2692,15 +2447,10 @@ def hpss(mag, kernel_f, kernel_t, power, hard, masks_only=False):
     outs = [_empty_like(mag) for _ in range(2 if masks_only else 4)]
     if mag.numel():
         null = ctypes.c_void_p(0)
-        with _native.on_device(mag.device):
-            rc = _native.lib().tac_hpss_f32(_native.ptr(rows), rows.shape[0], n_freqs, n_frames,
-                                            rows.stride(0) if rows.shape[0] > 1 else 0, rows.stride(1), rows.stride(2),
-                                            kernel_f, kernel_t, float(power), 1 if hard else 0,
-                                            null if masks_only else _native.ptr(outs[0]),
-                                            null if masks_only else _native.ptr(outs[1]), _native.ptr(outs[-2]),
-                                            _native.ptr(outs[-1]), _native.stream_ptr(mag.device))
-        _native.check(rc, 'tac_hpss_f32')
-        _count('tac_hpss_f32', *outs)
+        _launch('tac_hpss_f32', mag.device, outs, _native.ptr(rows), rows.shape[0], n_freqs, n_frames,
+                rows.stride(0) if rows.shape[0] > 1 else 0, rows.stride(1), rows.stride(2), kernel_f, kernel_t, float(power),
+                1 if hard else 0, null if masks_only else _native.ptr(outs[0]), null if masks_only else _native.ptr(outs[1]),
+                _native.ptr(outs[-2]), _native.ptr(outs[-1]))
     return tuple(outs)
 
 
@@ -2726,13 +2476,9 @@ def hpss_backward(mag, kernel_f, kernel_t, power, hard, grads):
     gmag = torch.zeros_like(mag)                                   # the kernel accumulates into it
     if mag.numel():
         null = ctypes.c_void_p(0)
-        with _native.on_device(mag.device):
-            rc = _native.lib().tac_hpss_backward_f32(
-                _native.ptr(rows), rows.shape[0], n_freqs, n_frames, rows.stride(0) if rows.shape[0] > 1 else 0, rows.stride(1),
-                rows.stride(2), kernel_f, kernel_t, float(power), 1 if hard else 0,
-                *[null if g is None else _native.ptr(g) for g in gs], _native.ptr(gmag), _native.stream_ptr(mag.device))
-        _native.check(rc, 'tac_hpss_backward_f32')
-        _count('tac_hpss_backward_f32')
+        _launch('tac_hpss_backward_f32', mag.device, (), _native.ptr(rows), rows.shape[0], n_freqs, n_frames,
+                rows.stride(0) if rows.shape[0] > 1 else 0, rows.stride(1), rows.stride(2), kernel_f, kernel_t, float(power),
+                1 if hard else 0, *[null if g is None else _native.ptr(g) for g in gs], _native.ptr(gmag))
     return gmag
 
 
@@ -2742,10 +2488,7 @@ def pcm16_to_f32(x):
     x = x if x.is_contiguous() else x.contiguous()
     out = _empty(x.shape, device=x.device)
     if x.numel():
-        with _native.on_device(x.device):
-            rc = _native.lib().tac_pcm16_to_f32(_native.ptr(x), x.numel(), _native.ptr(out), _native.stream_ptr(x.device))
-        _native.check(rc, 'tac_pcm16_to_f32')
-        _count('tac_pcm16_to_f32', out)
+        _launch('tac_pcm16_to_f32', x.device, (out,), _native.ptr(x), x.numel(), _native.ptr(out))
     return out
 
 
@@ -2772,13 +2515,8 @@ def melspectrogram_coded(samples, window, fb, n_fft, hop, win_length, center, pa
     lut = _mulaw_tables(samples.device)[4] if fmt != _native.SAMPLES_I16 else None
     src = _rows_of(samples, g)
     out = _empty(g.lead + (g.n_frames, fb.shape[1]), device=samples.device)
-    with _native.on_device(samples.device):
-        rc = _native.lib().tac_melspec_sparse_coded_f32(
-            _native.ptr(src), fmt, None if lut is None else _native.ptr(lut), _native.ptr(window), g.desc, float(power),
-            _native.ptr(wpack), _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), fb.shape[1], 1 if db else 0,
-            float(ref), float(amin), _native.ptr(out), _native.stream_ptr(samples.device))
-    if rc == _native.TAC_E_UNSUPPORTED:
-        return None
-    _native.check(rc, 'tac_melspec_sparse_coded_f32')
-    _count('tac_melspec_sparse_coded_f32', out)
-    return out.transpose(-2, -1)
+    rc = _launch('tac_melspec_sparse_coded_f32', samples.device, (out,), _native.ptr(src), fmt,
+                 None if lut is None else _native.ptr(lut), _native.ptr(window), g.desc, float(power), _native.ptr(wpack),
+                 _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), fb.shape[1], 1 if db else 0, float(ref), float(amin),
+                 _native.ptr(out), accept=_DECLINED)
+    return None if rc == _native.TAC_E_UNSUPPORTED else out.transpose(-2, -1)

@@ -10,6 +10,7 @@ import torch
 
 from . import _hip as H
 from . import _native
+from ._hip import _launch
 
 _F64 = torch.float64
 
@@ -52,14 +53,6 @@ def _desc(g):
 
 def _empty(shape, device):
     return H._empty(shape, dtype=_F64, device=device)
-
-
-def _launch(name, dev, filled, *args):
-    """One launch of ``name``; ``filled``: the tensors (or slices) it fills, checked for poison while that is on."""
-    with _native.on_device(dev):
-        rc = getattr(_native.lib(), name)(*args, _native.stream_ptr(dev))
-    _native.check(rc, name)
-    H._count(name, *filled)
 
 
 def stft(wave, window, n_fft, hop, win_length, center, pad_mode, normalized, onesided):

@@ -24,33 +24,6 @@ TAC_E_LAUNCH = -4
 PAD_MODES = {'constant': 0, 'reflect': 1, 'replicate': 2, 'circular': 3}
 SAMPLES_F32, SAMPLES_I16, SAMPLES_MULAW_U8, SAMPLES_MULAW_I64 = 0, 1, 2, 3
 
-EXPORTS = (
-    'tac_strerror', 'tac_last_hip_error', 'tac_abi_version', 'tac_num_frames', 'tac_num_bins',
-    'tac_stft_f32', 'tac_spectrogram_f32', 'tac_melspec_f32', 'tac_melspec_supported', 'tac_filterbank_plan',
-    'tac_melbank_pack', 'tac_melbank_pack_host', 'tac_melspec_sparse_f32',
-    'tac_apply_filterbank_f32', 'tac_apply_filterbank_sparse_f32', 'tac_apply_filterbank_sparse_db_f32', 'tac_complex_norm_f32', 'tac_magphase_f32', 'tac_phase_vocoder_f32', 'tac_phase_vocoder_f64', 'tac_phase_vocoder_backward_f32', 'tac_amplitude_to_db_f32',
-    'tac_stretch_norm_f32', 'tac_stretch_mel_f32', 'tac_stretch_norm_backward_f32',
-    'tac_db_to_amplitude_f32', 'tac_mulaw_encode_f32_i64', 'tac_mulaw_decode_i64_f32',
-    'tac_mulaw_decode_f32_f32', 'tac_mulaw_encode_f64_i64', 'tac_mulaw_decode_f64',
-    'tac_stft_backward_f32', 'tac_stft_norm_backward_f32', 'tac_spectrogram_backward_f32', 'tac_spectrogram_backward_ola_workspace', 'tac_spectrogram_backward_ola_f32', 'tac_melspectrogram_backward_ola_f32', 'tac_melspectrogram_backward_f32', 'tac_filterbank_adjoint_pack', 'tac_apply_filterbank_adjoint_f32', 'tac_overlap_add_f32', 'tac_complex_norm_backward_f32', 'tac_amplitude_to_db_backward_f32', 'tac_magphase_backward_f32', 'tac_db_to_amplitude_backward_f32', 'tac_hpss_f32', 'tac_hpss_backward_f32', 'tac_melspec_sparse_coded_f32', 'tac_pcm16_to_f32',
-    'tac_fold_twosided_f32', 'tac_window_grad_partials', 'tac_window_grad_f32', 'tac_sum_slabs_f32',
-    'tac_stft_f64', 'tac_spectrogram_f64', 'tac_apply_filterbank_f64', 'tac_magphase_f64', 'tac_amplitude_to_db_f64',
-    'tac_db_to_amplitude_f64',
-    'tac_last_route', 'tac_debug_clock_probe', 'tac_melbank_plan_pieces_host', 'tac_set_fft_pipe',
-    'tac_istft_workspace', 'tac_istft_envelope_f32', 'tac_istft_f32', 'tac_istft_grad_input_f32', 'tac_istft_grad_bins_f32',
-    'tac_dct_rows_f32', 'tac_polyphase_f32', 'tac_lfilter_chunk', 'tac_lfilter_supported', 'tac_lfilter_f32',
-    'tac_spectral_mac_tile', 'tac_spectral_mac_f32', 'tac_fftconvolve_default_n_fft', 'tac_fftconvolve_supported',
-    'tac_fftconvolve_spectra_workspace', 'tac_fftconvolve_spectra_f32', 'tac_fftconvolve_workspace', 'tac_fftconvolve_f32',
-    'tac_fftconvolve_direct_f32', 'tac_kaldi_num_frames', 'tac_kaldi_fbank_f32',
-    'tac_kaldi_mfcc_table_limit', 'tac_kaldi_mfcc_f32', 'tac_kaldi_spectrogram_f32',
-    'tac_sliding_cmn_chunk', 'tac_sliding_cmn_f32', 'tac_deltas_supported', 'tac_deltas_f32',
-    'tac_mask_spans_supported', 'tac_mask_spans_f32',
-    'tac_add_noise_tile', 'tac_add_noise_work_bytes', 'tac_add_noise_f32', 'tac_add_noise_grad_f32',
-    'tac_loudness_tile', 'tac_loudness_work_bytes', 'tac_loudness_f32',
-    'tac_pitch_max_win', 'tac_pitch_plan', 'tac_pitch_lags_f32', 'tac_pitch_smooth_i32', 'tac_pitch_frequency_f32',
-    'tac_psd_plan', 'tac_beamform_grid', 'tac_psd_f32', 'tac_mvdr_weights_souden_f32', 'tac_apply_beamforming_f32', 'tac_mvdr_souden_f32',
-    'tac_rtf_power_max_iter', 'tac_rtf_evd_f32', 'tac_rtf_power_f32', 'tac_mvdr_weights_rtf_f32', 'tac_rtf_mvdr_f32',
-)
 ABI_VERSION = 5          # tac_abi_version() of the library this binding was written against (csrc/host_common.hip)
 
 
@@ -60,6 +33,143 @@ class StftDesc(ctypes.Structure):
                 ('n_fft', ctypes.c_int32), ('hop', ctypes.c_int32), ('win_length', ctypes.c_int32),
                 ('center', ctypes.c_int32), ('pad_mode', ctypes.c_int32), ('normalized', ctypes.c_int32),
                 ('onesided', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+_P = ctypes.c_void_p
+_I32 = ctypes.c_int32
+_I64 = ctypes.c_int64
+_F = ctypes.c_float
+_D = ctypes.c_double
+_DESC = ctypes.POINTER(StftDesc)
+_INT = ctypes.c_int
+_STR = ctypes.c_char_p
+
+_SPEC = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _I64]          # spec, batch, channels, bins, frames, four strides
+_MASK = [_P, _I64, _I64, _I64]
+
+#: the C ABI of include/tac_amd.h, once: entry point -> (restype, argtypes).  ``lib()`` applies it to the loaded library;
+#: tests/test_abi_table_cpu.py holds every entry to the header's declaration.
+PROTOTYPES = {
+    'tac_strerror': (_STR, [_INT]),
+    'tac_last_hip_error': (_INT, []),
+    'tac_abi_version': (_INT, []),
+    'tac_num_frames': (_I64, [_I64, _INT, _INT, _INT]),
+    'tac_num_bins': (_INT, [_INT, _INT]),
+    'tac_stft_f32': (_INT, [_P, _P, _DESC, _P, _P]),
+    'tac_spectrogram_f32': (_INT, [_P, _P, _DESC, _F, _INT, _F, _F, _P, _P]),
+    'tac_melspec_f32': (_INT, [_P, _P, _DESC, _F, _P, _P, _I32, _INT, _F, _F, _P, _P]),
+    'tac_melspec_supported': (_INT, [_DESC, _F, _P, _I32]),
+    'tac_filterbank_plan': (_INT, [_P, _I32, _I32, _P, _P, _P]),
+    'tac_melbank_pack': (_INT, [_P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P]),
+    'tac_melbank_pack_host': (_INT, [_P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P]),
+    'tac_melspec_sparse_f32': (_INT, [_P, _P, _DESC, _F, _P, _P, _P, _I32, _INT, _F, _F, _P, _P]),
+    'tac_apply_filterbank_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _I32, _P, _P]),
+    'tac_apply_filterbank_sparse_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _I32, _P, _P]),
+    'tac_apply_filterbank_sparse_db_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _I32, _INT, _F, _F, _P, _P]),
+    'tac_complex_norm_f32': (_INT, [_P, _I64, _F, _P, _P]),
+    'tac_magphase_f32': (_INT, [_P, _I64, _F, _P, _P, _P]),
+    'tac_phase_vocoder_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P]),
+    'tac_phase_vocoder_f64': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P]),
+    'tac_phase_vocoder_backward_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P]),
+    'tac_amplitude_to_db_f32': (_INT, [_P, _I64, _F, _F, _P, _P]),
+    'tac_stretch_norm_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _I64, _F, _INT, _F, _F, _P, _P, _P]),
+    'tac_stretch_mel_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _I64, _F, _P, _P, _P, _I32, _INT, _F, _F, _P, _P, _P]),
+    'tac_stretch_norm_backward_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _I64, _F, _P, _P, _P]),
+    'tac_db_to_amplitude_f32': (_INT, [_P, _I64, _F, _P, _P]),
+    'tac_mulaw_encode_f32_i64': (_INT, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P]),
+    'tac_mulaw_decode_i64_f32': (_INT, [_P, _I64, _I32, _P, _P, _P]),
+    'tac_mulaw_decode_f32_f32': (_INT, [_P, _I64, _I32, _P, _P, _P]),
+    'tac_mulaw_encode_f64_i64': (_INT, [_P, _I64, _I32, _P, _P]),
+    'tac_mulaw_decode_f64': (_INT, [_P, _I32, _I64, _I32, _P, _P]),
+    'tac_stft_backward_f32': (_INT, [_P, _P, _DESC, _P, _P]),
+    'tac_stft_norm_backward_f32': (_INT, [_P, _P, _F, _P, _DESC, _P, _P]),
+    'tac_spectrogram_backward_f32': (_INT, [_P, _P, _DESC, _P, _F, _P, _P]),
+    'tac_spectrogram_backward_ola_workspace': (_I64, [_DESC]),
+    'tac_spectrogram_backward_ola_f32': (_INT, [_P, _P, _DESC, _P, _F, _P, _I64, _P, _I64, _P]),
+    'tac_melspectrogram_backward_ola_f32': (_INT, [_P, _P, _DESC, _P, _I32, _P, _I32, _F, _P, _I64, _P, _I64, _P]),
+    'tac_melspectrogram_backward_f32': (_INT, [_P, _P, _DESC, _P, _I32, _P, _I32, _F, _P, _P]),
+    'tac_filterbank_adjoint_pack': (_INT, [_P, _I32, _I32, _P, _P, _P]),
+    'tac_apply_filterbank_adjoint_f32': (_INT, [_P, _I64, _I32, _P, _I32, _P, _P]),
+    'tac_overlap_add_f32': (_INT, [_P, _DESC, _P, _I64, _P]),
+    'tac_complex_norm_backward_f32': (_INT, [_P, _P, _I64, _F, _P, _P]),
+    'tac_amplitude_to_db_backward_f32': (_INT, [_P, _P, _I64, _F, _P, _P]),
+    'tac_magphase_backward_f32': (_INT, [_P, _P, _P, _I64, _F, _P, _P]),
+    'tac_db_to_amplitude_backward_f32': (_INT, [_P, _P, _I64, _F, _P, _P]),
+    'tac_hpss_f32': (_INT, [_P, _I64, _I32, _I32, _I64, _I64, _I64, _I32, _I32, _F, _INT, _P, _P, _P, _P, _P]),
+    'tac_hpss_backward_f32': (_INT, [_P, _I64, _I32, _I32, _I64, _I64, _I64, _I32, _I32, _F, _INT, _P, _P, _P, _P, _P, _P]),
+    'tac_melspec_sparse_coded_f32': (_INT, [_P, _I32, _P, _P, _DESC, _F, _P, _P, _P, _I32, _INT, _F, _F, _P, _P]),
+    'tac_pcm16_to_f32': (_INT, [_P, _I64, _P, _P]),
+    'tac_fold_twosided_f32': (_INT, [_P, _I64, _I32, _I32, _P, _P]),
+    'tac_window_grad_partials': (_I64, [_DESC]),
+    'tac_window_grad_f32': (_INT, [_P, _P, _DESC, _P, _I64, _P]),
+    'tac_sum_slabs_f32': (_INT, [_P, _I64, _I64, _P, _P]),
+    'tac_stft_f64': (_INT, [_P, _P, _DESC, _P, _P]),
+    'tac_spectrogram_f64': (_INT, [_P, _P, _DESC, _D, _INT, _D, _D, _P, _P]),
+    'tac_apply_filterbank_f64': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _I32, _INT, _D, _D, _P, _P]),
+    'tac_magphase_f64': (_INT, [_P, _I64, _D, _P, _P, _P]),
+    'tac_amplitude_to_db_f64': (_INT, [_P, _I64, _D, _D, _P, _P]),
+    'tac_db_to_amplitude_f64': (_INT, [_P, _I64, _D, _P, _P]),
+    'tac_last_route': (_STR, []),
+    'tac_debug_clock_probe': (_INT, [_P, _I32]),
+    'tac_melbank_plan_pieces_host': (_INT, [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32]),
+    'tac_set_fft_pipe': (_INT, [_INT]),
+    'tac_istft_workspace': (_I64, [_DESC, _I64]),
+    'tac_istft_envelope_f32': (_INT, [_P, _DESC, _I64, _P, _P, _P]),
+    'tac_istft_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _DESC, _P, _I64, _P, _P]),
+    'tac_istft_grad_input_f32': (_INT, [_P, _I64, _P, _DESC, _I64, _P, _P]),
+    'tac_istft_grad_bins_f32': (_INT, [_P, _I64, _INT, _INT, _P]),
+    'tac_dct_rows_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _I32, _P, _P]),
+    'tac_polyphase_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P, _P]),
+    'tac_lfilter_chunk': (_I32, []),
+    'tac_lfilter_supported': (_INT, [_P, _P, _I32]),
+    'tac_lfilter_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I32, _INT, _INT, _P, _P]),
+    'tac_spectral_mac_tile': (_I32, [_I32]),
+    'tac_spectral_mac_f32': (_INT, [_P, _P, _P, _I64, _I64, _I32, _I32, _I32, _INT, _P, _P]),
+    'tac_fftconvolve_default_n_fft': (_I32, [_I64]),
+    'tac_fftconvolve_supported': (_INT, [_I64, _I64, _I32]),
+    'tac_fftconvolve_spectra_workspace': (_I64, [_I64, _I64, _I32]),
+    'tac_fftconvolve_spectra_f32': (_INT, [_P, _I64, _I64, _I64, _I32, _INT, _P, _I64, _P, _P]),
+    'tac_fftconvolve_workspace': (_I64, [_I64, _I64, _I64, _I32, _I64, _I64]),
+    'tac_fftconvolve_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I32, _I64, _I32, _INT, _I64, _I64, _P, _I64, _P, _I64, _P]),
+    'tac_fftconvolve_direct_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P]),
+    'tac_kaldi_num_frames': (_I64, [_I64, _I32, _I32, _INT]),
+    'tac_kaldi_fbank_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P]),
+    'tac_kaldi_mfcc_table_limit': (_I64, [_I32, _I32, _I32]),
+    'tac_kaldi_mfcc_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P]),
+    'tac_kaldi_spectrogram_f32': (_INT, [_P, _I64, _I64, _I64, _P, _I32, _I32, _I32, _I32, _F, _F, _P, _P]),
+    'tac_sliding_cmn_chunk': (_I64, [_I64, _I64, _I64, _I64, _I64]),
+    'tac_sliding_cmn_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _INT, _INT, _P, _P]),
+    'tac_deltas_supported': (_INT, [_I64, _I32, _I32, _INT]),
+    'tac_deltas_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _INT, _P, _P]),
+    'tac_mask_spans_supported': (_INT, [_I32, _I32]),
+    'tac_mask_spans_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I32, _I32, _P, _F, _P, _P]),
+    'tac_add_noise_tile': (_I64, []),
+    'tac_add_noise_work_bytes': (_I64, [_I64, _I64]),
+    'tac_add_noise_f32': (_INT, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _P]),
+    'tac_add_noise_grad_f32': (_INT, [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P,
+                                      _I64, _I32, _P, _P, _P, _P, _P]),
+    'tac_loudness_tile': (_I64, []),
+    'tac_loudness_work_bytes': (_I64, [_I64, _I32, _I64, _I64, _I64]),
+    'tac_loudness_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    'tac_pitch_max_win': (_I32, []),
+    'tac_pitch_plan': (_INT, [_I64, _I32, _I32, _P, _P]),
+    'tac_pitch_lags_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P]),
+    'tac_pitch_smooth_i32': (_INT, [_P, _I64, _I64, _I32, _I32, _P, _P]),
+    'tac_pitch_frequency_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    'tac_psd_plan': (_INT, [_I64, _P, _P]),
+    'tac_beamform_grid': (_I32, [_I32, _I32]),
+    'tac_psd_f32': (_INT, _SPEC + _MASK + _MASK + [_I32, _I32, _I32, _D, _I32, _P, _P, _P, _P, _P]),
+    'tac_mvdr_weights_souden_f32': (_INT, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _D, _D, _P, _P]),
+    'tac_apply_beamforming_f32': (_INT, [_P, _P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P]),
+    'tac_mvdr_souden_f32': (_INT, _SPEC + _MASK + _MASK + [_D, _P, _I64, _I32, _I32, _D, _D, _I32, _P, _P, _P, _P,
+                                                           _I64, _I64, _I64, _P]),
+    'tac_rtf_power_max_iter': (_I32, []),
+    'tac_rtf_evd_f32': (_INT, [_P, _I64, _I64, _I32, _P, _P]),
+    'tac_rtf_power_f32': (_INT, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32, _D, _P, _P]),
+    'tac_mvdr_weights_rtf_f32': (_INT, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _D, _D, _P, _P]),
+    'tac_rtf_mvdr_f32': (_INT, _SPEC + [_P, _P, _P, _I64, _I32, _I32, _D, _D, _P, _P, _I64, _I64, _I64, _P]),
+}
+EXPORTS = tuple(PROTOTYPES)
 
 
 class NativeLibraryError(RuntimeError):
@@ -88,13 +198,6 @@ def build(verbose=False):
 _lib = None
 _lock = threading.Lock()
 
-_P = ctypes.c_void_p
-_I32 = ctypes.c_int32
-_I64 = ctypes.c_int64
-_F = ctypes.c_float
-_D = ctypes.c_double
-_DESC = ctypes.POINTER(StftDesc)
-
 
 def lib():
     """Load (once) and return the ctypes handle; fail loudly when the library is absent."""
@@ -116,157 +219,9 @@ def lib():
             raise NativeLibraryError(
                 '%s reports ABI version %d, this binding needs %d — rebuild it with `make -C %s`'
                 % (LIB_PATH, found, ABI_VERSION, CSRC))
-        h.tac_strerror.restype = ctypes.c_char_p
-        h.tac_strerror.argtypes = [ctypes.c_int]
-        h.tac_last_hip_error.restype = ctypes.c_int
-        h.tac_abi_version.restype = ctypes.c_int
-        h.tac_num_frames.restype = _I64
-        h.tac_num_frames.argtypes = [_I64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-        h.tac_num_bins.restype = ctypes.c_int
-        h.tac_num_bins.argtypes = [ctypes.c_int, ctypes.c_int]
-        h.tac_stft_f32.argtypes = [_P, _P, _DESC, _P, _P]
-        h.tac_spectrogram_f32.argtypes = [_P, _P, _DESC, _F, ctypes.c_int, _F, _F, _P, _P]
-        h.tac_melspec_f32.argtypes = [_P, _P, _DESC, _F, _P, _P, _I32, ctypes.c_int, _F, _F, _P, _P]
-        h.tac_melspec_supported.argtypes = [_DESC, _F, _P, _I32]
-        h.tac_melbank_pack.argtypes = [_P, _I32, _I32, _I32, _P, _I32, _P, _I32, _P, _P]
-        h.tac_melspec_sparse_f32.argtypes = [_P, _P, _DESC, _F, _P, _P, _P, _I32, ctypes.c_int, _F, _F, _P, _P]
-        h.tac_filterbank_plan.argtypes = [_P, _I32, _I32, _P, _P, _P]
-        h.tac_apply_filterbank_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _I32, _P, _P]
-        h.tac_apply_filterbank_sparse_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _I32, _P, _P]
-        h.tac_apply_filterbank_sparse_db_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _I32, ctypes.c_int, _F, _F, _P, _P]
-        h.tac_complex_norm_f32.argtypes = [_P, _I64, _F, _P, _P]
-        h.tac_magphase_f32.argtypes = [_P, _I64, _F, _P, _P, _P]
-        h.tac_phase_vocoder_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P]
-        h.tac_phase_vocoder_f64.argtypes = h.tac_phase_vocoder_f32.argtypes
-        h.tac_phase_vocoder_backward_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _P, _P]
-        h.tac_stretch_norm_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _I64, _F, ctypes.c_int, _F, _F, _P, _P, _P]
-        h.tac_stretch_mel_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _I64, _F, _P, _P, _P, _I32, ctypes.c_int, _F, _F, _P, _P, _P]
-        h.tac_stretch_norm_backward_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _P, _P, _P, _I64, _F, _P, _P, _P]
-        h.tac_amplitude_to_db_f32.argtypes = [_P, _I64, _F, _F, _P, _P]
-        h.tac_stft_f64.argtypes = [_P, _P, _DESC, _P, _P]
-        h.tac_spectrogram_f64.argtypes = [_P, _P, _DESC, _D, _I32, _D, _D, _P, _P]
-        h.tac_apply_filterbank_f64.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _I32, _I32, _D, _D, _P, _P]
-        h.tac_magphase_f64.argtypes = [_P, _I64, _D, _P, _P, _P]
-        h.tac_amplitude_to_db_f64.argtypes = [_P, _I64, _D, _D, _P, _P]
-        h.tac_db_to_amplitude_f64.argtypes = [_P, _I64, _D, _P, _P]
-        h.tac_db_to_amplitude_f32.argtypes = [_P, _I64, _F, _P, _P]
-        h.tac_mulaw_encode_f32_i64.argtypes = [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P]
-        h.tac_mulaw_decode_i64_f32.argtypes = [_P, _I64, _I32, _P, _P, _P]
-        h.tac_mulaw_decode_f32_f32.argtypes = [_P, _I64, _I32, _P, _P, _P]
-        h.tac_stft_backward_f32.argtypes = [_P, _P, _DESC, _P, _P]
-        h.tac_stft_norm_backward_f32.argtypes = [_P, _P, _F, _P, _DESC, _P, _P]
-        h.tac_spectrogram_backward_f32.argtypes = [_P, _P, _DESC, _P, _F, _P, _P]
-        h.tac_spectrogram_backward_ola_workspace.argtypes = [_DESC]
-        h.tac_spectrogram_backward_ola_workspace.restype = _I64
-        h.tac_spectrogram_backward_ola_f32.argtypes = [_P, _P, _DESC, _P, _F, _P, _I64, _P, _I64, _P]
-        h.tac_melspectrogram_backward_ola_f32.argtypes = [_P, _P, _DESC, _P, _I32, _P, _I32, _F, _P, _I64, _P, _I64, _P]
-        h.tac_melspectrogram_backward_f32.argtypes = [_P, _P, _DESC, _P, _I32, _P, _I32, _F, _P, _P]
-        h.tac_filterbank_adjoint_pack.argtypes = [_P, _I32, _I32, _P, _P, _P]
-        h.tac_apply_filterbank_adjoint_f32.argtypes = [_P, _I64, _I32, _P, _I32, _P, _P]
-        h.tac_overlap_add_f32.argtypes = [_P, _DESC, _P, _I64, _P]
-        h.tac_complex_norm_backward_f32.argtypes = [_P, _P, _I64, _F, _P, _P]
-        h.tac_amplitude_to_db_backward_f32.argtypes = [_P, _P, _I64, _F, _P, _P]
-        h.tac_magphase_backward_f32.argtypes = [_P, _P, _P, _I64, _F, _P, _P]
-        h.tac_db_to_amplitude_backward_f32.argtypes = [_P, _P, _I64, _F, _P, _P]
-        h.tac_melspec_sparse_coded_f32.argtypes = [_P, _I32, _P, _P, _DESC, _F, _P, _P, _P, _I32, ctypes.c_int, _F, _F, _P, _P]
-        h.tac_pcm16_to_f32.argtypes = [_P, _I64, _P, _P]
-        h.tac_fold_twosided_f32.argtypes = [_P, _I64, _I32, _I32, _P, _P]
-        h.tac_window_grad_partials.argtypes = [_DESC]
-        h.tac_window_grad_partials.restype = _I64
-        h.tac_window_grad_f32.argtypes = [_P, _P, _DESC, _P, _I64, _P]
-        h.tac_sum_slabs_f32.argtypes = [_P, _I64, _I64, _P, _P]
-        h.tac_hpss_f32.argtypes = [_P, _I64, _I32, _I32, _I64, _I64, _I64, _I32, _I32, _F, ctypes.c_int, _P, _P, _P, _P, _P]
-        h.tac_hpss_backward_f32.argtypes = [_P, _I64, _I32, _I32, _I64, _I64, _I64, _I32, _I32, _F, ctypes.c_int, _P, _P, _P, _P, _P, _P]
-        h.tac_melbank_plan_pieces_host.argtypes = [_P, _I32, _I32, _P, _P, _P, _P, _P, _I32]
-        h.tac_melbank_plan_pieces_host.restype = ctypes.c_int
-        h.tac_last_route.restype = ctypes.c_char_p
-        h.tac_last_route.argtypes = []
-        h.tac_debug_clock_probe.restype = ctypes.c_int
-        h.tac_debug_clock_probe.argtypes = [_P, _I32]
-        h.tac_set_fft_pipe.restype = ctypes.c_int
-        h.tac_set_fft_pipe.argtypes = [ctypes.c_int]
-        h.tac_mulaw_encode_f64_i64.argtypes = [_P, _I64, _I32, _P, _P]
-        h.tac_mulaw_decode_f64.argtypes = [_P, _I32, _I64, _I32, _P, _P]
-        h.tac_mulaw_decode_f64.restype = ctypes.c_int
-        h.tac_istft_workspace.argtypes = [_DESC, _I64]
-        h.tac_istft_workspace.restype = _I64
-        h.tac_istft_envelope_f32.argtypes = [_P, _DESC, _I64, _P, _P, _P]
-        h.tac_istft_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _DESC, _P, _I64, _P, _P]
-        h.tac_istft_grad_input_f32.argtypes = [_P, _I64, _P, _DESC, _I64, _P, _P]
-        h.tac_istft_grad_bins_f32.argtypes = [_P, _I64, _I32, _I32, _P]
-        h.tac_dct_rows_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _P, _I32, _P, _P]
-        h.tac_polyphase_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _P, _P]
-        h.tac_lfilter_chunk.restype = _I32
-        h.tac_lfilter_chunk.argtypes = []
-        h.tac_lfilter_supported.argtypes = [_P, _P, _I32]
-        h.tac_lfilter_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, ctypes.c_int, ctypes.c_int, _P, _P]
-        h.tac_spectral_mac_tile.restype = _I32
-        h.tac_spectral_mac_tile.argtypes = [_I32]
-        h.tac_spectral_mac_f32.argtypes = [_P, _P, _P, _I64, _I64, _I32, _I32, _I32, ctypes.c_int, _P, _P]
-        h.tac_fftconvolve_default_n_fft.restype = _I32
-        h.tac_fftconvolve_default_n_fft.argtypes = [_I64]
-        h.tac_fftconvolve_supported.argtypes = [_I64, _I64, _I32]
-        h.tac_fftconvolve_spectra_workspace.restype = _I64
-        h.tac_fftconvolve_spectra_workspace.argtypes = [_I64, _I64, _I32]
-        h.tac_fftconvolve_spectra_f32.argtypes = [_P, _I64, _I64, _I64, _I32, ctypes.c_int, _P, _I64, _P, _P]
-        h.tac_fftconvolve_workspace.restype = _I64
-        h.tac_fftconvolve_workspace.argtypes = [_I64, _I64, _I64, _I32, _I64, _I64]
-        h.tac_fftconvolve_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I32, _I64, _I32, ctypes.c_int, _I64, _I64, _P, _I64, _P,
-                                          _I64, _P]
-        h.tac_fftconvolve_direct_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _P, _P]
-        h.tac_kaldi_num_frames.restype = _I64
-        h.tac_kaldi_num_frames.argtypes = [_I64, _I32, _I32, ctypes.c_int]
-        h.tac_kaldi_fbank_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P]
-        h.tac_kaldi_mfcc_table_limit.restype = _I64
-        h.tac_kaldi_mfcc_table_limit.argtypes = [_I32, _I32, _I32]
-        h.tac_kaldi_mfcc_f32.argtypes = [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P]
-        h.tac_kaldi_spectrogram_f32.argtypes = [_P, _I64, _I64, _I64, _P, _I32, _I32, _I32, _I32, _F, _F, _P, _P]
-        h.tac_sliding_cmn_chunk.restype = _I64
-        h.tac_sliding_cmn_chunk.argtypes = [_I64, _I64, _I64, _I64, _I64]
-        h.tac_sliding_cmn_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_int, _P, _P]
-        h.tac_deltas_supported.argtypes = [_I64, _I32, _I32, ctypes.c_int]
-        h.tac_deltas_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, ctypes.c_int, _P, _P]
-        h.tac_mask_spans_supported.argtypes = [_I32, _I32]
-        h.tac_mask_spans_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I32, _I32, _P, _F, _P, _P]
-        h.tac_add_noise_tile.restype = _I64
-        h.tac_add_noise_tile.argtypes = []
-        h.tac_add_noise_work_bytes.restype = _I64
-        h.tac_add_noise_work_bytes.argtypes = [_I64, _I64]
-        h.tac_add_noise_f32.argtypes = [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _I32, _P, _P, _P]
-        h.tac_add_noise_grad_f32.argtypes = [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P,
-                                             _I64, _I32, _P, _P, _P, _P, _P]
-        h.tac_loudness_tile.restype = _I64
-        h.tac_loudness_tile.argtypes = []
-        h.tac_loudness_work_bytes.restype = _I64
-        h.tac_loudness_work_bytes.argtypes = [_I64, _I32, _I64, _I64, _I64]
-        h.tac_loudness_f32.argtypes = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]
-        h.tac_pitch_max_win.restype = _I32
-        h.tac_pitch_max_win.argtypes = []
-        h.tac_pitch_plan.argtypes = [_I64, _I32, _I32, _P, _P]
-        h.tac_pitch_lags_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _P, _P]
-        h.tac_pitch_smooth_i32.argtypes = [_P, _I64, _I64, _I32, _I32, _P, _P]
-        h.tac_pitch_frequency_f32.argtypes = [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]
-        h.tac_psd_plan.argtypes = [_I64, _P, _P]
-        h.tac_beamform_grid.restype = _I32
-        h.tac_beamform_grid.argtypes = [_I32, _I32]
-        _spec = [_P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _I64]          # spec, batch, channels, bins, frames, four strides
-        _mask = [_P, _I64, _I64, _I64]
-        h.tac_psd_f32.argtypes = _spec + _mask + _mask + [_I32, _I32, _I32, _D, _I32, _P, _P, _P, _P, _P]
-        h.tac_mvdr_weights_souden_f32.argtypes = [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _D, _D, _P, _P]
-        h.tac_apply_beamforming_f32.argtypes = [_P, _P, _I64, _I32, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P]
-        h.tac_mvdr_souden_f32.argtypes = (_spec + _mask + _mask + [_D, _P, _I64, _I32, _I32, _D, _D, _I32, _P, _P, _P, _P,
-                                                                    _I64, _I64, _I64, _P])
-        h.tac_rtf_power_max_iter.restype = _I32
-        h.tac_rtf_power_max_iter.argtypes = []
-        h.tac_rtf_evd_f32.argtypes = [_P, _I64, _I64, _I32, _P, _P]
-        h.tac_rtf_power_f32.argtypes = [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32, _D, _P, _P]
-        h.tac_mvdr_weights_rtf_f32.argtypes = [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _D, _D, _P, _P]
-        h.tac_rtf_mvdr_f32.argtypes = _spec + [_P, _P, _P, _I64, _I32, _I32, _D, _D, _P, _P, _I64, _I64, _I64, _P]
-        for name in EXPORTS:
+        for name, (restype, argtypes) in PROTOTYPES.items():
             fn = getattr(h, name)
-            if name.endswith(('_f32', '_f64', '_i64', '_plan', '_supported', '_pack')):   # every launcher returns a TAC_* code
-                fn.restype = ctypes.c_int
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = h
     return _lib
 
