@@ -831,6 +831,48 @@ int tac_rtf_mvdr_f32(const float* spec, int64_t batch, int32_t channels, int64_t
                      const float* ref_vector, int64_t ref_stride_b, int32_t ref_channel, int32_t diagonal_loading, double diag_eps,
                      double eps, float* weights, float* out, int64_t out_b, int64_t out_f, int64_t out_t, void* stream);
 
+/* (27) functional.rnnt_loss and the RNNTLoss layer: the transducer loss of Graves (2012) with torchaudio's semantics, and its
+ *      gradient (csrc/rnnt.hip).  logits: float32 [batch][frames][targets1][classes] with targets1 = U + 1, unit stride along the
+ *      classes and positive element strides stride_b / stride_t / stride_u (a slice of a padded joint output is taken as it is);
+ *      element offsets are 64-bit.  targets: DEVICE int32 [batch][U], contiguous; logit_lengths (Tb), target_lengths (Ub): DEVICE
+ *      int32 [batch].  denominators, lp_blank, lp_label, alphas, betas: float32 [batch][frames][targets1]; costs, grad_costs:
+ *      float32 [batch]; grad_logits: float32 [batch][frames][targets1][classes], contiguous.  blank in [0, classes).  targets1 above
+ *      tac_rnnt_max_targets() (1024) and batch * frames * targets1 >= 2^31: TAC_E_UNSUPPORTED.  Every entry below is ONE launch;
+ *      the forward pass is tac_rnnt_rows_f32 then tac_rnnt_lattice_f32, the backward pass tac_rnnt_grad_f32.  The order of every
+ *      sum is fixed and nothing is atomic: the same bits from run to run, for the 16-byte and the dword form of the row loads (the
+ *      form follows from the alignment of base and strides and classes % 4), and for an entry whatever else is in the batch.
+ *
+ *      An entry with Tb outside [1, frames], Ub outside [0, U] or a used target (u < Ub) outside [0, classes) gets cost NaN, alphas
+ *      and betas NaN and a NaN gradient over its whole block; none of these values is used to form an address.
+ *
+ *      tac_rnnt_rows_f32: per row (b, t, u) with t < Tb and u <= Ub: denominators = logsumexp over the classes (fused != 0; else 0,
+ *      and the launch is only the gather), lp_blank = logits[blank] - denominator, lp_label = logits[targets[b][u]] - denominator
+ *      for u < Ub (else 0).  The other rows are not read: their denominators, lp_blank, lp_label, alphas and betas are written as 0.
+ *
+ *      tac_rnnt_lattice_f32: alphas and betas over t < Tb, u <= Ub from lp_blank / lp_label (one workgroup per entry and
+ *      direction, T_b + U_b dependent steps), costs[b] = -(alphas[Tb-1][Ub] + lp_blank[Tb-1][Ub]).  logaddexp(-inf, -inf) = -inf.
+ *      After both launches every element of the five arrays and of costs is written.
+ *
+ *      tac_rnnt_grad_f32: with g = logits[t][u][v] - denominators[t][u] + alphas[t][u] + costs[b],
+ *        grad = exp(g + betas[t][u])                                               (fused != 0; else 0)
+ *             - [v == blank and t == Tb-1 and u == Ub] exp(g) - [v == blank and t < Tb-1] exp(g + betas[t+1][u])
+ *             - [u < Ub and v == targets[b][u]] exp(g + betas[t][u+1]),
+ *      clipped to [-clamp, clamp] where clamp > 0, then times grad_costs[b]; zero for t >= Tb or u > Ub, without a read.  Every
+ *      element of grad_logits is written. */
+int32_t tac_rnnt_max_targets(void);
+int tac_rnnt_rows_f32(const float* logits, int64_t batch, int64_t frames, int64_t targets1, int64_t classes, int64_t stride_b,
+                      int64_t stride_t, int64_t stride_u, const int32_t* targets, const int32_t* logit_lengths,
+                      const int32_t* target_lengths, int32_t blank, int32_t fused, float* denominators, float* lp_blank,
+                      float* lp_label, float* alphas, float* betas, void* stream);
+int tac_rnnt_lattice_f32(int64_t batch, int64_t frames, int64_t targets1, int64_t classes, const int32_t* targets,
+                         const int32_t* logit_lengths, const int32_t* target_lengths, const float* lp_blank, const float* lp_label,
+                         float* alphas, float* betas, float* costs, void* stream);
+int tac_rnnt_grad_f32(const float* logits, int64_t batch, int64_t frames, int64_t targets1, int64_t classes, int64_t stride_b,
+                      int64_t stride_t, int64_t stride_u, const int32_t* targets, const int32_t* logit_lengths,
+                      const int32_t* target_lengths, const float* alphas, const float* betas, const float* denominators,
+                      const float* costs, const float* grad_costs, int32_t blank, float clamp, int32_t fused, float* grad_logits,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -745,3 +745,134 @@ def melspectrogram_mulaw(codes, window, bank, n_quantize, n_fft, hop, win_length
     wave = mu_law_decoding(codes, n_quantize, torch.float32)
     return melspectrogram(wave, window, bank, n_fft, hop, win_length, center, pad_mode, normalized, onesided, power, db,
                           ref, amin)
+
+
+# ----------------------------------------------------------------------------- rnnt_loss
+def _rnnt_work(logits):
+    return logits.float() if logits.dtype in (torch.float16, torch.bfloat16) else logits
+
+
+def rnnt_valid(logits, targets, logit_lengths, target_lengths):
+    """``(ok, Tb, Ub)``: which entries of the batch have ``1 <= Tb <= T``, ``0 <= Ub <= U`` and every used target inside ``[0, V)``
+    — the others get a NaN cost and gradient — and the lengths clamped into those ranges, so that no index leaves the tensors.
+    On the device of the inputs: nothing waits for the host."""
+    B, T, U1, V = logits.shape
+    U = U1 - 1
+    Tb, Ub = logit_lengths.long(), target_lengths.long()
+    ok = (Tb >= 1) & (Tb <= T) & (Ub >= 0) & (Ub <= U)
+    if U:
+        used = torch.arange(U, device=logits.device)[None, :] < Ub[:, None]
+        ok = ok & ~(used & ((targets < 0) | (targets >= V))).any(dim=1)
+    return ok, Tb.clamp(1, T), Ub.clamp(0, U)
+
+
+def _rnnt_logaddexp(a, b):
+    """``logaddexp`` from operators whose every derivative is finite at the finite "no path" value (``torch.logaddexp``'s second
+    derivative is not)"""
+    m = torch.maximum(a, b).detach()
+    return m + torch.log(torch.exp(a - m) + torch.exp(b - m))
+
+
+def _rnnt_skew(x, t_of, on):
+    """``(B, T, U + 1)`` → ``(B, T + U, U + 1)`` with ``[b, d, u] = x[b, d - u, u]``, ``-1e30`` (no path) where ``d - u`` is no frame"""
+    got = x.gather(1, t_of.expand(x.shape[0], -1, -1))
+    return torch.where(on, got, torch.full((), -1e30, dtype=x.dtype, device=x.device))
+
+
+def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, clamp, fused_log_softmax):
+    """torchaudio's ``functional.rnnt_loss`` before its reduction, in torch operators: ``(costs, alphas, betas, denominators)`` of
+    ``(B, T, U + 1, V)`` logits.  The recursion of Graves (2012) in log-space, one step of the Python loop per anti-diagonal
+    ``t + u = d`` (``T + U`` steps for alpha and as many for beta), the whole batch at once with the lengths as masks; every step is
+    a differentiable torch operator.  Cells with ``t >= Tb`` or ``u > Ub`` come back as zeros; an entry ``rnnt_valid`` refuses as
+    NaN.  ``clamp`` acts on the gradient alone (``rnnt_loss_grad``)."""
+    x = _rnnt_work(logits)
+    B, T, U1, V = x.shape
+    U, D = U1 - 1, T + U1 - 1
+    dev = x.device
+    # "no path" is a large finite number, not -inf: logaddexp(-inf, -inf) has a NaN derivative, and autograd visits the masked cells
+    ninf = torch.full((), -1e30, dtype=x.dtype, device=dev)
+    ok, Tb, Ub = rnnt_valid(x, targets, logit_lengths, target_lengths)
+    denom = torch.logsumexp(x, dim=-1) if fused_log_softmax else x.new_zeros((B, T, U1))
+    lpb = x[..., blank] - denom
+    if U:
+        lab = targets.long().clamp(0, V - 1)[:, None, :, None].expand(B, T, U, 1)
+        lpl = torch.cat([x[:, :, :U].gather(-1, lab).squeeze(-1) - denom[:, :, :U], ninf.expand(B, T, 1)], dim=2)
+    else:
+        lpl = ninf.expand(B, T, 1)
+    d_i = torch.arange(D, device=dev)[:, None]
+    u_i = torch.arange(U1, device=dev)[None, :]
+    t_of = d_i - u_i                                                  # (D, U1): the frame of column u on diagonal d
+    on = (t_of >= 0) & (t_of < T)
+    t_cl = t_of.clamp(0, T - 1)[None]
+    sb, sl = _rnnt_skew(lpb, t_cl, on[None]), _rnnt_skew(lpl, t_cl, on[None])
+    pad = ninf.expand(B, 1)
+    # alpha does not depend on the lengths: the whole grid, read at (Tb - 1, Ub)
+    row = torch.cat([x.new_zeros((B, 1)), ninf.expand(B, U)], dim=1) if U else x.new_zeros((B, 1))
+    rows = [row]
+    for d in range(1, D):
+        up = row + sb[:, d - 1]
+        left = torch.cat([pad, row[:, :-1] + sl[:, d - 1, :-1]], dim=1)
+        row = torch.where(on[d][None], _rnnt_logaddexp(up, left), ninf)
+        rows.append(row)
+    unskew = (torch.arange(T, device=dev)[:, None] + u_i)[None].expand(B, -1, -1)
+    alphas = torch.stack(rows, dim=1).gather(1, unskew)
+    last = ((Tb - 1) * U1 + Ub)[:, None]
+    costs = -(alphas.reshape(B, -1).gather(1, last) + lpb.reshape(B, -1).gather(1, last)).squeeze(1)
+    # beta ends at (Tb - 1, Ub) of its entry
+    t_b, u_b = t_of[None], u_i[None]
+    corner = (t_b == (Tb - 1)[:, None, None]) & (u_b == Ub[:, None, None])
+    inside = on[None] & (t_b < Tb[:, None, None]) & (u_b <= Ub[:, None, None])
+    row = ninf.expand(B, U1)
+    rows = [None] * D
+    for d in range(D - 1, -1, -1):
+        down = row + sb[:, d]
+        right = torch.cat([row[:, 1:], pad], dim=1) + sl[:, d]
+        row = torch.where(corner[:, d], sb[:, d], torch.where(inside[:, d], _rnnt_logaddexp(down, right), ninf))
+        rows[d] = row
+    betas = torch.stack(rows, dim=1).gather(1, unskew)
+    t_i = torch.arange(T, device=dev)[None, :, None]
+    cell = (t_i < Tb[:, None, None]) & (u_i[None] <= Ub[:, None, None])
+    nan = torch.full((), float('nan'), dtype=x.dtype, device=dev)
+    zero = x.new_zeros(())
+    keep = ok[:, None, None]
+    alphas, betas = (torch.where(keep, torch.where(cell, a, zero), nan) for a in (alphas, betas))
+    denom = torch.where(cell & keep, denom, zero)
+    costs = torch.where(ok, costs, nan)
+    return costs.to(logits.dtype), alphas, betas, denom
+
+
+def rnnt_loss_grad(logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs, grad_costs, blank, clamp,
+                   fused_log_softmax):
+    """the gradient of ``rnnt_loss``'s costs with respect to the logits in closed form, from what the forward pass saved: with
+    ``g = logits - denominators + alphas + costs``, ``exp(g + beta[t,u])`` minus the blank term ``exp(g + beta[t+1,u])`` (``exp(g)``
+    at the last cell) and the label term ``exp(g + beta[t,u+1])``; clipped to ``[-clamp, clamp]`` where ``clamp > 0``, then times
+    ``grad_costs``.  Not differentiable itself (the double backward differentiates ``rnnt_loss``)."""
+    x = _rnnt_work(logits).detach()
+    B, T, U1, V = x.shape
+    U = U1 - 1
+    dev = x.device
+    ninf = torch.full((), float('-inf'), dtype=x.dtype, device=dev)
+    zero = x.new_zeros(())
+    ok, Tb, Ub = rnnt_valid(x, targets, logit_lengths, target_lengths)
+    Tb_, Ub_ = Tb[:, None, None], Ub[:, None, None]
+    t_i = torch.arange(T, device=dev)[None, :, None]
+    u_i = torch.arange(U1, device=dev)[None, None, :]
+    cell = (t_i < Tb_) & (u_i <= Ub_)
+    alphas, betas, denominators = alphas.to(x.dtype), betas.to(x.dtype), denominators.to(x.dtype)
+    c = (alphas + costs.to(x.dtype)[:, None, None]) - denominators
+    below = torch.cat([betas[:, 1:], ninf.expand(B, 1, U1)], dim=1)
+    sb = torch.where(t_i < Tb_ - 1, below, torch.where(u_i == Ub_, zero, ninf))
+    beside = torch.cat([betas[:, :, 1:], ninf.expand(B, T, 1)], dim=2)
+    sl = torch.where(u_i < Ub_, beside, ninf)
+    g = x + c[..., None]
+    grad = torch.exp(g + betas[..., None]) if fused_log_softmax else torch.zeros_like(x)
+    grad[..., blank] -= torch.exp(g[..., blank] + sb)
+    if U:
+        lab = targets.long().clamp(0, V - 1)[:, None, :, None].expand(B, T, U, 1)
+        grad[:, :, :U].scatter_add_(-1, lab, -torch.exp(g[:, :, :U].gather(-1, lab) + sl[:, :, :U, None]))
+    grad = torch.where(cell[..., None], grad, zero)
+    if clamp > 0:
+        grad = grad.clamp(-clamp, clamp)
+    grad = grad * grad_costs.to(x.dtype)[:, None, None, None]
+    grad = torch.where(ok[:, None, None, None], grad, torch.full((), float('nan'), dtype=x.dtype, device=dev))
+    return grad.to(logits.dtype)

@@ -1268,6 +1268,65 @@ def rtf_mvdr(spec, rtf, psd_n, ref_vector, ref_channel, diagonal_loading, diag_e
     return out, w.reshape(lead + (F, C, 2))
 
 
+# ----------------------------------------------------------------------------- rnnt_loss (csrc/rnnt.hip)
+def rnnt_max_targets():
+    """the most ``U + 1`` the lattice launch takes: a lane per column of one workgroup"""
+    return _native.lib().tac_rnnt_max_targets()
+
+
+def rnnt_reason(logits):
+    """why the launches of csrc/rnnt.hip do not take these float32 ``(B, T, U + 1, V)`` logits as they lie, or None"""
+    B, T, U1, V = logits.shape
+    if V > 1 and logits.stride(3) != 1:
+        return 'a class axis without unit stride'
+    if any(st <= 0 for st, n in zip(logits.stride()[:3], logits.shape[:3]) if n > 1):
+        return 'expanded or non-positive strides'
+    if U1 > rnnt_max_targets():
+        return 'a target axis of %d (the kernel takes up to %d)' % (U1, rnnt_max_targets())
+    if B * T * U1 >= 2 ** 31:
+        return '%d lattice cells (the kernel takes fewer than 2^31)' % (B * T * U1)
+    return None
+
+
+def _rnnt_ints(t, device):
+    return t if (t.dtype == torch.int32 and t.is_contiguous() and t.device == device) else \
+        t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _rnnt_geometry(logits):
+    B, T, U1, V = logits.shape
+    return (_native.ptr(logits), B, T, U1, V, logits.stride(0), logits.stride(1), logits.stride(2))
+
+
+def rnnt_forward(logits, targets, logit_lengths, target_lengths, blank, fused):
+    """``(costs (B,), alphas, betas, denominators (B, T, U + 1))`` of float32 logits ``rnnt_reason`` passes: two launches — the
+    denominators with the two log-probabilities of every lattice cell, then alpha and beta together.  Nothing of the size of the
+    logits is allocated."""
+    B, T, U1, V = logits.shape
+    dev = logits.device
+    targets, tl, ul = _rnnt_ints(targets, dev), _rnnt_ints(logit_lengths, dev), _rnnt_ints(target_lengths, dev)
+    denom, lp_blank, lp_label, alphas, betas = (_empty((B, T, U1), device=dev) for _ in range(5))
+    costs = _empty((B,), device=dev)
+    _launch('tac_rnnt_rows_f32', dev, (denom, lp_blank, lp_label), *_rnnt_geometry(logits), _native.ptr(targets), _native.ptr(tl),
+            _native.ptr(ul), blank, 1 if fused else 0, _native.ptr(denom), _native.ptr(lp_blank), _native.ptr(lp_label),
+            _native.ptr(alphas), _native.ptr(betas))
+    _launch('tac_rnnt_lattice_f32', dev, (alphas, betas, costs), B, T, U1, V, _native.ptr(targets), _native.ptr(tl), _native.ptr(ul),
+            _native.ptr(lp_blank), _native.ptr(lp_label), _native.ptr(alphas), _native.ptr(betas), _native.ptr(costs))
+    return costs, alphas, betas, denom
+
+
+def rnnt_grad(logits, targets, logit_lengths, target_lengths, alphas, betas, denom, costs, grad_costs, blank, clamp, fused):
+    """the gradient with respect to the logits, contiguous ``(B, T, U + 1, V)``: one launch, one read of the logits, one write"""
+    dev = logits.device
+    targets, tl, ul = _rnnt_ints(targets, dev), _rnnt_ints(logit_lengths, dev), _rnnt_ints(target_lengths, dev)
+    alphas, betas, denom, costs, grad_costs = (t.contiguous() for t in (alphas, betas, denom, costs, grad_costs))
+    out = _empty(tuple(logits.shape), device=dev)
+    _launch('tac_rnnt_grad_f32', dev, (out,), *_rnnt_geometry(logits), _native.ptr(targets), _native.ptr(tl), _native.ptr(ul),
+            _native.ptr(alphas), _native.ptr(betas), _native.ptr(denom), _native.ptr(costs), _native.ptr(grad_costs), blank,
+            float(clamp), 1 if fused else 0, _native.ptr(out))
+    return out
+
+
 # ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
 #: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
 FFTCONV_SIZES = (2048, 4096, 8192)

@@ -168,6 +168,10 @@ PROTOTYPES = {
     'tac_rtf_power_f32': (_INT, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _I32, _D, _P, _P]),
     'tac_mvdr_weights_rtf_f32': (_INT, [_P, _P, _I64, _I64, _I32, _P, _I64, _I32, _I32, _D, _D, _P, _P]),
     'tac_rtf_mvdr_f32': (_INT, _SPEC + [_P, _P, _P, _I64, _I32, _I32, _D, _D, _P, _P, _I64, _I64, _I64, _P]),
+    'tac_rnnt_max_targets': (_I32, []),
+    'tac_rnnt_rows_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    'tac_rnnt_lattice_f32': (_INT, [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'tac_rnnt_grad_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _F, _I32, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

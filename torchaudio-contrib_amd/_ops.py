@@ -21,6 +21,7 @@ see them by name.
     tac_amd::detect_pitch_frequency   NCCF pitch of (…, L): correlations, peak choice and median in two launches (csrc/pitch.hip)
     tac_amd::psd, mvdr_weights_souden, apply_beamforming, mvdr_souden   mask-based MVDR beamforming over (…, C, F, T) (csrc/beamform.hip)
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
+    tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -1363,6 +1364,145 @@ def _rtf_mvdr_fake(spec, rtf, psd_n, ref_vector, ref_channel, diagonal_loading, 
 
 _register('rtf_mvdr', '(Tensor specgram, Tensor rtf, Tensor psd_n, Tensor ref_vector, int ref_channel, bool diagonal_loading, '
           'float diag_eps, float eps) -> Tensor', _rtf_mvdr_cuda, C.rtf_mvdr, _rtf_mvdr_fake, 4)
+
+
+# ============================================================================= rnnt_loss, rnnt_loss_grad
+def rnnt_check(logits, targets, logit_lengths, target_lengths, blank):
+    """torchaudio's argument checks of ``rnnt_loss`` that need no device memory, and for CPU tensors the two that do (the longest
+    logit length is T, the longest target length is U); returns ``blank`` counted from the front.  On a HIP device the lengths
+    and targets are not read on the host: an entry outside its ranges ends as NaN (``functional.rnnt_loss``)."""
+    if not (isinstance(logits, torch.Tensor) and logits.is_floating_point()):
+        raise ValueError('rnnt_loss: logits must be a floating-point tensor')
+    for name, t, dim in (('targets', targets, 2), ('logit_lengths', logit_lengths, 1), ('target_lengths', target_lengths, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise ValueError('rnnt_loss: %s must be an int32 tensor' % name)
+        if t.dim() != dim:
+            raise ValueError('rnnt_loss: %s must have %d dimension(s), got %d' % (name, dim, t.dim()))
+    if logits.dim() != 4:
+        raise ValueError('rnnt_loss: logits must be (batch, time, target + 1, class), got %d dimension(s)' % logits.dim())
+    B, T, U1, V = logits.shape
+    if T < 1 or U1 < 1 or V < 1:
+        raise ValueError('rnnt_loss: logits of shape %r have an empty time, target or class axis' % (tuple(logits.shape),))
+    if tuple(targets.shape) != (B, U1 - 1):
+        raise ValueError('rnnt_loss: targets of shape %r do not match logits of shape %r: expected (%d, %d)'
+                         % (tuple(targets.shape), tuple(logits.shape), B, U1 - 1))
+    if logit_lengths.shape[0] != B or target_lengths.shape[0] != B:
+        raise ValueError('rnnt_loss: %d logit lengths and %d target lengths for a batch of %d'
+                         % (logit_lengths.shape[0], target_lengths.shape[0], B))
+    if not -V <= blank < V:
+        raise ValueError('rnnt_loss: blank %d is outside the %d classes' % (blank, V))
+    _same_device('rnnt_loss', logits, targets, logit_lengths, target_lengths)
+    if B and not logits.is_cuda and logits.device.type == 'cpu':
+        if int(logit_lengths.max()) != T:
+            raise ValueError('rnnt_loss: the longest logit length is %d, the time axis of the logits %d' % (int(logit_lengths.max()), T))
+        if int(target_lengths.max()) != U1 - 1:
+            raise ValueError('rnnt_loss: the longest target length is %d, the target axis of the logits %d + 1'
+                             % (int(target_lengths.max()), U1 - 1))
+    return blank + V if blank < 0 else blank
+
+
+def _rnnt_work_dtype(logits):
+    return torch.float64 if logits.dtype == torch.float64 else torch.float32
+
+
+def rnnt_reason(logits):
+    """why the launches of csrc/rnnt.hip do not take these logits, or None"""
+    if logits.dtype != torch.float32:
+        return 'dtype %s' % str(logits.dtype).replace('torch.', '')
+    return H.rnnt_reason(logits)
+
+
+def _rnnt_empty(logits):
+    B, T, U1, V = logits.shape
+    w = _rnnt_work_dtype(logits)
+    return (logits.new_empty((B,)),) + tuple(logits.new_empty((B, T, U1), dtype=w) for _ in range(3))
+
+
+def _rnnt_loss_cuda(logits, targets, logit_lengths, target_lengths, blank, clamp, fused):
+    blank = rnnt_check(logits, targets, logit_lengths, target_lengths, blank)
+    if logits.shape[0] == 0:
+        return _rnnt_empty(logits)                                  # an empty batch: nothing is launched
+    reason = rnnt_reason(logits)
+    if reason is not None:
+        _composite_route('rnnt_loss', reason)
+        return C.rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, clamp, fused)
+    return H.rnnt_forward(logits, targets, logit_lengths, target_lengths, blank, fused)
+
+
+def _rnnt_loss_cpu(logits, targets, logit_lengths, target_lengths, blank, clamp, fused):
+    blank = rnnt_check(logits, targets, logit_lengths, target_lengths, blank)
+    if logits.shape[0] == 0:
+        return _rnnt_empty(logits)
+    return C.rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, clamp, fused)
+
+
+def _rnnt_loss_fake(logits, targets, logit_lengths, target_lengths, blank, clamp, fused):
+    return _rnnt_empty(logits)
+
+
+def _rnnt_grad_cuda(logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs, grad_costs, blank, clamp,
+                    fused):
+    if logits.numel() == 0:
+        return torch.empty(tuple(logits.shape), dtype=logits.dtype, device=logits.device)
+    reason = rnnt_reason(logits) or _hip_dtype(grad_costs)
+    if reason is None and not _plain_hip_f32(alphas, betas, denominators, costs, grad_costs):
+        reason = 'tensor subclass'
+    if reason is not None:
+        _composite_route('rnnt_loss', 'backward: ' + reason)
+        return C.rnnt_loss_grad(logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs, grad_costs, blank,
+                                clamp, fused)
+    return H.rnnt_grad(logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs, grad_costs, blank, clamp,
+                       fused)
+
+
+def _rnnt_grad_fake(logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs, grad_costs, blank, clamp,
+                    fused):
+    return torch.empty(tuple(logits.shape), dtype=logits.dtype, device=logits.device)
+
+
+def _register_rnnt_autograd():
+    """Backward of ``tac_amd::rnnt_loss``: the costs are the one differentiable output and the logits the one input with a gradient.
+    What the forward pass saved — alphas, betas, denominators, costs: three ``(B, T, U + 1)`` arrays and a vector, nothing of the
+    size of the logits — goes to ``tac_amd::rnnt_loss_grad``, which routes like every op (the kernel for float32 on a HIP device,
+    the closed form in torch operators otherwise, announced there).  A double backward differentiates the torch-operator recursion
+    on the saved logits, announced on a HIP device."""
+
+    def setup_context(ctx, inputs, output):
+        logits, targets, logit_lengths, target_lengths, blank, clamp, fused = inputs
+        costs, alphas, betas, denominators = output
+        ctx.mark_non_differentiable(alphas, betas, denominators)
+        ctx.save_for_backward(logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs)
+        ctx.rest = (blank + logits.shape[-1] if blank < 0 else blank, clamp, fused)
+
+    def backward(ctx, g, *unused):
+        logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs = ctx.saved_tensors
+        blank, clamp, fused = ctx.rest
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        if torch.is_grad_enabled():                                 # keep the graph: the saved logits are the caller's own
+            if logits.is_cuda:
+                _composite_route('rnnt_loss', 'backward: double backward (create_graph=True)')
+            with torch.enable_grad():
+                again = C.rnnt_loss(logits, targets, logit_lengths, target_lengths, blank, clamp, fused)[0]
+                (per_entry,) = torch.autograd.grad(again.sum(), logits, create_graph=True)
+                if clamp > 0:
+                    per_entry = per_entry.clamp(-clamp, clamp)
+                grad = per_entry * g.to(per_entry.dtype)[:, None, None, None]
+        else:
+            grad = call('rnnt_loss_grad', logits, targets, logit_lengths, target_lengths, alphas, betas, denominators, costs, g, blank,
+                        clamp, fused)
+        return (grad,) + (None,) * 6
+
+    torch.library.register_autograd('%s::rnnt_loss' % NS, backward, setup_context=setup_context, lib=_lib)
+
+
+_register('rnnt_loss', '(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, int blank, float clamp, '
+          'bool fused_log_softmax) -> (Tensor, Tensor, Tensor, Tensor)', _rnnt_loss_cuda, _rnnt_loss_cpu, _rnnt_loss_fake, 1,
+          differentiable=False)
+_register_rnnt_autograd()
+_register('rnnt_loss_grad', '(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, Tensor alphas, Tensor betas, '
+          'Tensor denominators, Tensor costs, Tensor grad_costs, int blank, float clamp, bool fused_log_softmax) -> Tensor',
+          _rnnt_grad_cuda, C.rnnt_loss_grad, _rnnt_grad_fake, 1, differentiable=False)
 
 
 # ============================================================================= lfilter

@@ -33,7 +33,7 @@ __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterba
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
-           'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf']
+           'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss']
 
 _call = _ops.call
 
@@ -710,6 +710,39 @@ def mvdr_weights_rtf(rtf, psd_n, reference_channel=None, diagonal_loading=True, 
     out = _call('mvdr_weights_rtf', d, n, _beamform.none(d) if u is None else u, r, bool(diagonal_loading), float(diag_eps),
                 float(eps))
     return _beamform.unpairs(out, was_complex)
+
+
+def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1.0, reduction='mean', fused_log_softmax=True):
+    """The transducer loss of Graves (2012) with torchaudio's ``functional.rnnt_loss`` signature, defaults and semantics.
+
+    ``logits`` is the joint network's ``(batch, time, target + 1, class)`` output, ``targets`` ``(batch, target)`` int32 without
+    blanks, ``logit_lengths`` (``Tb``) and ``target_lengths`` (``Ub``) ``(batch,)`` int32.  With ``lp = log_softmax(logits, -1)``
+    (``logits`` itself for ``fused_log_softmax=False``): ``alpha[0,0] = 0``, ``alpha[t,u] = logaddexp(alpha[t-1,u] + lp[t-1,u,blank],
+    alpha[t,u-1] + lp[t,u-1,targets[u-1]])`` and ``cost = -(alpha[Tb-1,Ub] + lp[Tb-1,Ub,blank])``.  A negative ``blank`` counts from
+    the end.  ``reduction``: ``'none'`` gives the ``(batch,)`` costs, ``'mean'`` and ``'sum'`` a scalar, in the dtype of ``logits``.
+    The gradient goes to ``logits`` alone; it is clipped to ``[-clamp, clamp]`` where ``clamp > 0`` BEFORE the incoming gradient
+    (the ``1 / batch`` of ``'mean'`` included) multiplies it, as in torchaudio, and is zero for ``t >= Tb`` or ``u > Ub``.
+
+    float32 on a HIP device whose class axis has unit stride (any positive other strides: a ``[:, :T', :U'+1]`` slice of a padded
+    joint output is read in place), with ``target + 1 <= 1024`` and fewer than 2^31 lattice cells, runs csrc/rnnt.hip: forward two
+    launches (one read of the valid part of the logits: the denominators and the two log-probabilities of every lattice cell;
+    then alpha and beta together), backward one (a second read of the logits, one write of the gradient).  Three ``(batch, time,
+    target + 1)`` arrays are kept for the backward pass — no copy of the logits and no gradient buffer.  Bit-identical from run
+    to run and, for an entry, whatever else is in the batch.  Other inputs take ``_composite.rnnt_loss``, announced.
+
+    The one deviation from torchaudio: its checks ``logit_lengths.max() == time`` and ``target_lengths.max() == target`` read
+    device memory, so they are made for CPU tensors only; on a HIP device nothing waits for the host.  There an entry with ``Tb``
+    outside ``[1, time]``, ``Ub`` outside ``[0, target]`` or a used target outside ``[0, class)`` gets a NaN cost and a NaN gradient
+    over its own block; the other entries are unaffected and no address outside the tensors is formed."""
+    if reduction not in ('none', 'mean', 'sum'):
+        raise ValueError("rnnt_loss: reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+    blank = _ops.rnnt_check(logits, targets, logit_lengths, target_lengths, int(blank))
+    costs = _call('rnnt_loss', logits, targets, logit_lengths, target_lengths, blank, float(clamp), bool(fused_log_softmax))[0]
+    if reduction == 'mean':
+        return costs.mean()
+    if reduction == 'sum':
+        return costs.sum()
+    return costs
 
 
 def preemphasis(waveforms, coeff=0.97):

@@ -669,6 +669,24 @@ class RTFMVDR(_ModuleNoStateBuffers):
         return _beamform.unpairs(out, was_complex)
 
 
+class RNNTLoss(_ModuleNoStateBuffers):
+    """torchaudio's ``transforms.RNNTLoss``: ``forward(logits, targets, logit_lengths, target_lengths)`` is ``functional.rnnt_loss``
+    with the ``blank``, ``clamp``, ``reduction`` and ``fused_log_softmax`` of the constructor.  No buffers, no parameters."""
+
+    def __init__(self, blank=-1, clamp=-1.0, reduction='mean', fused_log_softmax=True):
+        super(RNNTLoss, self).__init__()
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError("RNNTLoss: reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+        self.blank = blank
+        self.clamp = clamp
+        self.reduction = reduction
+        self.fused_log_softmax = fused_log_softmax
+
+    def forward(self, logits, targets, logit_lengths, target_lengths):
+        return F.rnnt_loss(logits, targets, logit_lengths, target_lengths, self.blank, self.clamp, self.reduction,
+                           self.fused_log_softmax)
+
+
 class MVDR(_ModuleNoStateBuffers):
     """torchaudio's mask-based ``transforms.MVDR`` at ``solution='ref_channel'``: ``forward(specgram, mask_s, mask_n=None)`` maps a
     ``(…, channel, freq, time)`` spectrogram and real ``(…, freq, time)`` masks (``(…, channel, freq, time)`` with ``multi_mask``,
