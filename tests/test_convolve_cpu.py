@@ -192,3 +192,153 @@ def test_kernel_cache_follows_in_place_writes(tac):
     H.invalidate(y)
     H.cached_on(y, '_tac_conv', ('spectra', 2048, False), build)
     assert len(built) == 4
+
+
+def test_cached_on_keeps_a_none_result(tac):
+    H = tac._hip
+    y = torch.arange(6.0)
+    calls = []
+
+    def build():
+        calls.append(1)
+    assert H.cached_on(y, '_tac_adj', (), build) is None and H.cached_on(y, '_tac_adj', (), build) is None
+    assert len(calls) == 1 and y._tac_adj[1] == {(): None}
+    y.add_(1.0)                                                          # ... per contents: a write asks again
+    assert H.cached_on(y, '_tac_adj', (), build) is None and len(calls) == 2
+
+
+def test_cached_on_limit_bounds_the_slot(tac):
+    H = tac._hip
+    y = torch.arange(6.0)
+    built = []
+
+    def build_for(key):
+        def build():
+            built.append(key)
+            return [key]
+        return build
+    a = H.cached_on(y, '_tac_dft', 'a', build_for('a'), limit=1)
+    assert H.cached_on(y, '_tac_dft', 'a', build_for('a'), limit=1) is a and built == ['a']
+    H.cached_on(y, '_tac_dft', 'b', build_for('b'), limit=1)             # a second key evicts the first
+    assert list(y._tac_dft[1]) == ['b']
+    assert H.cached_on(y, '_tac_dft', 'a', build_for('a'), limit=1) is not a and built == ['a', 'b', 'a']
+    for k in range(40):                                                  # the default: 16 kept, emptied when one more arrives
+        H.cached_on(y, '_tac_conv', k, build_for(k))
+        assert len(y._tac_conv[1]) == k % 16 + 1
+
+
+def test_cached_on_refuses_a_slot_invalidate_does_not_know(tac):
+    H = tac._hip
+    y = torch.arange(6.0)
+    with pytest.raises(ValueError, match='_CACHE_ATTRS'):
+        H.cached_on(y, '_tac_unlisted', 0, lambda: 1)
+    assert not hasattr(y, '_tac_unlisted')
+
+
+def test_cached_on_builds_outside_inference_mode(tac):
+    H = tac._hip
+    y = torch.arange(6.0)
+    with torch.inference_mode():
+        first = H.cached_on(y, '_tac_T', (), lambda: y.detach() * 2)
+        assert H.cached_on(y, '_tac_T', (), lambda: y.detach() * 2) is first
+    assert not first.is_inference() and torch.equal(first, torch.arange(6.0) * 2)
+
+
+def test_cached_on_rebuilds_for_a_tensor_made_in_inference_mode(tac):
+    H = tac._hip
+    with torch.inference_mode():
+        y = torch.arange(6.0)
+    built = []
+
+    def build():
+        built.append(float(y.sum()))
+        return y.detach() + 1
+    first = H.cached_on(y, '_tac_T', (), build)
+    with torch.inference_mode():
+        y.mul_(2.0)                                                      # (no version counter records it)
+    again = H.cached_on(y, '_tac_T', (), build)
+    assert built == [15.0, 30.0] and again is not first
+    assert torch.equal(first, torch.arange(6.0) + 1) and torch.equal(again, torch.arange(6.0) * 2 + 1)
+
+
+def test_invalidate_drops_every_slot_cached_on_wrote(tac):
+    H = tac._hip
+    y = torch.arange(6.0)
+    other = torch.arange(6.0)
+    for attr in H._CACHE_ATTRS:
+        H.cached_on(y, attr, 0, lambda: attr)
+        H.cached_on(other, attr, 0, lambda: attr)
+    assert all(hasattr(y, attr) for attr in H._CACHE_ATTRS)
+    e0 = H._epoch
+    H.invalidate(y)
+    assert not any(hasattr(y, attr) for attr in H._CACHE_ATTRS) and H._epoch == e0      # targeted: no epoch bump
+    assert all(getattr(other, attr)[1] == {0: attr} for attr in H._CACHE_ATTRS)
+
+
+def _table_builders(H):
+    """(name, tensor from contents, table of that tensor, slot) for the derived tables that need no library on CPU tensors"""
+    window = lambda v: v[:96].clone()
+    matrix = lambda v: v[:96].reshape(12, 8).clone()
+    return [('dft', window, lambda w: H._dft_matrix(w, 96, 96, True, False), '_tac_dft'),
+            ('dftT', window, lambda w: H._dft_matrix_t(w, 96, 96, False), '_tac_dftT'),
+            ('T', matrix, H.transposed_bank, '_tac_T'),
+            ('dct', matrix, lambda m: H._dct_matrix(m, True), '_tac_dct')]
+
+
+@pytest.mark.parametrize('which', [0, 1, 2, 3], ids=['dft', 'dftT', 'T', 'dct'])
+def test_derived_tables_follow_their_tensor(tac, which):
+    H = tac._hip
+    _, make, table, slot = _table_builders(H)[which]
+    values = torch.linspace(0.25, 1.0, 96)
+    t = make(values)
+    first = table(t)
+    assert table(t) is first and getattr(t, slot)[0] == H._stamp(t)      # unchanged tensor: the identical object
+    t.mul_(2)
+    again = table(t)
+    assert again is not first and table(t) is again
+    assert torch.equal(again, table(make(values * 2))) and not torch.equal(again, first)
+
+
+def test_window_holds_one_dft_matrix(tac):
+    H = tac._hip
+    w = torch.hann_window(96)
+    m96 = H._dft_matrix(w, 96, 96, True, False)
+    m100 = H._dft_matrix(w, 100, 96, True, False)
+    assert m96.shape == (96, 98) and m100.shape == (100, 102)
+    assert list(w._tac_dft[1].values())[0] is m100 and len(w._tac_dft[1]) == 1
+    H._dft_matrix_t(w, 96, 96, False)
+    H._dft_matrix_t(w, 100, 96, False)
+    assert len(w._tac_dftT[1]) == 1 and len(w._tac_dft[1]) == 1
+
+
+def test_bounded_dict_clears_when_full(tac):
+    from torchaudio_contrib_amd._bounded import Bounded
+    d = Bounded(4)
+    for k in range(5):
+        d[k] = k
+    assert len(d) == 5                                                   # limit + 1 entries
+    d[2] = 'again'                                                       # an existing key never clears
+    assert len(d) == 5 and d[2] == 'again'
+    d[5] = 5                                                             # the next new key leaves exactly one
+    assert dict(d) == {5: 5}
+    import copy, io, pickle
+    full = Bounded(2)
+    for k in range(3):
+        full[k] = [k]
+    for back in (pickle.loads(pickle.dumps(full)), copy.deepcopy(full), copy.copy(full)):
+        assert type(back) is Bounded and back.limit == 2 and dict(back) == {0: [0], 1: [1], 2: [2]}
+        back[3] = [3]
+        assert dict(back) == {3: [3]}
+    stft = tac.STFT(64, 16)
+    stft.__dict__['_recipes'] = Bounded(32)                              # what a deferred forward leaves on the module
+    stft.__dict__['_recipes'][('shape', 64)] = (stft.window, 'template')
+    buf = io.BytesIO()
+    torch.save(stft, buf)                                                # a whole-module checkpoint reads back
+    buf.seek(0)
+    loaded = torch.load(buf, weights_only=False)
+    assert type(loaded._recipes) is Bounded and loaded._recipes.limit == 32 and list(loaded._recipes) == [('shape', 64)]
+    assert torch.equal(loaded.window, stft.window)
+    for mod, name, limit in [(tac._hip, '_geometry_cache', 512), (tac._hip, '_ones_cache', 64), (tac._resample, '_banks', 64),
+                             (tac._filters, '_tensors', 256), (tac.functional, '_window_cache', 64),
+                             (tac._lazy, '_plans', 64), (tac._composite, '_kaldi_constants', 32)]:
+        assert type(getattr(mod, name)) is Bounded and getattr(mod, name).limit == limit, name

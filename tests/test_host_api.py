@@ -468,6 +468,31 @@ def test_invalidate_through_an_alias_drops_everything():
     assert _hip._epoch == e0 + 2
 
 
+def test_every_table_slot_goes_through_cached_on():
+    """Every ``_tac_*`` name in the package is a slot ``invalidate`` walks (``_hip._CACHE_ATTRS``) or one of the two names that
+    are no cache — the ``_tac_realizes`` class attribute and the ``_tac_ext`` module (its file is ``_tac_ext.so``: the name is
+    what stands before the first dot) — and no code outside ``cached_on`` / ``invalidate`` reaches a slot as an attribute."""
+    import ast
+    from torchaudio_contrib_amd import _hip
+    names = set(_hip._CACHE_ATTRS) | {'_tac_realizes', '_tac_ext'}
+    pkg = os.path.join(ROOT, 'torchaudio-contrib_amd')
+    for f in sorted(os.listdir(pkg)):
+        if not f.endswith('.py'):
+            continue
+        tree = ast.parse(open(os.path.join(pkg, f)).read(), f)
+        inside = set()              # (nodes of the two functions that may touch a slot)
+        for node in ast.walk(tree):
+            if f == '_hip.py' and isinstance(node, ast.FunctionDef) and node.name in ('cached_on', 'invalidate'):
+                inside.update(id(n) for n in ast.walk(node))
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Constant) and isinstance(node.value, str) and node.value.startswith('_tac_'):
+                assert node.value.split('.')[0] in names, (f, node.lineno, node.value)
+            elif isinstance(node, ast.Attribute) and node.attr.startswith('_tac_'):
+                assert id(node) in inside, (f, node.lineno, node.attr)
+            elif isinstance(node, ast.Name) and node.id.startswith('_tac_'):
+                assert node.id == '_tac_realizes' and isinstance(node.ctx, ast.Store), (f, node.lineno, node.id)
+
+
 def test_forced_collective_in_a_group_of_one():
     """all_gather_batch(force_collective=True) runs the real collective at world size 1 (what the RCCL smoke test of a 1-GPU
     box relies on) and returns the shard unchanged, for both exchange methods and for the strided views the layers return."""

@@ -27,6 +27,7 @@ from . import _filters
 from . import _kaldi
 from . import _pitch
 from . import _beamform
+from ._bounded import Bounded
 
 TWO_PI = 2.0 * math.pi
 
@@ -454,7 +455,7 @@ def compute_deltas(x, win_length, mode):
     return out.to(x.dtype).contiguous()
 
 
-_kaldi_constants = {}
+_kaldi_constants = Bounded(32)
 
 
 def mask_spans(x, spans, k_a, value):
@@ -509,8 +510,6 @@ def _kaldi_tables(p, w, n, dtype, device):
             if bins is not None:
                 bank = _kaldi.mel_bank64(bins, n, p.sample_frequency, p.low_freq, p.high_freq)[:, :-1]
                 bank = bank.to(dtype).to(device)
-        if len(_kaldi_constants) > 32:
-            _kaldi_constants.clear()
         hit = _kaldi_constants[key] = (window, bank)
     return hit
 

@@ -8,6 +8,8 @@ import math
 
 import torch
 
+from ._bounded import Bounded
+
 
 def check_coeffs(a_coeffs, b_coeffs):
     """``ValueError`` unless both are 1-D floating-point tensors of equal, non-zero length.  (``a_coeffs[0] != 0`` is checked on
@@ -133,7 +135,7 @@ def loudness_check(waveform, sample_rate, name='loudness'):
     return gate, step
 
 
-_tensors = {}
+_tensors = Bounded(256)
 
 
 def host_tensor(values):
@@ -143,7 +145,5 @@ def host_tensor(values):
     if hit is None:
         with torch.inference_mode(False):
             hit = torch.tensor(key, dtype=torch.float64)
-        if len(_tensors) > 256:
-            _tensors.clear()
         _tensors[key] = hit
     return hit

@@ -17,6 +17,7 @@ import torch
 from . import _kaldi
 from . import _native
 from . import _resample
+from ._bounded import Bounded
 
 _lock = threading.Lock()
 
@@ -48,9 +49,14 @@ def _launch(name, dev, filled, *args, accept=()):
 
 
 # ----------------------------------------------------------------------------- constant-table caches
-# Everything derived from a window / filterbank (packed weights, tile plans, transposes, adjoint tables, DFT matrices)
-# is cached ON the tensor object and stamped with what identifies its contents cheaply: the version counter (every
-# in-place torch op bumps it), the data pointer (``set_`` / ``.data = other``) and the invalidation epoch below.
+# Everything derived from a window / filterbank / coefficient tensor (packed weights, tile plans, transposes, adjoint tables,
+# DFT matrices, the istft envelope, host read-backs) hangs ON the tensor object, and ``cached_on`` below is the only code that
+# hangs it there.  A slot (one of ``_CACHE_ATTRS``, the list ``invalidate`` walks) holds ``(stamp, {key: table})``; the stamp
+# is what identifies the tensor's contents cheaply: the version counter (every in-place torch op bumps it), the data pointer
+# (``set_`` / ``.data = other``) and the invalidation epoch below.  A table that is ``None`` is a result like any other ("this
+# bank is not band-sparse" costs a host synchronisation to find out, once).  A slot keeps 16 tables unless its site says
+# otherwise: ``_tac_istft`` 64 small envelopes, ``_tac_dft`` / ``_tac_dftT`` ONE matrix each — at fft_length 8192 a matrix is
+# 8192 x 8194 floats = 268 MB, so a window used at a second geometry gives up the first one's matrix.
 # Writes that PyTorch itself does not record — ``t.data.mul_(2)`` (``.data`` has its own version counter), writes
 # through an alias created before the cache, ``from_dlpack`` / raw-pointer writers — cannot be seen without reading the
 # tensor back on every call; after such a write call ``invalidate(t)`` (or ``invalidate()`` for everything).
@@ -68,6 +74,36 @@ def _stamp(t):
     if t.is_inference():
         return ('unversioned', next(_unstamped))
     return (t._version, t.data_ptr(), _epoch)
+
+
+def cached_on(t, attr, key, build, limit=16):
+    """``build()`` once per (contents of ``t``, ``key``), whatever it returns (a ``None`` is kept like any table): the table
+    lives on the tensor object in the slot ``attr`` (one of ``_CACHE_ATTRS``), stamped as above, so an in-place write to ``t``
+    rebuilds it.  The slot keeps at most ``limit`` tables — exactly, unlike ``Bounded``, which may exceed its limit by one: a
+    ``limit`` of 1 has to mean one DFT matrix — and is emptied when one more arrives.  ``build`` runs outside
+    inference mode: its tensors may be saved for a later call's backward.  A tensor object that cannot carry attributes has
+    its tables rebuilt on every call."""
+    cache = getattr(t, attr, None)
+    stamp = _stamp(t)
+    if cache is None or cache[0] != stamp:
+        if attr not in _CACHE_ATTRS:            # (checked where a slot is written: a hit costs nothing for it)
+            raise ValueError('cached_on: %r is not in _CACHE_ATTRS, invalidate() would miss it' % (attr,))
+        cache = (stamp, {})
+        try:
+            setattr(t, attr, cache)
+        except (AttributeError, RuntimeError):
+            pass
+    tables = cache[1]
+    try:
+        return tables[key]
+    except KeyError:
+        pass
+    with torch.inference_mode(False):
+        made = build()
+    if len(tables) >= limit:
+        tables.clear()
+    tables[key] = made
+    return made
 
 
 def invalidate(tensor=None):
@@ -93,7 +129,7 @@ def invalidate(tensor=None):
             carried = True
             try:
                 delattr(tensor, name)
-            except Exception:
+            except (AttributeError, RuntimeError):
                 pass
     with _lock:
         carried = carried or any(k[0] == id(tensor) for g in _geometry_cache.values() for k in g.routes) \
@@ -127,7 +163,7 @@ class StftGeometry(object):
                  'stft_shape', 'spec_shape', 'routes')
 
 
-_geometry_cache = {}
+_geometry_cache = Bounded(512)
 
 
 def stft_frames(length, n_fft, hop, center):
@@ -237,8 +273,6 @@ def geometry(wave, n_fft, hop, win_length, center, pad_mode, normalized, oneside
     g.spec_shape = g.lead + (g.n_frames, g.n_bins)
     g.routes = {}
     with _lock:
-        if len(_geometry_cache) > 512:
-            _geometry_cache.clear()
         _geometry_cache[key] = g
     return g
 
@@ -251,28 +285,21 @@ def _rows_of(wave, g):
 def _dft_matrix(window, n_fft, win_length, onesided, normalized):
     """(N, 2F) float32 device matrix [w[n] cos(2 pi k n / N), -w[n] sin(2 pi k n / N)] for the DFT-matrix path,
     built on the device in float64 (angles reduced exactly through (n*k) mod N in int64) and rounded once — a
-    constant table like the FFT twiddles, cached on the window tensor per (version, geometry)."""
-    cache = getattr(window, '_tac_dft', None)
-    key = (_stamp(window), n_fft, win_length, bool(onesided), bool(normalized))
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    dev = window.device
-    w = torch.zeros(n_fft, dtype=torch.float64, device=dev)
-    off = (n_fft - win_length) // 2
-    w[off:off + win_length] = window.detach().double()
-    if normalized:
-        w = w / math.sqrt(n_fft)
-    n_bins = n_fft // 2 + 1 if onesided else n_fft
-    n = torch.arange(n_fft, dtype=torch.int64, device=dev)[:, None]
-    k = torch.arange(n_bins, dtype=torch.int64, device=dev)[None, :]
-    ang = ((n * k) % n_fft).double() * (2.0 * math.pi / n_fft)
-    mat = torch.stack([torch.cos(ang) * w[:, None], -torch.sin(ang) * w[:, None]], dim=-1)
-    mat = mat.to(torch.float32).reshape(n_fft, 2 * n_bins).contiguous()
-    try:
-        window._tac_dft = (key, mat)
-    except Exception:
-        pass
-    return mat
+    constant table like the FFT twiddles, cached on the window tensor: the matrix of ONE geometry (up to 268 MB)."""
+    def build():
+        dev = window.device
+        w = torch.zeros(n_fft, dtype=torch.float64, device=dev)
+        off = (n_fft - win_length) // 2
+        w[off:off + win_length] = window.detach().double()
+        if normalized:
+            w = w / math.sqrt(n_fft)
+        n_bins = n_fft // 2 + 1 if onesided else n_fft
+        n = torch.arange(n_fft, dtype=torch.int64, device=dev)[:, None]
+        k = torch.arange(n_bins, dtype=torch.int64, device=dev)[None, :]
+        ang = ((n * k) % n_fft).double() * (2.0 * math.pi / n_fft)
+        mat = torch.stack([torch.cos(ang) * w[:, None], -torch.sin(ang) * w[:, None]], dim=-1)
+        return mat.to(torch.float32).reshape(n_fft, 2 * n_bins).contiguous()
+    return cached_on(window, '_tac_dft', (n_fft, win_length, bool(onesided), bool(normalized)), build, limit=1)
 
 
 def _stft_dft(wave, window, g):
@@ -339,25 +366,12 @@ def istft_envelope(window, n_fft, hop, win_length, center, n_frames, kept):
     a constant of (window contents, geometry), cached on the window tensor like the other derived tables.  The first use of an
     entry for a kept range of ``kept`` samples reads min env once (a host synchronisation) and raises the ``RuntimeError``
     ``torch.istft`` raises when the window overlap-add vanishes there (NOLA); later calls synchronise nothing."""
-    cache = getattr(window, '_tac_istft', None)
-    stamp = _stamp(window)
-    if cache is None or cache[0] != stamp:
-        cache = (stamp, {})
-        try:
-            window._tac_istft = cache
-        except Exception:
-            pass
-    key = (n_fft, hop, win_length, bool(center), n_frames)
-    entry = cache[1].get(key)
-    if entry is None:
-        n_pos = hop * (n_frames - 1) + n_fft
-        with torch.inference_mode(False):
-            inv_env = torch.empty(n_pos, dtype=torch.float32, device=window.device)
+    def build():
+        inv_env = torch.empty(hop * (n_frames - 1) + n_fft, dtype=torch.float32, device=window.device)
         desc = _istft_desc(1, 1, 1, n_fft, hop, win_length, center, False)
         _launch('tac_istft_envelope_f32', window.device, (), _native.ptr(window), desc, n_frames, _native.ptr(inv_env), None)
-        if len(cache[1]) > 64:
-            cache[1].clear()
-        entry = cache[1][key] = (inv_env, set())
+        return inv_env, set()
+    entry = cached_on(window, '_tac_istft', (n_fft, hop, win_length, bool(center), n_frames), build, limit=64)
     if kept not in entry[1]:
         pad = n_fft // 2 if center else 0
         peak = float(entry[0][pad:pad + kept].max().item())         # (one table serves both: min env = 1 / max (1 / env))
@@ -534,30 +548,20 @@ def _melbank_pack(fb, n_fft):
     """(wpack, desc, info) device/host buffers of the band-sparse contraction for this filterbank and fft size, or
     None when the bank is not band-sparse enough (then the MFMA kernels are used).  Built once per filterbank
     version (one host sync) and cached on the tensor object."""
-    cache = getattr(fb, '_tac_pack', None)
-    if cache is None or cache[0] != _stamp(fb):
-        cache = (_stamp(fb), {})
-        try:
-            fb._tac_pack = cache
-        except Exception:
-            pass
-    if n_fft in cache[1]:
-        return cache[1][n_fft]
-    n_freqs, n_mels = fb.shape
-    wpack = torch.empty(24576, dtype=torch.float32, device=fb.device)
-    desc = torch.empty(8192, dtype=torch.int32, device=fb.device)
-    info = (ctypes.c_int32 * 8)()
-    with _native.on_device(fb.device):
-        rc = _native.lib().tac_melbank_pack(_native.ptr(fb), n_freqs, n_mels, n_fft, _native.ptr(wpack), 24576,
-                                            _native.ptr(desc), 8192, ctypes.cast(info, ctypes.c_void_p),
-                                            _native.stream_ptr(fb.device))
-    if rc == _native.TAC_E_UNSUPPORTED:
-        result = None
-    else:
+    def build():
+        n_freqs, n_mels = fb.shape
+        wpack = torch.empty(24576, dtype=torch.float32, device=fb.device)
+        desc = torch.empty(8192, dtype=torch.int32, device=fb.device)
+        info = (ctypes.c_int32 * 8)()
+        with _native.on_device(fb.device):
+            rc = _native.lib().tac_melbank_pack(_native.ptr(fb), n_freqs, n_mels, n_fft, _native.ptr(wpack), 24576,
+                                                _native.ptr(desc), 8192, ctypes.cast(info, ctypes.c_void_p),
+                                                _native.stream_ptr(fb.device))
+        if rc == _native.TAC_E_UNSUPPORTED:
+            return None
         _native.check(rc, 'tac_melbank_pack')
-        result = (wpack, desc, info)
-    cache[1][n_fft] = result
-    return result
+        return wpack, desc, info
+    return cached_on(fb, '_tac_pack', n_fft, build)
 
 
 # The fused fft_length-2048 float32 launches contract 128-band banks in the PAIR layout (csrc/melspec_sparse.hip pack_pairs: 14
@@ -582,22 +586,17 @@ def _filterbank_plan(fb):
     The plan rides on the filterbank tensor object itself (a module's constant buffer is scanned once — the only
     host sync on the path — and rescanned when modified in place); keying a cache on ``data_ptr`` would go stale
     when the allocator reuses an address."""
-    hit = getattr(fb, '_tac_plan', None)
-    if hit is not None and hit[0] == _stamp(fb) and hit[1].device == fb.device:
-        return hit[1], hit[2]
-    n_freqs, n_mels = fb.shape
-    n_ints = 2 * ((n_mels + 15) // 16)
-    plan = torch.empty(n_ints, dtype=torch.int32, device=fb.device)
-    host = (ctypes.c_int32 * n_ints)()
-    with _native.on_device(fb.device):
-        rc = _native.lib().tac_filterbank_plan(_native.ptr(fb), n_freqs, n_mels, _native.ptr(plan),
-                                               ctypes.cast(host, ctypes.c_void_p), _native.stream_ptr(fb.device))
-    _native.check(rc, 'tac_filterbank_plan')
-    try:
-        fb._tac_plan = (_stamp(fb), plan, host)
-    except Exception:       # exotic tensor subclasses without attribute storage: just recompute next time
-        pass
-    return plan, host
+    def build():
+        n_freqs, n_mels = fb.shape
+        n_ints = 2 * ((n_mels + 15) // 16)
+        plan = torch.empty(n_ints, dtype=torch.int32, device=fb.device)
+        host = (ctypes.c_int32 * n_ints)()
+        with _native.on_device(fb.device):
+            rc = _native.lib().tac_filterbank_plan(_native.ptr(fb), n_freqs, n_mels, _native.ptr(plan),
+                                                   ctypes.cast(host, ctypes.c_void_p), _native.stream_ptr(fb.device))
+        _native.check(rc, 'tac_filterbank_plan')
+        return plan, host
+    return cached_on(fb, '_tac_plan', fb.device, build)
 
 
 def _fused_mel_route(g, fb, power):
@@ -784,18 +783,10 @@ def _dct_matrix(mat, transposed):
     object per version, like the filterbank's packs and its transpose."""
     if not transposed and mat.dtype == torch.float32 and mat.is_contiguous():
         return mat.detach()
-    hit = getattr(mat, '_tac_dct', None)
-    if hit is None or hit[0] != _stamp(mat):
-        hit = (_stamp(mat), {})
-        try:
-            mat._tac_dct = hit
-        except Exception:
-            pass
-    m = hit[1].get(transposed)
-    if m is None:
+    def build():
         src = mat.detach().t() if transposed else mat.detach()
-        m = hit[1][transposed] = src.to(torch.float32).contiguous()
-    return m
+        return src.to(torch.float32).contiguous()
+    return cached_on(mat, '_tac_dct', bool(transposed), build)
 
 
 def dct_rows(x, mat, transposed=False):
@@ -849,7 +840,7 @@ def resample_covers(orig, new, lpw, rolloff, method, beta):
         resample_tile(_resample.adjoint_bank(orig, new, lpw, rolloff, method, beta)) is not None
 
 
-_resample_tables = {}
+_resample_tables = Bounded(64)
 
 
 def _resample_device_bank(key, adjoint, device):
@@ -860,8 +851,6 @@ def _resample_device_bank(key, adjoint, device):
         b = (_resample.adjoint_bank if adjoint else _resample.bank)(*key)
         taps = b.taps.t().contiguous().to(torch.float32).to(device)
         table = torch.tensor([b.off, b.run], dtype=torch.int32).to(device)
-        if len(_resample_tables) > 64:
-            _resample_tables.clear()
         hit = _resample_tables[(key, adjoint, device)] = (b, taps, table, min(b.off), max(b.off), min(b.run))
     return hit
 
@@ -892,7 +881,7 @@ LFILTER_TILE = 1024 * LFILTER_C
 #: coefficients per side the kernel takes (order <= 2)
 LFILTER_MAX_COEFFS = 3
 
-_lfilter_ok = {}
+_lfilter_ok = Bounded(256)
 _lfilter_chunk_checked = False
 
 
@@ -913,8 +902,6 @@ def lfilter_covers(b, a):
         else:
             cb, ca = _lfilter_arrays(*key)
             hit = _native.lib().tac_lfilter_supported(cb, ca, len(key[1])) == _native.TAC_OK
-        if len(_lfilter_ok) > 256:
-            _lfilter_ok.clear()
         _lfilter_ok[key] = hit
     return hit
 
@@ -922,17 +909,9 @@ def lfilter_covers(b, a):
 def host_coeffs(t):
     """The coefficients of a 1-D tensor as a tuple of Python floats (float32 converts exactly).  A device tensor is read back once
     per version of its contents (one host sync) and the tuple cached on the tensor object, like the tables of a window."""
-    if not t.is_cuda:
+    def build():
         return tuple(t.detach().to(torch.float64).tolist())
-    cache = getattr(t, '_tac_coef', None)
-    stamp = _stamp(t)
-    if cache is None or cache[0] != stamp:
-        cache = (stamp, tuple(t.detach().to(torch.float64).tolist()))
-        try:
-            t._tac_coef = cache
-        except (AttributeError, RuntimeError):
-            pass
-    return cache[1]
+    return cached_on(t, '_tac_coef', (), build) if t.is_cuda else build()
 
 
 def lfilter_rows(x, b, a, clamp, reverse=False):
@@ -1353,26 +1332,6 @@ def fftconvolve_covers(length, m, n_fft=0):
     return _native.lib().tac_fftconvolve_supported(length, m, n) == _native.TAC_OK
 
 
-def cached_on(t, attr, key, build):
-    """``build()`` once per (contents of ``t``, ``key``): the table lives on the tensor object under ``attr``, stamped like the
-    tables of a window (version counter, data pointer, invalidation epoch), so an in-place write to ``t`` rebuilds it."""
-    cache = getattr(t, attr, None)
-    stamp = _stamp(t)
-    if cache is None or cache[0] != stamp:
-        cache = (stamp, {})
-        try:
-            setattr(t, attr, cache)
-        except (AttributeError, RuntimeError):
-            pass
-    hit = cache[1].get(key)
-    if hit is None:
-        if len(cache[1]) > 16:
-            cache[1].clear()
-        with torch.inference_mode(False):
-            hit = cache[1][key] = build()
-    return hit
-
-
 def _conv_kernel_rows(y):
     m = int(y.shape[-1])
     rows = y.detach().reshape(-1, m)
@@ -1474,7 +1433,7 @@ KALDI_SIZES = (256, 512, 1024)
 KALDI_MAX_BINS = 128
 _KALDI_FLAGS = dict(snip_edges=1, remove_dc_offset=2, raw_energy=4, use_energy=8, htk_compat=16, use_log_fbank=32, use_power=64)
 
-_kaldi_tables = {}
+_kaldi_tables = Bounded(64)
 
 
 def _kaldi_device_tables(p, w, n, device):
@@ -1493,8 +1452,6 @@ def _kaldi_device_tables(p, w, n, device):
                 bank = _kaldi.mel_bank64(bins, n, p.sample_frequency, p.low_freq, p.high_freq).to(torch.float32)
                 weights, table = _kaldi.packed_runs(bank)
                 hit = (window.to(device), weights.to(device), table.contiguous().to(device), int(weights.numel()))
-        if len(_kaldi_tables) > 64:
-            _kaldi_tables.clear()
         _kaldi_tables[key] = hit
     return hit
 
@@ -1513,7 +1470,7 @@ def _kaldi_flags(p):
     return sum(bit for name, bit in _KALDI_FLAGS.items() if getattr(p, name, False))
 
 
-_kaldi_dct_tables = {}
+_kaldi_dct_tables = Bounded(64)
 
 
 def _kaldi_dct_table(p, device):
@@ -1524,8 +1481,6 @@ def _kaldi_dct_table(p, device):
     if hit is None:
         with torch.inference_mode(False):
             hit = _kaldi.mfcc_table64(p).to(torch.float32).contiguous().to(device)
-        if len(_kaldi_dct_tables) > 64:
-            _kaldi_dct_tables.clear()
         _kaldi_dct_tables[key] = hit
     return hit
 
@@ -1845,7 +1800,7 @@ def magphase(z, power):
     return mag, phase
 
 
-_PV_GRID_CACHE = {}
+_PV_GRID_CACHE = Bounded(64)
 
 
 def _phase_vocoder_grid(n_frames, rate, device, dtype):
@@ -1856,8 +1811,6 @@ def _phase_vocoder_grid(n_frames, rate, device, dtype):
     hit = _PV_GRID_CACHE.get(key)
     if hit is None:
         steps = torch.arange(0, n_frames, rate)
-        if len(_PV_GRID_CACHE) > 64:
-            _PV_GRID_CACHE.clear()
         hit = (steps.long().to(torch.int32).to(device), (steps + 1).long().to(torch.int32).to(device),
                torch.remainder(steps, torch.tensor(1., dtype=steps.dtype)).to(dtype).to(device))
         _PV_GRID_CACHE[key] = hit
@@ -1913,7 +1866,7 @@ def phase_vocoder_backward(spec, rate, grad_out):
 
 
 # ----------------------------------------------------------------------------- stretch on magnitudes (csrc/stretch.hip)
-_PV_BOUNDS_CACHE = {}
+_PV_BOUNDS_CACHE = Bounded(64)
 
 
 def _stretch_bounds(n_frames, rate, device):
@@ -1924,8 +1877,6 @@ def _stretch_bounds(n_frames, rate, device):
     hit = _PV_BOUNDS_CACHE.get(key)
     if hit is None:
         first = torch.arange(0, n_frames, rate).long()
-        if len(_PV_BOUNDS_CACHE) > 64:
-            _PV_BOUNDS_CACHE.clear()
         hit = torch.searchsorted(first, torch.arange(n_frames + 1)).to(torch.int32).to(device)
         _PV_BOUNDS_CACHE[key] = hit
     return hit
@@ -1934,15 +1885,7 @@ def _stretch_bounds(n_frames, rate, device):
 def finite_table(t):
     """Whether every element of a constant table (``TimeStretch.phase_advance``) is finite: read back once per buffer version
     (one host synchronisation) and cached on the tensor like the tables derived from windows and filterbanks."""
-    hit = getattr(t, '_tac_finite', None)
-    if hit is not None and hit[0] == _stamp(t):
-        return hit[1]
-    ok = bool(torch.isfinite(t).all())
-    try:
-        t._tac_finite = (_stamp(t), ok)
-    except Exception:
-        pass
-    return ok
+    return cached_on(t, '_tac_finite', (), lambda: bool(torch.isfinite(t).all()))
 
 
 def _magnitude_rows(mag):
@@ -2115,26 +2058,16 @@ def mu_law_decoding_f64(codes, n_quantize):
 def transposed_bank(fb):
     """(M, F) contiguous transpose of a filterbank, cached on the tensor per version (the adjoint of the filterbank
     stage is the same GEMM kernel with this matrix)."""
-    hit = getattr(fb, '_tac_T', None)
-    if hit is not None and hit[0] == _stamp(fb):
-        return hit[1]
-    t = fb.detach().t().contiguous()
-    try:
-        fb._tac_T = (_stamp(fb), t)
-    except Exception:
-        pass
-    return t
+    return cached_on(fb, '_tac_T', (), lambda: fb.detach().t().contiguous())
 
 
 def _adjoint_table(fb):
     """Per-bin {w0, w1, band0, band1} table of a bank with at most two non-zero weights per bin (every triangular mel
     bank), built on the device once per filterbank version (one host sync) and cached on the tensor; None otherwise."""
-    hit = getattr(fb, '_tac_adj', None)
-    if hit is not None and hit[0] == _stamp(fb):
-        return hit[1]
-    n_freqs, n_mels = fb.shape
-    table = None
-    if n_mels <= 512 and 16 * n_freqs + 4 * 4 * n_mels <= 64 * 1024:
+    def build():
+        n_freqs, n_mels = fb.shape
+        if n_mels > 512 or 16 * n_freqs + 4 * 4 * n_mels > 64 * 1024:
+            return None
         src = fb if fb.is_contiguous() else fb.contiguous()         # (the cache stays on the caller's tensor object)
         table = torch.empty(4 * n_freqs + 4, dtype=torch.float32, device=fb.device)
         nnz = ctypes.c_int32(0)
@@ -2143,13 +2076,8 @@ def _adjoint_table(fb):
                                                            ctypes.cast(ctypes.pointer(nnz), ctypes.c_void_p),
                                                            _native.stream_ptr(fb.device))
         _native.check(rc, 'tac_filterbank_adjoint_pack')
-        if nnz.value > 2:
-            table = None
-    try:
-        fb._tac_adj = (_stamp(fb), table)
-    except Exception:
-        pass
-    return table
+        return table if nnz.value <= 2 else None
+    return cached_on(fb, '_tac_adj', (), build)
 
 
 def apply_filterbank_backward(grad_out, fb):
@@ -2312,7 +2240,7 @@ def sum_slabs(x):
     return out
 
 
-_ones_cache = {}
+_ones_cache = Bounded(64)
 
 
 def _ones_window(device, n):
@@ -2327,16 +2255,9 @@ def _ones_window(device, n):
 
 def _dft_matrix_t(window, n_fft, win_length, normalized):
     """(2F, N) transpose of the one-sided windowed-DFT matrix: the adjoint of ``_stft_dft`` is the same GEMM with it."""
-    cache = getattr(window, '_tac_dftT', None)
-    key = (_stamp(window), n_fft, win_length, bool(normalized))
-    if cache is not None and cache[0] == key:
-        return cache[1]
-    mat = _dft_matrix(window, n_fft, win_length, True, normalized).t().contiguous()
-    try:
-        window._tac_dftT = (key, mat)
-    except Exception:
-        pass
-    return mat
+    def build():
+        return _dft_matrix(window, n_fft, win_length, True, normalized).t().contiguous()
+    return cached_on(window, '_tac_dftT', (n_fft, win_length, bool(normalized)), build, limit=1)
 
 
 def _desc(g, row_stride=None, onesided=None):

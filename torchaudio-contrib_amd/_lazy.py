@@ -32,8 +32,10 @@ import sys
 import torch
 from torch.utils._pytree import tree_map
 
+from ._bounded import Bounded
+
 _enabled = True
-_plans = {}             # (window id, filterbank id, stft args, power, dB) -> _hip.MelPlan of the fused chain, or a negative
+_plans = Bounded(64)    # (window id, filterbank id, stft args, power, dB) -> _hip.MelPlan of the fused chain, or a negative
                         # entry (_NO_PLAN, window, filterbank, layout) for a call no plan covers; mutated under _hip._lock
 _NO_PLAN = object()
 
@@ -299,8 +301,6 @@ class DeferredSpectral(torch.Tensor):
         except Exception:                       # noqa: BLE001 — the plan is an optimisation only
             plan = None
         with _hip_lock():                       # (invalidate() walks and prunes this dict under the same lock)
-            if len(_plans) > 64:
-                _plans.clear()
             if plan is not None:
                 _plans[key] = plan
             else:
@@ -405,7 +405,7 @@ def _carries_grad(args, kwargs):
     return bool(found)
 
 
-_stride_cache = {}
+_stride_cache = Bounded(256)
 
 
 def _transposed_strides(lead, tail, a, b):
@@ -413,8 +413,6 @@ def _transposed_strides(lead, tail, a, b):
     key = (lead, tail, a, b)
     hit = _stride_cache.get(key)
     if hit is None:
-        if len(_stride_cache) > 256:
-            _stride_cache.clear()
         hit = _stride_cache[key] = _compute_transposed_strides(lead, tail, a, b)
     return hit
 

@@ -20,6 +20,8 @@ import math
 
 import torch
 
+from ._bounded import Bounded
+
 METHODS = ('sinc_interp_hann', 'sinc_interp_kaiser')
 KAISER_BETA = 14.769656459379492
 
@@ -68,7 +70,7 @@ def out_length(length, orig, new):
     return (new * length + orig - 1) // orig
 
 
-_banks = {}
+_banks = Bounded(64)
 
 
 def bank(orig, new, lpw, rolloff, method, beta):
@@ -103,13 +105,11 @@ def bank(orig, new, lpw, rolloff, method, beta):
     taps = torch.gather(h, 1, cols) * (torch.arange(K).unsqueeze(0) < run.unsqueeze(1))
     off = torch.gather(d, 1, lead.unsqueeze(1)).squeeze(1)
     made = Bank(new, orig, taps.contiguous(), [int(v) for v in off], [int(v) for v in run])
-    if len(_banks) > 64:
-        _banks.clear()
     _banks[key] = made
     return made
 
 
-_adjoints = {}
+_adjoints = Bounded(64)
 
 
 def adjoint_bank(orig, new, lpw, rolloff, method, beta):
@@ -140,8 +140,6 @@ def adjoint_bank(orig, new, lpw, rolloff, method, beta):
     taps = torch.zeros(orig, Ka, dtype=torch.float64)
     taps[q, e - lo[q]] = w
     made = Bank(orig, new, taps, [int(v) for v in lo], [int(v) for v in run])
-    if len(_adjoints) > 64:
-        _adjoints.clear()
     _adjoints[key] = made
     return made
 

@@ -27,6 +27,7 @@ from . import _beamform
 from . import _resample
 from . import _specaug
 from . import _augment
+from ._bounded import Bounded
 from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
@@ -44,7 +45,7 @@ def _tensor(x, what):
     return _realize(x)
 
 
-_window_cache = {}
+_window_cache = Bounded(64)
 
 
 def default_window(n, like):
@@ -60,8 +61,6 @@ def default_window(n, like):
         # a later call's backward ("Inference tensors cannot be saved for backward")
         with torch.inference_mode(False):
             w = torch.hann_window(n, dtype=dtype, device=like.device)
-        if len(_window_cache) > 64:
-            _window_cache.clear()
         _window_cache[key] = w
     return w
 

@@ -23,6 +23,7 @@ from . import _beamform
 from . import _resample
 from . import _specaug
 from . import _augment
+from ._bounded import Bounded
 from ._lazy import DeferredSpectral, DeferredWave, can_defer, can_defer_codes, lazy_fusion_enabled, realize
 
 
@@ -79,15 +80,13 @@ class STFT(_ModuleNoStateBuffers):
                    self.normalized, self.onesided, id(self.window))
             hit = self.__dict__.get('_recipes')
             if hit is None:
-                hit = self.__dict__['_recipes'] = {}
+                hit = self.__dict__['_recipes'] = Bounded(32)
             tmpl = hit.get(key)
             if tmpl is None or tmpl[0] is not self.window:
                 n_fft, hop, win_length, window = F.resolve_stft_args(waveforms, self.fft_length, self.hop_length,
                                                                      self.win_length, self.window)
                 _hip.check_stft_args(waveforms.shape, n_fft, hop, win_length, self.center, self.pad_mode)
                 if window is self.window:
-                    if len(hit) > 32:
-                        hit.clear()
                     tmpl = hit[key] = (window, DeferredSpectral.template(
                         waveforms.shape, n_fft, hop, win_length, bool(self.center), self.pad_mode, bool(self.normalized),
                         bool(self.onesided)))
