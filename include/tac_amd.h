@@ -873,6 +873,38 @@ int tac_rnnt_grad_f32(const float* logits, int64_t batch, int64_t frames, int64_
                       const float* costs, const float* grad_costs, int32_t blank, float clamp, int32_t fused, float* grad_logits,
                       void* stream);
 
+/* (28) functional.forced_align: CTC Viterbi alignment (csrc/align.hip) — the recursion, the backtrack, paths and scores in ONE
+ *      launch, a workgroup per batch entry.  log_probs: float32 [batch][frames][classes] with positive element strides stride_b /
+ *      stride_t / stride_c (a slice of a padded model output is read where it lies; offsets are 64-bit).  targets: DEVICE
+ *      [batch][max_targets], contiguous, int64 where index64 != 0, else int32; paths: DEVICE [batch][frames] of the same integer
+ *      type; scores: float32 [batch][frames].  input_lengths (Tb), target_lengths (Lb): DEVICE int32 [batch], or NULL for frames /
+ *      max_targets in every entry.  blank in [0, classes).
+ *
+ *      Per entry: states s = 0 .. 2 Lb, even ones the blank, s = 2k + 1 targets[k]; alpha[0][0] = lp[0][blank], alpha[0][1] =
+ *      lp[0][targets[0]], -inf elsewhere; for t >= 1, with x0 = alpha[t-1][s], x1 = alpha[t-1][s-1] and x2 = alpha[t-1][s-2] (only
+ *      for odd s >= 3 with targets[s/2] != targets[s/2 - 1]; -inf otherwise and out of range): back-pointer 2 if x2 > x1 and
+ *      x2 > x0, else 1 if x1 > x0 and x1 > x2, else 0, and alpha[t][s] = chosen + lp[t][label(s)], one float32 addition.  The end
+ *      state is 2 Lb if alpha[Tb-1][2 Lb] > alpha[Tb-1][2 Lb - 1], else 2 Lb - 1 (0 for Lb = 0); the back-pointers are followed to
+ *      t = 0.  paths[t] = label of the state at t, scores[t] = log_probs[t][paths[t]] (the same bits); for t >= Tb: blank and 0.
+ *      Selection is by ordered compares: ties go to the lower back-pointer, a NaN where the compares send it.
+ *
+ *      An entry with Tb outside [1, frames], Lb outside [0, max_targets], a used target equal to blank or outside [0, classes),
+ *      or Tb < Lb + (number of i in [1, Lb) with targets[i] == targets[i-1]) gets paths -1 and scores NaN on all frames; none of
+ *      these values forms an address, and the other entries are unaffected.  The same bits from run to run and whatever else is
+ *      in the batch.
+ *
+ *      max_targets + 1 above tac_forced_align_max_targets() (1024): TAC_E_UNSUPPORTED.  workspace: DEVICE,
+ *      tac_forced_align_workspace(batch, frames, max_targets + 1) bytes (8-byte aligned; not initialised, not an output): the
+ *      back-pointers (24 bytes per step and 64 targets) of entries whose Tb - 1 steps exceed what the kernel keeps in the LDS
+ *      (6144 / (3 waves) steps, 2048 at most); may be NULL where that size is 0.  tac_forced_align_workspace returns -1 for
+ *      sizes tac_forced_align_f32 refuses. */
+int32_t tac_forced_align_max_targets(void);
+int64_t tac_forced_align_workspace(int64_t batch, int64_t frames, int64_t targets1);
+int tac_forced_align_f32(const float* log_probs, int64_t batch, int64_t frames, int64_t classes, int64_t stride_b,
+                         int64_t stride_t, int64_t stride_c, const void* targets, int64_t max_targets, int32_t index64,
+                         const int32_t* input_lengths, const int32_t* target_lengths, int32_t blank, void* workspace, void* paths,
+                         float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,8 @@ from .functional import (stft, istft, complex_norm, create_mel_filter, apply_fil
                          preemphasis, deemphasis, fftconvolve, convolve, kaldi_fbank, sliding_window_cmn,
                          compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid,
                          add_noise, speed, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
-                         apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss)
+                         apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, forced_align,
+                         merge_tokens, TokenSpan)
 from .layers import (STFT, ISTFT, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
                      MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis,

@@ -875,3 +875,74 @@ def rnnt_loss_grad(logits, targets, logit_lengths, target_lengths, alphas, betas
     grad = grad * grad_costs.to(x.dtype)[:, None, None, None]
     grad = torch.where(ok[:, None, None, None], grad, torch.full((), float('nan'), dtype=x.dtype, device=dev))
     return grad.to(logits.dtype)
+
+
+# ----------------------------------------------------------------------------- forced_align
+def align_valid(log_probs, targets, input_lengths, target_lengths, blank):
+    """``(ok, Tb, Lb, lab)``: which entries have ``1 <= Tb <= T``, ``0 <= Lb <= L``, every used target inside ``[0, C)`` and not the
+    blank, and ``Tb >= Lb + repeats`` — the others end as ``-1`` / NaN — with the lengths and labels clamped into their ranges, so
+    that no index leaves the tensors.  On the device of the inputs: nothing waits for the host."""
+    B, T, C = log_probs.shape
+    L = targets.shape[1]
+    dev = log_probs.device
+    Tb = torch.full((B,), T, dtype=torch.long, device=dev) if input_lengths is None else input_lengths.long()
+    Lb = torch.full((B,), L, dtype=torch.long, device=dev) if target_lengths is None else target_lengths.long()
+    ok = (Tb >= 1) & (Tb <= T) & (Lb >= 0) & (Lb <= L)
+    tg = targets.long()
+    if L:
+        used = torch.arange(L, device=dev)[None, :] < Lb[:, None]
+        ok = ok & ~(used & ((tg < 0) | (tg >= C) | (tg == blank))).any(dim=1)
+        repeats = (used[:, 1:] & (tg[:, 1:] == tg[:, :-1])).sum(dim=1)
+        ok = ok & (Tb >= Lb + repeats)
+    return ok, Tb.clamp(1, T), Lb.clamp(0, L), tg.clamp(0, C - 1)
+
+
+def forced_align(log_probs, targets, input_lengths, target_lengths, blank):
+    """torchaudio's ``functional.forced_align`` without its state window, for any batch, in torch operators: ``(paths, scores)`` of
+    ``(B, T, C)`` log-probabilities.  All states and the whole batch at once, one step of the Python loop per frame for the
+    recursion and one for the backtrack; the predecessor is chosen by ``torch.where`` on strict comparisons (back-pointer 2 if
+    ``x2 > x1 and x2 > x0``, else 1 if ``x1 > x0 and x1 > x2``, else 0), never by a maximum, and every alpha is one addition in the
+    dtype of ``log_probs``.  Frames ``t >= Tb`` come back as blank and 0; an entry ``align_valid`` refuses as ``-1`` and NaN."""
+    B, T, C = log_probs.shape
+    L = targets.shape[1]
+    S = 2 * L + 1
+    dev = log_probs.device
+    ok, Tb, Lb, lab = align_valid(log_probs, targets, input_lengths, target_lengths, blank)
+    ext = torch.full((B, S), blank, dtype=torch.long, device=dev)           # the label of every state
+    ext[:, 1::2] = lab
+    em = log_probs.detach().gather(2, ext[:, None, :].expand(B, T, S))
+    ninf = torch.full((), float('-inf'), dtype=em.dtype, device=dev)
+    skip = torch.zeros((B, S), dtype=torch.bool, device=dev)
+    if L > 1:
+        skip[:, 3::2] = lab[:, 1:] != lab[:, :-1]
+    alpha = ninf.expand(B, S).clone()
+    alpha[:, :2] = em[:, 0, :2]
+    final = alpha
+    pad1, pad2 = ninf.expand(B, 1), ninf.expand(B, 2)
+    two, one, zero = (torch.full((), v, dtype=torch.long, device=dev) for v in (2, 1, 0))
+    bps = [None]
+    for t in range(1, T):
+        x0 = alpha
+        x1 = torch.cat([pad1, alpha[:, :-1]], dim=1)
+        x2 = torch.where(skip, torch.cat([pad2, alpha[:, :-2]], dim=1)[:, :S], ninf)
+        c2 = (x2 > x1) & (x2 > x0)
+        c1 = ~c2 & (x1 > x0) & (x1 > x2)
+        bps.append(torch.where(c2, two, torch.where(c1, one, zero)))
+        alpha = torch.where(c2, x2, torch.where(c1, x1, x0)) + em[:, t]
+        final = torch.where((Tb == t + 1)[:, None], alpha, final)
+    last = (2 * Lb)[:, None]
+    before = (2 * Lb - 1).clamp(min=0)[:, None]
+    s = torch.where((Lb >= 1)[:, None] & ~(final.gather(1, last) > final.gather(1, before)), before, last)
+    states = torch.zeros((B, T), dtype=torch.long, device=dev)
+    for t in range(T - 1, -1, -1):
+        inside = (Tb > t)[:, None]
+        states[:, t:t + 1] = s
+        if t:
+            s = torch.where(inside, s - bps[t].gather(1, s), s)
+    frame = torch.arange(T, device=dev)[None, :] < Tb[:, None]
+    paths = torch.where(frame, ext.gather(1, states), torch.full((), blank, dtype=torch.long, device=dev))
+    scores = torch.where(frame, log_probs.gather(2, paths[:, :, None]).squeeze(2), log_probs.new_zeros(()))
+    keep = ok[:, None]
+    paths = torch.where(keep, paths, torch.full((), -1, dtype=torch.long, device=dev)).to(targets.dtype)
+    scores = torch.where(keep, scores, torch.full((), float('nan'), dtype=scores.dtype, device=dev))
+    return paths, scores

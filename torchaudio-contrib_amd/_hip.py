@@ -1306,6 +1306,43 @@ def rnnt_grad(logits, targets, logit_lengths, target_lengths, alphas, betas, den
     return out
 
 
+# ----------------------------------------------------------------------------- forced_align (csrc/align.hip)
+def align_max_targets():
+    """the most ``L + 1`` the launch takes: the pairs of states of one workgroup"""
+    return _native.lib().tac_forced_align_max_targets()
+
+
+def align_reason(log_probs, targets):
+    """why the launch of csrc/align.hip does not take these float32 ``(B, T, C)`` log-probabilities as they lie, or None"""
+    if any(st <= 0 for st, n in zip(log_probs.stride(), log_probs.shape) if n > 1):
+        return 'expanded or non-positive strides'
+    if targets.shape[1] + 1 > align_max_targets():
+        return 'a target axis of %d + 1 (the kernel takes up to %d)' % (targets.shape[1], align_max_targets())
+    if max(log_probs.shape) >= 2 ** 30:
+        return 'an axis of 2^30 or more'
+    return None
+
+
+def forced_align(log_probs, targets, input_lengths, target_lengths, blank):
+    """``(paths (B, T) in the dtype of targets, scores (B, T))`` of float32 log-probabilities ``align_reason`` passes: ONE launch.
+    The lengths may be None (``T`` and ``L`` in every entry)."""
+    B, T, C = log_probs.shape
+    L = targets.shape[1]
+    dev = log_probs.device
+    targets = targets if (targets.is_contiguous() and targets.device == dev) else targets.to(dev).contiguous()
+    il = None if input_lengths is None else _rnnt_ints(input_lengths, dev)
+    tl = None if target_lengths is None else _rnnt_ints(target_lengths, dev)
+    paths = _empty((B, T), dtype=targets.dtype, device=dev)
+    scores = _empty((B, T), device=dev)
+    need = _native.lib().tac_forced_align_workspace(B, T, L + 1)
+    work = torch.empty((need // 8,), dtype=torch.int64, device=dev) if need else None      # (not an output: plain)
+    _launch('tac_forced_align_f32', dev, (paths, scores), _native.ptr(log_probs), B, T, C, log_probs.stride(0), log_probs.stride(1),
+            log_probs.stride(2), _native.ptr(targets) if L else None, L, 1 if targets.dtype == torch.int64 else 0,
+            None if il is None else _native.ptr(il), None if tl is None else _native.ptr(tl), blank,
+            None if work is None else _native.ptr(work), _native.ptr(paths), _native.ptr(scores))
+    return paths, scores
+
+
 # ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
 #: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
 FFTCONV_SIZES = (2048, 4096, 8192)

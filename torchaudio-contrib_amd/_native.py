@@ -172,6 +172,9 @@ PROTOTYPES = {
     'tac_rnnt_rows_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     'tac_rnnt_lattice_f32': (_INT, [_I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'tac_rnnt_grad_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _F, _I32, _P, _P]),
+    'tac_forced_align_max_targets': (_I32, []),
+    'tac_forced_align_workspace': (_I64, [_I64, _I64, _I64]),
+    'tac_forced_align_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -22,6 +22,7 @@ see them by name.
     tac_amd::psd, mvdr_weights_souden, apply_beamforming, mvdr_souden   mask-based MVDR beamforming over (…, C, F, T) (csrc/beamform.hip)
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
+    tac_amd::forced_align       CTC Viterbi alignment of (B, T, C) log-probabilities: recursion, backtrack, paths and scores in one launch (csrc/align.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -1503,6 +1504,132 @@ _register_rnnt_autograd()
 _register('rnnt_loss_grad', '(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, Tensor alphas, Tensor betas, '
           'Tensor denominators, Tensor costs, Tensor grad_costs, int blank, float clamp, bool fused_log_softmax) -> Tensor',
           _rnnt_grad_cuda, C.rnnt_loss_grad, _rnnt_grad_fake, 1, differentiable=False)
+
+
+# ============================================================================= forced_align
+def align_check(log_probs, targets, input_lengths, target_lengths, blank):
+    """the argument checks of ``forced_align`` that need no device memory: dimensions, dtypes, ``blank`` in ``[0, C)``, batch
+    sizes, one device, no empty time or class axis.  ``ValueError`` on every route."""
+    if not (isinstance(log_probs, torch.Tensor) and log_probs.is_floating_point()):
+        raise ValueError('forced_align: log_probs must be a floating-point tensor')
+    if not isinstance(targets, torch.Tensor) or targets.dtype not in (torch.int32, torch.int64):
+        raise ValueError('forced_align: targets must be an int32 or int64 tensor')
+    if log_probs.dim() != 3:
+        raise ValueError('forced_align: log_probs must be (batch, time, class), got %d dimension(s)' % log_probs.dim())
+    if targets.dim() != 2:
+        raise ValueError('forced_align: targets must be (batch, target), got %d dimension(s)' % targets.dim())
+    B, T, C = log_probs.shape
+    if T < 1 or C < 1:
+        raise ValueError('forced_align: log_probs of shape %r have an empty time or class axis' % (tuple(log_probs.shape),))
+    if targets.shape[0] != B:
+        raise ValueError('forced_align: targets for a batch of %d, log_probs for a batch of %d' % (targets.shape[0], B))
+    for name, t in (('input_lengths', input_lengths), ('target_lengths', target_lengths)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError('forced_align: %s must be an integer tensor or None' % name)
+        if t.dim() != 1 or t.shape[0] != B:
+            raise ValueError('forced_align: %s must have shape (%d,), got %r' % (name, B, tuple(t.shape)))
+        if t.device != log_probs.device:
+            raise ValueError('forced_align: %s is on %s, log_probs on %s' % (name, t.device, log_probs.device))
+    if targets.device != log_probs.device:
+        raise ValueError('forced_align: targets are on %s, log_probs on %s' % (targets.device, log_probs.device))
+    if not 0 <= blank < C:
+        raise ValueError('forced_align: blank %d is outside the %d classes' % (blank, C))
+    return blank
+
+
+def align_check_values(log_probs, targets, input_lengths, target_lengths, blank):
+    """for CPU tensors, what torchaudio's own checks refuse, by entry: lengths out of range, a blank or an out-of-range index among
+    the used targets, fewer frames than targets plus repeats"""
+    B, T, C = log_probs.shape
+    L = targets.shape[1]
+    for b in range(B):
+        Tb = T if input_lengths is None else int(input_lengths[b])
+        Lb = L if target_lengths is None else int(target_lengths[b])
+        if not 1 <= Tb <= T:
+            raise ValueError('forced_align: entry %d: input length %d is outside [1, %d]' % (b, Tb, T))
+        if not 0 <= Lb <= L:
+            raise ValueError('forced_align: entry %d: target length %d is outside [0, %d]' % (b, Lb, L))
+        used = targets[b, :Lb].tolist()
+        if any(v == blank for v in used):
+            raise ValueError('forced_align: entry %d: targets must not contain the blank index %d' % (b, blank))
+        if any(v < 0 or v >= C for v in used):
+            raise ValueError('forced_align: entry %d: a target is outside the %d classes' % (b, C))
+        repeats = sum(1 for i in range(1, Lb) if used[i] == used[i - 1])
+        if Tb < Lb + repeats:
+            raise ValueError('forced_align: entry %d: %d frames cannot hold %d targets with %d repeats' % (b, Tb, Lb, repeats))
+
+
+def align_reason(log_probs, targets):
+    """why the launch of csrc/align.hip does not take these inputs, or None"""
+    if log_probs.dtype != torch.float32:
+        return 'dtype %s' % str(log_probs.dtype).replace('torch.', '')
+    return H.align_reason(log_probs, targets)
+
+
+def _align_empty(log_probs, targets):
+    B, T, C = log_probs.shape
+    return (torch.empty((B, T), dtype=targets.dtype, device=log_probs.device),
+            torch.empty((B, T), dtype=log_probs.dtype, device=log_probs.device))
+
+
+def _align_cuda(log_probs, targets, input_lengths, target_lengths, blank):
+    align_check(log_probs, targets, input_lengths, target_lengths, blank)
+    if log_probs.shape[0] == 0:
+        return _align_empty(log_probs, targets)                     # an empty batch: nothing is launched
+    reason = align_reason(log_probs, targets)
+    if reason is not None:
+        _composite_route('forced_align', reason)
+        return C.forced_align(log_probs, targets, input_lengths, target_lengths, blank)
+    return H.forced_align(log_probs.detach(), targets, input_lengths, target_lengths, blank)
+
+
+def _align_cpu(log_probs, targets, input_lengths, target_lengths, blank):
+    align_check(log_probs, targets, input_lengths, target_lengths, blank)
+    if log_probs.shape[0] == 0:
+        return _align_empty(log_probs, targets)
+    align_check_values(log_probs, targets, input_lengths, target_lengths, blank)
+    paths, scores = C.forced_align(log_probs.detach(), targets, input_lengths, target_lengths, blank)
+    return paths, scores
+
+
+def _align_fake(log_probs, targets, input_lengths, target_lengths, blank):
+    return _align_empty(log_probs, targets)
+
+
+def _register_align_autograd():
+    """Backward of ``tac_amd::forced_align``: ``paths`` carries no gradient, and ``scores`` is a gather of ``log_probs`` at ``paths``,
+    so its gradient is a scatter of ``grad_scores`` into zeros there (frames ``t >= Tb`` and refused entries hold constants: no
+    gradient).  Torch operators, announced on a HIP device like every other use of them there."""
+
+    def setup_context(ctx, inputs, output):
+        log_probs = inputs[0]
+        paths, scores = output
+        ctx.mark_non_differentiable(paths)
+        ctx.save_for_backward(paths, inputs[2])
+        ctx.like = (tuple(log_probs.shape), log_probs.dtype, log_probs.device)
+
+    def backward(ctx, grad_paths, g):
+        paths, input_lengths = ctx.saved_tensors
+        shape, dtype, dev = ctx.like
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        if dev.type == 'cuda':
+            _composite_route('forced_align', 'backward: the scatter of grad_scores at paths')
+        live = paths >= 0
+        if input_lengths is not None:
+            live = live & (torch.arange(shape[1], device=dev)[None, :] < input_lengths[:, None])
+        grad = torch.zeros(shape, dtype=dtype, device=dev)
+        grad.scatter_(2, paths.clamp(min=0).long()[:, :, None], torch.where(live, g.to(dtype), g.new_zeros(()).to(dtype))[:, :, None])
+        return (grad,) + (None,) * 4
+
+    torch.library.register_autograd('%s::forced_align' % NS, backward, setup_context=setup_context, lib=_lib)
+
+
+_register('forced_align', '(Tensor log_probs, Tensor targets, Tensor? input_lengths, Tensor? target_lengths, int blank) -> '
+          '(Tensor, Tensor)', _align_cuda, _align_cpu, _align_fake, 2, differentiable=False)
+_register_align_autograd()
 
 
 # ============================================================================= lfilter

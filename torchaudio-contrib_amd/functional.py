@@ -13,6 +13,7 @@ Where the work runs (decided by the dispatcher, like for any torch op):
 Outputs are fresh tensors; the STFT-family results are returned as the same strided views the reference
 produces (physically frame-major, logically ``(*, channel, freq, time[, 2])``).
 """
+import dataclasses
 import math
 
 import torch
@@ -34,7 +35,8 @@ __all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterba
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
-           'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss']
+           'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
+           'forced_align', 'merge_tokens', 'TokenSpan']
 
 _call = _ops.call
 
@@ -742,6 +744,71 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
     if reduction == 'sum':
         return costs.sum()
     return costs
+
+
+def forced_align(log_probs, targets, input_lengths=None, target_lengths=None, blank=0):
+    """CTC forced alignment with torchaudio's ``functional.forced_align`` signature and defaults: ``(paths, scores)``, the most
+    probable frame labelling of ``log_probs`` ``(batch, time, class)`` that collapses to ``targets`` ``(batch, target)`` (int32 or
+    int64, no blanks).  ``paths`` ``(batch, time)``, in the dtype of ``targets``, is the class emitted at each frame; ``scores``,
+    in the dtype of ``log_probs``, is ``log_probs[b, t, paths[b, t]]`` (the same bits).  ``input_lengths`` (``Tb``) and
+    ``target_lengths`` (``Lb``) are ``(batch,)`` integer tensors; ``None`` means ``time`` and ``target`` for every entry.
+
+    Per entry there are ``2 Lb + 1`` states, even ones the blank and ``2k + 1`` ``targets[k]``.  ``alpha[0][0] = lp[0][blank]``,
+    ``alpha[0][1] = lp[0][targets[0]]``, ``-inf`` elsewhere; for ``t >= 1`` with ``x0 = alpha[t-1][s]``, ``x1 = alpha[t-1][s-1]`` and
+    ``x2 = alpha[t-1][s-2]`` (only for odd ``s >= 3`` whose label differs from the label before): back-pointer 2 if ``x2 > x1 and
+    x2 > x0``, else 1 if ``x1 > x0 and x1 > x2``, else 0, and ``alpha[t][s] = chosen + lp[t][label(s)]``, one addition in the dtype
+    of ``log_probs``.  The end state is the last blank if its alpha is greater than the last label's, else the last label; the
+    back-pointers are followed down to the first frame.  Ties go to the lower back-pointer and a NaN where these comparisons
+    send it.  torchaudio's moving window of states only removes states on no complete path and is not applied.
+
+    float32 on a HIP device with positive strides (a slice of a padded model output is read in place) and ``target + 1 <= 1024``
+    runs csrc/align.hip: ONE launch for the recursion, the backtrack and both outputs, a workgroup per entry; the same bits from
+    run to run and whatever else is in the batch.  Other inputs take ``_composite.forced_align`` (a step of a Python loop per
+    frame), announced on a HIP device.  The gradient of ``scores`` with respect to ``log_probs`` is the scatter of the incoming
+    gradient at ``paths`` (torch operators); ``paths`` has none.
+
+    Deviations from torchaudio:
+
+    1. torchaudio refuses ``batch != 1``.  Here any ``batch >= 0`` is taken and the entries are independent; frames ``t >= Tb``
+       get ``paths = blank`` and ``scores = 0``.  An empty batch launches nothing.
+    2. On a HIP device nothing waits for the host: an entry that is infeasible (``Tb < Lb +`` the number of targets equal to the
+       one before), has ``Tb < 1``, ``Tb > time`` or ``Lb > target``, or has the blank or an index outside ``[0, class)`` among its
+       first ``Lb`` targets gets ``paths = -1`` and ``scores = NaN`` on all frames, and the other entries are unaffected.  For CPU
+       tensors the same conditions raise ``ValueError`` naming the entry, as torchaudio's checks do.
+    3. Dimensions, dtypes, ``blank`` in ``[0, class)``, agreeing batch sizes, one device and non-empty time and class axes are
+       checked on every route and raise ``ValueError``."""
+    blank = _ops.align_check(log_probs, targets, input_lengths, target_lengths, int(blank))
+    return _call('forced_align', log_probs, targets, input_lengths, target_lengths, blank)
+
+
+@dataclasses.dataclass
+class TokenSpan:
+    """A run of one token in an alignment (torchaudio's ``functional.TokenSpan``): frames ``[start, end)``, ``score`` their mean"""
+    token: int
+    start: int
+    end: int
+    score: float
+
+    def __len__(self):
+        return self.end - self.start
+
+
+def merge_tokens(tokens, scores, blank=0):
+    """Runs of equal tokens of a frame-level alignment as ``TokenSpan``s, blank runs dropped (torchaudio's
+    ``functional.merge_tokens``): ``tokens`` and ``scores`` are 1-D and of equal length, e.g. ``paths[0]`` and ``scores[0]`` of
+    ``forced_align``; a span's ``score`` is the mean of its frames' scores.  Host-side: one device-to-host copy per argument."""
+    if tokens.ndim != 1 or scores.ndim != 1:
+        raise ValueError('merge_tokens: `tokens` and `scores` must be 1D Tensor.')
+    if len(tokens) != len(scores):
+        raise ValueError('merge_tokens: `tokens` and `scores` must be the same length.')
+    toks, vals = tokens.detach().cpu().tolist(), scores.detach().cpu().double().tolist()
+    spans, start = [], 0
+    for i in range(1, len(toks) + 1):
+        if i == len(toks) or toks[i] != toks[start]:
+            if toks[start] != blank:
+                spans.append(TokenSpan(token=toks[start], start=start, end=i, score=sum(vals[start:i]) / (i - start)))
+            start = i
+    return spans
 
 
 def preemphasis(waveforms, coeff=0.97):
