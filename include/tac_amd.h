@@ -341,8 +341,8 @@ int tac_mulaw_decode_f64(const void* codes, int32_t codes_are_i64, int64_t n, in
  *       that read sample j, reflect / replicate / circular images included (a gather: deterministic, no atomics).
  *     tac_complex_norm_backward_f32: grad_z[i] = grad_out[i] * power * |z_i|^(power-2) * z_i (0 where z_i == 0),
  *       functional.py:126-128.
- *     tac_amplitude_to_db_backward_f32: grad_x = grad_out * 20 / (ln 10 * x) where x^2 >= amin, else 0,
- *       functional.py:291-296.
+ *     tac_amplitude_to_db_backward_f32: grad_x = grad_out * 20 / (ln 10 * x) where x^2 >= amin, else 0
+ *       (NaN where x is NaN), functional.py:291-296.
  *     tac_magphase_backward_f32 (round 6): gradient of magphase / angle (functional.py:187-201): grad_z[i] = grad_mag[i] * power *
  *       |z_i|^(power-2) * z_i + grad_phase[i] * (-im_i, re_i) / |z_i|^2, 0 where z_i == 0; grad_mag or grad_phase may be NULL.
  *     tac_db_to_amplitude_backward_f32 (round 6): grad_x = grad_out * ln(10) / 20 * (10^(x/10 + log10 ref))^0.5, functional.py:299-314.

@@ -165,6 +165,10 @@ def _register_autograd(op, fn, n_tensors, hip_backward=None, n_plain=None, save_
     the op's output is saved too and handed to ``hip_backward`` behind the input tensors."""
 
     def setup_context(ctx, inputs, output):
+        # an output nobody differentiated arrives in ``backward`` as None, not as a tensor of zeros: ``magphase`` with its phase
+        # unused then runs the magnitude's gradient alone, like ``complex_norm`` (a zero phase gradient times an infinite component
+        # was NaN where the reference, whose atan2 node never runs, gives 0), and nothing reads or fills the zeros
+        ctx.set_materialize_grads(False)
         if save_output is not None and save_output(inputs):
             ctx.save_for_backward(*inputs[:n_tensors], output)
         else:

@@ -853,13 +853,15 @@ complex_norm_backward_kernel(const float* __restrict__ z, const float* __restric
 }
 
 // d/dx of 10 (log10(clamp(x^2, amin)) - log10 ref) (functional.py:291-296): 20 / (ln 10 * x) where x^2 >= amin, else 0.
+// A NaN input stays NaN, as it does through the forward clamp (amp_to_db) and through torch's autograd of the formula: the
+// compare alone would send it to 0, and a gradient of 0 is what hides a diverged input from whoever checks the gradients.
 // VEC: 16 bytes per lane and stream (all three pointers 16-byte aligned; the tail runs scalar).
 template <bool VEC>
 __global__ void __launch_bounds__(256)
 amplitude_to_db_backward_kernel(const float* __restrict__ x, const float* __restrict__ gout, long long n, float amin,
                                 float* __restrict__ gx) {
     typedef float f4 __attribute__((ext_vector_type(4)));
-    auto one = [&](float v, float g) { return (v * v >= amin) ? g * (8.6858896380650366f / v) : 0.0f; };
+    auto one = [&](float v, float g) { return (v * v >= amin) ? g * (8.6858896380650366f / v) : (v == v ? 0.0f : v); };
     const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nth = (long long)gridDim.x * blockDim.x;
     const long long n4 = VEC ? n >> 2 : 0;
     for (long long i = tid; i < n4; i += nth) {
