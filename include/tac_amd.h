@@ -905,6 +905,24 @@ int tac_forced_align_f32(const float* log_probs, int64_t batch, int64_t frames, 
                          const int32_t* input_lengths, const int32_t* target_lengths, int32_t blank, void* workspace, void* paths,
                          float* scores, void* stream);
 
+/* (29) functional.griffinlim / GriffinLim (torchaudio's Griffin-Lim phase recovery; csrc/griffinlim.hip) around (1) and (13):
+ *      S = specgram^(1 / power), X_0 = S angles0 (or S), then n_iter times y = istft(X), R = stft(y),
+ *      X = S (R - m Rprev) / (|R - m Rprev| + 1e-16), Rprev = R, and a last istft.  M, X and R are frame-major float32,
+ *      [rows][T][F] and [rows][T][F][2], dense: what (1) writes and (13) reads in place.
+ *
+ *      tac_griffinlim_prepare_f32: once per call.  spec[r*stride_r + f*stride_f + t*stride_t] (element strides, positive on every
+ *      axis longer than one: a time-contiguous (…, F, T) tensor is turned in the LDS, a frame-major view is read along its rows),
+ *      angles: NULL or complex pairs at angles[2 (r*astride_r + f*astride_f + t*astride_t)] (strides in pairs).  The root is sqrtf at
+ *      power 2, none at power 1, powf(s, (float)(1 / power)) otherwise.  Writes mag[r][t][f] (skipped when mag is NULL: the caller's
+ *      input already is that tensor) and x0[r][t][f] = (mag, 0), or mag * angles.
+ *      tac_griffinlim_update_f32: x[i] = mag[i] A / (|A| + 1e-16), A = r[i] - m rprev[i] (A = r[i] when rprev is NULL or m is 0) over
+ *      n_bins complex bins.  |A| is formed on operands scaled by a power of two: right for every finite A, no overflow or underflow; a
+ *      zero bin gives exactly 0.  16-byte accesses where r, rprev, x are 16-byte and mag 8-byte aligned, dword accesses otherwise. */
+int tac_griffinlim_prepare_f32(const float* spec, int64_t rows, int64_t n_freqs, int64_t n_frames, int64_t stride_r, int64_t stride_f,
+                               int64_t stride_t, const float* angles, int64_t astride_r, int64_t astride_f, int64_t astride_t,
+                               float power, float* mag, float* x0, void* stream);
+int tac_griffinlim_update_f32(const float* r, const float* rprev, const float* mag, int64_t n_bins, float m, float* x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

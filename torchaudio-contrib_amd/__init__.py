@@ -12,7 +12,7 @@ from ._lazy import realize, set_lazy_fusion, lazy_fusion_enabled, DeferredSpectr
 from . import functional
 from . import layers
 from .functional import *      # noqa: F401,F403
-from .functional import (stft, istft, complex_norm, create_mel_filter, apply_filterbank, angle, magphase,
+from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filter, apply_filterbank, angle, magphase,
                          phase_vocoder, amplitude_to_db, db_to_amplitude, mu_law_encoding,
                          mu_law_decoding, hpss, create_dct, dct, resample, lfilter, biquad, lowpass_biquad,
                          highpass_biquad, bandpass_biquad, bandreject_biquad, allpass_biquad, equalizer_biquad,
@@ -21,7 +21,7 @@ from .functional import (stft, istft, complex_norm, create_mel_filter, apply_fil
                          add_noise, speed, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
                          apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, forced_align,
                          merge_tokens, TokenSpan)
-from .layers import (STFT, ISTFT, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
+from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
                      MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis,
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,

@@ -57,6 +57,28 @@ def istft(spec, window, n_fft, hop, win_length, center, normalized, onesided, le
     return out.reshape(tuple(batch_shape) + out.shape[1:])
 
 
+def griffinlim(specgram, window, angles0, n_fft, hop, win_length, power, n_iter, m, length):
+    """torchaudio's ``functional.griffinlim`` in its operator order: ``S = specgram ** (1 / power)``, then ``n_iter`` times
+    ``istft`` -> ``stft`` -> ``A = R - m Rprev`` (skipped for ``m == 0``) -> ``A / (|A| + 1e-16)``, and a last ``istft``.  ``m`` is
+    ``momentum / (1 + momentum)``; ``angles0`` (complex, the caller's draw, NOT normalised) or None for ``1 + 0j``."""
+    lead = tuple(specgram.shape[:-2])
+    S = specgram.reshape((-1,) + tuple(specgram.shape[-2:])).pow(1.0 / power)
+    A = torch.ones((), dtype=torch.complex128 if S.dtype == torch.float64 else torch.complex64, device=S.device) \
+        if angles0 is None else angles0.reshape(S.shape)
+    prev = None
+    for _ in range(n_iter):
+        y = torch.istft(S * A, n_fft, hop_length=hop, win_length=win_length, window=window, length=length)
+        R = torch.stft(y, n_fft, hop_length=hop, win_length=win_length, window=window, center=True, pad_mode='reflect',
+                       normalized=False, onesided=True, return_complex=True)
+        A = R
+        if m and prev is not None:
+            A = A - prev * m
+        A = A / (A.abs() + 1e-16)
+        prev = R
+    y = torch.istft(S * A, n_fft, hop_length=hop, win_length=win_length, window=window, length=length)
+    return y.reshape(lead + tuple(y.shape[-1:]))
+
+
 def complex_norm(z, power):
     """reference functional.py:126-128: 2-norm of the (re, im) pair; the exponent is a second pass."""
     length = z.norm(p=2, dim=-1)

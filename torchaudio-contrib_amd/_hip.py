@@ -451,6 +451,71 @@ def istft_backward(grad_out, window, n_fft, hop, win_length, center, normalized,
     return gspec.transpose(-3, -2)
 
 
+# ----------------------------------------------------------------------------- Griffin-Lim (csrc/griffinlim.hip)
+def griffinlim_covers(specgram, angles0=None):
+    """the layouts ``tac_griffinlim_prepare_f32`` reads where they lie: positive strides on every axis longer than one"""
+    for t in (specgram, angles0):
+        if t is not None and any(n > 1 and s <= 0 for n, s in zip(t.shape, t.stride())):
+            return False
+    return True
+
+
+def _gl_rows(t, n_freqs, n_frames):
+    """``(…, F, T)`` as ``(rows, F, T)`` with ONE row stride: a view where the leading dims fold, else a copy of plain data"""
+    try:
+        return t.view(-1, n_freqs, n_frames)
+    except RuntimeError:
+        return t.reshape(-1, n_freqs, n_frames)
+
+
+def griffinlim_prepare(specgram, angles0, power):
+    """``(rows, F, T)`` float32 with any positive strides (and ``angles0``, complex64 of that shape, or None) -> the frame-major
+    magnitude ``M (rows, T, F)`` and first iterate ``X0 (rows, T, F, 2)``, one launch.  A dense frame-major input at power 1 IS
+    ``M``: nothing is copied and only ``X0`` is written."""
+    rows, n_freqs, n_frames = (int(s) for s in specgram.shape)
+    dev = specgram.device
+    fm = specgram.transpose(1, 2)
+    keep = float(power) == 1.0 and fm.is_contiguous() and fm.data_ptr() % 16 == 0
+    mag = fm if keep else _empty((rows, n_frames, n_freqs), device=dev)
+    x0 = _empty((rows, n_frames, n_freqs, 2), device=dev)
+    a_args = (None, 0, 0, 0) if angles0 is None else (_native.ptr(angles0),) + tuple(int(s) for s in angles0.stride())
+    _launch('tac_griffinlim_prepare_f32', dev, (x0,) if keep else (mag, x0), _native.ptr(specgram), rows, n_freqs, n_frames,
+            *(int(s) for s in specgram.stride()), *a_args, float(power), None if keep else _native.ptr(mag), _native.ptr(x0))
+    return mag, x0
+
+
+def griffinlim_update(r, rprev, mag, m):
+    """``X = M (R - m Rprev) / (|R - m Rprev| + 1e-16)`` over frame-major ``(…, 2)`` pairs (``rprev`` None on the first step), one
+    launch.  The operands are read where they lie and have to be dense; any element alignment."""
+    x = _empty(tuple(r.shape), device=r.device)
+    _launch('tac_griffinlim_update_f32', r.device, (x,), _native.ptr(r), None if rprev is None else _native.ptr(rprev),
+            _native.ptr(mag), r.numel() // 2, float(m), _native.ptr(x))
+    return x
+
+
+def griffinlim(specgram, window, angles0, n_fft, hop, win_length, power, n_iter, m, length):
+    """``(…, F, T)`` float32 magnitudes -> ``(…, samples)``: one prepare launch, then per iteration ``tac_istft_f32`` (its fused
+    one-launch route at fft_length 2048), ``tac_stft_f32`` and the update kernel.  ``Rprev`` is the previous ``stft`` output kept by
+    reference; every buffer of an iteration is released to the allocator before the next one asks, so nothing grows with
+    ``n_iter``, and nothing inside the loop waits for the host (the NOLA check of the window's envelope is cached on the window)."""
+    n_freqs, n_frames = int(specgram.shape[-2]), int(specgram.shape[-1])
+    lead = tuple(int(s) for s in specgram.shape[:-2])
+    full = istft_full_length(n_frames, n_fft, hop, True)
+    out_len = full if length is None else int(length)
+    istft_envelope(window, n_fft, hop, win_length, True, n_frames, min(full + n_fft // 2, out_len))      # NOLA, before any launch of the op
+    spec3 = _gl_rows(specgram, n_freqs, n_frames)
+    ang3 = None if angles0 is None else _gl_rows(angles0, n_freqs, n_frames)
+    mag, x = griffinlim_prepare(spec3, ang3, power)
+    y = istft(x.transpose(1, 2), window, n_fft, hop, win_length, True, False, length)
+    prev = None
+    for _ in range(n_iter):
+        r = stft(y, window, n_fft, hop, win_length, True, 'reflect', False, True).transpose(1, 2)      # frame-major, dense
+        x = griffinlim_update(r, prev, mag, m)
+        y = istft(x.transpose(1, 2), window, n_fft, hop, win_length, True, False, length)
+        prev = r
+    return y.reshape(lead + (out_len,))
+
+
 # ----------------------------------------------------------------------------- poisoned outputs (test hook)
 # While ``set_poison_outputs(True)`` is on, every buffer a launcher here allocates for a kernel to fill starts as a fixed bit
 # pattern (a quiet NaN with a payload no arithmetic produces; a negative sentinel for int64 codes), and after each launch the

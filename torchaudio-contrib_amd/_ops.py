@@ -23,6 +23,7 @@ see them by name.
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
     tac_amd::forced_align       CTC Viterbi alignment of (B, T, C) log-probabilities: recursion, backtrack, paths and scores in one launch (csrc/align.hip)
+    tac_amd::griffinlim         Griffin-Lim phase recovery of (…, F, T) magnitudes: prepare, then stft + inverse a step (csrc/griffinlim.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
@@ -586,6 +587,35 @@ def _istft_fake(spec, window, n_fft, hop, win_length, center, normalized, onesid
 
 _register('istft', '(Tensor spec, Tensor window, int n_fft, int hop, int win_length, bool center, bool normalized, '
           'bool onesided, int? length) -> Tensor', _istft_cuda, C.istft, _istft_fake, 2)
+
+
+# ============================================================================= griffinlim
+def _griffinlim_cuda(specgram, window, angles0, n_fft, hop, win_length, power, n_iter, m, length):
+    _same_device('griffinlim', specgram, window, *(() if angles0 is None else (angles0,)))
+    reason = None
+    for t in (specgram, window):                # (half precision is not widened here: the iteration would run in float32)
+        if reason is None and t.dtype != torch.float32:
+            reason = 'dtype %s' % str(t.dtype).replace('torch.', '')
+    if reason is None and angles0 is not None and angles0.dtype != torch.complex64:
+        reason = 'dtype %s' % str(angles0.dtype).replace('torch.', '')
+    if reason is None and not H.istft_covers(n_fft):
+        reason = 'fft_length %d' % n_fft
+    if reason is None and not H.griffinlim_covers(specgram, angles0):
+        reason = 'expanded or non-positive strides'
+    if reason is not None:
+        _composite_route('griffinlim', reason)
+        return C.griffinlim(specgram, window, angles0, n_fft, hop, win_length, power, n_iter, m, length)
+    return H.griffinlim(specgram, window.contiguous(), angles0, n_fft, hop, win_length, power, n_iter, m, length)
+
+
+def _griffinlim_fake(specgram, window, angles0, n_fft, hop, win_length, power, n_iter, m, length):
+    n_out = hop * (specgram.shape[-1] - 1) if length is None else length
+    return torch.empty(tuple(specgram.shape[:-2]) + (n_out,), dtype=specgram.dtype, device=specgram.device)
+
+
+# (the gradient re-evaluates the listing with torch operators: announced, an error under strict unless backward=False)
+_register('griffinlim', '(Tensor specgram, Tensor window, Tensor? angles0, int n_fft, int hop, int win_length, float power, '
+          'int n_iter, float m, int? length) -> Tensor', _griffinlim_cuda, C.griffinlim, _griffinlim_fake, 2)
 
 
 # ============================================================================= spectrogram (stft + |.|^p [+ dB])

@@ -31,7 +31,7 @@ from . import _augment
 from ._bounded import Bounded
 from ._lazy import realize as _realize
 
-__all__ = ['stft', 'istft', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
+__all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
@@ -132,6 +132,59 @@ def istft(complex_specgrams, fft_length, hop_length=None, win_length=None, windo
         if length <= 0:
             raise RuntimeError('istft: expected length > 0, got %d' % length)
     return _call('istft', z, window, n_fft, hop, win_length, bool(center), bool(normalized), bool(onesided), length)
+
+
+def griffinlim(specgram, window, n_fft, hop_length, win_length, power, n_iter, momentum, length, rand_init):
+    """``(…, freq, time)`` real, non-negative magnitudes (``freq == n_fft // 2 + 1``) → ``(…, samples)``: torchaudio's
+    ``functional.griffinlim``, phase recovery by the fast Griffin-Lim iteration.  With ``m = momentum / (1 + momentum)`` and ``S =
+    specgram ** (1 / power)``: the angles start as ``1 + 0j``, or with ``rand_init`` as ``torch.rand`` complex pairs (uniform in the
+    unit square, NOT normalised); ``n_iter`` times ``y = istft(S A)``, ``R = stft(y)`` (``center``, reflect padding), ``A = R - m
+    Rprev``, ``A = A / (|A| + 1e-16)``; the result is ``istft(S A)``.  ``samples`` is ``hop_length * (time - 1)``, or ``length``.
+
+    ``ValueError`` for a momentum outside ``[0, 1)``; ``TypeError`` for a non-tensor; ``RuntimeError``, before anything is
+    launched, for a complex or integer ``specgram``, a wrong ``freq``, ``n_iter < 0``, ``power <= 0``, a ``length`` with ``1 +
+    length // hop_length != time`` (torchaudio fails there one iteration in) and too few samples to reflect-pad; a window without
+    overlap-add (NOLA) raises as ``istft`` does.
+
+    The draw is torch's: made here with ``torch.rand`` on the tensor's device before the op, so a generator state gives what the
+    composite of torch operators gives.  float32 on a HIP device: one prepare launch (csrc/griffinlim.hip: the root and the turn to
+    frame-major rows, the input read where it lies), then ``istft`` and ``stft`` on the package's kernels with the projection
+    between them in one elementwise launch: three launches a step at fft_length 2048 with hop 256 / 512 / 1024 (the fused
+    inverse), four elsewhere.  float64, half precision, expanded strides, other fft_lengths than ``istft``'s and the backward pass take
+    ``_composite.griffinlim`` (also the CPU path), announced with ``CompositeRouteWarning`` on a device."""
+    if not 0 <= momentum < 1:
+        raise ValueError('momentum must be in range [0, 1). Found: {}'.format(momentum))
+    x = _tensor(specgram, 'specgram')
+    if x.is_complex() or not x.is_floating_point():
+        raise RuntimeError('griffinlim: expected a real floating point specgram, got %s' % x.dtype)
+    n_fft, hop, win_length, n_iter = int(n_fft), int(hop_length), int(win_length), int(n_iter)
+    if x.dim() < 2 or x.shape[-2] != n_fft // 2 + 1 or any(int(s) == 0 for s in x.shape):
+        raise RuntimeError('griffinlim: expected a non-empty (*, %d, time) specgram for n_fft=%d, got %s'
+                           % (n_fft // 2 + 1, n_fft, tuple(x.shape)))
+    if n_iter < 0:
+        raise RuntimeError('griffinlim: expected n_iter >= 0, got %d' % n_iter)
+    if not power > 0:
+        raise RuntimeError('griffinlim: expected power > 0, got %r' % (power,))
+    if not torch.is_tensor(window) or window.dim() != 1 or window.shape[0] != win_length or window.device != x.device:
+        raise RuntimeError('griffinlim: expected a 1D window tensor of size win_length=%d on %s' % (win_length, x.device))
+    if n_fft <= 0 or hop <= 0 or hop > win_length or win_length > n_fft:
+        raise RuntimeError('griffinlim: expected 0 < hop_length <= win_length <= n_fft, got n_fft=%d hop_length=%d win_length=%d'
+                           % (n_fft, hop, win_length))
+    n_frames = int(x.shape[-1])
+    if length is not None:
+        length = int(length)
+        if length <= 0 or 1 + length // hop != n_frames:
+            raise RuntimeError('griffinlim: length=%d gives %d frames of hop_length=%d where the specgram has %d'
+                               % (length, 1 + length // hop if length > 0 else 0, hop, n_frames))
+    samples = hop * (n_frames - 1) if length is None else length
+    if samples <= 0:
+        raise RuntimeError('griffinlim: %d frame(s) leave no samples' % n_frames)
+    _hip.check_stft_args((samples,), n_fft, hop, win_length, True, 'reflect')
+    angles0 = None
+    if rand_init:
+        angles0 = torch.rand(x.shape, dtype=torch.complex128 if x.dtype == torch.float64 else torch.complex64, device=x.device)
+    return _call('griffinlim', x, window, angles0, n_fft, hop, win_length, float(power), n_iter,
+                 float(momentum / (1 + momentum)), length)
 
 
 def complex_norm(complex_tensor, power=1.0):

@@ -139,6 +139,37 @@ class ISTFT(_ModuleNoStateBuffers):
         return self.__class__.__name__ + head + tail
 
 
+class GriffinLim(_ModuleNoStateBuffers):
+    """``functional.griffinlim`` as a layer (torchaudio's ``transforms.GriffinLim``, its argument order and defaults):
+    ``forward(specgram)`` maps ``(…, n_fft // 2 + 1, time)`` magnitudes (to the ``power``) to the ``(…, samples)`` waveform.
+    ``win_length`` defaults to ``n_fft``, ``hop_length`` to ``win_length // 2``; the window ``window_fn(win_length, **wkwargs)`` is a
+    buffer that follows ``.to()`` and stays out of ``state_dict()``."""
+
+    def __init__(self, n_fft=400, n_iter=32, win_length=None, hop_length=None, window_fn=torch.hann_window, power=2.0,
+                 wkwargs=None, momentum=0.99, length=None, rand_init=True):
+        super(GriffinLim, self).__init__()
+        if not 0 <= momentum < 1:
+            raise ValueError('momentum must be in range [0, 1). Found: {}'.format(momentum))
+        self.n_fft = n_fft
+        self.n_iter = n_iter
+        self.win_length = win_length if win_length is not None else n_fft
+        self.hop_length = hop_length if hop_length is not None else self.win_length // 2
+        self.register_buffer('window', window_fn(self.win_length) if wkwargs is None else window_fn(self.win_length, **wkwargs))
+        self.length = length
+        self.power = power
+        self.momentum = momentum
+        self.rand_init = rand_init
+
+    def forward(self, specgram):
+        return F.griffinlim(specgram, self.window, self.n_fft, self.hop_length, self.win_length, self.power, self.n_iter,
+                            self.momentum, self.length, self.rand_init)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(n_fft={}, n_iter={}, win_length={}, hop_length={}, power={}, momentum={}, length={}, ' \
+            'rand_init={})'.format(self.n_fft, self.n_iter, self.win_length, self.hop_length, self.power, self.momentum,
+                                   self.length, self.rand_init)
+
+
 class ComplexNorm(nn.Module):
     """``|z| ** power`` over the trailing complex dim (reference layers.py:112-135)."""
 
