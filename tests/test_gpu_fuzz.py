@@ -42,6 +42,8 @@ FRAME_DFT = 5e-6    # complex rows and |X| of the windowed-DFT matrix route (one
 FRAME_POW = 2e-5    # |X|^p (p != 1), power and mel, per frame
 GRAD = 1e-4         # waveform gradients of linear / power / mel outputs, per row
 GRAD_DB = 1e-3      # ... through dB or |X|, per row
+FRAME_F64 = 2e-12   # the float64 chain: complex rows and |X|^p, per frame
+DB_F64 = 1e-8       # ... its dB values
 
 
 def frame_tol(n):
@@ -431,8 +433,8 @@ def test_fuzz_float64_chain(tac):
         want = torch_ref.stft(torch.from_numpy(x), n, hop, window=window, onesided=onesided, **kw).numpy()
         got = host(tac.stft(dev(x), n, hop_length=hop, window=window.cuda(), onesided=onesided, **kw))
         assert got.dtype == np.float64 and got.shape == want.shape, tag
-        assert np.abs(got - want).max() <= 2e-12 * max(np.abs(want).max(), 1e-300), tag
-        fbnd.check_frames(got, want, 'complex', 2e-12, 'fuzz_float64_chain', tag, n, signals.has_silence(x.shape, n, hop))
+        assert np.abs(got - want).max() <= FRAME_F64 * max(np.abs(want).max(), 1e-300), tag
+        fbnd.check_frames(got, want, 'complex', FRAME_F64, 'fuzz_float64_chain', tag, n, signals.has_silence(x.shape, n, hop))
         power = float(rng.choice([1.0, 2.0, 0.7]))
         mels = int(rng.choice([5, 40, 80]))
         bank = torch.from_numpy(signals.uniform((n // 2 + 1, mels), seed=6600 + case).astype(np.float64))
@@ -440,7 +442,7 @@ def test_fuzz_float64_chain(tac):
         want_m = torch_ref.amplitude_to_db(torch_ref.apply_filterbank(torch_ref.complex_norm(z, power), bank)).numpy()
         got_m = host(torch.ops.tac_amd.melspectrogram(dev(x), window.cuda(), bank.cuda(), n, hop, win_length, center, pad_mode,
                                                       normalized, True, power, True, 1.0, 1e-7))
-        assert got_m.dtype == np.float64 and np.abs(got_m - want_m).max() < 1e-8, tag
+        assert got_m.dtype == np.float64 and np.abs(got_m - want_m).max() < DB_F64, tag
         ran = {k: v - before.get(k, 0) for k, v in tac._hip.launches.items() if v != before.get(k, 0)}
         assert ran == {'tac_stft_f64': 1, 'tac_spectrogram_f64': 1, 'tac_apply_filterbank_f64': 1}, (tag, ran)
 

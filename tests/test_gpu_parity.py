@@ -31,6 +31,8 @@ TIGHT = 2e-6      # what fp32 kernels should really achieve on linear outputs
 DB_ABS = 1e-3     # absolute dB
 FRAME = 2e-6      # complex rows and |X|, per frame (frame_bounds)
 FRAME_POW = 2e-5  # power and mel, per frame
+F64_REL = 1e-12   # the float64 pair ops: |z|^p against the host's, of the tensor's maximum
+F64_PHASE = 1e-14 # ... the phase, in radians
 
 
 @pytest.fixture(scope='module')
@@ -1316,9 +1318,9 @@ def test_float64_chain_runs_on_the_f64_kernels(tac):
         p07, ang = tac.complex_norm(t, 0.7), tac.angle(t)
         assert launched_since(tac, before) == {'tac_magphase_f64': 3}
         zz = host(t)
-        assert np.abs(host(mag) - np.hypot(zz[..., 0], zz[..., 1])).max() < 1e-12 * np.abs(zz).max()
-        assert np.abs(host(p07) - np.hypot(zz[..., 0], zz[..., 1]) ** 0.7).max() < 1e-12 * np.abs(zz).max()
-        assert np.abs(host(ph) - np.arctan2(zz[..., 1], zz[..., 0])).max() < 1e-14 and np.array_equal(host(ph), host(ang))
+        assert np.abs(host(mag) - np.hypot(zz[..., 0], zz[..., 1])).max() < F64_REL * np.abs(zz).max()
+        assert np.abs(host(p07) - np.hypot(zz[..., 0], zz[..., 1]) ** 0.7).max() < F64_REL * np.abs(zz).max()
+        assert np.abs(host(ph) - np.arctan2(zz[..., 1], zz[..., 0])).max() < F64_PHASE and np.array_equal(host(ph), host(ang))
     # apply_filterbank on both layouts + the dB pair
     fb = tac.create_mel_filter(257, 40, 0.0, 8000.0, False).double().cuda()
     spec = tac.complex_norm(z, 2.0)

@@ -22,6 +22,7 @@
 #include "ola_runs.hpp"
 
 #include <algorithm>
+#include <cstdio>
 #include <type_traits>
 
 namespace tac {
@@ -920,8 +921,12 @@ static int launch_stft_backward(const FrameGeom& g, const Tables& tb, const floa
     } else {
         kern = stft_backward_kernel<NC, E, SRC_GRAD, false>;
     }
-    return launch_kernel(kern, persistent_blocks(groups, BW_WAVES, (long long)device_cu_count() * 2), BW_WAVES * 64, lds_bytes, stream, g, tb,
-                         gspec, gnorm, power, frames);
+    const int rc = launch_kernel(kern, persistent_blocks(groups, BW_WAVES, (long long)device_cu_count() * 2), BW_WAVES * 64, lds_bytes, stream, g, tb,
+                                 gspec, gnorm, power, frames);
+    if (rc != TAC_OK) return rc;
+    set_last_route("stft_backward_kernel<%d, %d, %s, %s>", NC, E, from_wave ? "SRC_WAVE" : (inverse ? "SRC_INV" : (gnorm ? "SRC_NORM" : "SRC_GRAD")),
+                   pow2 && (from_wave || (gnorm && !inverse)) ? "true" : "false");
+    return TAC_OK;
 }
 
 bool stft_smooth_covers(int n_fft);                                                                           // stft_smooth.hip
@@ -1205,6 +1210,8 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
     } else {
     rc = TAC_OK;
     OlaFuse fz{nullptr, 0, 0, 16};
+    char route[96] = "";                                   // the instantiation launched below (tac_last_route)
+    const char* const p2 = pow2 ? "true" : "false";
     // units of work: the segments of all rows, `streams_per_wave` of them a wave
     auto units = [&](int streams_per_wave) { return (g.rows * (long long)plan.segs_per_row + streams_per_wave - 1) / streams_per_wave; };
     auto launch = [&](auto kern, size_t lds_bytes, int streams_per_wave, int waves = OLA_WAVES) {
@@ -1253,6 +1260,7 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
             case 512: rc = pick(std::integral_constant<int, 4>{}); break;
             default: rc = pick(std::integral_constant<int, 8>{}); break;
         }
+        snprintf(route, sizeof(route), "melspec_backward_ring3_kernel<%s, %d, %s>", p2, d->hop >> 7, adj ? "true" : "false");
     } else if ((d->n_fft == 1024 || d->n_fft == 512) && (!adj || (n_mels >= 1 && n_mels <= 128)) && !lds_ring &&
                g.length >= d->n_fft && (d->hop == d->n_fft / 8 || d->hop == d->n_fft / 4 || d->hop == d->n_fft / 2)) {
         // fft_length 512 / 1024: the same on 4 / 2 lane groups per wave (backward_ring3_multi.hpp)
@@ -1289,6 +1297,8 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
             using NCT = std::integral_constant<int, 256>;
             rc = Hh == 2 ? pick(NCT{}, std::integral_constant<int, 2>{}) : (Hh == 4 ? pick(NCT{}, std::integral_constant<int, 4>{}) : pick(NCT{}, std::integral_constant<int, 8>{}));
         }
+        snprintf(route, sizeof(route), "melspec_backward_ring3_multi_kernel<%d, %s, %d, %s>", d->n_fft / 2, p2, Hh == 2 || Hh == 4 ? Hh : 8,
+                 adj ? "true" : "false");
     } else if (adj) {
         // one 8-wave workgroup per CU around one copy of the tables; the ring shrinks to its 16 - H live slots
         using F = WaveFft<OLA_NC, OLA_E>;
@@ -1305,6 +1315,7 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
         if (lds > 160 * 1024) return TAC_E_UNSUPPORTED;
         rc = pow2 ? launch(spectrogram_backward_ola_kernel<true, true, FW>, lds, 1, FW)
                   : launch(spectrogram_backward_ola_kernel<false, true, FW>, lds, 1, FW);
+        snprintf(route, sizeof(route), "spectrogram_backward_ola_kernel<%s, true, %d>", p2, FW);
     } else
     switch (d->n_fft) {
         case 2048: {
@@ -1312,28 +1323,33 @@ static int ola_backward_entry(const float* wave, const float* window, const tac_
             fz.ring_slots = 16;
             rc = pow2 ? launch(spectrogram_backward_ola_kernel<true, false, OLA_WAVES>, lds_for(OLA_NC, F::PADDED, 1), 1)
                       : launch(spectrogram_backward_ola_kernel<false, false, OLA_WAVES>, lds_for(OLA_NC, F::PADDED, 1), 1);
+            snprintf(route, sizeof(route), "spectrogram_backward_ola_kernel<%s, false, %d>", p2, OLA_WAVES);
             break;
         }
         case 1024: {
             using F = WaveFft<512, OLA_E>;
             rc = pow2 ? launch_multi(spectrogram_backward_ola_multi_kernel<512, true>, lds_for(512, F::PADDED, F::G), F::G)
                       : launch_multi(spectrogram_backward_ola_multi_kernel<512, false>, lds_for(512, F::PADDED, F::G), F::G);
+            snprintf(route, sizeof(route), "spectrogram_backward_ola_multi_kernel<512, %s>", p2);
             break;
         }
         case 512: {
             using F = WaveFft<256, OLA_E>;
             rc = pow2 ? launch_multi(spectrogram_backward_ola_multi_kernel<256, true>, lds_for(256, F::PADDED, F::G), F::G)
                       : launch_multi(spectrogram_backward_ola_multi_kernel<256, false>, lds_for(256, F::PADDED, F::G), F::G);
+            snprintf(route, sizeof(route), "spectrogram_backward_ola_multi_kernel<256, %s>", p2);
             break;
         }
         case 256: {
             using F = WaveFft<128, OLA_E>;
             rc = pow2 ? launch_multi(spectrogram_backward_ola_multi_kernel<128, true>, lds_for(128, F::PADDED, F::G), F::G)
                       : launch_multi(spectrogram_backward_ola_multi_kernel<128, false>, lds_for(128, F::PADDED, F::G), F::G);
+            snprintf(route, sizeof(route), "spectrogram_backward_ola_multi_kernel<128, %s>", p2);
             break;
         }
         default: return TAC_E_UNSUPPORTED;
     }
+    if (rc == TAC_OK) set_last_route("%s", route);
     }
     if (rc != TAC_OK) return rc;
     const unsigned fold_y = (unsigned)std::min<long long>(g.rows, 65535);

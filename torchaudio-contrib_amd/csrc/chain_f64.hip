@@ -330,11 +330,17 @@ int launch_stft_f64(const double* wave, const double* window, const tac_stft_des
     if (plan_f64(N, &plan)) {
         const bool tw_lds = N <= 4096;
         const size_t lds = ((size_t)(tw_lds ? M + 1 : 0) + 2 * (size_t)M * plan.group) * sizeof(cd);
-        return launch_kernel(tw_lds ? stft_f64_kernel<true> : stft_f64_kernel<false>, persistent_blocks(units, plan.group, cap), D_THREADS,
-                             lds, stream, g, tw, ep, plan, out);
+        rc = launch_kernel(tw_lds ? stft_f64_kernel<true> : stft_f64_kernel<false>, persistent_blocks(units, plan.group, cap), D_THREADS,
+                           lds, stream, g, tw, ep, plan, out);
+        if (rc != TAC_OK) return rc;
+        set_last_route("stft_f64_kernel<%s>, group %d", tw_lds ? "true" : "false", plan.group);
+        return TAC_OK;
     }
     const size_t lds = (size_t)N * sizeof(cd) + (size_t)N * sizeof(double);
-    return launch_kernel(stft_f64_direct_kernel, persistent_blocks(units, 1, cap), D_THREADS, lds, stream, g, tw, ep, out);
+    rc = launch_kernel(stft_f64_direct_kernel, persistent_blocks(units, 1, cap), D_THREADS, lds, stream, g, tw, ep, out);
+    if (rc != TAC_OK) return rc;
+    set_last_route("stft_f64_direct_kernel");
+    return TAC_OK;
 }
 
 // ------------------------------------------------------------------ filterbank contraction, float64

@@ -438,7 +438,10 @@ static int launch_pipe(const FrameGeom& g, const Tables& tb, const StftEpilogue&
     constexpr int WAVES = PIPE_WAVES;
     const size_t bytes = (size_t)WAVES * (((F::PADDED + 1) / 2) * 2) * sizeof(cf) + (size_t)64 * (E + 2) * sizeof(cf) + 16;
     const long long blocks = persistent_blocks(groups, WAVES, (long long)device_cu_count() * (8 / WAVES));
-    return launch_kernel(stft_pipe_kernel<NC, E, PMODE, WAVES>, blocks, WAVES * 64, bytes, stream, g, tb, ep);
+    const int rc = launch_kernel(stft_pipe_kernel<NC, E, PMODE, WAVES>, blocks, WAVES * 64, bytes, stream, g, tb, ep);
+    if (rc != TAC_OK) return rc;
+    set_last_route("stft_pipe_kernel<%d, %d, %d, %d>", NC, E, PMODE, WAVES);
+    return TAC_OK;
 }
 
 // three waves per SIMD (stft_stream3.hpp); TAC_STFT_PIPE2=1 keeps the two-wave pipelined kernel above
@@ -523,10 +526,18 @@ static int launch_stft(const FrameGeom& g, const Tables& tb, const StftEpilogue&
     if (per_cu > 2) per_cu = 2;
     if (per_cu < 1) per_cu = 1;
     const long long blocks = persistent_blocks(groups, waves, (long long)device_cu_count() * per_cu);
+    int rc = TAC_OK;
+    bool launched = false;
     if constexpr (WIDE_FITS) {
-        if (wide) return launch_kernel(stft_kernel<NC, E, MODE, NF, HOIST, 2 * STFT_WAVES>, blocks, waves * 64, lds_bytes, stream, g, tb, ep);
+        if (wide) {
+            rc = launch_kernel(stft_kernel<NC, E, MODE, NF, HOIST, 2 * STFT_WAVES>, blocks, waves * 64, lds_bytes, stream, g, tb, ep);
+            launched = true;
+        }
     }
-    return launch_kernel(stft_kernel<NC, E, MODE, NF, HOIST, STFT_WAVES>, blocks, waves * 64, lds_bytes, stream, g, tb, ep);
+    if (!launched) rc = launch_kernel(stft_kernel<NC, E, MODE, NF, HOIST, STFT_WAVES>, blocks, waves * 64, lds_bytes, stream, g, tb, ep);
+    if (rc != TAC_OK) return rc;
+    set_last_route("stft_kernel<%d, %d, %d, %d, %d, %d>", NC, E, MODE, NF, HOIST ? 1 : 0, waves);
+    return TAC_OK;
 }
 
 int try_launch_n4096(const FrameGeom& g, const StftEpilogue& ep, int mode, hipStream_t stream);

@@ -811,8 +811,12 @@ int launch_n400_backward(const FrameGeom& g, const float* gspec, const float* gn
         else kern = power == 2.0f ? stft_n400_backward_kernel<SRC_WAVE, true> : stft_n400_backward_kernel<SRC_WAVE, false>;
     } else if (!gnorm) kern = inverse ? stft_n400_backward_kernel<SRC_INV, false> : stft_n400_backward_kernel<SRC_GRAD, false>;
     else kern = power == 2.0f ? stft_n400_backward_kernel<SRC_NORM, true> : stft_n400_backward_kernel<SRC_NORM, false>;
-    return launch_kernel(kern, persistent_blocks(units, Q4_WAVES, device_cu_count()), Q4_WAVES * 64, bytes, stream, g, tb, gspec, gnorm,
-                         power, frames, adj, n_mels, gpad, edge, plan ? *plan : OlaPlan{});
+    const int rl = launch_kernel(kern, persistent_blocks(units, Q4_WAVES, device_cu_count()), Q4_WAVES * 64, bytes, stream, g, tb, gspec, gnorm,
+                                 power, frames, adj, n_mels, gpad, edge, plan ? *plan : OlaPlan{});
+    if (rl != TAC_OK) return rl;
+    set_last_route("stft_n400_backward_kernel<%s, %s, %s, %s>", from_wave ? "SRC_WAVE" : (!gnorm ? (inverse ? "SRC_INV" : "SRC_GRAD") : "SRC_NORM"),
+                   gnorm && power == 2.0f ? "true" : "false", from_wave && adj ? "true" : "false", from_wave && plan ? "true" : "false");
+    return TAC_OK;
 }
 
 // Entry used by stft_kernels.hip's dispatcher: TAC_E_UNSUPPORTED when this form does not apply (two-sided output,

@@ -475,7 +475,10 @@ static int launch_n4096(const FrameGeom& g, const Tables& tb1k, const Tables& tb
     constexpr int WS = ((F::PADDED + 1) / 2) * 2;
     const size_t bytes = (size_t)N4K_WAVES * 2 * WS * sizeof(cf) + (size_t)64 * 17 * sizeof(f4) + 16;
     const long long blocks = persistent_blocks(units, N4K_WAVES, device_cu_count());      // one 8-wave workgroup per CU (157 KB of LDS)
-    return launch_kernel(stft_n4096_kernel<MODE>, blocks, N4K_WAVES * 64, bytes, stream, g, tb1k, tb4k, ep);
+    const int rc = launch_kernel(stft_n4096_kernel<MODE>, blocks, N4K_WAVES * 64, bytes, stream, g, tb1k, tb4k, ep);
+    if (rc != TAC_OK) return rc;
+    set_last_route("stft_n4096_kernel<%d>", MODE);
+    return TAC_OK;
 }
 
 // Entry used by stft_kernels.hip's dispatcher: returns TAC_E_UNSUPPORTED when this form does not apply (two-sided

@@ -232,8 +232,10 @@ static int launch_small(const FrameGeom& g, const Tables& tb, const StftEpilogue
         // complex rows are bound by their stores (12 waves measure like the two-wave kernel, 16 slower); real rows gain 8-10 %
         // from the fourth wave per SIMD (profiles/r03/ab_stream3.txt)
         const int wv = getenv("TAC_SM3_WAVES") ? small3_waves() : (MODE == 0 ? 12 : 16);
-        if (wv == 12) return go(stft_small3_kernel<NC, MODE, false, 1, 12>, 12);
-        return go(stft_small3_kernel<NC, MODE, false, 1, 16>, 16);
+        const int rc = wv == 12 ? go(stft_small3_kernel<NC, MODE, false, 1, 12>, 12) : go(stft_small3_kernel<NC, MODE, false, 1, 16>, 16);
+        if (rc != TAC_OK) return rc;
+        set_last_route("stft_small3_kernel<%d, %d, 0, 1, %d>", NC, MODE, wv == 12 ? 12 : 16);
+        return TAC_OK;
     }
     if constexpr (NC < 256) {
         return TAC_E_UNSUPPORTED;                            // fft_length 256 has no two-wave form: the generic kernel

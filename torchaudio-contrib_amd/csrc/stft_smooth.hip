@@ -336,7 +336,7 @@ int launch_stft_smooth(int n_fft, const FrameGeom& g, const StftEpilogue& ep, in
     const int rl = mode == 0 ? (tpf == 64 ? go(stft_smooth_kernel<0, 64>) : (full ? go(stft_smooth_kernel<0, 256>) : go(stft_smooth_kernel<0, 256, false>)))
                              : (tpf == 64 ? go(stft_smooth_kernel<1, 64>) : (full ? go(stft_smooth_kernel<1, 256>) : go(stft_smooth_kernel<1, 256, false>)));
     if (rl != TAC_OK) return rl;
-    set_last_route("stft_smooth_kernel<%d, %d>", mode == 0 ? 0 : 1, tpf);
+    set_last_route("stft_smooth_kernel<%d, %d%s>", mode == 0 ? 0 : 1, tpf, full ? "" : ", false");
     return TAC_OK;
 }
 
@@ -361,11 +361,13 @@ int launch_stft_smooth_backward(int n_fft, const FrameGeom& g, const float* grad
     auto go = [&](auto kern) {
         return launch_kernel(kern, blocks, SM_THREADS, lds, stream, g, tw, reinterpret_cast<const cf*>(grad_spec), grad_frames, plan, n_fft);
     };
-    if (inverse)
-        return tpf == 64 ? go(stft_smooth_backward_kernel<64, true, true>)
-                       : (full ? go(stft_smooth_backward_kernel<256, true, true>) : go(stft_smooth_backward_kernel<256, false, true>));
-    return tpf == 64 ? go(stft_smooth_backward_kernel<64>)
-                     : (full ? go(stft_smooth_backward_kernel<256>) : go(stft_smooth_backward_kernel<256, false>));
+    const int rl = inverse ? (tpf == 64 ? go(stft_smooth_backward_kernel<64, true, true>)
+                                        : (full ? go(stft_smooth_backward_kernel<256, true, true>) : go(stft_smooth_backward_kernel<256, false, true>)))
+                           : (tpf == 64 ? go(stft_smooth_backward_kernel<64>)
+                                        : (full ? go(stft_smooth_backward_kernel<256>) : go(stft_smooth_backward_kernel<256, false>)));
+    if (rl != TAC_OK) return rl;
+    set_last_route("stft_smooth_backward_kernel<%d, %s, %s>", tpf, full ? "true" : "false", inverse ? "true" : "false");
+    return TAC_OK;
 }
 
 }  // namespace tac
