@@ -923,6 +923,23 @@ int tac_griffinlim_prepare_f32(const float* spec, int64_t rows, int64_t n_freqs,
                                float power, float* mag, float* x0, void* stream);
 int tac_griffinlim_update_f32(const float* r, const float* rprev, const float* mag, int64_t n_bins, float m, float* x, void* stream);
 
+/* (30) functional.pitch_shift's resampling tail, tac_amd::resample_fit: the sums of (15) for banks the LDS cannot hold, cut or
+ *      zero-padded to out_len samples a row in the store:
+ *      y[r][j*phases + p] = sum_{k < run[p]} bank[k][p] * x[r][j*step + off[p] + k]   for 0 <= j*phases + p < min(n_out, out_len),
+ *      y[r][n] = 0 for min(n_out, out_len) <= n < out_len;  x[r][i] = x[r*stride_r + i], zero outside 0 <= i < l_in; out:
+ *      float[rows][out_len], dense.  bank and table as in (15), read from global memory (consecutive lanes, consecutive
+ *      addresses); the arithmetic is (15)'s — one fused multiply-add chain over k ascending from 0, only k < run[p] — so the
+ *      bits are (15)'s wherever both take a bank.  No atomics, one writer per element, bit-identical from run to run.
+ *      The starts j*step + off[p] must not decrease in n = j*phases + p, and span is the most consecutive input samples that
+ *      `tile` (1024, 512 or 256) consecutive outputs read, from the first sample the tile's first output reads, over every tile
+ *      start (_hip.resample_wide_plan computes both on the host).  off and run are clamped to that span: a wrong table or plan
+ *      gives wrong sums, never an access outside a tile's LDS slot or a row.  taps <= 64, phases * taps <= 1 << 20,
+ *      span <= 8192 and four rows' spans within 160 KiB, TAC_E_UNSUPPORTED (nothing launched) otherwise.
+ *      16-byte loads where x and stride_r are 16-byte multiples, float loads otherwise. */
+int tac_polyphase_wide_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride_r, const float* bank, const int32_t* table,
+                           int32_t phases, int32_t taps, int32_t step, int32_t span, int32_t tile, int64_t n_out, int64_t out_len,
+                           float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filte
                          highpass_biquad, bandpass_biquad, bandreject_biquad, allpass_biquad, equalizer_biquad,
                          preemphasis, deemphasis, fftconvolve, convolve, kaldi_fbank, sliding_window_cmn,
                          compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid,
-                         add_noise, speed, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
+                         add_noise, speed, pitch_shift, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
                          apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, forced_align,
                          merge_tokens, TokenSpan)
 from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
@@ -26,7 +26,7 @@ from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filt
                      MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis,
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,
                      KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment,
-                     AddNoise, Speed, SpeedPerturbation, Loudness, PitchFrequency, PSD, SoudenMVDR, MVDR,
+                     AddNoise, Speed, SpeedPerturbation, PitchShift, Loudness, PitchFrequency, PSD, SoudenMVDR, MVDR,
                      RTFMVDR, RNNTLoss)
 from . import distributed
 from . import kaldi

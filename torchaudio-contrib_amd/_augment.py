@@ -40,6 +40,22 @@ def speed_rates(orig_freq, factor, name='speed'):
     return source // gcd, target // gcd
 
 
+def pitch_rates(sample_rate, n_steps, bins_per_octave=12, name='pitch_shift'):
+    """``(rate, source)``: the time-stretch factor ``2 ** (-n_steps / bins_per_octave)`` of torchaudio's ``pitch_shift`` and the rate
+    ``int(sample_rate / rate)`` its last stage resamples FROM, to ``sample_rate`` (16 kHz, 4 steps: 20158, i.e. 10079 : 8000).
+    ``ValueError`` for a sample rate that is no positive int, no bins, or a shift that leaves no source rate."""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or sample_rate <= 0:
+        raise ValueError('%s: sample_rate must be a positive int, got %r' % (name, sample_rate))
+    if bins_per_octave == 0:
+        raise ValueError('%s: bins_per_octave must not be 0' % name)
+    rate = 2.0 ** (-float(n_steps) / bins_per_octave)
+    source = int(sample_rate / rate)
+    if source <= 0:
+        raise ValueError('%s: n_steps %r at sample_rate %d leaves no sample rate (int(sample_rate / rate) = %d)'
+                         % (name, n_steps, sample_rate, source))
+    return rate, source
+
+
 def speed_lengths(lengths, source, target):
     """the valid lengths after ``resample(source -> target)``: ``ceil(lengths * target / source)`` in the dtype of ``lengths``, by
     torch operators where ``lengths`` lies"""

@@ -128,6 +128,54 @@ def resample(wave, orig, new, lowpass_filter_width, rolloff, method, beta):
     return out.reshape(tuple(wave.shape[:-1]) + (n_out,))
 
 
+_compact_tables = Bounded(16)
+
+
+def _compact_table(key, valid, length, device, dtype):
+    """(start, ok, weight) of the first ``valid`` outputs over rows of ``length`` samples, on ``device``: int64 ``(valid,)`` first
+    input sample, bool and ``dtype`` ``(K, valid)`` — tap ``k`` of output ``n`` is read (inside its phase's run and the row), and its
+    value (0 where it is not)"""
+    from . import _resample as RS
+    hit = _compact_tables.get((key, valid, length, str(device), dtype))
+    if hit is None:
+        with torch.inference_mode(False):
+            b = RS.bank(*key)
+            n = torch.arange(valid, dtype=torch.int64)
+            j = torch.div(n, b.phases, rounding_mode='floor')
+            p = n - j * b.phases
+            start = j * b.step + torch.tensor(b.off, dtype=torch.int64)[p]
+            k = torch.arange(b.K, dtype=torch.int64).unsqueeze(1)
+            idx = start.unsqueeze(0) + k
+            ok = (k < torch.tensor(b.run, dtype=torch.int64)[p].unsqueeze(0)) & (idx >= 0) & (idx < length)
+            weight = torch.where(ok, b.taps[p].t(), torch.zeros((), dtype=torch.float64))
+            hit = (start.to(device), ok.to(device), weight.to(device=device, dtype=dtype))
+        _compact_tables[(key, valid, length, str(device), dtype)] = hit
+    return hit
+
+
+def resample_compact(wave, orig, new, lowpass_filter_width, rolloff, method, beta, out_len):
+    """``resample`` by the reduced pair cut or zero-padded to ``out_len`` samples, from the COMPACT bank: ``K`` gathers and
+    multiply-adds in the tensor's dtype (``_resample.apply_bank64`` without the float64 cast), differentiable, ``O(n_out)`` memory.
+    The full-bank ``conv1d`` above cannot serve the pairs this is for: its kernel is 323 MB at 10079 : 8000 and 8.2 GB at
+    42763 : 48000.  Samples behind a phase's run are not multiplied (a NaN reaches what the kernels let it reach)."""
+    from . import _resample as RS
+    length = wave.shape[-1]
+    valid = min(RS.out_length(length, orig, new), out_len)
+    if orig == new:
+        out = wave[..., :valid]
+    else:
+        out = wave.new_zeros(tuple(wave.shape[:-1]) + (valid,))
+        if valid and length:
+            start, ok, weight = _compact_table((orig, new, lowpass_filter_width, rolloff, method, beta), valid, length, wave.device,
+                                               wave.dtype)
+            zero = wave.new_zeros(())
+            for k in range(weight.shape[0]):
+                out = out + weight[k] * torch.where(ok[k], wave[..., (start + k).clamp(0, length - 1)], zero)
+    if out_len > valid:
+        return TF.pad(out, (0, out_len - valid))
+    return out.clone(memory_format=torch.contiguous_format) if orig == new else out      # (an op may not return its input)
+
+
 def lfilter(wave, a_coeffs, b_coeffs, clamp):
     """torchaudio's ``functional.lfilter`` from the definition, ``a0 y[n] = sum_k b_k x[n-k] - sum_{k>=1} a_k y[n-k]`` with zero
     initial state: the feed-forward part as shifted sums, the recursion as a LOOP OVER TIME in torch ops, vectorised over the

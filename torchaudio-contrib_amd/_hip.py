@@ -938,6 +938,98 @@ def polyphase(x, key, n_out, adjoint=False):
     return out
 
 
+#: what ``tac_polyphase_wide_f32`` takes (csrc/resample.hip: RSW_*): floats of bank it reads from global memory (4 MB: an XCD's L2
+#: with the Infinity Cache behind it), taps per phase, floats of one tile's input span, rows of a unit, bytes of LDS
+RESAMPLE_WIDE_MAX_BANK = 1 << 20
+RESAMPLE_WIDE_MAX_TAPS = 64
+RESAMPLE_WIDE_SPAN_MAX = 8192
+RESAMPLE_WIDE_ROWS = 4
+_RSW_LDS_BYTES = 160 * 1024
+
+_wide_plans = Bounded(64)
+
+
+def resample_wide_starts(b):
+    """int64 ``(phases + 1,)``: the first input sample output ``n`` reads, ``j * step + off[p]``, for ``n = 0 .. phases``"""
+    off = torch.tensor(b.off, dtype=torch.int64)
+    return torch.cat((off, off[:1] + b.step))
+
+
+def resample_wide_plan(b):
+    """``(span, tile)`` of ``tac_polyphase_wide_f32`` for this bank, or None where the kernel does not take it.  The kernel stages,
+    per tile of ``tile`` consecutive outputs, the inputs from the first one its FIRST output reads — which is the first one any
+    of them reads only if the starts ``j * step + off[p]`` never decrease in ``n``, across the wrap ``p = phases - 1 -> 0`` too:
+    checked here.  ``span`` is the exact maximum, over every phase a tile can start at, of the samples from there to the last
+    one the tile reads (a sliding maximum of ``start + run`` over ``phases + tile - 1`` outputs).  Cached per bank."""
+    hit = _wide_plans.get(id(b))
+    if hit is not None and hit[0] is b:
+        return hit[1]
+    plan = None
+    start = resample_wide_starts(b)
+    if b.K <= RESAMPLE_WIDE_MAX_TAPS and b.phases * b.K <= RESAMPLE_WIDE_MAX_BANK and not bool((start[1:] < start[:-1]).any()):
+        off = torch.tensor(b.off, dtype=torch.int64)
+        run = torch.tensor(b.run, dtype=torch.int64).clamp(0, b.K)
+        for tile in (1024, 512, 256):
+            n = torch.arange(b.phases + tile - 1, dtype=torch.int64)
+            j = torch.div(n, b.phases, rounding_mode='floor')
+            p = n - j * b.phases
+            first = j * b.step + off[p]
+            last = (first + run[p]).unfold(0, tile, 1).max(dim=1).values           # (phases,): the end of the tile that starts at n
+            span = max(int((last - first[:b.phases]).max()), 1)
+            if span <= RESAMPLE_WIDE_SPAN_MAX and 4 * RESAMPLE_WIDE_ROWS * ((3 + span + b.K + 3) & ~3) <= _RSW_LDS_BYTES:
+                plan = (span, tile)
+                break
+    _wide_plans[id(b)] = (b, plan)
+    return plan
+
+
+def resample_fit_covers(key, length, out_len):
+    """True where ``resample_fit`` of ``(…, length)`` to ``out_len`` samples runs AND trains on the kernels: the LDS kernel where it
+    holds both banks and nothing is cut or padded, else the wide kernel where both banks have a plan."""
+    if resample_covers(*key) and out_len == _resample.out_length(length, key[0], key[1]):
+        return True
+    return resample_wide_plan(_resample.bank(*key)) is not None and resample_wide_plan(_resample.adjoint_bank(*key)) is not None
+
+
+def polyphase_wide(x, key, n_out, out_len, adjoint=False, l_in=None, out=None):
+    """``(…, L) -> (…, out_len)`` through ``tac_polyphase_wide_f32``: the sums of ``polyphase`` for ``n < min(n_out, out_len)``,
+    zeros behind them; one launch.  ``l_in``: the samples of a row that are read (the rest count as zero), all of them by default;
+    ``out``: a dense float32 tensor of the result's shape to fill instead of a new one."""
+    b, taps, table, _, _, _ = _resample_device_bank(key, adjoint, x.device)
+    plan = resample_wide_plan(b)
+    if plan is None:
+        raise RuntimeError('polyphase_wide: the bank of %d phases x %d taps has no plan (resample_wide_plan)' % (b.phases, b.K))
+    length = x.shape[-1] if l_in is None else min(int(l_in), x.shape[-1])
+    shape = tuple(x.shape[:-1]) + (out_len,)
+    if out is None:
+        out = _empty(shape, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError('polyphase_wide: out must be a dense float32 tensor of shape %r on %s' % (shape, x.device))
+    if out.numel():
+        if length <= 0 or n_out <= 0:
+            return out.zero_()
+        rows = x.reshape(-1, x.shape[-1])
+        if (x.shape[-1] > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+            rows = rows.contiguous()
+        _launch('tac_polyphase_wide_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0),
+                _native.ptr(taps), _native.ptr(table), b.phases, b.K, b.step, plan[0], plan[1], n_out, out_len, _native.ptr(out))
+    return out
+
+
+def resample_fit(x, key, out_len, adjoint=False, length=None, wide=None):
+    """``resample`` by the reduced pair of ``key`` cut or zero-padded to ``out_len`` samples; with ``adjoint`` its gradient: ``x`` is
+    grad_out ``(…, out_len)``, read as zero beyond ``min(n_out, out_len)``, and the result has ``length`` samples.  The LDS kernel
+    where it holds the banks and ``out_len == n_out``, the wide kernel otherwise — the same bits; ``wide`` forces either."""
+    n_out = _resample.out_length(length if adjoint else x.shape[-1], key[0], key[1])
+    if wide is None:
+        wide = not (out_len == n_out and resample_covers(*key))
+    if not wide:
+        return polyphase(x, key, length if adjoint else n_out, adjoint=adjoint)
+    if adjoint:
+        return polyphase_wide(x, key, length, length, adjoint=True, l_in=min(n_out, out_len))
+    return polyphase_wide(x, key, n_out, out_len)
+
+
 # ----------------------------------------------------------------------------- lfilter
 #: samples per lane and per tile of ``tac_lfilter_f32`` (csrc/lfilter.hip: LF_C, LF_TILE = 1024 lanes * LF_C); checked against the
 #: library's own value at the first launch

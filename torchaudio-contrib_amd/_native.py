@@ -177,6 +177,7 @@ PROTOTYPES = {
     'tac_forced_align_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I32, _P, _P, _I32, _P, _P, _P, _P]),
     'tac_griffinlim_prepare_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _F, _P, _P, _P]),
     'tac_griffinlim_update_f32': (_INT, [_P, _P, _P, _I64, _F, _P, _P]),
+    'tac_polyphase_wide_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I64, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -10,6 +10,7 @@ see them by name.
     tac_amd::stretch_mel            "      + apply_filterbank in the same launch
     tac_amd::dct                rows times the cepstral matrix, the step behind the mel dB rows (csrc/mfcc.hip)
     tac_amd::resample           polyphase windowed-sinc resampling of the waveform (csrc/resample.hip)
+    tac_amd::resample_fit       the same cut or zero-padded to a given length, for banks beyond the LDS too: pitch_shift's tail
     tac_amd::kaldi_fbank        Kaldi log mel filterbank features: framing, FFT, mel bank and log in one launch (csrc/kaldi_fbank.hip)
     tac_amd::kaldi_mfcc         Kaldi cepstra: the same launch with the DCT, lifter and energy substitution as its epilogue
     tac_amd::kaldi_spectrogram  Kaldi log power spectrogram: the same launch, every bin's logarithm, the energy as column 0
@@ -403,6 +404,18 @@ def _resample_hip_backward(saved, rest, needs, grads):
     return [H.polyphase(grads[0], tuple(rest), int(wave.shape[-1]), adjoint=True)]
 
 
+def _resample_fit_hip_backward(saved, rest, needs, grads):
+    (wave,) = saved
+    key, out_len, length = tuple(rest[:6]), rest[6], int(wave.shape[-1])
+    g = grads[0]
+    if g is None or not needs[0] or key[0] == key[1] or not H.resample_fit_covers(key, length, out_len):
+        return None
+    if any(st <= 0 for st, n in zip(g.stride(), g.shape) if n > 1):
+        g = g.contiguous()                                      # (an expanded grad_out is copied)
+    # the adjoint bank on the same kernel; grad_out counts as zero beyond min(n_out, out_len): the effective length is passed
+    return [H.resample_fit(g, key, out_len, adjoint=True, length=length)]
+
+
 def _lfilter_hip_backward(saved, rest, needs, grads):
     wave, a, b = saved[:3]
     (clamp,) = rest
@@ -486,7 +499,7 @@ def _add_noise_hip_backward(saved, rest, needs, grads):
 
 _HIP_BACKWARD = {'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
                  'mask_spans': _mask_spans_hip_backward, 'add_noise': _add_noise_hip_backward,
-                 'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+                 'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'resample_fit': _resample_fit_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -778,6 +791,32 @@ def _resample_fake(wave, orig, new, lowpass_filter_width, rolloff, method, beta)
 
 _register('resample', '(Tensor wave, int orig, int new, int lowpass_filter_width, float rolloff, str method, float? beta) '
           '-> Tensor', _resample_cuda, C.resample, _resample_fake, 1)
+
+
+# ============================================================================= resample_fit
+def _resample_fit_cuda(wave, orig, new, lowpass_filter_width, rolloff, method, beta, out_len):
+    key = (orig, new, lowpass_filter_width, rolloff, method, beta)
+    length = wave.shape[-1]
+    if orig == new or wave.numel() == 0 or out_len == 0:
+        return C.resample_compact(wave, *key, out_len)         # a copy / zeros: nothing is launched
+    reason = _hip_dtype(wave)
+    if reason is None and not H.resample_fit_covers(key, length, out_len):
+        reason = 'a polyphase bank outside the LDS and the wide kernel (%d -> %d)' % (orig, new)
+    if reason is None and any(st <= 0 for st, n in zip(wave.stride(), wave.shape) if n > 1):
+        reason = 'non-positive strides'
+    if reason is not None:
+        _composite_route('resample_fit', reason)
+        return C.resample_compact(wave, *key, out_len)
+    out = H.resample_fit(_f32(wave), key, out_len)
+    return out if wave.dtype == out.dtype else out.to(wave.dtype)
+
+
+def _resample_fit_fake(wave, orig, new, lowpass_filter_width, rolloff, method, beta, out_len):
+    return wave.new_empty(tuple(wave.shape[:-1]) + (out_len,))
+
+
+_register('resample_fit', '(Tensor wave, int orig, int new, int lowpass_filter_width, float rolloff, str method, float? beta, '
+          'int out_len) -> Tensor', _resample_fit_cuda, C.resample_compact, _resample_fit_fake, 1)
 
 
 # ============================================================================= fftconvolve

@@ -1,4 +1,5 @@
-// resample.hip — functional.resample: polyphase windowed-sinc resampling and its adjoint, one streaming kernel.
+// resample.hip — functional.resample: polyphase windowed-sinc resampling and its adjoint, one streaming kernel; below it the same
+// sums for banks the LDS cannot hold (tac_polyphase_wide_f32: resample_fit, the last stage of pitch_shift).
 //
 //   y[r][j*P + p] = sum_{k < run[p]} B[k][p] * x[r][j*S + off[p] + k]        0 <= j*P + p < L_out,  x zero outside [0, L_in)
 //
@@ -126,6 +127,139 @@ inline auto rs_pick(bool vec) {
     return vec ? polyphase_kernel<P1, SKEW, true> : polyphase_kernel<P1, SKEW, false>;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- wide banks
+// tac_polyphase_wide_f32 — the same sums for banks the LDS cannot hold (pitch_shift's 10079 : 8000, 42763 : 48000: up to 4 MB of
+// taps, which an XCD's L2 and the Infinity Cache behind it do hold).  What changes against polyphase_kernel:
+//   taps, off, run     read from global memory by the lane that uses them: consecutive lanes are consecutive n, i.e. consecutive
+//                      addresses of bank[k * P + p] except at a wrap p = P - 1 -> 0.  A lane's taps are fetched ONCE per unit into
+//                      registers (compile-time buckets of K) and serve every row of the unit.
+//   unit               a tile of TO consecutive outputs times a group of up to RSW_ROWS rows, whose spans are staged together:
+//                      one barrier pair a unit.
+//   span per tile      starts at the first input the tile's FIRST output reads, j0 * S + off[p0]: the host plan
+//                      (_hip.resample_wide_plan) has checked that the starts j * S + off[p] never decrease in n and hands over the
+//                      largest span any tile start needs.  off / run are clamped to that span: whatever the table holds, every LDS
+//                      index stays inside the row's slot (span + K floats behind a lead of at most 3).
+//   out_len            outputs per row that are WRITTEN: n < min(n_out, out_len) are sums, the rest exact zeros.
+// The arithmetic is polyphase_kernel's — one __builtin_fmaf chain over k ascending from 0, only k < run[p] — so the bits are too.
+// Measured on an MI355X, (256, 160000) at 10079 : 8000 (profiles/pitch_shift): 0.167 ms with four rows a unit against 0.273 ms
+// with one, where every row fetches its taps from L2 again (tools/ablation/README.md); K = 34 is the one case one row is level.
+constexpr int RSW_ROWS = 4;                     // rows of a unit
+constexpr int RSW_MAX_TAPS = 64;                // K
+constexpr long long RSW_MAX_BANK = 1LL << 20;   // floats of bank (P * K): 4 MB
+constexpr int RSW_SPAN_MAX = 8192;              // floats of input span a tile may take: four rows of it are 128 KiB
+
+template <int KB, bool VEC>
+__global__ void __launch_bounds__(RS_THREADS)
+polyphase_wide_kernel(const float* __restrict__ x, long long stride_r, long long l_in, long long rows,
+                      const float* __restrict__ bank, const int* __restrict__ table, int P, int K, int S, int span, int pitch,
+                      int tile_log, long long tiles_per_row, long long units, long long n_out, long long out_len,
+                      float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+    const int tid = threadIdx.x;
+    const int TO = 1 << tile_log;
+    const int span4 = (3 + span + 3) >> 2;                          // 16-byte groups staged per row: lead + span, rounded up
+    for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+        const long long grp = u / tiles_per_row;
+        const long long n0 = (u - grp * tiles_per_row) << tile_log;
+        const long long row0 = grp * RSW_ROWS;
+        const int rg = (int)(rows - row0 < RSW_ROWS ? rows - row0 : RSW_ROWS);
+        const int nt = (int)(out_len - n0 < TO ? out_len - n0 : TO);        // outputs the tile writes ...
+        const long long left = n_out - n0;
+        const int nv = left <= 0 ? 0 : (left < nt ? (int)left : nt);        // ... of which the first nv are sums
+        const long long j0 = n0 / P;
+        const int p0 = (int)(n0 - j0 * P);
+        const long long start0 = (long long)table[p0];                      // off of the tile's first output
+        const long long a0 = j0 * S + start0;                               // first input sample the tile reads
+        const long long a0f = a0 & ~3LL;
+        const int lead = (int)(a0 - a0f);
+        if (nv > 0) {
+            // the rows' spans as ONE index space: every lane has loads in flight whatever the span's length
+            if constexpr (VEC) {
+                for (int e = tid; e < rg * span4; e += RS_THREADS) {
+                    const int r = e / span4, q = e - r * span4;
+                    const float* src = x + (row0 + r) * stride_r;
+                    const long long g = a0f + 4 * q;
+                    rs_f4 v;
+                    if (g >= 0 && g + 3 < l_in) {
+                        v = *reinterpret_cast<const rs_f4*>(src + g);
+                    } else {
+                        v.x = (g >= 0 && g < l_in) ? src[g] : 0.0f;
+                        v.y = (g + 1 >= 0 && g + 1 < l_in) ? src[g + 1] : 0.0f;
+                        v.z = (g + 2 >= 0 && g + 2 < l_in) ? src[g + 2] : 0.0f;
+                        v.w = (g + 3 >= 0 && g + 3 < l_in) ? src[g + 3] : 0.0f;
+                    }
+                    *reinterpret_cast<rs_f4*>(rs_lds + r * pitch + 4 * q) = v;
+                }
+            } else {
+                for (int e = tid; e < rg * 4 * span4; e += RS_THREADS) {
+                    const int r = e / (4 * span4), i = e - r * (4 * span4);
+                    const long long g = a0f + i;
+                    rs_lds[r * pitch + i] = (g >= 0 && g < l_in) ? x[(row0 + r) * stride_r + g] : 0.0f;
+                }
+            }
+            __syncthreads();                                        // the spans of the unit's rows are in the LDS
+        }
+        for (int o = tid; o < nt; o += RS_THREADS) {
+            float acc[RSW_ROWS];
+#pragma unroll
+            for (int r = 0; r < RSW_ROWS; ++r) acc[r] = 0.0f;
+            if (o < nv) {
+                const int m = p0 + o;
+                const int jl = m / P;
+                const int p = m - jl * P;
+                // clamped to what the plan sized the span for: 0 <= xi <= span and run <= K, so xi + k < span + K
+                long long xl = (long long)jl * S + (long long)table[p] - start0;
+                xl = xl < 0 ? 0 : (xl > span ? span : xl);
+                const int xi = lead + (int)xl;
+                int run = table[P + p];
+                run = run < 0 ? 0 : (run > K ? K : run);
+                float w[KB];
+#pragma unroll
+                for (int k = 0; k < KB; ++k) w[k] = k < run ? bank[(long long)k * P + p] : 0.0f;
+#pragma unroll
+                for (int r = 0; r < RSW_ROWS; ++r) {
+                    if (r < rg) {
+                        const float* xs = rs_lds + r * pitch + xi;
+                        float a = 0.0f;
+#pragma unroll
+                        for (int k = 0; k < KB; ++k)
+                            if (k < run) a = __builtin_fmaf(w[k], xs[k], a);
+                        acc[r] = a;
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < RSW_ROWS; ++r)
+                if (r < rg) out[(row0 + r) * out_len + n0 + o] = acc[r];
+        }
+        if (nv > 0) __syncthreads();                                // nobody reads the spans any more
+    }
+}
+
+template <int KB>
+inline auto rsw_pick(bool vec) {
+    return vec ? polyphase_wide_kernel<KB, true> : polyphase_wide_kernel<KB, false>;
+}
+
+static int launch_polyphase_wide(const float* x, long long rows, long long l_in, long long stride_r, const float* bank, const int* table,
+                                 int phases, int taps, int step, int span, int tile_log, long long n_out, long long out_len, float* out,
+                                 hipStream_t stream) {
+    const int pitch = (3 + span + taps + 3) & ~3;
+    const size_t bytes = 4 * (size_t)RSW_ROWS * (size_t)pitch;
+    if (bytes > (size_t)RS_LDS_BYTES) return TAC_E_UNSUPPORTED;
+    const long long tiles_per_row = (out_len + (1LL << tile_log) - 1) >> tile_log;
+    const long long groups = (rows + RSW_ROWS - 1) / RSW_ROWS;
+    const long long units = groups * tiles_per_row;
+    long long per_cu = (long long)(RS_LDS_BYTES / bytes);
+    per_cu = per_cu > 8 ? 8 : per_cu;
+    const long long blocks = persistent_blocks(units, 1, (long long)device_cu_count() * per_cu);
+    const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (stride_r & 3) == 0;
+    auto kern = taps <= 16 ? rsw_pick<16>(vec) : (taps <= 32 ? rsw_pick<32>(vec) : (taps <= 48 ? rsw_pick<48>(vec)
+                                                                                                  : rsw_pick<64>(vec)));
+    return launch_kernel(kern, blocks, RS_THREADS, bytes, stream, x, stride_r, l_in, rows, bank, table, phases, taps, step, span, pitch,
+                         tile_log, tiles_per_row, units, n_out, out_len, out);
+}
+
 }  // namespace tac
 
 extern "C" {
@@ -162,6 +296,21 @@ int tac_polyphase_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride
     return launch_kernel(kern, blocks, RS_THREADS, bytes, (hipStream_t)stream, x, (long long)stride_r, (long long)l_in, bank,
                          (const int*)table, (int)phases, (int)taps, (int)taps_min, (int)step, (int)off_min, (int)off_max,
                          tile_log, tiles_per_row, units, (long long)l_out, out);
+}
+
+int tac_polyphase_wide_f32(const float* x, int64_t rows, int64_t l_in, int64_t stride_r, const float* bank, const int32_t* table,
+                           int32_t phases, int32_t taps, int32_t step, int32_t span, int32_t tile, int64_t n_out, int64_t out_len,
+                           float* out, void* stream) {
+    using namespace tac;
+    if (!x || !bank || !table || !out) return TAC_E_INVALID;
+    if (rows <= 0 || l_in <= 0 || n_out <= 0 || out_len <= 0 || phases <= 0 || taps <= 0 || step <= 0 || span <= 0) return TAC_E_INVALID;
+    if (tile != 1024 && tile != 512 && tile != 256) return TAC_E_INVALID;
+    if (rows == 1) stride_r = 0;
+    if (rows > 1 && stride_r <= 0) return TAC_E_INVALID;
+    if (taps > RSW_MAX_TAPS || (long long)phases * taps > RSW_MAX_BANK || span > RSW_SPAN_MAX) return TAC_E_UNSUPPORTED;
+    const int tile_log = tile == 1024 ? 10 : (tile == 512 ? 9 : 8);
+    return launch_polyphase_wide(x, rows, l_in, stride_r, bank, (const int*)table, phases, taps, step, span, tile_log, n_out, out_len, out,
+                                 (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -33,7 +33,7 @@ from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
            'forced_align', 'merge_tokens', 'TokenSpan']
@@ -299,6 +299,50 @@ def resample(waveforms, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.9
     if args[0] == args[1]:
         return x
     return _call('resample', x, *args)
+
+
+_phase_advances = Bounded(64)
+
+
+def _phase_advance(n_fft, hop, like):
+    """``linspace(0, pi * hop, n_fft // 2 + 1)[:, None]``: the expected phase advance per hop of every bin, cached like the windows"""
+    if type(like) is not torch.Tensor or torch.compiler.is_compiling():
+        return torch.linspace(0, math.pi * hop, n_fft // 2 + 1, dtype=like.dtype, device=like.device)[..., None]
+    key = (n_fft, hop, str(like.device), like.dtype)
+    pa = _phase_advances.get(key)
+    if pa is None:
+        with torch.inference_mode(False):
+            pa = torch.linspace(0, math.pi * hop, n_fft // 2 + 1, dtype=like.dtype, device=like.device)[..., None]
+        _phase_advances[key] = pa
+    return pa
+
+
+def pitch_shift(waveform, sample_rate, n_steps, bins_per_octave=12, n_fft=512, win_length=None, hop_length=None, window=None):
+    """``(…, L) → (…, L)``: torchaudio's ``functional.pitch_shift`` — the pitch moved by ``n_steps`` of ``bins_per_octave`` to the
+    octave at unchanged duration.  With ``rate = 2 ** (-n_steps / bins_per_octave)``: ``stft`` (centred, reflect padding, periodic
+    Hann of ``win_length`` unless a window is given, ``hop_length = n_fft // 4``), ``phase_vocoder`` by ``rate``, ``istft`` to
+    ``round(L / rate)`` samples, then ``resample`` from ``int(sample_rate / rate)`` to ``sample_rate`` cut or zero-padded to ``L``.
+    Composed from the package's own ops, each with its gradient kernel; the last stage is ``tac_amd::resample_fit``: that pair
+    almost never reduces (16 kHz, 4 steps: 10079 : 8000), so on a HIP device it runs on the wide polyphase kernel, which takes
+    its taps from global memory and writes the ``L`` samples in the same launch (csrc/resample.hip)."""
+    x = _tensor(waveform, 'waveform')
+    rate, source = _augment.pitch_rates(sample_rate, n_steps, bins_per_octave)
+    if x.dim() < 1:
+        raise RuntimeError('pitch_shift: expected a tensor of shape (…, time), got a scalar')
+    if not x.is_floating_point():
+        raise RuntimeError('pitch_shift: expected a floating-point waveform, got %s' % x.dtype)
+    n_fft = int(n_fft)
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    win_length = n_fft if win_length is None else int(win_length)
+    length = x.shape[-1]
+    rows = x.reshape(-1, length)
+    spec = stft(rows, n_fft, hop, win_length, window, center=True, pad_mode='reflect', normalized=False, onesided=True)
+    stretched = phase_vocoder(spec, rate, _phase_advance(n_fft, hop, spec))
+    y = istft(stretched, n_fft, hop, win_length, window, length=int(round(length / rate)))
+    args = _resample.constants(source, sample_rate)
+    if args[0] != args[1]:                  # (equal rates, n_steps = 0: ``y`` has the L samples already)
+        y = _call('resample_fit', y, *args, length)
+    return y.reshape(x.shape)
 
 
 def kaldi_fbank(waveforms, blackman_coeff=0.42, dither=0.0, energy_floor=1.0, frame_length=25.0, frame_shift=10.0, high_freq=0.0,

@@ -404,6 +404,37 @@ class Resample(_ModuleNoStateBuffers):
             self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
 
 
+class PitchShift(_ModuleNoStateBuffers):
+    """``functional.pitch_shift`` as a layer (torchaudio's ``transforms.PitchShift``): ``(…, time)`` → ``(…, time)``, the pitch
+    moved by ``n_steps`` of ``bins_per_octave`` to the octave.  The window ``window_fn(win_length, **wkwargs)`` is a non-persistent
+    buffer; the compact polyphase banks of the last stage (forward and gradient) and their tile plans are built here, once."""
+
+    def __init__(self, sample_rate, n_steps, bins_per_octave=12, n_fft=512, win_length=None, hop_length=None,
+                 window_fn=torch.hann_window, wkwargs=None):
+        super(PitchShift, self).__init__()
+        self.sample_rate = sample_rate
+        self.n_steps = n_steps
+        self.bins_per_octave = bins_per_octave
+        self.n_fft = n_fft
+        self.win_length = win_length if win_length is not None else n_fft
+        self.hop_length = hop_length if hop_length is not None else self.n_fft // 4
+        self.register_buffer('window', window_fn(self.win_length) if wkwargs is None else window_fn(self.win_length, **wkwargs))
+        _, source = _augment.pitch_rates(sample_rate, n_steps, bins_per_octave, 'PitchShift')
+        args = _resample.constants(source, sample_rate)
+        if args[0] != args[1]:
+            from . import _hip
+            _hip.resample_wide_plan(_resample.bank(*args))
+            _hip.resample_wide_plan(_resample.adjoint_bank(*args))
+
+    def forward(self, waveform):
+        return F.pitch_shift(waveform, self.sample_rate, self.n_steps, self.bins_per_octave, self.n_fft, self.win_length,
+                             self.hop_length, self.window)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sample_rate={}, n_steps={}, bins_per_octave={}, n_fft={}, win_length={}, hop_length={})'.format(
+            self.sample_rate, self.n_steps, self.bins_per_octave, self.n_fft, self.win_length, self.hop_length)
+
+
 class LFilter(_ModuleNoStateBuffers):
     """``functional.lfilter`` as a layer: ``(…, time)`` → ``(…, time)``.  The two 1-D coefficient tensors are the non-persistent
     buffers ``a_coeffs`` / ``b_coeffs`` (kept in float64 unless given otherwise; they follow ``.to()`` — a change of dtype rounds
