@@ -940,6 +940,39 @@ int tac_polyphase_wide_f32(const float* x, int64_t rows, int64_t l_in, int64_t s
                            int32_t phases, int32_t taps, int32_t step, int32_t span, int32_t tile, int64_t n_out, int64_t out_len,
                            float* out, void* stream);
 
+/* (31) functional.vad / vad_start / Vad: torchaudio's SoX voice-activity detector behind the |X| rows of (2) (csrc/vad.hip).
+ *      mag: float[rows][n_frames][dft / 2 + 1], the frame-major rows tac_spectrogram_f32 writes at n_fft = dft, power 1, for the
+ *      measurement windows scaled by 2 / sqrt(mlen).  Per row, with S = N = 0 and t = 0, 1, … over the bins [s0, s1):
+ *        m = t / (1 + t) while t <= boot_max (every frame if boot_max < 0), else decay[0];   S = S m + |X_t| (1 - m);   d = S^2
+ *        m2 = 0 in those boot frames, else decay[2] where d > N and decay[4] elsewhere;      N = N m2 + d (1 - m2)
+ *        e = sqrt(max(0, d - nra N));  c = the dft / 2-point transform of e win at [s0, s1), zeros elsewhere
+ *        r = sum over q in [c0, c1) of |c_q|^2;   meas[row][t] = r > 0 ? max(0, 21 + log(r / (c1 - c0))) : 0
+ *      decay: HOST array of six floats, (smooth, 1 - smooth, up, 1 - up, down, 1 - down), the complements formed in float64 and
+ *      rounded once; win: DEVICE float[s1 - s0], the scaled cepstral window; tab: DEVICE float[dft / 2][2], the cosine and sine of 2 pi i / (dft / 2).
+ *      float32 throughout, every sum in a fixed order, no atomics: bit-identical from run to run and whatever the batch holds.  A
+ *      non-finite sample makes its row's measures 0 from that frame on.
+ *      tac_vad_decide_f32: groups of `channels` consecutive rows of meas.  Every row's mean = mean trig + meas[k] otrig over k; the
+ *      trigger frame k is the first at which a row's mean reaches level, i* the lowest such row; every row i >= i* searches
+ *      back from k (jT = jZ = n; for j < n with v = meas[i][k - j], 0 before frame 0: v >= level and j <= jT + gap sets jZ = jT =
+ *      j, else v == 0 and jT >= jZ sets jZ = j), flush = the largest min(n - 1, jZ), start[g] = max(0, (k - flush) period - pre),
+ *      triggered[g] = 1; a group that never triggers gets max(0, time - keep) and 0.  triggered: DEVICE bytes.
+ *      tac_vad_start_f32: both launches on the stream (meas: DEVICE scratch float[groups * channels][n_frames], all written); no
+ *      host wait.  tac_vad_plan: the bins a lane keeps, the parts of the partial transform and the LDS bytes of the measuring
+ *      launch, the longest search the deciding launch takes (n_search beyond it: TAC_E_UNSUPPORTED) and the workgroups per CU its
+ *      persistent grid is capped at; TAC_E_UNSUPPORTED where s1 - s0 exceeds 2048, c1 - c0 512 or the LDS 144 KiB.  dft a power of
+ *      two >= 16, 1 <= s0 < s1 <= dft / 2, 0 <= c0 < c1 <= dft / 4, TAC_E_INVALID otherwise. */
+int tac_vad_plan(int32_t dft, int32_t s0, int32_t s1, int32_t c0, int32_t c1, int32_t* bins_per_lane, int32_t* parts, int32_t* lds_bytes,
+                 int32_t* max_search, int32_t* blocks_per_cu);
+int tac_vad_measures_f32(const float* mag, int64_t rows, int64_t n_frames, int32_t dft, int32_t s0, int32_t s1, int32_t c0, int32_t c1,
+                         int32_t boot_max, const float* decay, float nra, const float* win, const float* tab, float* meas, void* stream);
+int tac_vad_decide_f32(const float* meas, int64_t groups, int64_t channels, int64_t n_frames, int64_t time, int32_t n_search, int32_t gap,
+                       int64_t period, int64_t pre, int64_t keep, float level, float trig, float otrig, int64_t* start, void* triggered,
+                       void* stream);
+int tac_vad_start_f32(const float* mag, int64_t groups, int64_t channels, int64_t n_frames, int64_t time, int32_t dft, int32_t s0, int32_t s1,
+                      int32_t c0, int32_t c1, int32_t boot_max, const float* decay, float nra, const float* win, const float* tab,
+                      int32_t n_search, int32_t gap, int64_t period, int64_t pre, int64_t keep, float level, float trig, float otrig,
+                      float* meas, int64_t* start, void* triggered, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

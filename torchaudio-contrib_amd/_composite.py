@@ -26,6 +26,7 @@ import torch.nn.functional as TF
 from . import _filters
 from . import _kaldi
 from . import _pitch
+from . import _vad
 from . import _beamform
 from ._bounded import Bounded
 
@@ -285,6 +286,75 @@ def detect_pitch_frequency(waveform, sample_rate, frame_time=1e-2, win_length=30
     rows = waveform.reshape(-1, waveform.shape[-1])
     freq = pitch_smooth(pitch_lags(pitch_nccf(rows, geo), geo), win_length, sample_rate)
     return freq.reshape(tuple(waveform.shape[:-1]) + (geo.n_out,))
+
+
+def vad_measures(waveform, p):
+    """``(…, time)`` → ``(…, T)``: the measures of ``vad`` for the ``_vad.Plan`` ``p`` in torch operators, vectorised over rows and
+    bins with one loop over the frames.  float64 input is measured in float64, every other dtype in float32 (the windows are the
+    float32 Hann values in both).  The CPU route of ``tac_amd::vad_measures`` and its announced composite route."""
+    dtype = torch.float64 if waveform.dtype == torch.float64 else torch.float32
+    time = waveform.shape[-1]
+    n_frames = _vad.frames(time, p)
+    x = waveform.reshape(-1, time).to(dtype)
+    meas = x.new_zeros((x.shape[0], n_frames))
+    if meas.numel() == 0:
+        return meas.reshape(tuple(waveform.shape[:-1]) + (n_frames,))
+    nb, nq = p.s1 - p.s0, p.c1 - p.c0
+    win = torch.hann_window(p.mlen, dtype=torch.float32, device=x.device).to(dtype) * (2.0 / math.sqrt(p.mlen))
+    win2 = torch.hann_window(nb, dtype=torch.float32, device=x.device).to(dtype) * (2.0 / math.sqrt(nb))
+    frames = x.unfold(-1, p.mlen, p.period)[:, :n_frames]
+    mag = torch.fft.rfft(frames * win, n=p.dft).abs()[..., p.s0:p.s1]                        # (rows, T, nb)
+    spec = x.new_zeros((x.shape[0], nb))
+    noise = x.new_zeros((x.shape[0], nb))
+    buf = x.new_zeros((x.shape[0], n_frames, p.dft // 2))
+    boot = 0
+    for t in range(n_frames):
+        m = boot / (1.0 + boot) if boot >= 0 else p.smooth
+        spec = spec * m + mag[:, t] * (1.0 - m)
+        d = spec * spec
+        m2 = torch.zeros_like(d) if boot >= 0 else torch.where(d > noise, d.new_tensor(p.up), d.new_tensor(p.down))
+        noise = noise * m2 + d * (1.0 - m2)
+        buf[:, t, p.s0:p.s1] = torch.sqrt(torch.clamp(d - p.nra * noise, min=0.0)) * win2   # (clamp keeps a NaN)
+        if boot >= 0:
+            boot = -1 if boot == p.boot_max else boot + 1
+    c = torch.fft.rfft(buf)[..., p.c0:p.c1]
+    r = (c.real * c.real + c.imag * c.imag).sum(-1)
+    meas = torch.where(r > 0, torch.clamp(21.0 + torch.log(r / nq), min=0.0), torch.zeros_like(r))
+    return meas.reshape(tuple(waveform.shape[:-1]) + (n_frames,))
+
+
+def vad_start(meas, p, time):
+    """``(groups, channels, T)`` measures → ``(start int64 (groups,), triggered bool (groups,))``: the decision of ``vad`` in torch
+    operators, vectorised over groups and channels, with one loop over the frames and one over the backward search; ``start`` is
+    clamped at 0.  The CPU route of ``tac_amd::vad_start`` and its announced composite route."""
+    groups, channels, n_frames = meas.shape
+    dev = meas.device
+    which = torch.arange(channels, device=dev)
+    mean = meas.new_zeros((groups, channels))
+    k = torch.zeros(groups, dtype=torch.int64, device=dev)
+    first = torch.zeros(groups, dtype=torch.int64, device=dev)
+    found = torch.zeros(groups, dtype=torch.bool, device=dev)
+    for t in range(n_frames):
+        mean = mean * p.trig + meas[:, :, t] * (1.0 - p.trig)
+        hit = mean >= p.level
+        new = hit.any(1) & ~found
+        k = torch.where(new, torch.full_like(k, t), k)
+        first = torch.where(new, torch.where(hit, which, channels).amin(1), first)
+        found = found | new
+    j_t = torch.full((groups, channels), p.n, dtype=torch.int64, device=dev)
+    j_z = j_t.clone()
+    for j in range(p.n if n_frames and channels else 0):
+        at = k - j
+        v = meas.gather(2, at.clamp(min=0)[:, None, None].expand(groups, channels, 1))[..., 0]
+        v = torch.where((at >= 0)[:, None], v, torch.zeros_like(v))
+        take = (v >= p.level) & (j <= j_t + p.gap)
+        zero = ~take & (v == 0) & (j_t >= j_z)
+        j_t = torch.where(take, torch.full_like(j_t, j), j_t)
+        j_z = torch.where(take | zero, torch.full_like(j_z, j), j_z)
+    flush = torch.where(which[None, :] >= first[:, None], j_z.clamp(max=p.n - 1), torch.zeros_like(j_z))
+    flush = flush.amax(1) if channels else k
+    start = torch.where(found, (k - flush) * p.period - p.pre, torch.full_like(k, time - p.keep))
+    return start.clamp(min=0), found
 
 
 def _complex(t):

@@ -1203,6 +1203,121 @@ def pitch_frequency(x, sample_rate, frame, max_lag, lag_min, win_length):
     return out.reshape(tuple(x.shape[:-1]) + (n_out,))
 
 
+# ----------------------------------------------------------------------------- vad / vad_start (csrc/vad.hip)
+_vad_tables = Bounded(16)
+
+
+def vad_limits(p):
+    """``(bins per lane, parts, LDS bytes, longest search, workgroups per CU)`` of the measuring launch for the ``_vad.Plan`` ``p``,
+    or None where ``tac_vad_plan`` declines its bins (more than 2048 spectrum bins, 512 cepstrum bins or 144 KiB of LDS)"""
+    out = [ctypes.c_int32(0) for _ in range(5)]
+    rc = _native.lib().tac_vad_plan(p.dft, p.s0, p.s1, p.c0, p.c1, *[ctypes.byref(v) for v in out])
+    if rc == _native.TAC_E_UNSUPPORTED:
+        return None
+    _native.check(rc, 'tac_vad_plan')
+    return tuple(v.value for v in out)
+
+
+def vad_max_search():
+    """the longest backward search (measures) ``tac_vad_decide_f32`` takes"""
+    out = ctypes.c_int32(0)
+    _native.lib().tac_vad_plan(16, 1, 2, 0, 1, None, None, None, ctypes.byref(out), None)
+    return out.value
+
+
+def vad_covers_dft(dft):
+    """the transform lengths ``tac_spectrogram_f32`` has an FFT kernel for, among the powers of two ``vad`` asks for"""
+    return fft_kernel_size(dft) or big_fft_size(dft)
+
+
+def _vad_device_tables(p, device):
+    """(measurement window ``2 / sqrt(mlen) hann(mlen)``, cepstral window ``2 / sqrt(nb) hann(nb)``, ``(cos, sin)(2 pi i / (dft / 2))`` as ``(dft / 2, 2)``) on
+    ``device`` as float32: the windows from torch's float32 Hann values, the table from float64 on the host, each rounded once;
+    cached per geometry and device"""
+    key = (p.mlen, p.dft, p.s0, p.s1, device)
+    hit = _vad_tables.get(key)
+    if hit is None:
+        with torch.inference_mode(False):
+            nb, half = p.s1 - p.s0, p.dft // 2
+            win = torch.hann_window(p.mlen, dtype=torch.float32) * (2.0 / math.sqrt(p.mlen))
+            win2 = torch.hann_window(nb, dtype=torch.float32) * (2.0 / math.sqrt(nb))
+            angle = torch.arange(half, dtype=torch.float64) * (2.0 * math.pi / half)
+            tab = torch.stack([torch.cos(angle), torch.sin(angle)], -1)
+            tab[half // 4, 0] = tab[3 * half // 4, 0] = tab[half // 2, 1] = 0.0     # (the zeros of both, exactly)
+            hit = (win.to(device), win2.to(device), tab.to(torch.float32).to(device))
+        _vad_tables[key] = hit
+    return hit
+
+
+def _vad_decay(p):
+    """the host array ``tac_vad_measures_f32`` takes: smooth, up and down with their complements, formed in float64"""
+    return (ctypes.c_float * 6)(p.smooth, 1.0 - p.smooth, p.up, 1.0 - p.up, p.down, 1.0 - p.down)
+
+
+def vad_magnitudes(x, p):
+    """``(…, time)`` float32 → the frame-major ``(rows, T, dft / 2 + 1)`` rows ``|X_t|`` of the measurement windows, one
+    ``tac_spectrogram_f32`` launch.  torch's framing puts a window of ``mlen`` in the middle of ``dft`` samples, the definition at
+    their front: the rows are copied once behind ``(dft - mlen) // 2`` zeros (and in front of the rest), which also makes any
+    layout dense — data movement by torch, like the padding of every centred STFT here."""
+    time = x.shape[-1]
+    left = (p.dft - p.mlen) // 2
+    rows = torch.nn.functional.pad(x.reshape(-1, time), (left, p.dft - p.mlen - left))
+    win = _vad_device_tables(p, x.device)[0]
+    spec = spectrogram(rows, win, p.dft, p.period, p.mlen, False, 'constant', False, True, 1.0, False, 1.0, 1e-10)
+    return spec.transpose(-2, -1)
+
+
+def vad_measures_of(mag, p):
+    """the frame-major ``(rows, T, dft / 2 + 1)`` rows of ``vad_magnitudes`` → float32 ``(rows, T)``: launch 2 alone,
+    ``tac_vad_measures_f32``"""
+    rows, n_frames = mag.shape[0], mag.shape[1]
+    _, win2, tab = _vad_device_tables(p, mag.device)
+    meas = _empty((rows, n_frames), device=mag.device)
+    _launch('tac_vad_measures_f32', mag.device, (meas,), _native.ptr(mag), rows, n_frames, p.dft, p.s0, p.s1, p.c0, p.c1,
+            min(p.boot_max, 2 ** 31 - 1), _vad_decay(p), p.nra, _native.ptr(win2), _native.ptr(tab), _native.ptr(meas))
+    return meas
+
+
+def vad_measures(x, p):
+    """``(…, time)`` float32 → float32 ``(…, T)``: launches 1 and 2 of ``vad``, ``tac_spectrogram_f32`` and ``tac_vad_measures_f32``"""
+    n_frames = (x.shape[-1] - p.mlen) // p.period + 1 if x.shape[-1] >= p.mlen else 0
+    rows = math.prod(x.shape[:-1])
+    if not (rows and n_frames):
+        return _empty(tuple(x.shape[:-1]) + (n_frames,), device=x.device)
+    return vad_measures_of(vad_magnitudes(x, p), p).reshape(tuple(x.shape[:-1]) + (n_frames,))
+
+
+def vad_decide(meas, p, time):
+    """float32 ``(groups, channels, T)`` → ``(start int64 (groups,), triggered bool (groups,))``: launch 3 alone, ``tac_vad_decide_f32``"""
+    groups, channels, n_frames = meas.shape
+    meas = meas.contiguous()
+    start = _empty((groups,), dtype=torch.int64, device=meas.device)
+    triggered = torch.empty((groups,), dtype=torch.bool, device=meas.device)
+    _launch('tac_vad_decide_f32', meas.device, (start,), _native.ptr(meas), groups, channels, n_frames, time, p.n, min(p.gap, p.n), p.period,
+            p.pre, p.keep, p.level, p.trig, 1.0 - p.trig, _native.ptr(start), _native.ptr(triggered))
+    return start, triggered
+
+
+def vad_start(x, p, groups, channels):
+    """``(…, time)`` float32 of ``groups * channels`` rows → ``(start int64 (groups,), triggered bool (groups,))``: one
+    ``tac_spectrogram_f32`` launch and one ``tac_vad_start_f32`` entry of two, all on the current stream; nothing waits for the host.
+    The float32 measures between the launches come from torch's allocator."""
+    time = x.shape[-1]
+    n_frames = (time - p.mlen) // p.period + 1 if time >= p.mlen else 0
+    if n_frames == 0:            # no measurement window fits: never triggered, nothing to launch
+        return (torch.full((groups,), max(time - p.keep, 0), dtype=torch.int64, device=x.device),
+                torch.zeros((groups,), dtype=torch.bool, device=x.device))
+    mag = vad_magnitudes(x, p)
+    _, win2, tab = _vad_device_tables(p, x.device)
+    meas = _empty((groups * channels, n_frames), device=x.device)
+    start = _empty((groups,), dtype=torch.int64, device=x.device)
+    triggered = torch.empty((groups,), dtype=torch.bool, device=x.device)
+    _launch('tac_vad_start_f32', x.device, (start, meas), _native.ptr(mag), groups, channels, n_frames, time, p.dft, p.s0, p.s1, p.c0, p.c1,
+            min(p.boot_max, 2 ** 31 - 1), _vad_decay(p), p.nra, _native.ptr(win2), _native.ptr(tab), p.n, min(p.gap, p.n), p.period, p.pre, p.keep, p.level, p.trig,
+            1.0 - p.trig, _native.ptr(meas), _native.ptr(start), _native.ptr(triggered))
+    return start, triggered
+
+
 # ----------------------------------------------------------------------------- psd / mvdr_weights_souden / apply_beamforming (csrc/beamform.hip)
 #: how the last calls got their spectrograms: read where they lay (frame-major views, channel slices, any 8-byte aligned pairs whose
 #: bins run faster than their frames), or copied into the frame-major layout first

@@ -178,6 +178,11 @@ PROTOTYPES = {
     'tac_griffinlim_prepare_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _F, _P, _P, _P]),
     'tac_griffinlim_update_f32': (_INT, [_P, _P, _P, _I64, _F, _P, _P]),
     'tac_polyphase_wide_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I64, _P, _P]),
+    'tac_vad_plan': (_INT, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    'tac_vad_measures_f32': (_INT, [_P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _P, _P, _P, _P]),
+    'tac_vad_decide_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I32, _I32, _I64, _I64, _I64, _F, _F, _F, _P, _P, _P]),
+    'tac_vad_start_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _P, _P, _I32, _I32, _I64, _I64,
+                                 _I64, _F, _F, _F, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -20,6 +20,7 @@ see them by name.
     tac_amd::add_noise          noise mixed into (…, L) at a signal-to-noise ratio, under a length mask (csrc/add_noise.hip)
     tac_amd::loudness           ITU-R BS.1770-4 gated loudness of (…, channels, L): K-weighting, blocks and gates (csrc/loudness.hip)
     tac_amd::detect_pitch_frequency   NCCF pitch of (…, L): correlations, peak choice and median in two launches (csrc/pitch.hip)
+    tac_amd::vad_measures, vad_start   the SoX voice-activity detector of (…, L): measures and trim point behind one spectrogram launch (csrc/vad.hip)
     tac_amd::psd, mvdr_weights_souden, apply_beamforming, mvdr_souden   mask-based MVDR beamforming over (…, C, F, T) (csrc/beamform.hip)
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
@@ -43,6 +44,7 @@ filterbank GEMM with the transposed bank, elementwise adjoints; the fused ops re
 saving it).  Gradients w.r.t. the window / filterbank, float64, CPU tensors and the remaining ops differentiate by
 re-evaluating the op with torch operators under ``enable_grad``.
 """
+import math
 import warnings
 
 import torch
@@ -54,6 +56,7 @@ from . import _hip as H
 from . import _hip64 as H64
 from . import _kaldi as K
 from . import _pitch as PT
+from . import _vad as VD
 from . import _beamform as BF
 from . import _resample as RS
 
@@ -1235,6 +1238,101 @@ def _pitch_fake(waveform, sample_rate, frame_time, win_length, freq_low, freq_hi
 # (no autograd: the result is piecewise constant in the waveform and carries no gradient, as torchaudio's carries none)
 _register('detect_pitch_frequency', '(Tensor waveform, int sample_rate, float frame_time, int win_length, float freq_low, '
           'float freq_high) -> Tensor', _pitch_cuda, _pitch_cpu, _pitch_fake, 1, differentiable=False)
+
+
+# ============================================================================= vad_measures, vad_start
+_VAD_ARGS = ', '.join('float %s' % name for name in VD.ARGS)
+
+
+def vad_reason(waveform, sample_rate, *args):
+    """why the launches of csrc/vad.hip (behind ``tac_spectrogram_f32``) do not take this call, or None"""
+    p = VD.check(waveform, sample_rate, *args)
+    reason = _hip_dtype(waveform)
+    if reason is None and any(st <= 0 for st, n in zip(waveform.stride(), waveform.shape) if n > 1):
+        reason = 'expanded or non-positive strides'
+    if reason is None and not H.vad_covers_dft(p.dft):
+        reason = 'measurement windows of %d samples (a transform of %d points is none of the spectrogram kernels\')' % (p.mlen, p.dft)
+    if reason is None and (p.period >= 2 ** 31 or waveform.shape[-1] >= 2 ** 40):
+        reason = 'a period of %d over %d samples (beyond the launches\' int32 hop)' % (p.period, waveform.shape[-1])
+    if reason is None and H.vad_limits(p) is None:
+        reason = '%d spectrum and %d cepstrum bins (beyond the registers and the LDS plan of the measuring launch)' % (p.s1 - p.s0, p.c1 - p.c0)
+    if reason is None and p.n > H.vad_max_search():
+        reason = 'a search of %d measures (the deciding launch takes %d or fewer)' % (p.n, H.vad_max_search())
+    return reason
+
+
+def _vad_dtype(waveform):
+    return torch.float64 if waveform.dtype == torch.float64 else torch.float32
+
+
+def _vad_measures_cuda(waveform, sample_rate, *args):
+    p = VD.check(waveform, sample_rate, *args)
+    n_frames = VD.frames(waveform.shape[-1], p)
+    if 0 in waveform.shape[:-1] or n_frames == 0:
+        return waveform.new_empty(tuple(waveform.shape[:-1]) + (n_frames,), dtype=_vad_dtype(waveform))      # nothing is launched
+    reason = vad_reason(waveform, sample_rate, *args)
+    if reason is not None:
+        _composite_route('vad_measures', reason)
+        return C.vad_measures(waveform, p)
+    return H.vad_measures(_f32(waveform), p)
+
+
+def _vad_measures_cpu(waveform, sample_rate, *args):
+    return C.vad_measures(waveform, VD.check(waveform, sample_rate, *args))
+
+
+def _vad_measures_fake(waveform, sample_rate, *args):
+    p = VD.plan(sample_rate, *args)
+    return waveform.new_empty(tuple(waveform.shape[:-1]) + (VD.frames(waveform.shape[-1], p),), dtype=_vad_dtype(waveform))
+
+
+def _vad_start_empty(waveform, p, lead, channels):
+    """the result without a row to measure: no group at all, or (``joint='all'``) a group of no channel, which never triggers"""
+    if 0 in lead:
+        return waveform.new_empty(lead, dtype=torch.int64), waveform.new_empty(lead, dtype=torch.bool)
+    return (torch.full(lead, max(waveform.shape[-1] - p.keep, 0), dtype=torch.int64, device=waveform.device),
+            torch.zeros(lead, dtype=torch.bool, device=waveform.device))
+
+
+def _vad_start_composite(waveform, p, lead, channels):
+    meas = C.vad_measures(waveform, p)
+    start, triggered = C.vad_start(meas.reshape(math.prod(lead), channels, meas.shape[-1]), p, waveform.shape[-1])
+    return start.reshape(lead), triggered.reshape(lead)
+
+
+def _vad_start_cuda(waveform, sample_rate, *rest):
+    args, joint = rest[:-1], rest[-1]
+    p = VD.check(waveform, sample_rate, *args)
+    lead, channels = VD.groups(waveform.shape, joint)
+    if 0 in lead or channels == 0:
+        return _vad_start_empty(waveform, p, lead, channels)                  # nothing is launched
+    reason = vad_reason(waveform, sample_rate, *args)
+    if reason is not None:
+        _composite_route('vad_start', reason)
+        return _vad_start_composite(waveform, p, lead, channels)
+    start, triggered = H.vad_start(_f32(waveform), p, math.prod(lead), channels)
+    return start.reshape(lead), triggered.reshape(lead)
+
+
+def _vad_start_cpu(waveform, sample_rate, *rest):
+    args, joint = rest[:-1], rest[-1]
+    p = VD.check(waveform, sample_rate, *args)
+    lead, channels = VD.groups(waveform.shape, joint)
+    if 0 in lead or channels == 0:
+        return _vad_start_empty(waveform, p, lead, channels)
+    return _vad_start_composite(waveform, p, lead, channels)
+
+
+def _vad_start_fake(waveform, sample_rate, *rest):
+    lead, _ = VD.groups(waveform.shape, rest[-1])
+    return waveform.new_empty(lead, dtype=torch.int64), waveform.new_empty(lead, dtype=torch.bool)
+
+
+# (no autograd: the measures feed a decision and the result is an index)
+_register('vad_measures', '(Tensor waveform, int sample_rate, %s) -> Tensor' % _VAD_ARGS, _vad_measures_cuda, _vad_measures_cpu,
+          _vad_measures_fake, 1, differentiable=False)
+_register('vad_start', '(Tensor waveform, int sample_rate, %s, str joint) -> (Tensor, Tensor)' % _VAD_ARGS, _vad_start_cuda, _vad_start_cpu,
+          _vad_start_fake, 1, differentiable=False)
 
 
 # ============================================================================= psd, mvdr_weights_souden, apply_beamforming, mvdr_souden

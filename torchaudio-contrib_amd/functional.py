@@ -15,6 +15,7 @@ produces (physically frame-major, logically ``(*, channel, freq, time[, 2])``).
 """
 import dataclasses
 import math
+import warnings
 
 import torch
 
@@ -24,6 +25,7 @@ from . import _ops
 from . import _filters
 from . import _kaldi
 from . import _pitch
+from . import _vad
 from . import _beamform
 from . import _resample
 from . import _specaug
@@ -36,7 +38,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
-           'forced_align', 'merge_tokens', 'TokenSpan']
+           'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start']
 
 _call = _ops.call
 
@@ -712,6 +714,69 @@ def detect_pitch_frequency(waveform, sample_rate, frame_time=1e-2, win_length=30
     _pitch.check(x, sample_rate, frame_time, win_length, freq_low, freq_high)
     # (detached: the op is registered without autograd and its result is piecewise constant)
     return _call('detect_pitch_frequency', x.detach(), sample_rate, float(frame_time), win_length, float(freq_low), float(freq_high))
+
+
+def vad_start(waveform, sample_rate, trigger_level=7.0, trigger_time=0.25, search_time=1.0, allowed_gap=0.25, pre_trigger_time=0.0,
+              boot_time=0.35, noise_up_time=0.1, noise_down_time=0.01, noise_reduction_amount=1.35, measure_freq=20.0,
+              measure_duration=None, measure_smooth_time=0.4, hp_filter_freq=50.0, lp_filter_freq=6000.0, hp_lifter_freq=150.0,
+              lp_lifter_freq=2000.0, joint='all'):
+    """``(…, time)`` → ``(start int64, triggered bool)`` on the waveform's device: the sample at which ``vad`` would cut, and
+    whether the detector triggered at all, with no host read.  The batched form torchaudio lacks: ``joint='all'`` takes every
+    leading dimension as a channel of ONE group (torchaudio's grouping; 0-d results), ``'channel'`` takes axis -2 as the channels
+    (results of shape ``waveform.shape[:-2]``), ``'none'`` every row on its own (``waveform.shape[:-1]``).  A group that never
+    triggers gets ``start = max(0, time - keep)`` and ``triggered = False``.  The definition is ``vad``'s."""
+    x = _tensor(waveform, 'waveform')
+    args = _vad.resolve((trigger_level, trigger_time, search_time, allowed_gap, pre_trigger_time, boot_time, noise_up_time,
+                         noise_down_time, noise_reduction_amount, measure_freq, measure_duration, measure_smooth_time, hp_filter_freq,
+                         lp_filter_freq, hp_lifter_freq, lp_lifter_freq))
+    _vad.check(x, sample_rate, *args)
+    _vad.groups(x.shape, joint)
+    # (detached: the op is registered without autograd and its result is an index)
+    return _call('vad_start', x.detach(), sample_rate, *args, joint)
+
+
+def vad(waveform, sample_rate, trigger_level=7.0, trigger_time=0.25, search_time=1.0, allowed_gap=0.25, pre_trigger_time=0.0,
+        boot_time=0.35, noise_up_time=0.1, noise_down_time=0.01, noise_reduction_amount=1.35, measure_freq=20.0, measure_duration=None,
+        measure_smooth_time=0.4, hp_filter_freq=50.0, lp_filter_freq=6000.0, hp_lifter_freq=150.0, lp_lifter_freq=2000.0):
+    """``(…, time)`` → ``(…, time - start)``: torchaudio's ``functional.vad``, the SoX voice-activity detector that trims everything
+    before the first speech.  As in torchaudio every leading dimension is a channel of one decision (more than two dimensions get
+    its warning), and the result is the slice ``waveform[..., start:]`` — a view.
+
+    With ``mlen = int(sample_rate (measure_duration or 2 / measure_freq) + 0.5)``, ``period = int(sample_rate / measure_freq + 0.5)``
+    and ``dft`` the power of two >= max(16, mlen), frame ``t`` of a row is ``x[t period : t period + mlen]``, ``T = 1 + (time - mlen)
+    // period`` of them.  Per row and spectrum bin in ``[s0, s1)`` the modulus ``|X_t|`` of the frame times ``2 / sqrt(mlen)
+    hann(mlen)`` is smoothed (``S = S m + |X_t| (1 - m)``, ``m = boot / (1 + boot)`` while booting, then ``exp(-1 / (measure_smooth_time
+    measure_freq))``), its power ``d = S^2`` tracked by the noise estimate ``N`` (up with ``noise_up_time``, down with
+    ``noise_down_time``, equal to ``d`` while booting), ``e = sqrt(max(0, d - noise_reduction_amount N))`` windowed and transformed
+    (``dft / 2`` points), and the power of its cepstrum bins ``[c0, c1)`` gives ``meas[t] = max(0, 21 + log(r / (c1 - c0)))`` (0 for
+    ``r`` not above 0, a NaN included).  A row's decayed mean of the measures reaching ``trigger_level`` triggers its group at
+    frame ``k``; every channel from the lowest triggering one searches back over ``n = ceil(search_time measure_freq)`` measures
+    for where the speech began, ``flush`` is the furthest any of them gets, and ``start = (k - flush) period - pre``
+    (``_vad.plan`` holds every integer; DESIGN §3.28 the full statement).  A group that never triggers keeps its last ``keep =
+    pre + n period + mlen`` samples.
+
+    ONE deviation from torchaudio: a negative ``start`` (``pre_trigger_time`` or the search reaching before sample 0, or a short
+    input that never triggers) is clamped at 0 — the whole waveform is kept — where Python's slice would wrap around and keep
+    the tail.
+
+    ``ValueError``, before anything touches a device, for an empty spectrum or cepstrum range (``s1 <= s0``, ``c1 <= c0``), a
+    non-positive ``sample_rate``, ``measure_freq`` or time constant, a non-floating tensor and a tensor without a time axis.
+
+    float32 on a HIP device (float16 / bfloat16 widened) is three launches on the stream behind one padded copy of the rows:
+    ``tac_spectrogram_f32`` for the ``|X_t|``, and the measuring and the deciding launch of csrc/vad.hip (one entry,
+    ``tac_vad_start_f32``).  The length of the result depends on the data, so ``start`` is read on the host ONCE, after the third
+    launch: that is the op's only synchronisation (``vad_start`` has none).  float64, expanded or non-positive strides, a ``dft``
+    the spectrogram kernels do not take, bins beyond the measuring launch's plan and searches beyond 1024 measures take
+    ``_composite.vad_measures`` / ``_composite.vad_start`` (also the CPU path), announced with ``CompositeRouteWarning`` on a device."""
+    x = _tensor(waveform, 'waveform')
+    if x.dim() > 2:
+        warnings.warn('Expected input tensor dimension of 1 for single channel or 2 for multi-channel. Got %d instead. Batch '
+                      'semantics is not supported. Please refer to https://github.com/pytorch/audio/issues/1348 and '
+                      'https://github.com/pytorch/audio/issues/1468.' % x.dim())
+    start, _ = vad_start(x, sample_rate, trigger_level, trigger_time, search_time, allowed_gap, pre_trigger_time, boot_time,
+                         noise_up_time, noise_down_time, noise_reduction_amount, measure_freq, measure_duration, measure_smooth_time,
+                         hp_filter_freq, lp_filter_freq, hp_lifter_freq, lp_lifter_freq, 'all')
+    return x[..., int(start):]          # (the one host read)
 
 
 def psd(specgram, mask=None, normalize=True, eps=1e-10):

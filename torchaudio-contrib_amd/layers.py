@@ -19,6 +19,7 @@ from . import _hip
 from . import _lazy
 from . import _ops
 from . import _pitch
+from . import _vad
 from . import _beamform
 from . import _resample
 from . import _specaug
@@ -680,6 +681,31 @@ class PitchFrequency(_ModuleNoStateBuffers):
     def __repr__(self):
         return self.__class__.__name__ + '(sample_rate={}, frame_time={}, win_length={}, freq_low={}, freq_high={})'.format(
             self.sample_rate, self.frame_time, self.win_length, self.freq_low, self.freq_high)
+
+
+class Vad(_ModuleNoStateBuffers):
+    """``functional.vad`` as a layer (torchaudio's ``transforms.Vad``, its constructor): ``forward(waveform)`` maps ``(…, time)`` to
+    ``(…, time - start)``, everything before the first speech trimmed.  No buffers."""
+
+    def __init__(self, sample_rate, trigger_level=7.0, trigger_time=0.25, search_time=1.0, allowed_gap=0.25, pre_trigger_time=0.0,
+                 boot_time=0.35, noise_up_time=0.1, noise_down_time=0.01, noise_reduction_amount=1.35, measure_freq=20.0,
+                 measure_duration=None, measure_smooth_time=0.4, hp_filter_freq=50.0, lp_filter_freq=6000.0, hp_lifter_freq=150.0,
+                 lp_lifter_freq=2000.0):
+        super(Vad, self).__init__()
+        self.sample_rate = sample_rate
+        self.args = (trigger_level, trigger_time, search_time, allowed_gap, pre_trigger_time, boot_time, noise_up_time, noise_down_time,
+                     noise_reduction_amount, measure_freq, measure_duration, measure_smooth_time, hp_filter_freq, lp_filter_freq,
+                     hp_lifter_freq, lp_lifter_freq)
+        _vad.plan(sample_rate, *_vad.resolve(self.args))                  # (every error but the tensor's)
+        for name, value in zip(_vad.ARGS, self.args):
+            setattr(self, name, value)
+
+    def forward(self, waveform):
+        return F.vad(waveform, self.sample_rate, *self.args)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sample_rate={}, {})'.format(
+            self.sample_rate, ', '.join('{}={}'.format(name, value) for name, value in zip(_vad.ARGS, self.args)))
 
 
 class PSD(_ModuleNoStateBuffers):
