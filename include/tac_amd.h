@@ -973,6 +973,34 @@ int tac_vad_start_f32(const float* mag, int64_t groups, int64_t channels, int64_
                       int32_t n_search, int32_t gap, int64_t period, int64_t pre, int64_t keep, float level, float trig, float otrig,
                       float* meas, int64_t* start, void* triggered, void* stream);
 
+/* (32) functional.simulate_rir_ism / simulate_rir_ism_batch / SimulateRirIsm: image-source room impulse responses (csrc/rir.hip).
+ *      room, source: float[rooms][dims]; mic: float[rooms][mics][dims]; dims 2 or 3.  absorption: float[rooms or 1][n_band][2 dims], the
+ *      walls as x_lo, x_hi, y_lo, y_hi, z_lo, z_hi; absorption_stride: floats between two rooms' coefficients, 0 where all share one
+ *      set.  images: DEVICE int8[n_img][dims], the integer vectors X with sum |X_d| <= max_order in cartesian_prod order (last axis
+ *      fastest).  tap_table: DEVICE float[filter_length][2], cos and sin of pi m / 2P for m = -P … P, P = filter_length / 2.
+ *      Per (room, image, band b, microphone c), in float64: loc_d = room_d (X_d + 1) - source_d where X_d is odd, else room_d X_d +
+ *      source_d; att_b = prod_d tr_lo^|floor(X_d / 2)| tr_hi^|floor((X_d + 1) / 2)| with tr = sqrt(1 - absorption); dist = |loc - mic_c|;
+ *      delay = dist sample_rate / sound_speed; di = ceil(delay); f = di - delay.  (att_b / dist) w(m + f), w(x) = sinc(x) cos^2(pi x /
+ *      2P) for |x| <= P and 0 beyond, is added to sample di + m + P of the raw response of (room, b, c) in image order.
+ *      out: float[rooms][n_band][mics][length], samples [start, start + length) of the raw responses: ONE launch, every element
+ *      written once, zeros included; float32 taps from f, att / dist, sinpi(f) and (cos, sin)(pi f / 2P) rounded once; no atomics,
+ *      the same bits every run and whatever else the batch holds.  dist = 0 gives its (room, channel) rows the inf and NaN of the
+ *      formulas and no other row any.  TAC_E_UNSUPPORTED for n_band above 8, filter_length below 3 or above 255, max_order above 32
+ *      (tac_rir_limits reports the three and the shortest tile); an even filter_length is TAC_E_INVALID.
+ *      tile: the samples of a row a wave owns, a power of two from 128 to 2048 (1024 above 2 bands, 512 above 4), or 0 for the
+ *      launch's own choice, which tac_rir_tile reports for rooms * mics rows of `length` samples: the longest tile that leaves 16
+ *      waves a CU.  The result's bits do not depend on it.
+ *      tac_rir_span_f32: out[0] (DEVICE int64) = max di + filter_length - P over every (room, image, microphone), one launch of one
+ *      workgroup; any odd filter_length. */
+int tac_rir_limits(int32_t* min_tile, int32_t* max_bands, int32_t* max_filter_length, int32_t* max_order);
+int tac_rir_tile(int64_t rows, int64_t length, int32_t n_band, int32_t* tile, int32_t* max_tile);
+int tac_rir_ism_f32(const float* room, const float* source, const float* mic, const float* absorption, int64_t absorption_stride,
+                    const void* images, const float* tap_table, int64_t rooms, int64_t mics, int32_t dims, int32_t n_band, int64_t n_img,
+                    int32_t max_order, int64_t start, int64_t length, int32_t filter_length, double sound_speed, double sample_rate,
+                    int32_t tile, float* out, void* stream);
+int tac_rir_span_f32(const float* room, const float* source, const float* mic, const void* images, int64_t rooms, int64_t mics, int32_t dims,
+                     int64_t n_img, int32_t filter_length, double sound_speed, double sample_rate, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,14 +20,14 @@ from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filte
                          compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid,
                          add_noise, speed, pitch_shift, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
                          apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, forced_align,
-                         merge_tokens, TokenSpan, vad, vad_start)
+                         merge_tokens, TokenSpan, vad, vad_start, simulate_rir_ism, simulate_rir_ism_batch)
 from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
                      MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis,
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,
                      KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment,
                      AddNoise, Speed, SpeedPerturbation, PitchShift, Loudness, PitchFrequency, PSD, SoudenMVDR, MVDR,
-                     RTFMVDR, RNNTLoss, Vad)
+                     RTFMVDR, RNNTLoss, Vad, SimulateRirIsm)
 from . import distributed
 from . import kaldi
 

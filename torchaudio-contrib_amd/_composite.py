@@ -1086,3 +1086,71 @@ def forced_align(log_probs, targets, input_lengths, target_lengths, blank):
     paths = torch.where(keep, paths, torch.full((), -1, dtype=torch.long, device=dev)).to(targets.dtype)
     scores = torch.where(keep, scores, torch.full((), float('nan'), dtype=scores.dtype, device=dev))
     return paths, scores
+
+
+# ============================================================================= rir_ism, rir_ism_span
+def _rir_geometry(room, source, mic_array, max_order, sound_speed, sample_rate):
+    """float64 ``(X (I, D) int64, dist (B, I, M), delay (B, I, M), di (B, I, M) float64)`` of the image sources: the definition's
+    steps 1 and 2, every product and sum a torch operator of its own"""
+    from . import _rir
+    D = room.shape[-1]
+    X = _rir.images(max_order, D, room.device).to(torch.int64)
+    r, s, m = room.double()[:, None, :], source.double()[:, None, :], mic_array.double()
+    Xf = X.double()[None]
+    loc = torch.where((X % 2 == 1)[None], r * (Xf + 1.0) - s, r * Xf + s)                       # (B, I, D)
+    diff = loc[:, :, None, :] - m[:, None, :, :]                                                # (B, I, M, D)
+    sq = diff[..., 0] * diff[..., 0]
+    for d in range(1, D):
+        sq = sq + diff[..., d] * diff[..., d]
+    dist = torch.sqrt(sq)
+    delay = dist * float(sample_rate) / float(sound_speed)
+    return X, dist, delay, torch.ceil(delay)
+
+
+def rir_ism(room, source, mic_array, absorption, max_order, start, length, delay_filter_length, sound_speed, sample_rate):
+    """``(B, D)``, ``(B, D)``, ``(B, M, D)``, ``(B or 1, n_band, 2 D)`` → ``(B, n_band, M, length)``: samples ``[start, start + length)`` of the
+    raw image-source responses, the definition of ``functional.simulate_rir_ism`` in torch operators — evaluated in float64
+    whatever the inputs' dtype, summed with ``index_add_`` and rounded once (float32 unless an input is float64)."""
+    out_dtype = torch.float64 if torch.float64 in (room.dtype, source.dtype, mic_array.dtype, absorption.dtype) else torch.float32
+    B, D = room.shape
+    M = mic_array.shape[1]
+    nb = absorption.shape[1]
+    P, L = delay_filter_length // 2, delay_filter_length
+    X, dist, delay, di = _rir_geometry(room, source, mic_array, max_order, sound_speed, sample_rate)
+    tr = torch.sqrt(1.0 - absorption.double())                                                  # (B or 1, nb, 2 D)
+    e_lo = torch.div(X, 2, rounding_mode='floor').abs()
+    e_hi = torch.div(X + 1, 2, rounding_mode='floor').abs()
+    att = None
+    for d in range(D):
+        term = tr[:, :, None, 2 * d] ** e_lo[None, None, :, d].double() * tr[:, :, None, 2 * d + 1] ** e_hi[None, None, :, d].double()
+        att = term if att is None else att * term                                               # (B or 1, nb, I)
+    amp = att[:, :, :, None] / dist[:, None, :, :]                                              # (B, nb, I, M)
+    f = di - delay
+    mm = torch.arange(-P, P + 1, dtype=torch.float64, device=room.device)
+    x = mm + f[..., None]                                                                       # (B, I, M, L)
+    if P > 0:
+        hann = torch.where(x.abs() <= P, 0.5 * (1.0 + torch.cos(TWO_PI * x / (2.0 * P))), torch.zeros_like(x))
+    else:
+        hann = torch.ones_like(x)
+    w = torch.sinc(x) * hann
+    vals = amp[..., None] * w[:, None]                                                          # (B, nb, I, M, L)
+    # a non-finite delay (NaN inputs) has no sample to add to: it adds nothing
+    fine = torch.isfinite(di) & (di < 4.0e18)
+    pos = torch.where(fine, di, torch.zeros_like(di)).to(torch.int64)[..., None] + torch.arange(L, device=room.device) - start
+    keep = fine[..., None] & (pos >= 0) & (pos < length)
+    pos = torch.where(keep, pos, torch.full_like(pos, length))                                  # (the dropped taps: one spare sample a row)
+    rows = (torch.arange(B, device=room.device)[:, None, None, None, None] * nb
+            + torch.arange(nb, device=room.device)[None, :, None, None, None]) * M + torch.arange(M, device=room.device)[None, None, None, :, None]
+    index = (rows * (length + 1) + pos[:, None]).reshape(-1)
+    vals = torch.where(keep[:, None].expand_as(vals), vals, torch.zeros_like(vals))
+    flat = torch.zeros(B * nb * M * (length + 1), dtype=torch.float64, device=room.device)
+    flat = flat.index_add(0, index, vals.reshape(-1))
+    return flat.reshape(B, nb, M, length + 1)[..., :length].to(out_dtype)
+
+
+def rir_ism_span(room, source, mic_array, max_order, delay_filter_length, sound_speed, sample_rate):
+    """int64 scalar on the inputs' device: ``max(delay_i) + L - P`` over the batch, the natural length of the responses"""
+    _, _, _, di = _rir_geometry(room, source, mic_array, max_order, sound_speed, sample_rate)
+    fine = torch.isfinite(di) & (di < 4.0e18)
+    top = torch.where(fine, di, torch.zeros_like(di)).max().to(torch.int64)
+    return top + (delay_filter_length - delay_filter_length // 2)

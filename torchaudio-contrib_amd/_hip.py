@@ -17,6 +17,7 @@ import torch
 from . import _kaldi
 from . import _native
 from . import _resample
+from . import _rir
 from ._bounded import Bounded
 
 _lock = threading.Lock()
@@ -1316,6 +1317,53 @@ def vad_start(x, p, groups, channels):
             min(p.boot_max, 2 ** 31 - 1), _vad_decay(p), p.nra, _native.ptr(win2), _native.ptr(tab), p.n, min(p.gap, p.n), p.period, p.pre, p.keep, p.level, p.trig,
             1.0 - p.trig, _native.ptr(meas), _native.ptr(start), _native.ptr(triggered))
     return start, triggered
+
+
+# ----------------------------------------------------------------------------- simulate_rir_ism (csrc/rir.hip)
+_rir_limits = None               # (constants of the library: asked for once)
+
+
+def rir_limits():
+    """``(shortest tile, most bands, longest delay filter, highest order)`` of ``tac_rir_ism_f32``"""
+    global _rir_limits
+    if _rir_limits is None:
+        out = [ctypes.c_int32(0) for _ in range(4)]
+        _native.check(_native.lib().tac_rir_limits(*[ctypes.byref(v) for v in out]), 'tac_rir_limits')
+        _rir_limits = tuple(v.value for v in out)
+    return _rir_limits
+
+
+def rir_tile(rows, length, n_band):
+    """``(tile, longest tile)``: the samples of a row a wave owns in a launch of ``rows`` rows of ``length`` samples and ``n_band`` bands, as
+    ``tac_rir_ism_f32`` chooses it, and the longest it takes at that many bands"""
+    out = [ctypes.c_int32(0) for _ in range(2)]
+    _native.check(_native.lib().tac_rir_tile(rows, length, n_band, *[ctypes.byref(v) for v in out]), 'tac_rir_tile')
+    return tuple(v.value for v in out)
+
+
+def rir_ism(room, source, mic_array, absorption, max_order, start, length, delay_filter_length, sound_speed, sample_rate, tile=0):
+    """contiguous float32 ``(B, D)``, ``(B, D)``, ``(B, M, D)``, ``(B or 1, n_band, 2 D)`` → float32 ``(B, n_band, M, length)``: samples
+    ``[start, start + length)`` of the raw responses, ONE launch of ``tac_rir_ism_f32`` that writes every element.  ``tile``: the samples of
+    a row a wave owns (a power of two, ``rir_tile``'s range), 0 for the launch's own choice; the bits do not depend on it."""
+    B, D = room.shape
+    M, nb = mic_array.shape[1], absorption.shape[1]
+    img = _rir.images(max_order, D, room.device)
+    tab = _rir.tap_table(delay_filter_length, room.device)
+    out = _empty((B, nb, M, length), device=room.device)
+    _launch('tac_rir_ism_f32', room.device, (out,), _native.ptr(room), _native.ptr(source), _native.ptr(mic_array), _native.ptr(absorption),
+            nb * 2 * D if absorption.shape[0] > 1 else 0, _native.ptr(img), _native.ptr(tab), B, M, D, nb, img.shape[0], max_order, start,
+            length, delay_filter_length, float(sound_speed), float(sample_rate), tile, _native.ptr(out))
+    return out
+
+
+def rir_ism_span(room, source, mic_array, max_order, delay_filter_length, sound_speed, sample_rate):
+    """→ int64 scalar on the device, ``max(delay_i) + L - P`` over the batch: one launch of ``tac_rir_span_f32``, nothing read on the host"""
+    B, D = room.shape
+    img = _rir.shell(max_order, D, room.device)              # (the farthest image is in the two outermost shells)
+    out = _empty((), dtype=torch.int64, device=room.device)
+    _launch('tac_rir_span_f32', room.device, (out,), _native.ptr(room), _native.ptr(source), _native.ptr(mic_array), _native.ptr(img), B,
+            mic_array.shape[1], D, img.shape[0], delay_filter_length, float(sound_speed), float(sample_rate), _native.ptr(out))
+    return out
 
 
 # ----------------------------------------------------------------------------- psd / mvdr_weights_souden / apply_beamforming (csrc/beamform.hip)

@@ -183,6 +183,10 @@ PROTOTYPES = {
     'tac_vad_decide_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I32, _I32, _I64, _I64, _I64, _F, _F, _F, _P, _P, _P]),
     'tac_vad_start_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _P, _F, _P, _P, _I32, _I32, _I64, _I64,
                                  _I64, _F, _F, _F, _P, _P, _P, _P]),
+    'tac_rir_limits': (_INT, [_P, _P, _P, _P]),
+    'tac_rir_tile': (_INT, [_I64, _I64, _I32, _P, _P]),
+    'tac_rir_ism_f32': (_INT, [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _I64, _I32, _I64, _I64, _I32, _D, _D, _I32, _P, _P]),
+    'tac_rir_span_f32': (_INT, [_P, _P, _P, _P, _I64, _I64, _I32, _I64, _I32, _D, _D, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -21,6 +21,7 @@ see them by name.
     tac_amd::loudness           ITU-R BS.1770-4 gated loudness of (…, channels, L): K-weighting, blocks and gates (csrc/loudness.hip)
     tac_amd::detect_pitch_frequency   NCCF pitch of (…, L): correlations, peak choice and median in two launches (csrc/pitch.hip)
     tac_amd::vad_measures, vad_start   the SoX voice-activity detector of (…, L): measures and trim point behind one spectrogram launch (csrc/vad.hip)
+    tac_amd::rir_ism, rir_ism_span   image-source room impulse responses of a batch of rooms: raw responses in one launch, and their natural length (csrc/rir.hip)
     tac_amd::psd, mvdr_weights_souden, apply_beamforming, mvdr_souden   mask-based MVDR beamforming over (…, C, F, T) (csrc/beamform.hip)
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
@@ -1333,6 +1334,80 @@ _register('vad_measures', '(Tensor waveform, int sample_rate, %s) -> Tensor' % _
           _vad_measures_fake, 1, differentiable=False)
 _register('vad_start', '(Tensor waveform, int sample_rate, %s, str joint) -> (Tensor, Tensor)' % _VAD_ARGS, _vad_start_cuda, _vad_start_cpu,
           _vad_start_fake, 1, differentiable=False)
+
+
+# ============================================================================= rir_ism, rir_ism_span
+_RIR_GEOMETRY = 'int max_order, int delay_filter_length, float sound_speed, float sample_rate'
+
+
+def rir_reason(room, source, mic_array, absorption, max_order, delay_filter_length):
+    """why the launch of csrc/rir.hip does not take this call, or None"""
+    tensors = (room, source, mic_array) + (() if absorption is None else (absorption,))
+    reason = None
+    for t in tensors:                      # (no widening here: the geometry is read as given, and half has no room for it)
+        if t.dtype != torch.float32:
+            reason = 'dtype %s' % str(t.dtype).replace('torch.', '')
+            break
+    if reason is None and any(st <= 0 for t in tensors for st, n in zip(t.stride(), t.shape) if n > 1):
+        reason = 'expanded or non-positive strides'
+    _, max_bands, max_taps, top_order = H.rir_limits()
+    if reason is None and absorption is not None and absorption.shape[1] > max_bands:
+        reason = '%d absorption bands (the kernel takes %d or fewer)' % (absorption.shape[1], max_bands)
+    if reason is None and not 3 <= delay_filter_length <= max_taps:
+        reason = 'a delay filter of %d taps (the kernel takes 3 to %d)' % (delay_filter_length, max_taps)
+    if reason is None and max_order > top_order:
+        reason = 'max_order %d (the kernel takes %d or lower)' % (max_order, top_order)
+    return reason
+
+
+def _rir_out_dtype(*tensors):
+    return torch.float64 if any(t.dtype == torch.float64 for t in tensors) else torch.float32
+
+
+def _rir_cuda(room, source, mic_array, absorption, max_order, start, length, delay_filter_length, sound_speed, sample_rate):
+    _same_device('rir_ism', room, source, mic_array, absorption)
+    B, M, nb = room.shape[0], mic_array.shape[1], absorption.shape[1]
+    if B == 0 or M == 0:
+        return room.new_empty((B, nb, M, length), dtype=_rir_out_dtype(room, source, mic_array, absorption))     # nothing is launched
+    reason = rir_reason(room, source, mic_array, absorption, max_order, delay_filter_length)
+    if reason is not None:
+        _composite_route('rir_ism', reason)
+        return C.rir_ism(room, source, mic_array, absorption, max_order, start, length, delay_filter_length, sound_speed, sample_rate)
+    return H.rir_ism(room.contiguous(), source.contiguous(), mic_array.contiguous(), absorption.contiguous(), max_order, start, length,
+                     delay_filter_length, sound_speed, sample_rate)
+
+
+def _rir_cpu(room, source, mic_array, absorption, max_order, start, length, delay_filter_length, sound_speed, sample_rate):
+    B, M, nb = room.shape[0], mic_array.shape[1], absorption.shape[1]
+    if B == 0 or M == 0:
+        return room.new_empty((B, nb, M, length), dtype=_rir_out_dtype(room, source, mic_array, absorption))
+    return C.rir_ism(room, source, mic_array, absorption, max_order, start, length, delay_filter_length, sound_speed, sample_rate)
+
+
+def _rir_fake(room, source, mic_array, absorption, max_order, start, length, delay_filter_length, sound_speed, sample_rate):
+    return room.new_empty((room.shape[0], absorption.shape[1], mic_array.shape[1], length),
+                          dtype=_rir_out_dtype(room, source, mic_array, absorption))
+
+
+def _rir_span_cuda(room, source, mic_array, max_order, delay_filter_length, sound_speed, sample_rate):
+    _same_device('rir_ism_span', room, source, mic_array)
+    reason = rir_reason(room, source, mic_array, None, 0, 3)            # (the span has no limit on order or taps)
+    if reason is not None:
+        _composite_route('rir_ism_span', reason)
+        return C.rir_ism_span(room, source, mic_array, max_order, delay_filter_length, sound_speed, sample_rate)
+    return H.rir_ism_span(room.contiguous(), source.contiguous(), mic_array.contiguous(), max_order, delay_filter_length, sound_speed,
+                          sample_rate)
+
+
+def _rir_span_fake(room, source, mic_array, max_order, delay_filter_length, sound_speed, sample_rate):
+    return room.new_empty((), dtype=torch.int64)
+
+
+# (no gradient kernel: the backward pass differentiates the definition in torch operators, announced, as loudness's does)
+_register('rir_ism', '(Tensor room, Tensor source, Tensor mic_array, Tensor absorption, int max_order, int start, int length, '
+          'int delay_filter_length, float sound_speed, float sample_rate) -> Tensor', _rir_cuda, _rir_cpu, _rir_fake, 4)
+_register('rir_ism_span', '(Tensor room, Tensor source, Tensor mic_array, %s) -> Tensor' % _RIR_GEOMETRY, _rir_span_cuda, C.rir_ism_span,
+          _rir_span_fake, 3, differentiable=False)
 
 
 # ============================================================================= psd, mvdr_weights_souden, apply_beamforming, mvdr_souden

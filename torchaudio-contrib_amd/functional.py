@@ -26,6 +26,7 @@ from . import _filters
 from . import _kaldi
 from . import _pitch
 from . import _vad
+from . import _rir
 from . import _beamform
 from . import _resample
 from . import _specaug
@@ -38,7 +39,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
-           'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start']
+           'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch']
 
 _call = _ops.call
 
@@ -777,6 +778,76 @@ def vad(waveform, sample_rate, trigger_level=7.0, trigger_time=0.25, search_time
                          noise_up_time, noise_down_time, noise_reduction_amount, measure_freq, measure_duration, measure_smooth_time,
                          hp_filter_freq, lp_filter_freq, hp_lifter_freq, lp_lifter_freq, 'all')
     return x[..., int(start):]          # (the one host read)
+
+
+def _simulate_rir(what, room, source, mic_array, max_order, absorption, output_length, delay_filter_length, center_frequency,
+                  sound_speed, sample_rate, batch):
+    room, source, mic_array = _tensor(room, 'room'), _tensor(source, 'source'), _tensor(mic_array, 'mic_array')
+    D = _rir.check(room, source, mic_array, max_order, delay_filter_length, output_length, sound_speed, sample_rate, batch)
+    a = _rir.absorption_of(absorption, room, D, batch)
+    centres = _rir.centres_of(center_frequency, a.shape[1])
+    if not batch:
+        room, source, mic_array = room[None], source[None], mic_array[None]
+    P, L = delay_filter_length // 2, delay_filter_length
+    geometry = (max_order, L, float(sound_speed), float(sample_rate))
+    if output_length is None:
+        if 0 in mic_array.shape[:2]:
+            output_length = L - P
+        else:
+            output_length = int(_call('rir_ism_span', room.detach(), source.detach(), mic_array.detach(), *geometry))    # (the one host read)
+    if centres is None:
+        out = _call('rir_ism', room, source, mic_array, a, max_order, P, output_length, L, float(sound_speed), float(sample_rate))[:, 0]
+    else:
+        raw = _call('rir_ism', room, source, mic_array, a, max_order, 0, P + output_length + _rir.FILTER_TAPS // 2, L, float(sound_speed),
+                    float(sample_rate))
+        filters = _rir.band_filters(centres, sample_rate, raw.device, raw.dtype)[:, None, :]                # (n_band, 1, 511)
+        if batch:
+            out = torch.sum(fftconvolve(raw, filters[None], mode='same'), dim=1)[..., P:P + output_length]
+        else:
+            out = torch.sum(fftconvolve(raw[0], filters, mode='same'), dim=0)[None, ..., P:P + output_length]
+    return out if batch else out[0]
+
+
+def simulate_rir_ism(room, source, mic_array, max_order, absorption, output_length=None, delay_filter_length=81, center_frequency=None,
+                     sound_speed=343.0, sample_rate=16000.0):
+    """``room (D,)``, ``source (D,)``, ``mic_array (M, D)``, ``D`` 2 or 3 → ``(M, output_length)``: torchaudio's
+    ``prototype.functional.simulate_rir_ism``, the room impulse responses of a shoebox room by the image-source method.
+    ``absorption`` is a float, ``(2 D,)`` or ``(n_band, 2 D)``, the walls as ``[x_lo, x_hi, y_lo, y_hi, z_lo, z_hi]``; more than one band
+    needs ``center_frequency`` of as many entries.
+
+    With ``P = delay_filter_length // 2`` and ``L = 2 P + 1``: every integer vector ``X`` with ``sum |X_d| <= max_order`` (in
+    ``torch.cartesian_prod``'s order) is an image at ``room (X + 1) - source`` per axis where ``X`` is odd, else ``room X + source``, attenuated per
+    band by ``prod_d tr_lo^|floor(X_d / 2)| tr_hi^|floor((X_d + 1) / 2)|``, ``tr = sqrt(1 - absorption)``.  For a microphone at ``dist`` it has
+    ``amp = att / dist``, ``delay = dist sample_rate / sound_speed``, ``delay_i = ceil(delay)``, ``f = delay_i - delay``, and adds ``amp w(m + f)``,
+    ``m = -P … P``, to sample ``delay_i + m + P`` of the raw response, ``w(x) = sinc(x) (1 + cos(2 pi x / 2P)) / 2`` for ``|x| <= P`` and 0 beyond.
+    One band: the result is ``raw[P : P + output_length]`` (``None``: ``max(delay_i) + L - P`` samples, which costs the call's one host
+    read; with ``output_length`` given nothing waits for the host).  Several bands: the per-band raw responses go through the band
+    filters of ``_rir.band_filters`` with this package's ``fftconvolve(mode='same')``, are summed with ``torch.sum`` and cut the same way.
+
+    TWO deviations from torchaudio: the raw responses are zero-extended, so the band filters' tails run on past the natural
+    length where torchaudio cuts them; and a microphone exactly on an image gives that (room, channel) the infinities and NaNs
+    of the formulas, and no other row any.
+
+    ``ValueError`` for a room that is not 1-D with 2 or 3 entries, a source of another shape, a ``mic_array`` that is not ``(M, D)``, an even
+    ``delay_filter_length``, and several bands without a ``center_frequency`` of matching length.
+
+    float32 on a HIP device: ONE launch of csrc/rir.hip for the whole raw response (``tac_amd::rir_ism``): geometry in float64 on
+    chip, float32 taps without cancellation, image-order sums in the LDS, no atomics, the same bits every run.  float64, expanded or
+    non-positively strided inputs, more than 8 bands, filters beyond 255 taps, orders beyond 32 and the backward pass take
+    ``_composite.rir_ism`` (float64 torch operators rounded once; also the CPU path), announced with ``CompositeRouteWarning`` on a
+    device."""
+    return _simulate_rir('simulate_rir_ism', room, source, mic_array, max_order, absorption, output_length, delay_filter_length,
+                         center_frequency, sound_speed, sample_rate, False)
+
+
+def simulate_rir_ism_batch(room, source, mic_array, max_order, absorption, output_length=None, delay_filter_length=81,
+                           center_frequency=None, sound_speed=343.0, sample_rate=16000.0):
+    """``room (B, D)``, ``source (B, D)``, ``mic_array (B, M, D)`` → ``(B, M, output_length)``: ``simulate_rir_ism`` for a batch of rooms in the same
+    one launch — the form torchaudio lacks.  A batch of 1 gives the bits of the single call, and an entry's result does not depend
+    on the rest of the batch.  ``absorption`` is a float, ``(2 D,)`` or ``(n_band, 2 D)`` shared by the batch (a 2-D tensor is always that),
+    or ``(B, n_band, 2 D)`` per room (``(B, 1, 2 D)`` for one band).  ``output_length=None`` is the longest natural length of the batch."""
+    return _simulate_rir('simulate_rir_ism_batch', room, source, mic_array, max_order, absorption, output_length, delay_filter_length,
+                         center_frequency, sound_speed, sample_rate, True)
 
 
 def psd(specgram, mask=None, normalize=True, eps=1e-10):

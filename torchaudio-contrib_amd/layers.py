@@ -708,6 +708,29 @@ class Vad(_ModuleNoStateBuffers):
             self.sample_rate, ', '.join('{}={}'.format(name, value) for name, value in zip(_vad.ARGS, self.args)))
 
 
+class SimulateRirIsm(_ModuleNoStateBuffers):
+    """``functional.simulate_rir_ism`` / ``simulate_rir_ism_batch`` as a layer: ``forward(room, source, mic_array)`` maps a room ``(D,)`` to
+    ``(M, output_length)`` and a batch of rooms ``(B, D)`` to ``(B, M, output_length)``.  No buffers."""
+
+    def __init__(self, max_order, absorption, output_length=None, delay_filter_length=81, center_frequency=None, sound_speed=343.0,
+                 sample_rate=16000.0):
+        super(SimulateRirIsm, self).__init__()
+        if isinstance(delay_filter_length, bool) or not isinstance(delay_filter_length, int) or delay_filter_length % 2 != 1:
+            raise ValueError('SimulateRirIsm: delay_filter_length must be odd, got %r' % (delay_filter_length,))
+        self.max_order, self.absorption, self.output_length = max_order, absorption, output_length
+        self.delay_filter_length, self.center_frequency = delay_filter_length, center_frequency
+        self.sound_speed, self.sample_rate = sound_speed, sample_rate
+
+    def forward(self, room, source, mic_array):
+        fn = F.simulate_rir_ism_batch if room.dim() == 2 else F.simulate_rir_ism
+        return fn(room, source, mic_array, self.max_order, self.absorption, self.output_length, self.delay_filter_length,
+                  self.center_frequency, self.sound_speed, self.sample_rate)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(max_order={}, output_length={}, delay_filter_length={}, sound_speed={}, sample_rate={})'.format(
+            self.max_order, self.output_length, self.delay_filter_length, self.sound_speed, self.sample_rate)
+
+
 class PSD(_ModuleNoStateBuffers):
     """``functional.psd`` as a layer (torchaudio's ``transforms.PSD``): ``forward(specgram, mask=None)`` maps ``(…, channel, freq,
     time)`` to ``(…, freq, channel, channel)``.  With ``multi_mask`` the mask is ``(…, channel, freq, time)`` and is averaged over
