@@ -13,8 +13,9 @@ ceil(units / per_block)`` (the workgroups an unbounded grid would have) and ``gr
 
 Beside each function stand the source file (under the package's ``csrc/``) and the launcher expressions it restates, verbatim:
 tests/test_grid_rules_cpu.py looks every one of them up in that file, so that a retuned cap fails there and not by a GPU test that
-silently stopped wrapping.  Where ``per_cu`` depends on the LDS bytes of a bank (``tac_polyphase_f32``) the upper bound 8 is taken:
-a smaller real grid only wraps more often.
+silently stopped wrapping.  Where ``per_cu`` depends on the LDS bytes of a bank (``tac_polyphase_f32``) it is the launcher's own,
+from the ``bytes`` formula restated in tests/polyphase_rules.py (``lds_variant``), as is the tile: 2 .. 8 workgroups per CU for the
+banks used here, at 1024, 512 and 256 outputs per tile.
 
 ``shapes(cus)`` gives every size tests/test_grid_wrap_gpu.py uses on a device of ``cus`` compute units; ``launches_of(cus, case)`` computes
 ``(work, grid)`` from those sizes and ``assert_wraps`` holds them to the case's rule (the GPU tests call it before they launch).  The
@@ -27,6 +28,7 @@ arguments and the route its launcher records, ``chain_shapes(cus)`` (a part of `
 two rounds — three long rows, and many rows of the fewest frames the launcher takes."""
 import math
 
+import polyphase_rules as PR
 import resample_rules as RS
 
 CU_COUNTS = (256, 304)
@@ -82,13 +84,20 @@ POLYPHASE = ('resample.hip', (
     'persistent_blocks(units, 1, (long long)device_cu_count() * per_cu)',
     'for (long long u = blockIdx.x; u < units; u += gridDim.x) {',
 ))
-POLYPHASE_TILE = 1024                   # outputs per tile for every bank used here (the GPU tests assert it: _hip.resample_tile)
+POLYPHASE_TILE = 1024                   # outputs per tile for the short banks (the GPU tests assert it: _hip.resample_tile)
 POLYPHASE_PER_CU = 8                    # the upper bound of per_cu
 
 
-def polyphase_launch(cus, rows, l_out, tile=POLYPHASE_TILE):
-    """a unit is a tile of ``tile`` outputs of one row"""
-    return _launch(rows * ceil_div(l_out, tile), 1, POLYPHASE_PER_CU * cus)
+def polyphase_form(orig, new, adjoint=False):
+    """(tile, per_cu) of the launch with the forward or the adjoint bank of ``orig -> new`` at the default filter"""
+    v = PR.lds_variant(PR.geometry(orig, new, adjoint=adjoint), True)
+    return v[0], v[4]
+
+
+def polyphase_launch(cus, rows, l_out, tile=POLYPHASE_TILE, per_cu=POLYPHASE_PER_CU):
+    """a unit is a tile of ``tile`` outputs of one row; ``per_cu`` the launcher's, from the LDS bytes of the bank"""
+    assert 1 <= per_cu <= POLYPHASE_PER_CU
+    return _launch(rows * ceil_div(l_out, tile), 1, per_cu * cus)
 
 
 # ----------------------------------------------------------------------------- tac_dct_rows_f32
@@ -803,14 +812,18 @@ def _two_rounds_rows(grid, per_row=1):
 
 
 def _resample_case(cus, orig, new, adjoint=False):
-    """five base rows whose OUTPUT is three tiles and a remainder (tests/test_resample_gpu.py's longest length); the gradient runs
-    the adjoint bank from that output back to the input, whose tiles then count"""
-    length = 3 * POLYPHASE_TILE * orig // new + orig // 2 + 5
+    """five base rows whose OUTPUT is three tiles and a remainder (tests/test_resample_gpu.py's longest length) at the tile the
+    forward bank takes; the gradient runs the adjoint bank from that output back to the input, whose tiles — of the adjoint bank's
+    size — then count: at least three of those and a remainder too.  The grid is the real one: ``per_cu`` of the bank that runs."""
+    tile, per_cu = polyphase_form(orig, new, adjoint)
+    length = 3 * polyphase_form(orig, new)[0] * orig // new + orig // 2 + 5
+    if adjoint:
+        length = max(length, 3 * tile + orig // 2 + 5)
     n_out = RS.out_length(length, orig, new)
-    per_row = ceil_div(length if adjoint else n_out, POLYPHASE_TILE)
-    rows = _two_rounds_rows(POLYPHASE_PER_CU * cus, per_row)
+    per_row = ceil_div(length if adjoint else n_out, tile)
+    rows = _two_rounds_rows(per_cu * cus, per_row)
     return dict(entry='tac_polyphase_f32', rule=TWO_ROUNDS, orig=orig, new=new, length=length, n_out=n_out, rows=rows,
-                adjoint=adjoint, floats=rows * (max(length, n_out) + 3))
+                adjoint=adjoint, tile=tile, per_cu=per_cu, floats=rows * (max(length, n_out) + 3))
 
 
 def _dct_case(cus, n_in, n_out, rows, gradient=False):
@@ -852,9 +865,12 @@ def shapes(cus):
     for tag, length in (('16-byte loads', LFILTER_TILE + 36), ('float loads', LFILTER_TILE + 37), ('full last tile', 2 * LFILTER_TILE)):
         out['lfilter, ' + tag] = dict(entry='tac_lfilter_f32', rule=TWO_ROUNDS, rows=rows, length=length, floats=rows * (length + 1))
     # 2. resample
-    for orig, new in ((2, 1), (3, 2), (160, 441)):
+    # 2. resample: 1024 outputs per tile; 12:1 takes 512 and 16:1 256 (2 - 3 times the LDS per workgroup: fewer per CU), and the
+    # gradient of 1:12 runs the bank of 12:1
+    for orig, new in ((2, 1), (3, 2), (160, 441), (12, 1), (16, 1)):
         out['resample %d:%d' % (orig, new)] = _resample_case(cus, orig, new)
     out['resample 3:2 gradient'] = _resample_case(cus, 3, 2, adjoint=True)
+    out['resample 1:12 gradient'] = _resample_case(cus, 1, 12, adjoint=True)
     # 3. dct
     for n_in, n_out in ((40, 13), (256, 128)):
         for rows in (1, 3):
@@ -898,7 +914,7 @@ def launches_of(cus, c):
     if e == 'tac_lfilter_f32':
         return [lfilter_launch(cus, c['rows'])]
     if e == 'tac_polyphase_f32':
-        return [polyphase_launch(cus, c['rows'], c['length'] if c['adjoint'] else c['n_out'])]
+        return [polyphase_launch(cus, c['rows'], c['length'] if c['adjoint'] else c['n_out'], c['tile'], c['per_cu'])]
     if e == 'tac_dct_rows_f32':
         k_in, k_out = (c['n_out'], c['n_in']) if c['gradient'] else (c['n_in'], c['n_out'])
         return [dct_launch(cus, c['rows'], c['n_frames'], k_in, k_out)]
@@ -919,7 +935,7 @@ def launches_of(cus, c):
 def can_be_odd(c):
     """False where every row is an even number of units and the remainder over two rounds is even with it"""
     if c['entry'] == 'tac_polyphase_f32':
-        return ceil_div(c['length'] if c['adjoint'] else c['n_out'], POLYPHASE_TILE) % 2 == 1
+        return ceil_div(c['length'] if c['adjoint'] else c['n_out'], c['tile']) % 2 == 1
     return True
 
 

@@ -25,7 +25,7 @@ def tac():
 def test_every_shape_wraps_its_grid(cus):
     cases = G.shapes(cus)
     chain = G.chain_shapes(cus)                      # (the STFT chain's part: tests/test_chain_wrap_rules_cpu.py holds it to more)
-    assert len(cases) == 20 + len(chain) and all(cases[name] == c for name, c in chain.items())
+    assert len(cases) == 23 + len(chain) and all(cases[name] == c for name, c in chain.items())
     for name, c in cases.items():
         ratio = G.assert_wraps(cus, name, c)
         print('%d CUs, %s: work / grid %.3f, largest tensor %.0f MB' % (cus, name, ratio, 4e-6 * c['floats']))
@@ -47,7 +47,12 @@ def test_the_sizes_on_a_256_cu_part():
     """the figures the rules were written down with"""
     s = G.shapes(256)
     assert s['lfilter, float loads']['rows'] == 2 * 512 + 5 and s['lfilter, float loads']['length'] == 16384 + 37
-    assert s['resample 160:441']['n_out'] > 3 * 1024 and s['resample 160:441']['rows'] * 4 == 2 * 2048 + 4
+    assert s['resample 160:441']['n_out'] > 3 * 1024 and s['resample 160:441']['rows'] * 4 == 2 * 5 * 256 + 4    # 5 per CU: 31 KB of LDS
+    assert s['resample 2:1']['rows'] * 4 == 2 * 2048 + 4 and (s['resample 2:1']['tile'], s['resample 2:1']['per_cu']) == (1024, 8)
+    assert (s['resample 12:1']['tile'], s['resample 12:1']['per_cu'], s['resample 12:1']['rows'] * 4) == (512, 6, 2 * 6 * 256 + 4)
+    assert (s['resample 16:1']['tile'], s['resample 16:1']['per_cu']) == (256, 8) and 3 * 256 < s['resample 16:1']['n_out'] < 4 * 256
+    g = s['resample 1:12 gradient']
+    assert (g['tile'], g['per_cu']) == (512, 6) and 3 * 512 < g['length'] < 4 * 512 and G.polyphase_form(1, 12) == (1024, 8)
     assert G.dct_tile(40, 13) == (64, 16384) and G.dct_tile(256, 128)[0] == 16 and G.DCT_LDS_BYTES // G.dct_tile(256, 128)[1] == 1
     assert s['dct 256 x 128, 1 row']['n_frames'] == (2 * 256 + 4) * 16 + 1
     assert [G.mac_tile(p) for p in (4, 8, 16, 17)] == [16, 32, 64, 80]
@@ -68,6 +73,10 @@ def test_quoted_launcher_expressions_are_in_the_sources(tac):
         key = tac._resample.constants(orig, new)
         assert tac._hip.resample_tile(tac._resample.bank(*key)) == G.POLYPHASE_TILE
     assert tac._hip.resample_tile(tac._resample.adjoint_bank(*tac._resample.constants(3, 2))) == G.POLYPHASE_TILE
+    for orig, new in ((12, 1), (16, 1), (1, 12), (160, 441)):
+        key = tac._resample.constants(orig, new)
+        for adjoint, bank in ((False, tac._resample.bank(*key)), (True, tac._resample.adjoint_bank(*key))):
+            assert tac._hip.resample_tile(bank) == G.polyphase_form(orig, new, adjoint)[0]
 
 
 # ----------------------------------------------------------------------------- big batch = repeated base rows, on the CPU route
@@ -90,7 +99,7 @@ def test_repeated_rows_repeat_the_result_lfilter(tac):
 
 
 def test_repeated_rows_repeat_the_result_resample(tac):
-    for orig, new in ((2, 1), (3, 2), (160, 441)):
+    for orig, new in ((2, 1), (3, 2), (160, 441), (12, 1), (16, 1), (1, 12)):
         base = resample_rules.waveform((G.BASE_ROWS, 311), seed=orig)
         small = tac.resample(torch.from_numpy(base), orig, new)
         resample_rules.assert_within(small, base, orig, new, 'resample %d:%d' % (orig, new))

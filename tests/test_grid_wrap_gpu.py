@@ -27,6 +27,7 @@ import grad_rules as gr
 import grid_rules as G
 import istft_rules as IR
 import lfilter_rules as LR
+import polyphase_rules as PR
 import resample_rules as RR
 
 pytestmark = pytest.mark.gpu
@@ -185,14 +186,16 @@ def resample_once(tac_, xt, orig, new, what):
     return got
 
 
-@pytest.mark.parametrize('orig,new', [(2, 1), (3, 2), (160, 441)])
+@pytest.mark.parametrize('orig,new', [(2, 1), (3, 2), (160, 441), (12, 1), (16, 1)])
 def test_resample_tiles_beyond_the_grid(tac, cus, orig, new):
-    """(2, 1): one phase and a skewed span; (3, 2): phases, no skew; (160, 441): phases, skew and a large bank"""
+    """(2, 1): one phase and a skewed span; (3, 2): phases, no skew; (160, 441): phases, skew and a large bank; (12, 1) and
+    (16, 1): 512 and 256 outputs per tile on the grid of their own workgroups per CU"""
     c = wrapping(cus, 'resample %d:%d' % (orig, new))
     rows, length = c['rows'], c['length']
     key = tac._resample.constants(orig, new)
-    assert tac._hip.resample_tile(tac._resample.bank(*key)) == G.POLYPHASE_TILE and tac._hip.resample_covers(*key)
-    assert 3 * G.POLYPHASE_TILE < c['n_out'] < 4 * G.POLYPHASE_TILE
+    assert c['tile'] == PR.pinned_tile(orig, new)
+    assert tac._hip.resample_tile(tac._resample.bank(*key)) == c['tile'] and tac._hip.resample_covers(*key)
+    assert 3 * c['tile'] < c['n_out'] < 4 * c['tile']
     base = RR.waveform((G.BASE_ROWS, length), seed=1000 * orig + new)
     ref, bound = RR.reference(base, orig, new)
     what = 'resample %d:%d, %d rows of %d' % (orig, new, rows, length)
@@ -208,14 +211,14 @@ def test_resample_tiles_beyond_the_grid(tac, cus, orig, new):
         got = resample_once(tac, xt, orig, new, what + ', ' + tag)
         assert same_bits(got, repeat_rows(small, rows)), '%s, %s: a row depends on where in the batch it stands' % (what, tag)
     assert forms == {False, True}, 'both load forms'
-    print('%s: worst |err| / bound %.3f' % (what, worst))
+    print('%s, tile %d, %d per CU: worst |err| / bound %.3f' % (what, c['tile'], c['per_cu'], worst))
 
 
-def test_resample_gradient_tiles_beyond_the_grid(tac, cus):
-    orig, new = 3, 2
-    c = wrapping(cus, 'resample 3:2 gradient')
+def resample_gradient_beyond_the_grid(tac, cus, orig, new):
+    c = wrapping(cus, 'resample %d:%d gradient' % (orig, new))
     rows, length, n_out = c['rows'], c['length'], c['n_out']
-    assert tac._hip.resample_tile(tac._resample.adjoint_bank(*tac._resample.constants(orig, new))) == G.POLYPHASE_TILE
+    assert c['tile'] == PR.pinned_tile(orig, new, adjoint=True) and length > 3 * c['tile']
+    assert tac._hip.resample_tile(tac._resample.adjoint_bank(*tac._resample.constants(orig, new))) == c['tile']
     g = RR.waveform((G.BASE_ROWS, n_out), seed=7)
     aref, abound = RR.adjoint_reference(g, length, orig, new)
 
@@ -230,9 +233,19 @@ def test_resample_gradient_tiles_beyond_the_grid(tac, cus):
         return gx
 
     small = gradient(G.BASE_ROWS)
-    worst = RR.assert_close(small, aref, abound, 'resample 3:2 gradient: the base rows')
+    worst = RR.assert_close(small, aref, abound, 'resample %d:%d gradient: the base rows' % (orig, new))
     assert same_bits(gradient(rows), repeat_rows(small, rows)), 'a row of the gradient depends on where in the batch it stands'
-    print('resample 3:2 gradient, %d rows of %d: worst |err| / bound %.3f' % (rows, n_out, worst))
+    print('resample %d:%d gradient, %d rows of %d, tile %d, %d per CU: worst |err| / bound %.3f' % (
+        orig, new, rows, n_out, c['tile'], c['per_cu'], worst))
+
+
+def test_resample_gradient_tiles_beyond_the_grid(tac, cus):
+    resample_gradient_beyond_the_grid(tac, cus, 3, 2)
+
+
+def test_resample_gradient_narrow_tiles_beyond_the_grid(tac, cus):
+    """the gradient of 1:12 runs the bank of 12:1 at 512 outputs per tile"""
+    resample_gradient_beyond_the_grid(tac, cus, 1, 12)
 
 
 # ----------------------------------------------------------------------------- 3. dct

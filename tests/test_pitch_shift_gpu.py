@@ -4,7 +4,12 @@
 Reference and bound of the resampling: tests/resample_rules.py through tests/pitch_shift_rules.py — the float64 sum per output sample
 and, per element, ``(K_n + 2) * 2^-24 * sum |h64| |x|``; every element is checked.  A reference is computed once per case and shared
 by the layouts: three dense rows, one row, and six rows (a partial second row group) that are ``x[:, 1:]`` of a padded buffer —
-4-byte aligned only, a row stride that is no multiple of four."""
+4-byte aligned only, a row stride that is no multiple of four.
+
+``test_wide_variants_within_the_bound`` walks the table of tests/polyphase_rules.py: every instantiation
+``polyphase_wide_kernel<KB, VEC>`` at every tile public arguments reach (tests/test_polyphase_rules_cpu.py holds the table to the
+census), for the forward and for the adjoint bank, each asserted through the restated launcher rule before the launch; a fourth
+layout there — six rows a multiple of four floats apart — gives 16-byte loads with more than one row of a group whatever the length."""
 import warnings
 
 import numpy as np
@@ -12,6 +17,7 @@ import pytest
 import torch
 
 import pitch_shift_rules as PS
+import polyphase_rules as PR
 import resample_rules as R
 
 pytestmark = pytest.mark.gpu
@@ -110,6 +116,84 @@ def test_wide_kernel_within_the_bound(tac, case):
         assert tuple(gx.shape) == (rows, length), what
         worst_adj = max(worst_adj, R.assert_close(gx, aref[:rows], abound[:rows], 'gradient, ' + what))
     print('resample_fit %s: worst |err| / bound %.3f forward, %.3f adjoint' % (case_id(case), worst, worst_adj))
+
+
+# ----------------------------------------------------------------------------- every bucket of K, every tile
+def sixteen_byte_rows(x):
+    return x.data_ptr() % 16 == 0 and (x.shape[0] == 1 or x.stride(0) % 4 == 0)
+
+
+def aligned(x):
+    """the rows a multiple of four floats apart in a NaN-filled buffer: 16-byte loads whatever the length, with every row of
+    a group staged behind the first (``r * pitch``)"""
+    rows, length = x.shape
+    store = torch.full((rows, length + ((-length) % 4 or 4)), float('nan'), device='cuda')
+    store[:, :length] = dev(x)
+    return store[:, :length]
+
+
+VARIANT_LAYOUTS = LAYOUTS + (('6 rows a multiple of four floats apart', 6, aligned),)
+
+
+@pytest.mark.parametrize('case', PR.WIDE_CASES, ids=PR.case_id)
+def test_wide_variants_within_the_bound(tac, case):
+    """Inputs long enough for three tiles and a remainder of the forward launch (``n_out`` outputs at the forward bank's tile) AND
+    of the gradient's (``length`` outputs at the adjoint bank's), with ``out_len`` natural, cut and zero-padded; and inputs whose
+    natural length is about one tile with ``out_len`` one tile minus one / exactly / plus one.  Forward and gradient of every
+    layout; the gradient at the cut ``out_len`` (tests/test_polyphase_sweeps_gpu.py draws the others)."""
+    orig, new, kw = case
+    key = tac._resample.constants(orig, new, **product_kw(kw))
+    banks = tac._resample.bank(*key), tac._resample.adjoint_bank(*key)
+    fwd, adj = (PR.wide_variant(b, True) for b in banks)
+    assert fwd is not None and adj is not None and tac._hip.resample_fit_covers(key, 1000, 1)
+    assert fwd[:2] == PR.wide_variant(PR.case_geometry(case), True)[:2] and adj[:2] == PR.wide_variant(PR.case_geometry(case, True), True)[:2]
+    assert all(tac._hip.resample_wide_plan(b)[1] == v[0] for b, v in zip(banks, (fwd, adj)))
+    lds = tac._hip.resample_covers(*key)                    # (8:1, 16:1 and back: the natural out_len would take the LDS kernel)
+    long = max(3 * fwd[0] * orig // new, 3 * adj[0]) + (fwd[0] // 3) * orig // new + 5
+    one = fwd[0] * orig // new
+    worst = worst_adj = 0.0
+    loads, grad_loads = set(), set()
+    for length in (long, one):
+        n_out = R.out_length(length, orig, new)
+        x = R.waveform((6, length), seed=orig + new + length)
+        ref, bound = R.reference(x, orig, new, **kw)
+        if length == long:
+            assert n_out > 3 * fwd[0] and length > 3 * adj[0]
+            out_lens = [n_out + 1 if lds else n_out, n_out - fwd[0] // 2 - 7, n_out + 300]
+        else:
+            assert fwd[0] - new - 1 <= n_out <= fwd[0]
+            out_lens = [fwd[0] - 1, fwd[0] + 1] + ([] if lds and n_out == fwd[0] else [fwd[0]])
+        for out_len in out_lens:
+            want, allowed = PS.fit(ref, out_len), PS.fit(bound, out_len)
+            gradient = length == long and out_len < n_out           # (grad_out cut short of n_out: the rest of the row reads zeros)
+            if gradient:
+                g = R.waveform((6, out_len), seed=orig + new + out_len)
+                aref, abound = PS.fit_adjoint_reference(g, length, orig, new, **kw)
+            for tag, rows, build in VARIANT_LAYOUTS:
+                what = '%s, length %d to %d of %d, %s' % (PR.case_id(case), length, out_len, n_out, tag)
+                xt = build(x[:rows]).requires_grad_(True)
+                loads.add((rows > 1, sixteen_byte_rows(xt)))
+                if gradient:
+                    grad_loads.add((rows > 1, sixteen_byte_rows(build(g[:rows]))))
+                before = dict(tac._hip.launches)
+                got = fit(tac, xt, key, out_len)
+                assert launched_since(tac, before) == {WIDE: 1}, what
+                assert got.dtype == torch.float32 and got.is_contiguous() and tuple(got.shape) == (rows, out_len), what
+                worst = max(worst, R.assert_close(got, want[:rows], allowed[:rows], what))
+                assert not bool(got[:, n_out:].any()), what                         # the zero tail: exactly 0.0, every one written
+                if gradient:
+                    before = dict(tac._hip.launches)
+                    with warnings.catch_warnings():
+                        warnings.simplefilter('error', tac.CompositeRouteWarning)
+                        (gx,) = torch.autograd.grad(got, xt, grad_outputs=build(g[:rows]))
+                    assert launched_since(tac, before) == {WIDE: 1}, what
+                    assert tuple(gx.shape) == (rows, length), what
+                    worst_adj = max(worst_adj, R.assert_close(gx, aref[:rows], abound[:rows], 'gradient, ' + what))
+    # both load forms with more than one row of a group, for the input and for grad_out
+    assert {(True, False), (True, True)} <= loads and {(True, False), (True, True)} <= grad_loads, (loads, grad_loads)
+    print('resample_fit %s: forward tile %d, KB %d, %d per CU (K %d); adjoint tile %d, KB %d, %d per CU (K %d); VEC 0 and 1: '
+          'worst |err| / bound %.3f forward, %.3f adjoint' % (PR.case_id(case), fwd[0], fwd[1], fwd[3], banks[0].K, adj[0], adj[1], adj[3],
+                                                            banks[1].K, worst, worst_adj))
 
 
 # ----------------------------------------------------------------------------- the same bits as the LDS kernel
@@ -296,6 +380,12 @@ def test_routes_outside_the_kernels(tac):
             fit(tac, xin, k, n_out)
     with pytest.raises(RuntimeError, match='strict mode'):
         tac.resample(xt, 2000, 2001)                                        # resample itself still refuses what it refused
+    # 65 taps a phase (2001 : 2000 at width 32; 63 at width 31 runs) are one more than the last bucket holds: no plan
+    wide65 = tac._resample.constants(2001, 2000, lowpass_filter_width=32)
+    assert tac._resample.bank(*wide65).K == 65 and tac._hip.resample_wide_plan(tac._resample.bank(*wide65)) is None
+    assert tac._hip.resample_wide_plan(tac._resample.bank(*tac._resample.constants(2001, 2000, lowpass_filter_width=31))) is not None
+    with pytest.raises(RuntimeError, match='strict mode'):
+        fit(tac, xt, wide65, n_out)
     assert launched_since(tac, before) == {}
     tac.set_strict(False)
     try:

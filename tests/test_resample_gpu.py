@@ -4,26 +4,30 @@ tests/test_mfcc_gpu.py.
 Reference and bound: tests/resample_rules.py — the float64 sum per output sample and, per element,
 ``(K_n + 2) * 2^-24 * sum |h64| |x|``; every element is checked.  The lengths are the smallest that reach each path of the
 kernel: 1, 2, ``width``, ``orig - 1 / orig / orig + 1`` (less than one block of phases, exactly one, one and a sample), the input
-span of one tile of ``TILE`` = 1024 outputs minus one / exactly / plus one (the last output of a tile, the first of the next), and
-three tiles plus a remainder (every tile position of a row, the span's start at every alignment; at most 3 rows x 4 tiles = 12 units
+span of one tile of the case's 1024, 512 or 256 outputs minus one / exactly / plus one (the last output of a tile, the first of the
+next), and three tiles plus a remainder (every tile position of a row, the span's start at every alignment; at most 3 rows x 4 tiles = 12 units
 on a grid of 12 workgroups, so no workgroup takes a second unit here: tests/test_grid_wrap_gpu.py does that).  Rows 1 and 3; dense
 rows (16-byte loads), a padded row stride and a start one float into the allocation (float loads), a padded stride of four floats
-(16-byte loads across rows), and a (2, 3, L) batch.  A reference is computed once per (filter, length) and shared by the layouts."""
+(16-byte loads across rows), and a (2, 3, L) batch.  A reference is computed once per (filter, length) and shared by the layouts.
+
+The cases come from tests/polyphase_rules.py, whose census (tests/test_polyphase_rules_cpu.py) holds them to every instantiation
+``polyphase_kernel<P1, SKEW, VEC>`` at every tile that public arguments reach, for the forward and for the adjoint bank; each test
+asserts the instantiation the restated launcher rule predicts before it launches, and prints it."""
 import warnings
 
 import numpy as np
 import pytest
 import torch
 
+import polyphase_rules as PR
 import resample_rules as R
 
 pytestmark = pytest.mark.gpu
 
 ENTRY = 'tac_polyphase_f32'
-TILE = 1024                         # outputs per tile of the kernel (_hip.RESAMPLE_TILE; asserted below for every case)
-HANN, WIDE, KAISER = dict(), dict(lpw=16, rolloff=0.9), dict(method='sinc_interp_kaiser')
-CASES = [(2, 1, HANN), (1, 2, HANN), (3, 1, HANN), (3, 2, HANN), (2, 3, HANN), (7, 5, HANN), (147, 160, HANN), (441, 160, HANN),
-         (160, 441, HANN), (3, 2, WIDE), (3, 2, KAISER), (441, 160, KAISER)]
+TILE = 1024                         # outputs per tile of the kernel for the short banks (_hip.RESAMPLE_TILE)
+HANN, WIDE, KAISER = PR.HANN, PR.WIDE_FILTER, PR.KAISER
+CASES = PR.LDS_CASES                # the first twelve take TILE outputs per tile (asserted below), the rest 512 and 256
 
 
 def case_id(c):
@@ -80,14 +84,29 @@ def misaligned(x):
     return store[1:].view(x.shape)
 
 
+def variant_of(tac_, case, adjoint=False):
+    """(tile, P1, SKEW, per_cu) the restated launcher rule gives the case's bank, which ``_hip.resample_tile`` must agree with"""
+    key = tac_._resample.constants(case[0], case[1], **product_kw(case[2]))
+    bank = (tac_._resample.adjoint_bank if adjoint else tac_._resample.bank)(*key)
+    v = PR.lds_variant(bank, True)
+    assert v is not None and tac_._hip.resample_tile(bank) == v[0] and tac_._hip.resample_covers(*key), case_id(case)
+    return v[0], v[1], v[2], v[4]
+
+
+def sixteen_byte_rows(x):
+    """the launcher's VEC: a 16-byte aligned start and, with more than one row, a row stride that is a multiple of four"""
+    rows = x.reshape(-1, x.shape[-1])
+    return rows.data_ptr() % 16 == 0 and (rows.shape[0] == 1 or rows.stride(0) % 4 == 0)
+
+
 LAYOUTS = (('dense', dev), ('padded by 3', lambda x: padded(x, 3)), ('padded by 4', lambda x: padded(x, 4)),
            ('misaligned', misaligned))
 
 
-def lengths_of(orig, new, kw):
+def lengths_of(orig, new, kw, tile):
     _, width, _ = R.filter_constants(orig, new, kw.get('lpw', 6), kw.get('rolloff', 0.99))
-    span = TILE * orig // new                   # the longest input whose output is one tile
-    want = [1, 2, width, orig - 1, orig, orig + 1, span - 1, span, span + 1, 3 * TILE * orig // new + orig // 2 + 5]
+    span = tile * orig // new                   # the longest input whose output is one tile
+    want = [1, 2, width, orig - 1, orig, orig + 1, span - 1, span, span + 1, 3 * tile * orig // new + orig // 2 + 5]
     return sorted(set(n for n in want if n >= 1))
 
 
@@ -104,10 +123,10 @@ def run_one(tac_, xt, orig, new, kw, what):
 @pytest.mark.parametrize('case', CASES, ids=case_id)
 def test_kernel_within_the_bound(tac, case):
     orig, new, kw = case
-    key = tac._resample.constants(orig, new, **product_kw(kw))
-    assert tac._hip.resample_tile(tac._resample.bank(*key)) == TILE and tac._hip.resample_covers(*key)
-    worst = 0.0
-    lengths = lengths_of(orig, new, kw)
+    tile, p1, skew, per_cu = variant_of(tac, case)
+    assert (tile == TILE) == (case in CASES[:12]) and (tile, p1, skew) == PR.lds_variant(PR.case_geometry(case), True)[:3]
+    worst, loads = 0.0, set()
+    lengths = lengths_of(orig, new, kw, tile)
     for length in lengths:
         x = R.waveform((3, length), seed=1000 * orig + 10 * new + length)
         ref, bound = R.reference(x, orig, new, **kw)
@@ -116,6 +135,7 @@ def test_kernel_within_the_bound(tac, case):
                 what = '%s, %d rows of %d, %s' % (case_id(case), rows, length, tag)
                 xt = build(x[:rows])
                 assert tuple(xt.shape) == (rows, length) and np.array_equal(xt.cpu().numpy(), x[:rows]), what
+                loads.add(sixteen_byte_rows(xt))
                 got = run_one(tac, xt, orig, new, kw, what)
                 worst = max(worst, R.assert_close(got, ref[:rows], bound[:rows], what))
     for length in (lengths[-4], lengths[-1] // 3):
@@ -127,7 +147,9 @@ def test_kernel_within_the_bound(tac, case):
         swapped = dev(np.ascontiguousarray(np.swapaxes(x4, 0, 1))).transpose(0, 1)
         worst = max(worst, R.assert_close(run_one(tac, swapped, orig, new, kw, what + ' swapped'), ref, bound, what))
         worst = max(worst, R.assert_close(run_one(tac, dev(x4[1, 2]), orig, new, kw, what + ' 1-D'), ref[1, 2], bound[1, 2], what))
-    print('resample %s: worst |err| / bound %.3f' % (case_id(case), worst))
+    assert loads == {False, True}, 'both load forms'
+    print('resample %s: tile %d, P1 %d, SKEW %d, VEC 0 and 1, %d per CU, K %d: worst |err| / bound %.3f' % (
+        case_id(case), tile, p1, skew, per_cu, PR.case_geometry(case).K, worst))
 
 
 def test_exact_zeros_stay_exact(tac):
@@ -138,16 +160,21 @@ def test_exact_zeros_stay_exact(tac):
 
 
 def test_two_calls_agree_bit_for_bit(tac):
-    for orig, new in ((3, 1), (441, 160), (160, 441), (2, 3)):
-        xt = dev(R.waveform((3, 3 * TILE * orig // new + 77), seed=orig))
+    for orig, new in ((3, 1), (441, 160), (160, 441), (2, 3), (12, 1), (25, 2), (16, 1), (50, 3)):
+        tile = variant_of(tac, (orig, new, HANN))[0]
+        assert tile == PR.pinned_tile(orig, new)
+        xt = dev(R.waveform((3, 3 * tile * orig // new + 77), seed=orig))
         assert torch.equal(tac.resample(xt, orig, new), tac.resample(xt, orig, new))
 
 
-@pytest.mark.parametrize('case', [(3, 1, HANN), (2, 3, HANN), (441, 160, HANN), (160, 441, HANN), (3, 2, KAISER)], ids=case_id)
+@pytest.mark.parametrize('case', [(3, 1, HANN), (2, 3, HANN), (441, 160, HANN), (160, 441, HANN), (3, 2, KAISER),
+                                  (12, 1, HANN), (25, 2, HANN), (17, 1, HANN), (50, 3, HANN)], ids=case_id)
 def test_nan_reaches_the_outputs_the_rules_say(tac, case):
     orig, new, kw = case
-    length = TILE * orig // new + 2 * orig + 3
-    for index in (0, length // 2, TILE * orig // new - 1, length - 1):
+    tile = variant_of(tac, case)[0]
+    assert tile == PR.pinned_tile(orig, new)
+    length = tile * orig // new + 2 * orig + 3
+    for index in (0, length // 2, tile * orig // new - 1, length - 1):
         x = R.waveform((3, length), seed=5 + index)
         clean = x.copy()
         x[1, index] = np.nan
@@ -165,16 +192,27 @@ def test_nan_reaches_the_outputs_the_rules_say(tac, case):
 
 
 # ----------------------------------------------------------------------------- gradient
-@pytest.mark.parametrize('case', [(3, 1, HANN), (2, 3, HANN), (441, 160, HANN)], ids=case_id)
+@pytest.mark.parametrize('case', PR.LDS_GRADIENT_CASES, ids=case_id)
 def test_gradient_is_the_kernel_with_the_adjoint_bank(tac, case):
+    """the launch of the gradient makes ``length`` outputs with the adjoint bank: lengths on both sides of one of ITS tiles too.
+    grad_out goes to the launcher where it lies: dense, rows 3 floats apart, rows a multiple of four floats apart (16-byte
+    loads whatever ``n_out`` is) and dense one float into its allocation (float loads whatever it is) — both forms at each length"""
     orig, new, kw = case
     assert tac._ops.strict()
-    for length in (orig + 1, TILE * orig // new + orig + 3):
+    tile, p1, skew, per_cu = variant_of(tac, case, adjoint=True)
+    forward_tile = variant_of(tac, case)[0]
+    assert (tile, p1, skew) == PR.lds_variant(PR.case_geometry(case, True), True)[:3]
+    assert tile == PR.pinned_tile(orig, new, adjoint=True) and forward_tile == PR.pinned_tile(orig, new)
+    for length in sorted({orig + 1, forward_tile * orig // new + orig + 3, tile - 3, tile + orig + 3}):
         n_out = R.out_length(length, orig, new)
         x = dev(R.waveform((3, length), seed=length)).requires_grad_(True)
         g = R.waveform((3, n_out), seed=length + 1)
         aref, abound = R.adjoint_reference(g, length, orig, new, **kw)
-        for tag, gt in (('dense', dev(g)), ('padded', padded(g, 3))):
+        loads = set()
+        for tag, gt in (('dense', dev(g)), ('padded', padded(g, 3)), ('stride a multiple of four', padded(g, (-n_out) % 4 or 4)),
+                        ('misaligned', misaligned(g))):
+            assert gt.stride(-1) == 1 and tuple(gt.shape) == (3, n_out)
+            loads.add(sixteen_byte_rows(gt))
             y = tac.resample(x, orig, new, **product_kw(kw))
             before = dict(tac._hip.launches)
             with warnings.catch_warnings():
@@ -186,11 +224,42 @@ def test_gradient_is_the_kernel_with_the_adjoint_bank(tac, case):
             ratio = R.assert_close(gx, aref, abound, what)
             (again,) = torch.autograd.grad(tac.resample(x, orig, new, **product_kw(kw)), x, grad_outputs=gt)
             assert torch.equal(gx, again)
-        print('%s: worst |err| / bound %.3f' % (what, ratio))
+        assert loads == {False, True}, 'both load forms, length %d' % length
+        print('%s, VEC 0 and 1, adjoint tile %d, P1 %d, SKEW %d, %d per CU: worst |err| / bound %.3f' % (what, tile, p1, skew, per_cu, ratio))
     # double backward has no kernel: refused under strict
     y = tac.resample(x, orig, new)
     with pytest.raises(RuntimeError, match='strict mode'):
         torch.autograd.grad(y, x, grad_outputs=dev(g), create_graph=True)
+
+
+# ----------------------------------------------------------------------------- the layers on a narrow tile
+@pytest.mark.parametrize('orig_freq,new_freq', [(96000, 8000), (8000, 96000)])
+def test_layers_on_the_narrow_tile(tac, orig_freq, new_freq):
+    """12:1 runs the forward on 512 outputs per tile, 1:12 the gradient: a (2, 2, L) batch of three such tiles and a remainder,
+    one launch each way, nothing announced, both results held to their references"""
+    orig, new = R.reduced(orig_freq, new_freq)
+    case = (orig, new, HANN)
+    tiles = variant_of(tac, case)[0], variant_of(tac, case, adjoint=True)[0]
+    assert tiles == (PR.pinned_tile(orig, new), PR.pinned_tile(orig, new, adjoint=True)) and set(tiles) == {512, TILE}
+    length = 3 * 512 * orig + 17
+    layer = tac.Resample(orig_freq, new_freq).cuda()
+    x = R.waveform((2, 2, length), seed=orig_freq // 1000)
+    xt = dev(x).requires_grad_(True)
+    before = dict(tac._hip.launches)
+    y = layer(xt)
+    assert launched_since(tac, before) == {ENTRY: 1} and tuple(y.shape) == (2, 2, R.out_length(length, orig, new))
+    y.retain_grad()
+    before = dict(tac._hip.launches)
+    with warnings.catch_warnings():
+        warnings.simplefilter('error', tac.CompositeRouteWarning)
+        y.square().mean().backward()
+    assert launched_since(tac, before) == {ENTRY: 1}
+    worst = R.assert_close(y, *R.reference(x, orig, new), 'Resample(%d, %d)' % (orig_freq, new_freq))
+    # the gradient against the adjoint of the grad_out the kernel was handed (2 y / N, as the device rounded it)
+    aref, abound = R.adjoint_reference(y.grad.cpu().numpy(), length, orig, new)
+    assert bool(y.grad.any()) and tuple(xt.grad.shape) == (2, 2, length)
+    worst_adj = R.assert_close(xt.grad, aref, abound, 'gradient of Resample(%d, %d)' % (orig_freq, new_freq))
+    print('Resample(%d, %d), tiles %r: worst |err| / bound %.3f forward, %.3f gradient' % (orig_freq, new_freq, tiles, worst, worst_adj))
 
 
 # ----------------------------------------------------------------------------- refusals
@@ -206,6 +275,11 @@ def test_routes_outside_the_kernel(tac):
         tac.resample(xt.double(), 3, 2)                                     # float64 on the device
     with pytest.raises(RuntimeError, match='strict mode'):
         tac.resample(xt[:1].expand(3, 300), 3, 2)                           # a stride of zero
+    # 60:1 is the integer decimation just beyond the last the kernel holds (48:1; 59:1 is refused for its span like 60:1)
+    assert tac._hip.resample_covers(*tac._resample.constants(48, 1)) and not tac._hip.resample_covers(*tac._resample.constants(59, 1))
+    assert not tac._hip.resample_covers(*tac._resample.constants(60, 1))
+    with pytest.raises(RuntimeError, match='strict mode'):
+        tac.resample(xt, 60, 1)
     assert launched_since(tac, before) == {}
     # equal rates and empty inputs launch nothing and are no route at all
     assert tac.resample(xt, 48000, 48000) is xt
