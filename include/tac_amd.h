@@ -1001,6 +1001,25 @@ int tac_rir_ism_f32(const float* room, const float* source, const float* mic, co
 int tac_rir_span_f32(const float* room, const float* source, const float* mic, const void* images, int64_t rooms, int64_t mics, int32_t dims,
                      int64_t n_img, int32_t filter_length, double sound_speed, double sample_rate, int64_t* out, void* stream);
 
+/* (33) functional.sosfilt / SosFilt (and filtfilt above order 2): a cascade of second-order sections along a row in ONE launch
+ *      (csrc/sosfilt.hip).  sos: HOST double[n_sections][6], rows (b0, b1, b2, a0, a1, a2) as scipy lays them out; section s + 1
+ *      filters the output of section s, each as (16) with zero initial state; x, out, stride_r, clamp as in (16) (clamp limits the
+ *      cascade's result only).  reverse != 0 runs the sections in reverse order, each from the END of the row: the adjoint.
+ *      The waveform is read once and written once as float32; everything between the sections is float64 and stays on chip, so
+ *      the result is the float64 cascade rounded once.  No workspace, no atomics, one writer per element, bit-identical from run to
+ *      run and whatever else the batch holds; a non-finite sample reaches the samples after it (before it, with reverse) in its
+ *      own row, and nothing else.  16-byte loads where x and stride_r are 16-byte multiples, float loads otherwise.
+ *      n_sections 1 .. tac_sosfilt_max_sections() (8), TAC_E_UNSUPPORTED above, TAC_E_INVALID below; a section with a zero or
+ *      non-finite a0 is TAC_E_INVALID, one whose scan matrices overflow float64 (tac_lfilter_supported's rule) TAC_E_UNSUPPORTED;
+ *      tac_sosfilt_supported reports the same without launching.  A row is walked by one workgroup in tiles of tac_sosfilt_tile()
+ *      samples; the persistent grid holds at most tac_sosfilt_blocks_per_cu() workgroups per CU, each taking every grid-th row. */
+int32_t tac_sosfilt_max_sections(void);
+int32_t tac_sosfilt_tile(void);
+int32_t tac_sosfilt_blocks_per_cu(void);
+int tac_sosfilt_supported(const double* sos, int32_t n_sections);
+int tac_sosfilt_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const double* sos, int32_t n_sections,
+                    int clamp, int reverse, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

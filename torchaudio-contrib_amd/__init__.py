@@ -14,7 +14,7 @@ from . import layers
 from .functional import *      # noqa: F401,F403
 from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filter, apply_filterbank, angle, magphase,
                          phase_vocoder, amplitude_to_db, db_to_amplitude, mu_law_encoding,
-                         mu_law_decoding, hpss, create_dct, dct, resample, lfilter, biquad, lowpass_biquad,
+                         mu_law_decoding, hpss, create_dct, dct, resample, lfilter, sosfilt, tf2sos, filtfilt, biquad, lowpass_biquad,
                          highpass_biquad, bandpass_biquad, bandreject_biquad, allpass_biquad, equalizer_biquad,
                          preemphasis, deemphasis, fftconvolve, convolve, kaldi_fbank, sliding_window_cmn,
                          compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid,
@@ -23,7 +23,7 @@ from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filte
                          merge_tokens, TokenSpan, vad, vad_start, simulate_rir_ism, simulate_rir_ism_batch)
 from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
-                     MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, Preemphasis, Deemphasis,
+                     MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, SosFilt, Preemphasis, Deemphasis,
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,
                      KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment,
                      AddNoise, Speed, SpeedPerturbation, PitchShift, Loudness, PitchFrequency, PSD, SoudenMVDR, MVDR,

@@ -218,6 +218,22 @@ def lfilter(wave, a_coeffs, b_coeffs, clamp):
     return y.reshape(wave.shape)
 
 
+def sosfilt(wave, sos, clamp):
+    """A cascade of second-order sections, ``sos`` of shape ``(S, 6)`` with rows ``(b0, b1, b2, a0, a1, a2)``: ``lfilter`` above
+    section by section.  The signal between two sections stays float64; it is rounded to the input's dtype once, behind the last
+    one, and clipped there when ``clamp``.  Differentiable w.r.t. the waveform and ``sos``, and as slow as ``lfilter``: the CPU
+    path of ``tac_amd::sosfilt`` and its announced route on a device."""
+    if wave.numel() == 0:
+        return torch.zeros_like(wave, memory_format=torch.contiguous_format)
+    y = wave.to(torch.float64)
+    for s in range(sos.shape[0]):
+        y = lfilter(y, sos[s, 3:], sos[s, :3], False)
+    y = y.to(wave.dtype)
+    if clamp:
+        y = y.clamp(-1.0, 1.0)
+    return y.contiguous()
+
+
 def loudness(waveform, sample_rate):
     """torchaudio's ``functional.loudness`` (ITU-R BS.1770-4) in torch operators, in the input's dtype: ``(…, channels, time)`` →
     ``(…)``.  The K-weighting is this package's ``treble_biquad`` and ``highpass_biquad`` (``lfilter`` above, each clipped to [-1, 1]

@@ -6,6 +6,7 @@ Every design returns ``(b, a)``, two tuples of three floats, with ``w0 = 2 pi f 
 the denominator of all of them is ``a = (1 + alpha, -2 cos w0, 1 - alpha)`` except the equalizer's."""
 import math
 
+import numpy as np
 import torch
 
 from ._bounded import Bounded
@@ -133,6 +134,127 @@ def loudness_check(waveform, sample_rate, name='loudness'):
         raise ValueError('%s: the waveform has %d samples, shorter than one block of 400 ms (%d samples at %d Hz)'
                          % (name, waveform.size(-1), gate, sample_rate))
     return gate, step
+
+
+def check_sos(sos):
+    """``ValueError`` unless ``sos`` is a floating-point ``(S, 6)`` tensor with ``S >= 1``.  (Every ``a0`` finite and not zero is
+    checked on the host values, ``check_sos_values``.)"""
+    if not torch.is_tensor(sos):
+        raise ValueError('sosfilt: sos must be a tensor, got %s' % type(sos).__name__)
+    if sos.dim() != 2 or sos.shape[1] != 6:
+        raise ValueError('sosfilt: sos must have shape (sections, 6) with rows (b0, b1, b2, a0, a1, a2), got %s' % (tuple(sos.shape),))
+    if sos.shape[0] == 0:
+        raise ValueError('sosfilt: sos has no section')
+    if not sos.is_floating_point():
+        raise ValueError('sosfilt: sos must be floating point, got %s' % sos.dtype)
+
+
+def check_sos_values(rows):
+    """``rows``: the sections as tuples of Python floats"""
+    for s, row in enumerate(rows):
+        if row[3] == 0.0 or not math.isfinite(row[3]):
+            raise ValueError('sosfilt: a0 of section %d must be finite and not zero, got %r' % (s, row[3]))
+
+
+def _pair_roots(r):
+    """Roots of a real polynomial as one list: a conjugate pair by its member of positive imaginary part (the mean of it and of
+    the conjugate of its partner, so the pair is exact), a real root as a complex number of imaginary part zero"""
+    r = np.asarray(r, dtype=np.complex128)
+    real = np.abs(r.imag) <= 100.0 * np.finfo(np.float64).eps * np.abs(r)
+    out = [complex(v.real, 0.0) for v in r[real]]
+    pos, neg = list(r[~real & (r.imag > 0)]), list(r[~real & (r.imag < 0)])
+    if len(pos) != len(neg):
+        raise ValueError('tf2sos: the roots do not pair into conjugates (are the coefficients finite?)')
+    for v in pos:
+        k = int(np.argmin([abs(v - w.conjugate()) for w in neg]))
+        out.append(0.5 * (v + neg.pop(k).conjugate()))
+    return out
+
+
+def _is_real(v):
+    return v.imag == 0.0
+
+
+def _take_nearest(pool, to, kind=None):
+    """Remove and return the entry of ``pool`` nearest ``to`` among the real (``kind`` 'real'), the complex ('complex') or all"""
+    ks = [k for k, v in enumerate(pool) if kind is None or _is_real(v) == (kind == 'real')]
+    k = min(ks, key=lambda k: abs(pool[k] - to) if math.isfinite(pool[k].real) else math.inf)
+    return pool.pop(k)
+
+
+def _quadratic(r1, r2):
+    """The coefficients in z^-1 of (1 - r1 z^-1)(1 - r2 z^-1): ``r2`` None is the conjugate of ``r1``, an infinite root stands for
+    the factor z^-1 (a leading zero of the numerator)"""
+    if r2 is None:
+        return (1.0, -2.0 * r1.real, r1.real * r1.real + r1.imag * r1.imag)
+    f1 = (0.0, 1.0) if math.isinf(r1.real) else (1.0, -r1.real)
+    f2 = (0.0, 1.0) if math.isinf(r2.real) else (1.0, -r2.real)
+    return (f1[0] * f2[0], f1[0] * f2[1] + f1[1] * f2[0], f1[1] * f2[1])
+
+
+def _tf2sos(b, a):
+    n = len(a) - 1
+    if n <= 2:
+        bn = [v / a[0] for v in b] + [0.0] * (2 - n)
+        an = [v / a[0] for v in a] + [0.0] * (2 - n)
+        return [bn + [1.0] + an[1:]]
+    lead = next((k for k, v in enumerate(b) if v != 0.0), None)
+    if lead is None:
+        gain, zeros = 0.0, [complex(0.0, 0.0)] * n
+    else:           # a numerator that starts with `lead` zeros is z^-lead times a shorter one: `lead` roots at infinity
+        gain = b[lead] / a[0]
+        zeros = _pair_roots(np.roots(np.asarray(b[lead:], dtype=np.float64))) + [complex(math.inf, 0.0)] * lead
+    poles = _pair_roots(np.roots(np.asarray(a, dtype=np.float64)))
+    sections = []
+    while poles:
+        p1 = poles.pop(int(np.argmin([abs(1.0 - abs(p)) for p in poles])))
+        real_zeros = sum(1 for z in zeros if _is_real(z))
+        if _is_real(p1) and not any(_is_real(p) for p in poles):
+            # the last real pole of an odd order: a first-order section with the nearest real zero
+            z1 = _take_nearest(zeros, p1, 'real')
+            sections.append((_quadratic(z1, complex(0.0, 0.0)), _quadratic(p1, complex(0.0, 0.0))))
+            continue
+        # (a second-order section never takes the only real zero left: its partner would have to be complex)
+        z1 = _take_nearest(zeros, p1, 'complex' if real_zeros == 1 else None)
+        if not _is_real(p1):
+            den = _quadratic(p1, None)
+            num = _quadratic(z1, None) if not _is_real(z1) else _quadratic(z1, _take_nearest(zeros, p1, 'real'))
+        elif not _is_real(z1):
+            num = _quadratic(z1, None)
+            den = _quadratic(p1, _take_nearest(poles, z1, 'real'))
+        else:
+            reals = [k for k, p in enumerate(poles) if _is_real(p)]
+            p2 = poles.pop(min(reals, key=lambda k: abs(1.0 - abs(poles[k]))))
+            den = _quadratic(p1, p2)
+            num = _quadratic(z1, _take_nearest(zeros, p2, 'real'))
+        sections.append((num, den))
+    sections.reverse()                          # the section nearest the unit circle comes last
+    rows = [[v + 0.0 for v in num + den] for num, den in sections]           # (+ 0.0: no negative zeros)
+    rows[0][:3] = [gain * v for v in rows[0][:3]]
+    return rows
+
+
+_sections = Bounded(256)
+
+
+def tf2sos(b_coeffs, a_coeffs):
+    """The transfer function ``b / a`` (sequences of floats, equal length, ``a[0] != 0``) as second-order sections: a float64 host
+    tensor ``(ceil(order / 2), 6)`` with rows ``(b0, b1, b2, 1, a1, a2)``, cached by value.  scipy's ``tf2sos`` algorithm in numpy
+    and float64: the roots of both polynomials, conjugate pairs kept together, the pole (pair) nearest the unit circle matched
+    with the zeros nearest it, the sections ordered so that that one comes last, the gain ``b0 / a0`` in the first.  An odd order
+    leaves one first-order section (``b2 = a2 = 0``); orders 1 and 2 give the input itself, divided by ``a0``."""
+    key = (tuple(float(v) for v in b_coeffs), tuple(float(v) for v in a_coeffs))
+    hit = _sections.get(key)
+    if hit is None:
+        b, a = key
+        if len(b) != len(a) or len(a) == 0:
+            raise ValueError('tf2sos: b_coeffs and a_coeffs must have the same non-zero length, got %d and %d' % (len(b), len(a)))
+        if a[0] == 0.0 or not all(math.isfinite(v) for v in a + b):
+            raise ValueError('tf2sos: the coefficients must be finite and a_coeffs[0] not zero')
+        with torch.inference_mode(False):
+            hit = torch.tensor(_tf2sos(list(b), list(a)), dtype=torch.float64)
+        _sections[key] = hit
+    return hit
 
 
 _tensors = Bounded(256)

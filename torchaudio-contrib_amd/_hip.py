@@ -1095,6 +1095,64 @@ def lfilter_rows(x, b, a, clamp, reverse=False):
     return out
 
 
+# ----------------------------------------------------------------------------- sosfilt (csrc/sosfilt.hip)
+#: sections per launch of ``tac_sosfilt_f32`` (SOS_MAX: order 16), its samples per tile (LF_TILE, shared with ``lfilter``) and the
+#: cap of its persistent grid per CU (SOS_BLOCKS_PER_CU); checked against the library's own values at the first launch
+SOSFILT_MAX_SECTIONS = 8
+SOSFILT_TILE = LFILTER_TILE
+SOSFILT_BLOCKS_PER_CU = 2
+
+_sosfilt_ok = Bounded(256)
+_sosfilt_checked = False
+
+
+def _sosfilt_array(sos):
+    flat = [v for row in sos for v in row]
+    return (ctypes.c_double * len(flat))(*flat)
+
+
+def host_sos(t):
+    """The sections of an ``(S, 6)`` tensor as a tuple of tuples of Python floats; a device tensor is read back once per version
+    of its contents, as ``host_coeffs`` reads a coefficient vector."""
+    def build():
+        return tuple(tuple(row) for row in t.detach().to(torch.float64).tolist())
+    return cached_on(t, '_tac_coef', 'sos', build) if t.is_cuda else build()
+
+
+def sosfilt_covers(sos):
+    """True where ``tac_sosfilt_f32`` takes these sections (a tuple of ``(b0, b1, b2, a0, a1, a2)`` tuples, every ``a0`` finite and
+    not zero already checked): at most ``SOSFILT_MAX_SECTIONS`` of them, each passing ``lfilter_covers``' rule."""
+    hit = _sosfilt_ok.get(sos)
+    if hit is None:
+        hit = 1 <= len(sos) <= SOSFILT_MAX_SECTIONS and \
+            _native.lib().tac_sosfilt_supported(_sosfilt_array(sos), len(sos)) == _native.TAC_OK
+        _sosfilt_ok[sos] = hit
+    return hit
+
+
+def sosfilt_rows(x, sos, clamp, reverse=False):
+    """``(…, L) -> (…, L)`` through ``tac_sosfilt_f32``: the whole cascade in one launch.  ``sos`` as for ``sosfilt_covers``;
+    ``reverse`` runs the adjoint (the sections in reverse order, each from the end of the row).  ``x`` is read where it lies when
+    its leading dims collapse into one positive row stride over unit-stride rows; it is copied otherwise."""
+    global _sosfilt_checked
+    length = x.shape[-1]
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        h = _native.lib()
+        if not _sosfilt_checked:
+            found = (h.tac_sosfilt_max_sections(), h.tac_sosfilt_tile(), h.tac_sosfilt_blocks_per_cu())
+            if found != (SOSFILT_MAX_SECTIONS, SOSFILT_TILE, SOSFILT_BLOCKS_PER_CU):
+                raise RuntimeError('libtac_amd.so reports (sections, tile, blocks per CU) = %r for sosfilt, _hip says %r'
+                                   % (found, (SOSFILT_MAX_SECTIONS, SOSFILT_TILE, SOSFILT_BLOCKS_PER_CU)))
+            _sosfilt_checked = True
+        rows = x.reshape(-1, length)
+        if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+            rows = rows.contiguous()
+        _launch('tac_sosfilt_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0), _sosfilt_array(sos),
+                len(sos), int(bool(clamp)), int(bool(reverse)), _native.ptr(out))
+    return out
+
+
 # ----------------------------------------------------------------------------- loudness (csrc/loudness.hip)
 #: samples of one row per tile of ``tac_loudness_f32`` (csrc/loudness.hip: LO_TILE), checked against the library's own value at the
 #: first launch, and the shortest hop its bins take (LO_C: at most one bin edge in a lane's chunk)

@@ -187,6 +187,11 @@ PROTOTYPES = {
     'tac_rir_tile': (_INT, [_I64, _I64, _I32, _P, _P]),
     'tac_rir_ism_f32': (_INT, [_P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _I64, _I32, _I64, _I64, _I32, _D, _D, _I32, _P, _P]),
     'tac_rir_span_f32': (_INT, [_P, _P, _P, _P, _I64, _I64, _I32, _I64, _I32, _D, _D, _P, _P]),
+    'tac_sosfilt_max_sections': (_I32, []),
+    'tac_sosfilt_tile': (_I32, []),
+    'tac_sosfilt_blocks_per_cu': (_I32, []),
+    'tac_sosfilt_supported': (_INT, [_P, _I32]),
+    'tac_sosfilt_f32': (_INT, [_P, _I64, _I64, _I64, _P, _I32, _INT, _INT, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

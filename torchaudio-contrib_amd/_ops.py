@@ -29,6 +29,8 @@ see them by name.
     tac_amd::griffinlim         Griffin-Lim phase recovery of (…, F, T) magnitudes: prepare, then stft + inverse a step (csrc/griffinlim.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
+    tac_amd::sosfilt            cascade of up to 8 second-order sections along time in one launch, float64 between them (csrc/sosfilt.hip)
+    tac_amd::lfilter_reverse, sosfilt_reverse   the two above run from the end of each row: filtfilt's second half (private)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -420,20 +422,41 @@ def _resample_fit_hip_backward(saved, rest, needs, grads):
     return [H.resample_fit(g, key, out_len, adjoint=True, length=length)]
 
 
-def _lfilter_hip_backward(saved, rest, needs, grads):
-    wave, a, b = saved[:3]
-    (clamp,) = rest
-    if grads[0] is None or needs[1] or needs[2]:
-        return None                 # (the coefficients' gradient: the stock-torch route, announced)
-    ha, hb = H.host_coeffs(a), H.host_coeffs(b)
-    if not H.lfilter_covers(hb, ha):
-        return None
-    g = grads[0]
-    if clamp:                       # the clamp passes the gradient where the saved output lies strictly inside (-1, 1)
-        y = saved[3]
-        g = g * ((y > -1.0) & (y < 1.0))
-    # the adjoint of a causal filter is the same filter run backwards in time: the same kernel, walking each row from its end
-    return [H.lfilter_rows(g, hb, ha, False, reverse=True) if needs[0] else None, None, None]
+def _lfilter_hip_backward_of(reverse):
+    def backward(saved, rest, needs, grads):
+        wave, a, b = saved[:3]
+        (clamp,) = rest
+        if grads[0] is None or needs[1] or needs[2]:
+            return None                 # (the coefficients' gradient: the stock-torch route, announced)
+        ha, hb = H.host_coeffs(a), H.host_coeffs(b)
+        if not H.lfilter_covers(hb, ha):
+            return None
+        g = grads[0]
+        if clamp:                       # the clamp passes the gradient where the saved output lies strictly inside (-1, 1)
+            y = saved[3]
+            g = g * ((y > -1.0) & (y < 1.0))
+        # the adjoint of a causal filter is the same filter run backwards in time: the same kernel, walking each row from its end
+        # (and from its start for the op that itself runs from the end)
+        return [H.lfilter_rows(g, hb, ha, False, reverse=not reverse) if needs[0] else None, None, None]
+    return backward
+
+
+def _sosfilt_hip_backward_of(reverse):
+    def backward(saved, rest, needs, grads):
+        wave, sos = saved[:2]
+        (clamp,) = rest
+        if grads[0] is None or needs[1]:
+            return None                 # (the sections' gradient: the stock-torch route, announced)
+        hs = H.host_sos(sos)
+        if not H.sosfilt_covers(hs):
+            return None
+        g = grads[0]
+        if clamp:
+            y = saved[2]
+            g = g * ((y > -1.0) & (y < 1.0))
+        # the adjoint of the cascade: its sections in reverse order, each run against time — the same kernel, ``reverse`` flipped
+        return [H.sosfilt_rows(g, hs, False, reverse=not reverse) if needs[0] else None, None]
+    return backward
 
 
 def _fftconvolve_hip_backward(saved, rest, needs, grads):
@@ -503,7 +526,7 @@ def _add_noise_hip_backward(saved, rest, needs, grads):
 
 _HIP_BACKWARD = {'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
                  'mask_spans': _mask_spans_hip_backward, 'add_noise': _add_noise_hip_backward,
-                 'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'resample_fit': _resample_fit_hip_backward, 'lfilter': _lfilter_hip_backward, 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
+                 'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'resample_fit': _resample_fit_hip_backward, 'lfilter': _lfilter_hip_backward_of(False), 'lfilter_reverse': _lfilter_hip_backward_of(True), 'sosfilt': _sosfilt_hip_backward_of(False), 'sosfilt_reverse': _sosfilt_hip_backward_of(True), 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
                  'complex_norm': _complex_norm_hip_backward, 'amplitude_to_db': _amplitude_to_db_hip_backward,
                  'angle': _angle_hip_backward, 'magphase': _magphase_hip_backward, 'db_to_amplitude': _db_to_amplitude_hip_backward,
@@ -1905,6 +1928,70 @@ def _lfilter_fake(wave, a_coeffs, b_coeffs, clamp):
 # (the wave alone has to be a float32 HIP tensor for the gradient kernel; the output is saved where the clamp needs its mask)
 _register('lfilter', '(Tensor wave, Tensor a_coeffs, Tensor b_coeffs, bool clamp) -> Tensor', _lfilter_cuda, C.lfilter,
           _lfilter_fake, 3, n_plain=1, save_output=lambda inputs: bool(inputs[3]))
+
+
+# ============================================================================= sosfilt, and the filters run against time
+def _sosfilt_reverse_cpu(wave, sos, clamp):
+    return C.sosfilt(wave.flip(-1), sos.flip(0), clamp).flip(-1)
+
+
+def _lfilter_reverse_cpu(wave, a_coeffs, b_coeffs, clamp):
+    return C.lfilter(wave.flip(-1), a_coeffs, b_coeffs, clamp).flip(-1)
+
+
+def _sosfilt_cuda_of(op, reverse, composite):
+    def run(wave, sos, clamp):
+        if wave.numel() == 0:
+            return torch.empty_like(wave, memory_format=torch.contiguous_format)
+        reason = _hip_dtype(wave)
+        if reason is None and sos.shape[0] > H.SOSFILT_MAX_SECTIONS:
+            reason = '%d sections (the kernel takes at most %d)' % (sos.shape[0], H.SOSFILT_MAX_SECTIONS)
+        if reason is None and any(st <= 0 for st, n in zip(wave.stride(), wave.shape) if n > 1):
+            reason = 'non-positive strides'
+        if reason is None:
+            hs = H.host_sos(sos)
+            if not H.sosfilt_covers(hs):
+                reason = 'a section whose state transition over one tile overflows float64'
+        if reason is not None:
+            _composite_route(op, reason)
+            return composite(wave, sos, clamp)
+        out = H.sosfilt_rows(_f32(wave), hs, clamp, reverse=reverse)
+        return out if wave.dtype == out.dtype else out.to(wave.dtype)
+    return run
+
+
+def _lfilter_reverse_cuda(wave, a_coeffs, b_coeffs, clamp):
+    """filtfilt's second half up to order 2: the lfilter kernel's ``reverse`` mode, which ``tac_amd::lfilter``'s schema does not
+    expose.  (filtfilt hands over only what ``tac_amd::lfilter`` took just before; everything else is announced.)"""
+    if wave.numel() == 0:
+        return torch.empty_like(wave, memory_format=torch.contiguous_format)
+    reason = _hip_dtype(wave)
+    if reason is None and any(st <= 0 for st, n in zip(wave.stride(), wave.shape) if n > 1):
+        reason = 'non-positive strides'
+    if reason is None:
+        ha, hb = H.host_coeffs(a_coeffs), H.host_coeffs(b_coeffs)
+        if not H.lfilter_covers(hb, ha):
+            reason = 'a filter outside the lfilter kernel'
+    if reason is not None:
+        _composite_route('lfilter_reverse', reason)
+        return _lfilter_reverse_cpu(wave, a_coeffs, b_coeffs, clamp)
+    out = H.lfilter_rows(_f32(wave), hb, ha, clamp, reverse=True)
+    return out if wave.dtype == out.dtype else out.to(wave.dtype)
+
+
+def _sosfilt_fake(wave, sos, clamp):
+    return torch.empty_like(wave, memory_format=torch.contiguous_format)
+
+
+# (as lfilter: the wave alone has to be a float32 HIP tensor for the gradient kernel; the output is saved for the clamp's mask.
+# The two ``_reverse`` ops are private: filtfilt's second halves, the sections in reverse order and each run from the end of the row.)
+_register('sosfilt', '(Tensor wave, Tensor sos, bool clamp) -> Tensor', _sosfilt_cuda_of('sosfilt', False, C.sosfilt), C.sosfilt,
+          _sosfilt_fake, 2, n_plain=1, save_output=lambda inputs: bool(inputs[2]))
+_register('sosfilt_reverse', '(Tensor wave, Tensor sos, bool clamp) -> Tensor',
+          _sosfilt_cuda_of('sosfilt_reverse', True, _sosfilt_reverse_cpu), _sosfilt_reverse_cpu, _sosfilt_fake, 2, n_plain=1,
+          save_output=lambda inputs: bool(inputs[2]))
+_register('lfilter_reverse', '(Tensor wave, Tensor a_coeffs, Tensor b_coeffs, bool clamp) -> Tensor', _lfilter_reverse_cuda,
+          _lfilter_reverse_cpu, _lfilter_fake, 3, n_plain=1, save_output=lambda inputs: bool(inputs[3]))
 
 
 # ============================================================================= complex pairs

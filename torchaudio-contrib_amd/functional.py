@@ -36,7 +36,7 @@ from ._lazy import realize as _realize
 
 __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', 'apply_filterbank', 'angle', 'magphase',
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
-           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
+           'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'sosfilt', 'tf2sos', 'filtfilt', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
            'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch']
@@ -600,12 +600,77 @@ def lfilter(waveforms, a_coeffs, b_coeffs, clamp=True):
     it as doubles (float32 tensors convert exactly; a device tensor is read back once and cached).  Its gradient w.r.t. the
     waveform is the same kernel run from the end of each row.  Higher orders, float64, non-positive strides and the gradient
     w.r.t. the coefficients take the time loop of ``_composite.lfilter`` (also the CPU path): correct and slow, announced with
-    ``CompositeRouteWarning`` on a device."""
+    ``CompositeRouteWarning`` on a device.  The kernel route above order 2 is the cascade: ``sosfilt(x, tf2sos(b, a))``."""
     x = _waveform(waveforms, 'lfilter')
     _filters.check_coeffs(a_coeffs, b_coeffs)
     if not torch.compiler.is_compiling() and _hip.host_coeffs(a_coeffs)[0] == 0.0:
         raise ValueError('lfilter: a_coeffs[0] must not be zero')
     return _call('lfilter', x, a_coeffs, b_coeffs, bool(clamp))
+
+
+def sosfilt(waveforms, sos, clamp=False):
+    """``(…, L) → (…, L)``: a cascade of second-order sections along the last axis, what ``scipy.signal.sosfilt`` computes with zero
+    initial state.  ``sos`` is a floating-point ``(S, 6)`` tensor with rows ``(b0, b1, b2, a0, a1, a2)`` in scipy's layout, every
+    ``a0`` finite and not zero, ``S >= 1`` (``ValueError`` otherwise); it may be float64 and may live on the host.  Section
+    ``s + 1`` filters the output of section ``s``; ``clamp`` limits the final result to [-1, 1].  This is the way to filters above
+    order 2 — ``sosfilt(x, tf2sos(b, a))``, or a design made as sections (``scipy.signal.butter(..., output='sos')``).
+
+    float32 on a HIP device with at most eight sections runs ONE launch of the gfx950 kernel (csrc/sosfilt.hip): the waveform is
+    read once and written once as float32 and everything between the sections is float64 on chip, so the result is the float64
+    cascade rounded once.  Its gradient w.r.t. the waveform is the same kernel with the sections reversed and each row walked
+    from its end.  More sections, float64, non-positive strides, a section so unstable that the kernel's scan overflows, the
+    gradient w.r.t. ``sos`` and double backward take ``_composite.sosfilt`` (also the CPU path): ``_composite.lfilter`` section by
+    section in float64, announced with ``CompositeRouteWarning`` on a device."""
+    x = _waveform(waveforms, 'sosfilt')
+    _filters.check_sos(sos)
+    if not torch.compiler.is_compiling():
+        _filters.check_sos_values(_hip.host_sos(sos))
+    return _call('sosfilt', x, sos, bool(clamp))
+
+
+def _host_floats(c, name):
+    if torch.is_tensor(c):
+        if c.dim() != 1 or not c.is_floating_point():
+            raise ValueError('tf2sos: %s must be a 1-D floating-point tensor, got %s of shape %s' % (name, c.dtype, tuple(c.shape)))
+        return _hip.host_coeffs(c)
+    return tuple(float(v) for v in c)
+
+
+def tf2sos(b_coeffs, a_coeffs):
+    """The transfer function ``b_coeffs / a_coeffs`` (1-D tensors or sequences of equal length, ``a_coeffs[0] != 0``; note the
+    order, scipy's) as second-order sections for ``sosfilt``: a float64 HOST tensor of shape ``(ceil(order / 2), 6)``, computed on
+    the host in float64 by scipy's ``tf2sos`` algorithm (``_filters.tf2sos``) and cached by value."""
+    return _filters.tf2sos(_host_floats(b_coeffs, 'b_coeffs'), _host_floats(a_coeffs, 'a_coeffs'))
+
+
+#: coefficients per side up to which ``filtfilt`` runs as two cascades of ``tf2sos``' sections (order 16: eight sections)
+_FILTFILT_MAX_COEFFS = 2 * _hip.SOSFILT_MAX_SECTIONS + 1
+
+
+def filtfilt(waveforms, a_coeffs, b_coeffs, clamp=True):
+    """``(…, L) → (…, L)``: torchaudio's ``functional.filtfilt``, signature and semantics — ``lfilter`` forward without clamp, then
+    the same filter over the time-reversed result with ``clamp``, reversed back.  The intermediate is in the input's dtype and
+    there is NO edge padding: this is not scipy's ``filtfilt``.  ``a_coeffs`` / ``b_coeffs`` as for ``lfilter``.
+
+    Up to three coefficients per side: two launches of the ``lfilter`` kernel, the second in its ``reverse`` mode (nothing is
+    flipped in memory).  4 to 17 per side: ``tf2sos`` on the host values, then two launches of the ``sosfilt`` kernel, the second
+    with the sections reversed and each row walked from its end.  Longer filters, coefficients that need a gradient, and
+    everything ``lfilter`` itself hands to torch operators take ``_composite.lfilter`` twice, announced on a device.  The gradient
+    w.r.t. the waveform follows from the two halves."""
+    x = _waveform(waveforms, 'filtfilt')
+    _filters.check_coeffs(a_coeffs, b_coeffs)
+    n = a_coeffs.numel()
+    sections = False
+    if not torch.compiler.is_compiling():
+        ha = _hip.host_coeffs(a_coeffs)
+        if ha[0] == 0.0:
+            raise ValueError('filtfilt: a_coeffs[0] must not be zero')
+        sections = _hip.LFILTER_MAX_COEFFS < n <= _FILTFILT_MAX_COEFFS and not (
+            torch.is_grad_enabled() and (a_coeffs.requires_grad or b_coeffs.requires_grad))
+    if sections:
+        sos = _filters.tf2sos(_hip.host_coeffs(b_coeffs), ha)
+        return _call('sosfilt_reverse', _call('sosfilt', x, sos, False), sos, bool(clamp))
+    return _call('lfilter_reverse', _call('lfilter', x, a_coeffs, b_coeffs, False), a_coeffs, b_coeffs, bool(clamp))
 
 
 def biquad(waveforms, b0, b1, b2, a0, a1, a2):

@@ -459,6 +459,26 @@ class LFilter(_ModuleNoStateBuffers):
         return self.__class__.__name__ + '(order={}, clamp={})'.format(self.a_coeffs.numel() - 1, self.clamp)
 
 
+class SosFilt(_ModuleNoStateBuffers):
+    """``functional.sosfilt`` as a layer: ``(…, time)`` → ``(…, time)``.  The ``(S, 6)`` sections are the non-persistent buffer
+    ``sos`` (kept in float64 unless given otherwise; it follows ``.to()`` and stays out of ``state_dict()``, as ``LFilter``'s
+    coefficients do)."""
+
+    def __init__(self, sos, clamp=False):
+        super(SosFilt, self).__init__()
+        s = torch.as_tensor(sos, dtype=None if torch.is_tensor(sos) else torch.float64)
+        _filters.check_sos(s)
+        _filters.check_sos_values(_hip.host_sos(s))
+        self.clamp = bool(clamp)
+        self.register_buffer('sos', s.detach().clone())
+
+    def forward(self, waveforms):
+        return _ops.call('sosfilt', F._waveform(waveforms, 'sosfilt'), self.sos, self.clamp)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sections={}, clamp={})'.format(self.sos.shape[0], self.clamp)
+
+
 class Preemphasis(_ModuleNoStateBuffers):
     """``functional.preemphasis`` as a layer: ``y[n] = x[n] - coeff x[n-1]``.  No buffers: ``coeff`` is a Python float, and the
     two float64 host tensors the op takes are plain attributes (they stay float64 on the host whatever ``.to()`` is given)."""
