@@ -1020,6 +1020,48 @@ int tac_sosfilt_supported(const double* sos, int32_t n_sections);
 int tac_sosfilt_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const double* sos, int32_t n_sections,
                     int clamp, int reverse, float* out, void* stream);
 
+/* (34) functional.overdrive / phaser / flanger: the SoX effects defined by a loop over time, each in ONE launch
+ *      (csrc/sox_effects.hip).  x, out, rows, length, stride_r as in (16): float32 rows of unit stride, out dense.  The waveform is
+ *      read once and written once as float32 and every state between is float64 on chip.  No workspace, no atomics, one writer per
+ *      element, bit-identical from run to run and whatever else the batch holds; a non-finite sample reaches only later samples
+ *      of its own row.  16-byte loads where x and stride_r are 16-byte multiples (not the flanger's feedback path).
+ *      overdrive: t = shape(g x + c) (-2/3 below -1, 2/3 above 1, t - t^3 / 3 between), v[n] = t[n] - t[n-1] + 0.995 v[n-1],
+ *        out = clamp(0.5 x + 0.75 v).  g, c finite (TAC_E_INVALID otherwise; tac_overdrive_supported reports it).  lfilter's tile
+ *        walk: tiles of tac_overdrive_tile() samples, at most tac_overdrive_blocks_per_cu() workgroups per CU, one row each.
+ *      phaser: y[n] = gain_in x[n] + decay y[n - d(n)], d(n) = L - mod[n % P] + 1 clipped to [1, L], out = clamp(gain_out y).
+ *        mod: DEVICE int32[P].  L, P >= 1 (TAC_E_INVALID), L <= tac_phaser_max_delay() (TAC_E_UNSUPPORTED);
+ *        tac_phaser_supported reports both.  Pointer jumping over tiles of tac_phaser_tile() samples in the LDS.
+ *        tac_phaser_seq_f32 computes the same with one lane per row (L <= tac_phaser_seq_max_delay()): the ablation variant.
+ *      flanger: rows = entries * channels, row r is channel r % channels; lfo: DEVICE float32[P]; phases: HOST int32[channels],
+ *        each >= 0.  D = lfo[(i + phases[c]) % P], k = floor(D) clipped to [0, Lb - 2], w[i] = x[i] + fb delayed[i-1], delayed[i]
+ *        the linear (quadratic != 0: SoX's quadratic) interpolation of w[i-k], w[i-k-1] (, w[i-k-2]), out = clamp(in_gain x +
+ *        delay_gain delayed).  fb == 0: a streaming FIR over tiles of tac_flanger_tile() samples.  fb != 0: a wave per row, W slots
+ *        per step (the caller passes W <= 1 + min k; W <= tac_flanger_max_block()), x staged in chunks of tac_flanger_chunk().
+ *        2 <= Lb <= tac_flanger_max_delay(), W <= Lb - 1, channels <= 4: TAC_E_UNSUPPORTED otherwise, tac_flanger_supported. */
+int32_t tac_overdrive_tile(void);
+int32_t tac_overdrive_blocks_per_cu(void);
+int tac_overdrive_supported(double g, double c);
+int tac_overdrive_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, double g, double c, float* out, void* stream);
+int32_t tac_phaser_tile(void);
+int32_t tac_phaser_max_delay(void);
+int32_t tac_phaser_seq_max_delay(void);
+int32_t tac_phaser_blocks_per_cu(void);
+int tac_phaser_supported(int32_t L, int32_t P);
+int tac_phaser_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const int32_t* mod, int32_t P, int32_t L,
+                   double gain_in, double decay, double gain_out, float* out, void* stream);
+int tac_phaser_seq_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const int32_t* mod, int32_t P, int32_t L,
+                       double gain_in, double decay, double gain_out, float* out, void* stream);
+int32_t tac_flanger_tile(void);
+int32_t tac_flanger_chunk(void);
+int32_t tac_flanger_max_block(void);
+int32_t tac_flanger_max_delay(void);
+int32_t tac_flanger_blocks_per_cu(void);
+int32_t tac_flanger_fb_blocks_per_cu(void);
+int tac_flanger_supported(int32_t Lb, int32_t P, int32_t W, int32_t channels);
+int tac_flanger_f32(const float* x, int64_t rows, int32_t channels, int64_t length, int64_t stride_r, const float* lfo, int32_t P,
+                    const int32_t* phases, int32_t Lb, int32_t W, double fb, double in_gain, double delay_gain, int quadratic,
+                    float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

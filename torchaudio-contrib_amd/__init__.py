@@ -20,10 +20,11 @@ from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filte
                          compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid,
                          add_noise, speed, pitch_shift, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
                          apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, forced_align,
-                         merge_tokens, TokenSpan, vad, vad_start, simulate_rir_ism, simulate_rir_ism_batch)
+                         merge_tokens, TokenSpan, vad, vad_start, simulate_rir_ism, simulate_rir_ism_batch,
+                         overdrive, phaser, flanger)
 from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
-                     MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, SosFilt, Preemphasis, Deemphasis,
+                     MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, SosFilt, Overdrive, Phaser, Flanger, Preemphasis, Deemphasis,
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,
                      KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment,
                      AddNoise, Speed, SpeedPerturbation, PitchShift, Loudness, PitchFrequency, PSD, SoudenMVDR, MVDR,

@@ -1170,3 +1170,73 @@ def rir_ism_span(room, source, mic_array, max_order, delay_filter_length, sound_
     fine = torch.isfinite(di) & (di < 4.0e18)
     top = torch.where(fine, di, torch.zeros_like(di)).max().to(torch.int64)
     return top + (delay_filter_length - delay_filter_length // 2)
+
+
+# ============================================================================= SoX effects with a loop over time
+def overdrive(waveform, gain, colour):
+    """torchaudio's ``functional.overdrive`` in elementwise torch operators around this package's ``lfilter`` (the recursion
+    ``v[n] = t[n] - t[n-1] + 0.995 v[n-1]`` is a first-order filter): ``(…, time)`` → the same, in the input's dtype.  The CPU path
+    of ``tac_amd::overdrive`` and its announced route on a device; differentiable."""
+    from . import _ops, _sox
+    if waveform.numel() == 0:
+        return torch.zeros_like(waveform, memory_format=torch.contiguous_format)
+    g, c = _sox.overdrive_constants(gain, colour)
+    t = waveform * g + c
+    t = torch.where(t < -1.0, torch.full_like(t, -2.0 / 3.0), torch.where(t > 1.0, torch.full_like(t, 2.0 / 3.0), t - t * t * t / 3.0))
+    a = torch.tensor([1.0, -0.995], dtype=torch.float64)
+    b = torch.tensor([1.0, -1.0], dtype=torch.float64)
+    v = _ops.call('lfilter', t, a, b, False)
+    return (waveform * 0.5 + v * 0.75).clamp(-1.0, 1.0).contiguous()
+
+
+def phaser(waveform, mod, L, gain_in, gain_out, decay):
+    """torchaudio's ``functional.phaser`` as the recursion ``y[n] = gain_in x[n] + decay y[n - d(n)]``, ``d(n) = L - mod[n % P] + 1``
+    (the closed form of its ring buffer), one column per step.  ``mod``: the LFO table as a sequence of HOST integers, so the
+    loop never reads the device.  In the input's dtype; differentiable; as slow as a loop over time is."""
+    if waveform.numel() == 0:
+        return torch.zeros_like(waveform, memory_format=torch.contiguous_format)
+    x = waveform.reshape(-1, waveform.shape[-1]) * gain_in
+    period = len(mod)
+    cols = []
+    for n, xn in enumerate(x.unbind(-1)):
+        p = n - (L - mod[n % period] + 1)
+        cols.append(xn + cols[p] * decay if p >= 0 else xn)
+    y = torch.stack(cols, dim=-1) * gain_out
+    return y.clamp(-1.0, 1.0).reshape(waveform.shape).contiguous()
+
+
+def flanger(waveform, plan):
+    """torchaudio's ``functional.flanger`` from a ``_sox.FlangerPlan``: ``(…, channel, time)`` → the same.  The ring buffer is a
+    list of columns ``w[i] = x[i] + fb delayed[i-1]``; the LFO values, their floors and fractions are HOST floats, so the loop
+    never reads the device.  In the input's dtype; differentiable."""
+    if waveform.numel() == 0:
+        return torch.zeros_like(waveform, memory_format=torch.contiguous_format)
+    channels, length = waveform.shape[-2], waveform.shape[-1]
+    x = waveform.reshape(-1, channels, length)
+    lfo = plan.lfo.tolist()
+    zero = torch.zeros_like(x[..., 0])
+    w, outs = [], []
+    last = zero
+    for i, xi in enumerate(x.unbind(-1)):
+        wi = xi + last * plan.fb
+        w.append(wi)
+        per_channel = []
+        for c in range(channels):
+            d = lfo[(i + plan.phases[c]) % plan.P]
+            k = int(d)
+            fr = d - k
+
+            def tap(back):      # the ring wraps: `Lb` back is the sample just written
+                back = back % plan.Lb
+                return w[i - back][:, c] if i - back >= 0 else zero[:, c]
+            d0, d1 = tap(k), tap(k + 1)
+            if plan.quadratic:
+                d2 = tap(k + 2) - d0
+                e1 = d1 - d0
+                per_channel.append(d0 + ((d2 * 0.5 - e1) * fr + (e1 * 2.0 - d2 * 0.5)) * fr)
+            else:
+                per_channel.append(d0 + (d1 - d0) * fr)
+        last = torch.stack(per_channel, dim=-1)
+        outs.append(xi * plan.in_gain + last * plan.delay_gain)
+    y = torch.stack(outs, dim=-1).clamp(-1.0, 1.0)
+    return y.reshape(waveform.shape).contiguous()

@@ -1153,6 +1153,109 @@ def sosfilt_rows(x, sos, clamp, reverse=False):
     return out
 
 
+# ----------------------------------------------------------------------------- SoX effects (csrc/sox_effects.hip)
+#: samples per tile of ``tac_overdrive_f32`` (lfilter's walk), of ``tac_phaser_f32`` and of the flanger's FIR path, the samples the
+#: flanger's feedback path stages per chunk, the longest delays the kernels hold in the LDS and the caps of their persistent
+#: grids per CU; checked against the library's own values at the first launch
+OVERDRIVE_TILE = LFILTER_TILE
+OVERDRIVE_BLOCKS_PER_CU = 2
+PHASER_TILE = 4096
+PHASER_MAX_DELAY = 1024
+PHASER_SEQ_MAX_DELAY = 256
+PHASER_BLOCKS_PER_CU = 1
+FLANGER_TILE = 4096
+FLANGER_CHUNK = 1024
+FLANGER_MAX_BLOCK = 64
+FLANGER_MAX_DELAY = 4096
+FLANGER_BLOCKS_PER_CU = 4
+FLANGER_FB_BLOCKS_PER_CU = 8
+
+_sox_checked = False
+
+
+def _sox_check():
+    global _sox_checked
+    if not _sox_checked:
+        h = _native.lib()
+        found = (h.tac_overdrive_tile(), h.tac_overdrive_blocks_per_cu(), h.tac_phaser_tile(), h.tac_phaser_max_delay(),
+                 h.tac_phaser_seq_max_delay(), h.tac_phaser_blocks_per_cu(), h.tac_flanger_tile(), h.tac_flanger_chunk(),
+                 h.tac_flanger_max_block(), h.tac_flanger_max_delay(), h.tac_flanger_blocks_per_cu(), h.tac_flanger_fb_blocks_per_cu())
+        said = (OVERDRIVE_TILE, OVERDRIVE_BLOCKS_PER_CU, PHASER_TILE, PHASER_MAX_DELAY, PHASER_SEQ_MAX_DELAY, PHASER_BLOCKS_PER_CU,
+                FLANGER_TILE, FLANGER_CHUNK, FLANGER_MAX_BLOCK, FLANGER_MAX_DELAY, FLANGER_BLOCKS_PER_CU, FLANGER_FB_BLOCKS_PER_CU)
+        if found != said:
+            raise RuntimeError('libtac_amd.so reports %r for the SoX effects\' tiles, delays and grids, _hip says %r' % (found, said))
+        _sox_checked = True
+
+
+def _sox_rows(x):
+    """``x`` as ``(rows, length)`` read where it lies when its leading dims collapse into one positive row stride over unit-stride
+    rows; copied otherwise (``lfilter_rows``' rule)"""
+    length = x.shape[-1]
+    rows = x.reshape(-1, length)
+    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+        rows = rows.contiguous()
+    return rows
+
+
+def sox_table(host, device):
+    """The device copy of a host LFO table (``_sox.phaser_plan`` / ``flanger_plan``), uploaded once per device and kept on the host
+    tensor object"""
+    return cached_on(host, '_tac_coef', ('sox', str(device)), lambda: host.to(device))
+
+
+def overdrive_covers(g, c):
+    return _native.lib().tac_overdrive_supported(float(g), float(c)) == _native.TAC_OK
+
+
+def overdrive_rows(x, g, c):
+    """``(…, L) -> (…, L)`` through ``tac_overdrive_f32``: one launch.  ``g``, ``c``: the linear gain and the offset."""
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        _sox_check()
+        rows = _sox_rows(x)
+        _launch('tac_overdrive_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], x.shape[-1], rows.stride(0), float(g), float(c),
+                _native.ptr(out))
+    return out
+
+
+def phaser_covers(L, P):
+    return _native.lib().tac_phaser_supported(int(L), int(P)) == _native.TAC_OK
+
+
+def phaser_rows(x, table, L, gain_in, gain_out, decay, sequential=False):
+    """``(…, L) -> (…, L)`` through ``tac_phaser_f32``: one launch.  ``table``: the int32 HOST tensor of the LFO period
+    (``_sox.phaser_plan``).  ``sequential`` launches the one-lane-per-row ablation variant instead (``tac_phaser_seq_f32``)."""
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        _sox_check()
+        rows = _sox_rows(x)
+        mod = sox_table(table, x.device)
+        _launch('tac_phaser_seq_f32' if sequential else 'tac_phaser_f32', x.device, (out,), _native.ptr(rows), rows.shape[0],
+                x.shape[-1], rows.stride(0), _native.ptr(mod), int(table.numel()), int(L), float(gain_in), float(decay),
+                float(gain_out), _native.ptr(out))
+    return out
+
+
+def flanger_covers(plan, channels):
+    return _native.lib().tac_flanger_supported(int(plan.Lb), int(plan.P), int(plan.W), int(channels)) == _native.TAC_OK
+
+
+def flanger_rows(x, plan):
+    """``(…, C, L) -> (…, C, L)`` through ``tac_flanger_f32``: one launch, the FIR path where ``plan.fb == 0`` and the
+    wave-per-row feedback path otherwise.  ``plan``: a ``_sox.FlangerPlan`` made for ``C`` channels."""
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        _sox_check()
+        channels = x.shape[-2]
+        rows = _sox_rows(x)
+        lfo = sox_table(plan.lfo, x.device)
+        phases = (ctypes.c_int32 * channels)(*plan.phases[:channels])
+        _launch('tac_flanger_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], channels, x.shape[-1], rows.stride(0),
+                _native.ptr(lfo), int(plan.P), phases, int(plan.Lb), int(plan.W), float(plan.fb), float(plan.in_gain),
+                float(plan.delay_gain), int(bool(plan.quadratic)), _native.ptr(out))
+    return out
+
+
 # ----------------------------------------------------------------------------- loudness (csrc/loudness.hip)
 #: samples of one row per tile of ``tac_loudness_f32`` (csrc/loudness.hip: LO_TILE), checked against the library's own value at the
 #: first launch, and the shortest hop its bins take (LO_C: at most one bin edge in a lane's chunk)

@@ -192,6 +192,25 @@ PROTOTYPES = {
     'tac_sosfilt_blocks_per_cu': (_I32, []),
     'tac_sosfilt_supported': (_INT, [_P, _I32]),
     'tac_sosfilt_f32': (_INT, [_P, _I64, _I64, _I64, _P, _I32, _INT, _INT, _P, _P]),
+    'tac_overdrive_tile': (_I32, []),
+    'tac_overdrive_blocks_per_cu': (_I32, []),
+    'tac_overdrive_supported': (_INT, [_D, _D]),
+    'tac_overdrive_f32': (_INT, [_P, _I64, _I64, _I64, _D, _D, _P, _P]),
+    'tac_phaser_tile': (_I32, []),
+    'tac_phaser_max_delay': (_I32, []),
+    'tac_phaser_seq_max_delay': (_I32, []),
+    'tac_phaser_blocks_per_cu': (_I32, []),
+    'tac_phaser_supported': (_INT, [_I32, _I32]),
+    'tac_phaser_f32': (_INT, [_P, _I64, _I64, _I64, _P, _I32, _I32, _D, _D, _D, _P, _P]),
+    'tac_phaser_seq_f32': (_INT, [_P, _I64, _I64, _I64, _P, _I32, _I32, _D, _D, _D, _P, _P]),
+    'tac_flanger_tile': (_I32, []),
+    'tac_flanger_chunk': (_I32, []),
+    'tac_flanger_max_block': (_I32, []),
+    'tac_flanger_max_delay': (_I32, []),
+    'tac_flanger_blocks_per_cu': (_I32, []),
+    'tac_flanger_fb_blocks_per_cu': (_I32, []),
+    'tac_flanger_supported': (_INT, [_I32, _I32, _I32, _I32]),
+    'tac_flanger_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _P, _I32, _P, _I32, _I32, _D, _D, _D, _INT, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -31,6 +31,7 @@ see them by name.
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
     tac_amd::sosfilt            cascade of up to 8 second-order sections along time in one launch, float64 between them (csrc/sosfilt.hip)
     tac_amd::lfilter_reverse, sosfilt_reverse   the two above run from the end of each row: filtfilt's second half (private)
+    tac_amd::overdrive, phaser, flanger         the SoX effects defined by a loop over time, one launch each (csrc/sox_effects.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -62,6 +63,7 @@ from . import _pitch as PT
 from . import _vad as VD
 from . import _beamform as BF
 from . import _resample as RS
+from . import _sox as SX
 
 NS = 'tac_amd'
 _lib = Library(NS, 'DEF')
@@ -459,6 +461,22 @@ def _sosfilt_hip_backward_of(reverse):
     return backward
 
 
+def _overdrive_hip_backward(saved, rest, needs, grads):
+    """d out / d x of ``overdrive``: the clamp's mask, the shaper's slope ``g (1 - t^2)`` inside [-1, 1] (zero outside) and, between
+    them, the adjoint of ``v = lfilter(t, (1, -0.995), (1, -1))`` — lfilter's kernel run from the end of each row.  The
+    elementwise steps are torch operators on the device; nothing here is the stock-torch route of the op."""
+    wave, y = saved[0], saved[1]
+    gain, colour = rest
+    if grads[0] is None or SX.inside(SX.OVERDRIVE_RANGES, gain=gain, colour=colour) is not None:
+        return None
+    g, c = SX.overdrive_constants(gain, colour)
+    gy = grads[0] * ((y > -1.0) & (y < 1.0))
+    t = wave.double() * g + c
+    slope = torch.where((t < -1.0) | (t > 1.0), torch.zeros_like(t), (1.0 - t * t) * g).float()
+    gt = H.lfilter_rows(gy * 0.75, (1.0, -1.0), (1.0, -0.995), False, reverse=True)
+    return [gy * 0.5 + slope * gt if needs[0] else None]
+
+
 def _fftconvolve_hip_backward(saved, rest, needs, grads):
     x, y = saved
     (n_fft,) = rest
@@ -524,7 +542,7 @@ def _add_noise_hip_backward(saved, rest, needs, grads):
     return [None if t is None else t.sum_to_size(ref.shape) for t, ref in zip(got, saved)]
 
 
-_HIP_BACKWARD = {'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
+_HIP_BACKWARD = {'overdrive': _overdrive_hip_backward, 'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
                  'mask_spans': _mask_spans_hip_backward, 'add_noise': _add_noise_hip_backward,
                  'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'resample_fit': _resample_fit_hip_backward, 'lfilter': _lfilter_hip_backward_of(False), 'lfilter_reverse': _lfilter_hip_backward_of(True), 'sosfilt': _sosfilt_hip_backward_of(False), 'sosfilt_reverse': _sosfilt_hip_backward_of(True), 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
@@ -1992,6 +2010,87 @@ _register('sosfilt_reverse', '(Tensor wave, Tensor sos, bool clamp) -> Tensor',
           save_output=lambda inputs: bool(inputs[2]))
 _register('lfilter_reverse', '(Tensor wave, Tensor a_coeffs, Tensor b_coeffs, bool clamp) -> Tensor', _lfilter_reverse_cuda,
           _lfilter_reverse_cpu, _lfilter_fake, 3, n_plain=1, save_output=lambda inputs: bool(inputs[3]))
+
+
+# ============================================================================= overdrive, phaser, flanger (SoX)
+def _sox_layout(wave):
+    """None where the SoX kernels read this tensor where it lies or after a plain copy, else the reason they do not: float32 only
+    (half precision is not widened: the composites keep the input's dtype), no expanded or reversed views"""
+    if wave.dtype != torch.float32:
+        return 'dtype %s' % str(wave.dtype).replace('torch.', '')
+    if any(st <= 0 for st, n in zip(wave.stride(), wave.shape) if n > 1):
+        return 'expanded or non-positive strides'
+    return None
+
+
+def _overdrive_cuda(wave, gain, colour):
+    if wave.numel() == 0:
+        return torch.empty_like(wave, memory_format=torch.contiguous_format)
+    reason = _sox_layout(wave) or SX.inside(SX.OVERDRIVE_RANGES, gain=gain, colour=colour)
+    if reason is not None:
+        _composite_route('overdrive', reason)
+        return C.overdrive(wave, gain, colour)
+    return H.overdrive_rows(wave, *SX.overdrive_constants(gain, colour))
+
+
+def _phaser_cpu(wave, sample_rate, gain_in, gain_out, delay_ms, decay, mod_speed, sinusoidal):
+    L, _, table = SX.phaser_plan(sample_rate, delay_ms, mod_speed, sinusoidal)
+    return C.phaser(wave, table.tolist(), L, gain_in, gain_out, decay)
+
+
+def _phaser_cuda(wave, sample_rate, gain_in, gain_out, delay_ms, decay, mod_speed, sinusoidal):
+    if wave.numel() == 0:
+        return torch.empty_like(wave, memory_format=torch.contiguous_format)
+    L, P, table = SX.phaser_plan(sample_rate, delay_ms, mod_speed, sinusoidal)
+    reason = _sox_layout(wave) or SX.inside(SX.PHASER_RANGES, gain_in=gain_in, delay_ms=delay_ms, decay=decay, mod_speed=mod_speed)
+    if reason is None and not math.isfinite(gain_out):
+        reason = 'gain_out = %r' % (gain_out,)
+    if reason is None and not H.phaser_covers(L, P):
+        reason = 'a delay of %d samples (the kernel holds %d)' % (L, H.PHASER_MAX_DELAY)
+    if reason is not None:
+        _composite_route('phaser', reason)
+        return C.phaser(wave, table.tolist(), L, gain_in, gain_out, decay)
+    return H.phaser_rows(wave, table, L, gain_in, gain_out, decay)
+
+
+def _flanger_plan(wave, sample_rate, delay, depth, regen, width, speed, phase, modulation, interpolation):
+    if wave.dim() < 2:
+        raise ValueError('flanger: expected a waveform of shape (…, channel, time), got %s' % (tuple(wave.shape),))
+    if wave.shape[-2] > SX.FLANGER_MAX_CHANNELS:
+        raise ValueError('flanger: at most %d channels, got %d' % (SX.FLANGER_MAX_CHANNELS, wave.shape[-2]))
+    return SX.flanger_plan(sample_rate, delay, depth, regen, width, speed, phase, modulation, interpolation, wave.shape[-2])
+
+
+def _flanger_cpu(wave, sample_rate, delay, depth, regen, width, speed, phase, modulation, interpolation):
+    return C.flanger(wave, _flanger_plan(wave, sample_rate, delay, depth, regen, width, speed, phase, modulation, interpolation))
+
+
+def _flanger_cuda(wave, sample_rate, delay, depth, regen, width, speed, phase, modulation, interpolation):
+    plan = _flanger_plan(wave, sample_rate, delay, depth, regen, width, speed, phase, modulation, interpolation)
+    if wave.numel() == 0:
+        return torch.empty_like(wave, memory_format=torch.contiguous_format)
+    reason = _sox_layout(wave) or SX.inside(SX.FLANGER_RANGES, delay=delay, depth=depth, regen=regen, width=width, speed=speed,
+                                            phase=phase)
+    if reason is None and not H.flanger_covers(plan, wave.shape[-2]):
+        reason = 'a delay line of %d samples (the kernel holds %d)' % (plan.Lb, H.FLANGER_MAX_DELAY)
+    if reason is not None:
+        _composite_route('flanger', reason)
+        return C.flanger(wave, plan)
+    return H.flanger_rows(wave, plan)
+
+
+def _sox_fake(wave, *args):
+    return torch.empty_like(wave, memory_format=torch.contiguous_format)
+
+
+# (overdrive's gradient is elementwise torch around lfilter's reverse launch, and needs the output for the clamp's mask; phaser and
+# flanger have no gradient kernel: their backward re-evaluates the composites, announced)
+_register('overdrive', '(Tensor waveform, float gain, float colour) -> Tensor', _overdrive_cuda, C.overdrive, _sox_fake, 1,
+          save_output=lambda inputs: True)
+_register('phaser', '(Tensor waveform, float sample_rate, float gain_in, float gain_out, float delay_ms, float decay, float mod_speed, '
+          'bool sinusoidal) -> Tensor', _phaser_cuda, _phaser_cpu, _sox_fake, 1)
+_register('flanger', '(Tensor waveform, float sample_rate, float delay, float depth, float regen, float width, float speed, float phase, '
+          'str modulation, str interpolation) -> Tensor', _flanger_cuda, _flanger_cpu, _sox_fake, 1)
 
 
 # ============================================================================= complex pairs

@@ -31,6 +31,7 @@ from . import _beamform
 from . import _resample
 from . import _specaug
 from . import _augment
+from . import _sox
 from ._bounded import Bounded
 from ._lazy import realize as _realize
 
@@ -39,7 +40,8 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'sosfilt', 'tf2sos', 'filtfilt', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
-           'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch']
+           'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
+           'overdrive', 'phaser', 'flanger']
 
 _call = _ops.call
 
@@ -671,6 +673,54 @@ def filtfilt(waveforms, a_coeffs, b_coeffs, clamp=True):
         sos = _filters.tf2sos(_hip.host_coeffs(b_coeffs), ha)
         return _call('sosfilt_reverse', _call('sosfilt', x, sos, False), sos, bool(clamp))
     return _call('lfilter_reverse', _call('lfilter', x, a_coeffs, b_coeffs, False), a_coeffs, b_coeffs, bool(clamp))
+
+
+def overdrive(waveform, gain=20, colour=20):
+    """``(…, time) → (…, time)``: torchaudio's ``functional.overdrive`` (SoX's effect).  With ``g = 10^(gain / 20)`` and
+    ``c = colour / 200``: ``t = g x + c`` shaped to ``-2/3`` below -1, ``2/3`` above 1 and ``t - t^3 / 3`` between; ``v[n] = t[n] -
+    t[n-1] + 0.995 v[n-1]`` from zero state; the result is ``clamp(0.5 x + 0.75 v, -1, 1)``.
+
+    float32 on a HIP device with ``gain`` and ``colour`` in SoX's ranges (0 to 100) runs ONE launch of the gfx950 kernel
+    (csrc/sox_effects.hip): float32 is read and written once around a float64 recursion on lfilter's tile walk.  Its gradient
+    w.r.t. the waveform is lfilter's kernel run from the end of each row between elementwise torch operators.  Other dtypes,
+    expanded views, parameters outside the ranges and CPU tensors take ``_composite.overdrive`` (elementwise operators around
+    ``lfilter``), announced with ``CompositeRouteWarning`` on a device."""
+    x = _waveform(waveform, 'overdrive')
+    return _call('overdrive', x, float(gain), float(colour))
+
+
+def phaser(waveform, sample_rate, gain_in=0.4, gain_out=0.74, delay_ms=3.0, decay=0.4, mod_speed=0.5, sinusoidal=True):
+    """``(…, time) → (…, time)``: torchaudio's ``functional.phaser`` (SoX's effect).  With ``L = int(delay_ms sample_rate / 1000 +
+    0.5)`` delay samples and an LFO of ``P = int(sample_rate / mod_speed + 0.5)`` integer values ``m`` in ``[1, L]`` (sine or
+    triangle): ``y[n] = gain_in x[n] + decay y[n - (L - m[n mod P] + 1)]`` from zero state, and the result is
+    ``clamp(gain_out y, -1, 1)``.  ``L < 1``, ``P < 1`` and ``sample_rate <= 0`` are a ``ValueError``.
+
+    float32 on a HIP device with the parameters in SoX's ranges (``gain_in`` 0 to 1, ``delay_ms`` 0 to 5, ``decay`` 0 to 0.99,
+    ``mod_speed`` 0.1 to 2) and ``L <= 1024`` runs ONE launch of the gfx950 kernel (csrc/sox_effects.hip): every sample has one
+    parent, and pointer jumping in float64 over tiles held in the LDS solves the recursion in parallel.  Everything else — and the
+    gradient — takes the time loop of ``_composite.phaser``, announced with ``CompositeRouteWarning`` on a device."""
+    x = _waveform(waveform, 'phaser')
+    return _call('phaser', x, float(sample_rate), float(gain_in), float(gain_out), float(delay_ms), float(decay), float(mod_speed),
+                 bool(sinusoidal))
+
+
+def flanger(waveform, sample_rate, delay=0.0, depth=2.0, regen=0.0, width=71.0, speed=0.5, phase=25.0, modulation='sinusoidal',
+            interpolation='linear'):
+    """``(…, channel, time) → (…, channel, time)``: torchaudio's ``functional.flanger`` (SoX's effect), at most 4 channels.  A
+    delay line read at the LFO's position ``D`` (``delay`` to ``delay + depth`` ms, ``speed`` Hz, channel ``c`` shifted by
+    ``c * phase`` percent of a period) with ``linear`` or ``quadratic`` interpolation; ``regen`` percent of the delayed signal is
+    fed back into the line and ``width`` percent of it is mixed into the result, which is clipped to [-1, 1].  More than 4
+    channels and unknown ``modulation`` / ``interpolation`` names are a ``ValueError``.
+
+    float32 on a HIP device with the parameters in SoX's ranges (``delay`` 0 to 30, ``depth`` 0 to 10, ``regen`` -95 to 95,
+    ``width`` 0 to 100, ``speed`` 0.1 to 10, ``phase`` 0 to 100) and a delay line of at most 4096 samples runs ONE launch of the
+    gfx950 kernel (csrc/sox_effects.hip).  ``regen == 0`` is a streaming time-varying FIR.  Otherwise a wave walks each (entry,
+    channel) row and advances ``min(64, 1 + delay in samples)`` samples per step — with ``delay = 0`` that is ONE sample per
+    step, latency-bound by construction.  Everything else — and the gradient — takes the time loop of ``_composite.flanger``,
+    announced with ``CompositeRouteWarning`` on a device."""
+    x = _waveform(waveform, 'flanger')
+    return _call('flanger', x, float(sample_rate), float(delay), float(depth), float(regen), float(width), float(speed), float(phase),
+                 modulation, interpolation)
 
 
 def biquad(waveforms, b0, b1, b2, a0, a1, a2):

@@ -479,6 +479,54 @@ class SosFilt(_ModuleNoStateBuffers):
         return self.__class__.__name__ + '(sections={}, clamp={})'.format(self.sos.shape[0], self.clamp)
 
 
+class Overdrive(nn.Module):
+    """``functional.overdrive`` as a layer: ``(…, time)`` → ``(…, time)``.  No buffers."""
+
+    def __init__(self, gain=20, colour=20):
+        super(Overdrive, self).__init__()
+        self.gain, self.colour = float(gain), float(colour)
+
+    def forward(self, waveform):
+        return F.overdrive(waveform, self.gain, self.colour)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(gain={}, colour={})'.format(self.gain, self.colour)
+
+
+class Phaser(nn.Module):
+    """``functional.phaser`` as a layer: ``(…, time)`` → ``(…, time)``.  No buffers: the LFO table is kept by value on the host
+    and per device."""
+
+    def __init__(self, sample_rate, gain_in=0.4, gain_out=0.74, delay_ms=3.0, decay=0.4, mod_speed=0.5, sinusoidal=True):
+        super(Phaser, self).__init__()
+        self.args = (float(sample_rate), float(gain_in), float(gain_out), float(delay_ms), float(decay), float(mod_speed),
+                     bool(sinusoidal))
+        F._sox.phaser_plan(self.args[0], self.args[3], self.args[5], self.args[6])      # (argument errors at construction)
+
+    def forward(self, waveform):
+        return F.phaser(waveform, *self.args)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sample_rate={}, gain_in={}, gain_out={}, delay_ms={}, decay={}, mod_speed={}, sinusoidal={})'.format(*self.args)
+
+
+class Flanger(nn.Module):
+    """``functional.flanger`` as a layer: ``(…, channel, time)`` → ``(…, channel, time)``.  No buffers."""
+
+    def __init__(self, sample_rate, delay=0.0, depth=2.0, regen=0.0, width=71.0, speed=0.5, phase=25.0, modulation='sinusoidal',
+                 interpolation='linear'):
+        super(Flanger, self).__init__()
+        self.args = (float(sample_rate), float(delay), float(depth), float(regen), float(width), float(speed), float(phase),
+                     modulation, interpolation)
+        F._sox.flanger_plan(*self.args, 1)                                              # (argument errors at construction)
+
+    def forward(self, waveform):
+        return F.flanger(waveform, *self.args)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sample_rate={}, delay={}, depth={}, regen={}, width={}, speed={}, phase={}, modulation={!r}, interpolation={!r})'.format(*self.args)
+
+
 class Preemphasis(_ModuleNoStateBuffers):
     """``functional.preemphasis`` as a layer: ``y[n] = x[n] - coeff x[n-1]``.  No buffers: ``coeff`` is a Python float, and the
     two float64 host tensors the op takes are plain attributes (they stay float64 on the host whatever ``.to()`` is given)."""
