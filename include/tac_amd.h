@@ -1062,6 +1062,48 @@ int tac_flanger_f32(const float* x, int64_t rows, int32_t channels, int64_t leng
                     const int32_t* phases, int32_t Lb, int32_t W, double fb, double in_gain, double delay_gain, int quadratic,
                     float* out, void* stream);
 
+/* (35) functional.oscillator_bank / filter_waveform and their gradients (csrc/ddsp.hip).  float32 in and out, no atomics, one writer
+ *      per element, bit-identical from run to run; the forward results do not depend on what else the batch holds.
+ *      oscillator_bank: f, a are (rows, time, n) tensors read through their own strides in elements (row, time, oscillator; >= 0, any
+ *        layout — the loads walk whichever of time / oscillator has the smaller stride); out is dense (rows, time) for reduction
+ *        0 (sum) and 1 (mean), (rows, time, n) for 2 (none).  The phase is a 64-bit integer accumulator of frac(f / sample_rate)
+ *        turns (float64 division); sin / cos are float64; a' = 0 where |f| >= sample_rate / 2.  A workgroup owns a (row, span) of
+ *        steps, tac_oscbank_spans(rows, time) spans per row: one where rows >= 2 x CUs or time <= tac_oscbank_span(), spans of
+ *        tac_oscbank_span() steps otherwise, walked in tiles of tac_oscbank_tile() steps, tac_oscbank_chunk() per lane.  workspace:
+ *        DEVICE, 16 * rows * spans * n bytes, 8-byte aligned (forward: may be NULL with one span).  Forward: one launch, two with
+ *        more than one span; gradient: two launches, three with more than one span.  g: the upstream gradient through its strides
+ *        (zero strides allowed; g_stride_n is ignored unless reduction == 2); grad_a, grad_f: dense (rows, time, n).
+ *        n <= tac_oscbank_max_oscillators() (TAC_E_UNSUPPORTED); sample_rate > 0 and finite (TAC_E_INVALID).
+ *      filter_waveform: x is (rows, length) with unit stride along time; h holds n_filters filters of taps taps per row: row r reads
+ *        h + (r / h_div) h_stride_outer + (r % h_div) h_stride_inner + j h_stride_f + k h_stride_k (zero strides share filters).
+ *        C = ceil(length / n_filters); out[t] = sum_k h_{(t + shift - k) / C}[k] x[t + shift - k] (adjoint == 0) or
+ *        out[m] = sum_k h_{m / C}[k] x[m - shift + k] (adjoint != 0: the gradient w.r.t. the waveform, x the upstream gradient); out
+ *        is dense (rows, length); tiles of tac_filter_waveform_tile() outputs.  0 <= shift <= taps - 1 (TAC_E_INVALID), taps <=
+ *        tac_filter_waveform_max_taps() (TAC_E_UNSUPPORTED).  grad_kernels: part is dense (rows, n_filters, P, taps), P =
+ *        tac_filter_waveform_pieces(length, n_filters) pieces of tac_filter_waveform_piece() samples per chunk; part[r][j][p][k] =
+ *        sum over the piece's samples m < length of x[m] g[m - shift + k]: the caller adds pieces and sharing rows. */
+int32_t tac_oscbank_tile(void);
+int32_t tac_oscbank_chunk(void);
+int32_t tac_oscbank_span(void);
+int32_t tac_oscbank_max_oscillators(void);
+int64_t tac_oscbank_spans(int64_t rows, int64_t time);
+int tac_oscbank_f32(const float* f, const float* a, int64_t rows, int64_t time, int64_t n, int64_t f_stride_r, int64_t f_stride_t,
+                    int64_t f_stride_n, int64_t a_stride_r, int64_t a_stride_t, int64_t a_stride_n, double sample_rate,
+                    int reduction, void* workspace, float* out, void* stream);
+int tac_oscbank_grad_f32(const float* f, const float* a, const float* g, int64_t rows, int64_t time, int64_t n, int64_t f_stride_r,
+                         int64_t f_stride_t, int64_t f_stride_n, int64_t a_stride_r, int64_t a_stride_t, int64_t a_stride_n,
+                         int64_t g_stride_r, int64_t g_stride_t, int64_t g_stride_n, double sample_rate, int reduction,
+                         void* workspace, float* grad_a, float* grad_f, void* stream);
+int32_t tac_filter_waveform_tile(void);
+int32_t tac_filter_waveform_max_taps(void);
+int32_t tac_filter_waveform_piece(void);
+int64_t tac_filter_waveform_pieces(int64_t length, int64_t n_filters);
+int tac_filter_waveform_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* h, int64_t h_div,
+                            int64_t h_stride_outer, int64_t h_stride_inner, int64_t h_stride_f, int64_t h_stride_k, int64_t n_filters,
+                            int64_t taps, int64_t shift, int adjoint, float* out, void* stream);
+int tac_filter_waveform_grad_kernels_f32(const float* x, int64_t stride_r, const float* g, int64_t g_stride_r, int64_t rows,
+                                         int64_t length, int64_t n_filters, int64_t taps, int64_t shift, float* part, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

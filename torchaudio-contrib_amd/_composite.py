@@ -1240,3 +1240,53 @@ def flanger(waveform, plan):
         outs.append(xi * plan.in_gain + last * plan.delay_gain)
     y = torch.stack(outs, dim=-1).clamp(-1.0, 1.0)
     return y.reshape(waveform.shape).contiguous()
+
+
+def oscillator_bank(frequencies, amplitudes, sample_rate, reduction, dtype=torch.float64):
+    """torchaudio's ``prototype.functional.oscillator_bank`` in torch operators, literally: ``(…, time, N)`` frequencies and
+    amplitudes → ``(…, time)`` (``'sum'`` / ``'mean'``) or ``(…, time, N)`` (``'none'``).  The increments ``2 pi f / sample_rate mod
+    2 pi`` are formed in the input's dtype, accumulated along time in ``dtype`` and cast back before the sine; amplitudes at and
+    beyond Nyquist are zeroed (host tensors warn about it, as torchaudio does; on a device that would be a read-back).  The CPU
+    path of ``tac_amd::oscillator_bank`` and its announced route on a device; differentiable."""
+    invalid = frequencies.abs() >= sample_rate / 2
+    if not frequencies.is_cuda and frequencies.numel() and bool(invalid.any()):
+        import warnings
+        warnings.warn('Some frequencies are above nyquist frequency. Setting the corresponding amplitude to zero. '
+                      'This might cause numerically unstable gradient.')
+    amplitudes = torch.where(invalid, torch.zeros((), dtype=amplitudes.dtype, device=amplitudes.device), amplitudes)
+    freqs = frequencies * TWO_PI / sample_rate % TWO_PI
+    phases = torch.cumsum(freqs, dim=-2, dtype=dtype)
+    if phases.dtype != freqs.dtype:
+        phases = phases.to(freqs.dtype)
+    waveform = amplitudes * torch.sin(phases)
+    if reduction == 'sum':
+        return waveform.sum(-1)
+    if reduction == 'mean':
+        return waveform.mean(-1)
+    return waveform
+
+
+def filter_waveform(waveform, kernels, delay_compensation):
+    """torchaudio's ``prototype.functional.filter_waveform`` in torch operators: the waveform ``(…, T)`` is cut into ``F`` chunks of
+    ``C = ceil(T / F)`` samples, chunk ``j`` is convolved with ``kernels[…, j, :]`` (``K`` taps) through an FFT of ``C + K - 1``
+    points, and the chunks' results are overlap-added (``fold``); the result is read from sample ``delay_compensation`` (``K // 2``
+    where negative) on.  ``kernels``: ``(F, K)`` or ``(…, F, K)`` broadcast against the waveform's leading dims.  The CPU path of
+    ``tac_amd::filter_waveform`` and its announced route on a device; differentiable."""
+    T = waveform.shape[-1]
+    F, K = kernels.shape[-2:]
+    lead = tuple(waveform.shape[:-1])
+    if waveform.numel() == 0:
+        return torch.zeros_like(waveform, memory_format=torch.contiguous_format)
+    if waveform.dtype in (torch.float16, torch.bfloat16):       # (the FFT takes half precision at powers of two only)
+        return filter_waveform(waveform.float(), kernels.float(), delay_compensation).to(waveform.dtype)
+    C = -(-T // F)
+    s = delay_compensation if delay_compensation >= 0 else K // 2
+    x = TF.pad(waveform, (0, C * F - T)).reshape(lead + (F, C))
+    n = C + K - 1
+    seg = torch.fft.irfft(torch.fft.rfft(x, n=n) * torch.fft.rfft(kernels, n=n), n=n)
+    rows = 1
+    for d in lead:
+        rows *= d
+    seg = seg.expand(lead + (F, n)).reshape(rows, F, n).transpose(1, 2)
+    full = TF.fold(seg, output_size=(1, C * F + K - 1), kernel_size=(1, n), stride=(1, C)).reshape(lead + (C * F + K - 1,))
+    return full[..., s:s + T].contiguous()

@@ -1256,6 +1256,101 @@ def flanger_rows(x, plan):
     return out
 
 
+# ----------------------------------------------------------------------------- oscillator_bank / filter_waveform (csrc/ddsp.hip)
+#: steps per tile, per lane and per span of ``tac_oscbank_f32``, the oscillators whose carries it holds, outputs per tile of
+#: ``tac_filter_waveform_f32``, its longest filter and the samples per piece of the kernels' gradient; checked against the
+#: library's own values at the first launch
+OSCBANK_TILE = 256
+OSCBANK_CHUNK = 8
+OSCBANK_SPAN = 2048
+OSCBANK_MAX_OSCILLATORS = 1024
+FILTER_WAVEFORM_TILE = 1024
+FILTER_WAVEFORM_MAX_TAPS = 768
+FILTER_WAVEFORM_PIECE = 2048
+_OSCBANK_REDUCTIONS = {'sum': 0, 'mean': 1, 'none': 2}
+
+_ddsp_checked = False
+
+
+def _ddsp_check():
+    global _ddsp_checked
+    if not _ddsp_checked:
+        h = _native.lib()
+        found = (h.tac_oscbank_tile(), h.tac_oscbank_chunk(), h.tac_oscbank_span(), h.tac_oscbank_max_oscillators(),
+                 h.tac_filter_waveform_tile(), h.tac_filter_waveform_max_taps(), h.tac_filter_waveform_piece())
+        said = (OSCBANK_TILE, OSCBANK_CHUNK, OSCBANK_SPAN, OSCBANK_MAX_OSCILLATORS, FILTER_WAVEFORM_TILE, FILTER_WAVEFORM_MAX_TAPS,
+                FILTER_WAVEFORM_PIECE)
+        if found != said:
+            raise RuntimeError('libtac_amd.so reports %r for the DDSP kernels\' tiles and limits, _hip says %r' % (found, said))
+        _ddsp_checked = True
+
+
+def _oscbank_workspace(t3):
+    """the int64 workspace of the span totals (16 bytes per row, span and oscillator) and the spans per row"""
+    rows, T, N = t3.shape
+    with _native.on_device(t3.device):
+        spans = int(_native.lib().tac_oscbank_spans(rows, T))
+    return torch.empty(2 * rows * spans * N, dtype=torch.int64, device=t3.device), spans
+
+
+def oscillator_bank_rows(f, a, sample_rate, reduction):
+    """``(…, T, N)`` frequencies and amplitudes → ``(…, T)`` (``(…, T, N)`` for ``'none'``) through ``tac_oscbank_f32``: one
+    launch, two where a row is cut into spans.  Both tensors are read through their strides, whichever axis is contiguous."""
+    T, N = f.shape[-2:]
+    out = _empty(tuple(f.shape) if reduction == 'none' else tuple(f.shape[:-1]), device=f.device)
+    if out.numel():
+        _ddsp_check()
+        f3, a3 = f.reshape(-1, T, N), a.reshape(-1, T, N)
+        work, _ = _oscbank_workspace(f3)
+        _launch('tac_oscbank_f32', f.device, (out,), _native.ptr(f3), _native.ptr(a3), f3.shape[0], T, N, *f3.stride(), *a3.stride(),
+                float(sample_rate), _OSCBANK_REDUCTIONS[reduction], _native.ptr(work), _native.ptr(out))
+    return out
+
+
+def oscillator_bank_grad_rows(f, a, g, sample_rate, reduction):
+    """``(d amplitudes, d frequencies)``, both dense ``(…, T, N)``, through ``tac_oscbank_grad_f32``: the phase is recomputed, the
+    frequency gradient is a float64 suffix sum walked from the end of each row.  ``g`` is read through its strides (an expanded
+    upstream gradient is not copied)."""
+    T, N = f.shape[-2:]
+    ga, gf = _empty(tuple(f.shape), device=f.device), _empty(tuple(f.shape), device=f.device)
+    if ga.numel():
+        _ddsp_check()
+        f3, a3 = f.reshape(-1, T, N), a.reshape(-1, T, N)
+        g3 = g.reshape(-1, T, N) if reduction == 'none' else g.reshape(-1, T, 1)
+        work, _ = _oscbank_workspace(f3)
+        _launch('tac_oscbank_grad_f32', f.device, (ga, gf), _native.ptr(f3), _native.ptr(a3), _native.ptr(g3), f3.shape[0], T, N,
+                *f3.stride(), *a3.stride(), *g3.stride(), float(sample_rate), _OSCBANK_REDUCTIONS[reduction], _native.ptr(work),
+                _native.ptr(ga), _native.ptr(gf))
+    return ga, gf
+
+
+def filter_waveform_rows(x, kernels, plan, shift, adjoint=False):
+    """``(…, T) -> (…, T)`` through ``tac_filter_waveform_f32``: one launch.  ``plan``: ``_ddsp.kernel_rows`` of the kernels;
+    ``adjoint`` computes the gradient w.r.t. the waveform from the upstream gradient ``x``."""
+    out = _empty(tuple(x.shape), device=x.device)
+    if out.numel():
+        _ddsp_check()
+        rows = _sox_rows(x)
+        F, K = kernels.shape[-2:]
+        _launch('tac_filter_waveform_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], x.shape[-1], rows.stride(0),
+                _native.ptr(kernels), plan[0], plan[1], plan[2], kernels.stride(-2), kernels.stride(-1), F, K, int(shift),
+                int(bool(adjoint)), _native.ptr(out))
+    return out
+
+
+def filter_waveform_grad_kernels_rows(x, g, n_filters, taps, shift):
+    """``(…, F, K)``: every row's own gradient w.r.t. its filters through ``tac_filter_waveform_grad_kernels_f32`` (one launch of
+    per-piece partial sums) and one ``torch.sum`` over the pieces of long chunks; the caller adds the rows that share filters."""
+    _ddsp_check()
+    xr, gr = _sox_rows(x), _sox_rows(g)
+    pieces = int(_native.lib().tac_filter_waveform_pieces(x.shape[-1], n_filters))
+    part = _empty((xr.shape[0], n_filters, pieces, taps), device=x.device)
+    _launch('tac_filter_waveform_grad_kernels_f32', x.device, (part,), _native.ptr(xr), xr.stride(0), _native.ptr(gr), gr.stride(0),
+            xr.shape[0], x.shape[-1], n_filters, taps, int(shift), _native.ptr(part))
+    part = part[:, :, 0] if pieces == 1 else part.sum(2)
+    return part.reshape(tuple(x.shape[:-1]) + (n_filters, taps))
+
+
 # ----------------------------------------------------------------------------- loudness (csrc/loudness.hip)
 #: samples of one row per tile of ``tac_loudness_f32`` (csrc/loudness.hip: LO_TILE), checked against the library's own value at the
 #: first launch, and the shortest hop its bins take (LO_C: at most one bin edge in a lane's chunk)

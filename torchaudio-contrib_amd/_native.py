@@ -211,6 +211,19 @@ PROTOTYPES = {
     'tac_flanger_fb_blocks_per_cu': (_I32, []),
     'tac_flanger_supported': (_INT, [_I32, _I32, _I32, _I32]),
     'tac_flanger_f32': (_INT, [_P, _I64, _I32, _I64, _I64, _P, _I32, _P, _I32, _I32, _D, _D, _D, _INT, _P, _P]),
+    'tac_oscbank_tile': (_I32, []),
+    'tac_oscbank_chunk': (_I32, []),
+    'tac_oscbank_span': (_I32, []),
+    'tac_oscbank_max_oscillators': (_I32, []),
+    'tac_oscbank_spans': (_I64, [_I64, _I64]),
+    'tac_oscbank_f32': (_INT, [_P, _P, _I64, _I64, _I64] + [_I64] * 6 + [_D, _INT, _P, _P, _P]),
+    'tac_oscbank_grad_f32': (_INT, [_P, _P, _P, _I64, _I64, _I64] + [_I64] * 9 + [_D, _INT, _P, _P, _P, _P]),
+    'tac_filter_waveform_tile': (_I32, []),
+    'tac_filter_waveform_max_taps': (_I32, []),
+    'tac_filter_waveform_piece': (_I32, []),
+    'tac_filter_waveform_pieces': (_I64, [_I64, _I64]),
+    'tac_filter_waveform_f32': (_INT, [_P, _I64, _I64, _I64, _P] + [_I64] * 8 + [_INT, _P, _P]),
+    'tac_filter_waveform_grad_kernels_f32': (_INT, [_P, _I64, _P, _I64] + [_I64] * 5 + [_P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -64,6 +64,7 @@ from . import _vad as VD
 from . import _beamform as BF
 from . import _resample as RS
 from . import _sox as SX
+from . import _ddsp as DD
 
 NS = 'tac_amd'
 _lib = Library(NS, 'DEF')
@@ -477,6 +478,75 @@ def _overdrive_hip_backward(saved, rest, needs, grads):
     return [gy * 0.5 + slope * gt if needs[0] else None]
 
 
+def _ddsp_layout(*tensors):
+    """None where the DDSP kernels read these tensors as they lie (float32, every dim of more than one element at a positive
+    stride), else the reason they do not; half precision is not widened here"""
+    for t in tensors:
+        if t.dtype != torch.float32:
+            return 'dtype %s' % str(t.dtype).replace('torch.', '')
+        if any(st <= 0 for st, n in zip(t.stride(), t.shape) if n > 1):
+            return 'an expanded view or non-positive strides'
+    return None
+
+
+def _oscillator_bank_route(frequencies, amplitudes):
+    reason = _ddsp_layout(frequencies, amplitudes)
+    if reason is None and frequencies.shape[-1] > H.OSCBANK_MAX_OSCILLATORS:
+        reason = '%d oscillators (the kernel holds %d)' % (frequencies.shape[-1], H.OSCBANK_MAX_OSCILLATORS)
+    return reason
+
+
+def _oscillator_bank_hip_backward(saved, rest, needs, grads):
+    """both gradients from one entry (csrc/ddsp.hip): the phase is recomputed, nothing was saved but the inputs"""
+    frequencies, amplitudes = saved
+    sample_rate, reduction = rest[:2]
+    if grads[0] is None or not frequencies.numel() or _oscillator_bank_route(frequencies, amplitudes) is not None:
+        return None
+    ga, gf = H.oscillator_bank_grad_rows(frequencies, amplitudes, grads[0], sample_rate, reduction)
+    return [gf if needs[0] else None, ga if needs[1] else None]
+
+
+def _filter_waveform_route(waveform, kernels):
+    """(reason, plan): the kernels' row plan where the filter kernels take the call"""
+    reason = _hip_dtype_f32(waveform, kernels)
+    if reason is None and any(st <= 0 for st, n in zip(waveform.stride(), waveform.shape) if n > 1):
+        reason = 'an expanded view or non-positive strides'
+    if reason is None and any(st <= 0 for st, n in zip(kernels.stride()[-2:], kernels.shape[-2:]) if n > 1):
+        reason = 'expanded kernels'
+    if reason is None and kernels.shape[-1] > H.FILTER_WAVEFORM_MAX_TAPS:
+        reason = '%d taps (the kernel holds %d)' % (kernels.shape[-1], H.FILTER_WAVEFORM_MAX_TAPS)
+    plan = DD.kernel_rows(tuple(waveform.shape[:-1]), kernels) if reason is None else None
+    if reason is None and plan is None:
+        reason = 'kernels whose leading dims do not collapse into two strides'
+    return reason, plan
+
+
+def _hip_dtype_f32(*tensors):
+    for t in tensors:
+        if t.dtype != torch.float32:
+            return 'dtype %s' % str(t.dtype).replace('torch.', '')
+    return None
+
+
+def _filter_waveform_hip_backward(saved, rest, needs, grads):
+    """d waveform: the forward kernel's adjoint mode on the upstream gradient; d kernels: per-row partial sums from the gradient
+    kernel, the rows that share filters added by one ``sum_to_size``"""
+    waveform, kernels = saved
+    if grads[0] is None or not waveform.numel():
+        return None
+    reason, plan = _filter_waveform_route(waveform, kernels)
+    if reason is not None:
+        return None
+    F, K = kernels.shape[-2:]
+    s = DD.filter_shift(K, rest[0])
+    gx = H.filter_waveform_rows(grads[0], kernels, plan, s, adjoint=True) if needs[0] else None
+    gh = None
+    if needs[1]:
+        gh = H.filter_waveform_grad_kernels_rows(waveform, grads[0], F, K, s)
+        gh = gh.reshape(-1, F, K).sum(0) if kernels.dim() == 2 else gh.sum_to_size(kernels.shape)
+    return [gx, gh]
+
+
 def _fftconvolve_hip_backward(saved, rest, needs, grads):
     x, y = saved
     (n_fft,) = rest
@@ -542,7 +612,8 @@ def _add_noise_hip_backward(saved, rest, needs, grads):
     return [None if t is None else t.sum_to_size(ref.shape) for t, ref in zip(got, saved)]
 
 
-_HIP_BACKWARD = {'overdrive': _overdrive_hip_backward, 'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
+_HIP_BACKWARD = {'overdrive': _overdrive_hip_backward, 'oscillator_bank': _oscillator_bank_hip_backward,
+                 'filter_waveform': _filter_waveform_hip_backward,'sliding_window_cmn': _sliding_window_cmn_hip_backward, 'compute_deltas': _compute_deltas_hip_backward,
                  'mask_spans': _mask_spans_hip_backward, 'add_noise': _add_noise_hip_backward,
                  'stft': _stft_hip_backward, 'fftconvolve': _fftconvolve_hip_backward, 'dct': _dct_hip_backward, 'resample': _resample_hip_backward, 'resample_fit': _resample_fit_hip_backward, 'lfilter': _lfilter_hip_backward_of(False), 'lfilter_reverse': _lfilter_hip_backward_of(True), 'sosfilt': _sosfilt_hip_backward_of(False), 'sosfilt_reverse': _sosfilt_hip_backward_of(True), 'istft': _istft_hip_backward, 'spectrogram': _spectrogram_hip_backward,
                  'melspectrogram': _melspectrogram_hip_backward, 'apply_filterbank': _apply_filterbank_hip_backward,
@@ -2091,6 +2162,52 @@ _register('phaser', '(Tensor waveform, float sample_rate, float gain_in, float g
           'bool sinusoidal) -> Tensor', _phaser_cuda, _phaser_cpu, _sox_fake, 1)
 _register('flanger', '(Tensor waveform, float sample_rate, float delay, float depth, float regen, float width, float speed, float phase, '
           'str modulation, str interpolation) -> Tensor', _flanger_cuda, _flanger_cpu, _sox_fake, 1)
+
+
+# ============================================================================= oscillator_bank / filter_waveform
+def _oscillator_bank_cpu(frequencies, amplitudes, sample_rate, reduction, dtype):
+    DD.check_oscillator_bank(frequencies, amplitudes, sample_rate, reduction, dtype)
+    return C.oscillator_bank(frequencies, amplitudes, sample_rate, reduction, dtype)
+
+
+def _oscillator_bank_cuda(frequencies, amplitudes, sample_rate, reduction, dtype):
+    DD.check_oscillator_bank(frequencies, amplitudes, sample_rate, reduction, dtype)
+    _same_device('oscillator_bank', frequencies, amplitudes)
+    if frequencies.numel() == 0:
+        return _oscillator_bank_fake(frequencies, amplitudes, sample_rate, reduction, dtype)
+    reason = _oscillator_bank_route(frequencies, amplitudes)
+    if reason is not None:
+        _composite_route('oscillator_bank', reason)
+        return C.oscillator_bank(frequencies, amplitudes, sample_rate, reduction, dtype)
+    return H.oscillator_bank_rows(frequencies, amplitudes, sample_rate, reduction)
+
+
+def _oscillator_bank_fake(frequencies, amplitudes, sample_rate, reduction, dtype):
+    shape = tuple(frequencies.shape) if reduction == 'none' else tuple(frequencies.shape[:-1])
+    return torch.empty(shape, dtype=frequencies.dtype, device=frequencies.device)
+
+
+def _filter_waveform_cpu(waveform, kernels, delay_compensation):
+    DD.check_filter_waveform(waveform, kernels, delay_compensation)
+    return C.filter_waveform(waveform, kernels, delay_compensation)
+
+
+def _filter_waveform_cuda(waveform, kernels, delay_compensation):
+    s = DD.check_filter_waveform(waveform, kernels, delay_compensation)
+    _same_device('filter_waveform', waveform, kernels)
+    if waveform.numel() == 0:
+        return torch.empty_like(waveform, memory_format=torch.contiguous_format)
+    reason, plan = _filter_waveform_route(waveform, kernels)
+    if reason is not None:
+        _composite_route('filter_waveform', reason)
+        return C.filter_waveform(waveform, kernels, delay_compensation)
+    return H.filter_waveform_rows(waveform, kernels, plan, s)
+
+
+_register('oscillator_bank', '(Tensor frequencies, Tensor amplitudes, float sample_rate, str reduction, ScalarType dtype) -> Tensor',
+          _oscillator_bank_cuda, _oscillator_bank_cpu, _oscillator_bank_fake, 2)
+_register('filter_waveform', '(Tensor waveform, Tensor kernels, int delay_compensation) -> Tensor', _filter_waveform_cuda,
+          _filter_waveform_cpu, _sox_fake, 2)
 
 
 # ============================================================================= complex pairs

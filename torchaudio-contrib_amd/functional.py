@@ -32,6 +32,7 @@ from . import _resample
 from . import _specaug
 from . import _augment
 from . import _sox
+from . import _ddsp
 from ._bounded import Bounded
 from ._lazy import realize as _realize
 
@@ -41,7 +42,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
            'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
-           'overdrive', 'phaser', 'flanger']
+           'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform']
 
 _call = _ops.call
 
@@ -721,6 +722,44 @@ def flanger(waveform, sample_rate, delay=0.0, depth=2.0, regen=0.0, width=71.0, 
     x = _waveform(waveform, 'flanger')
     return _call('flanger', x, float(sample_rate), float(delay), float(depth), float(regen), float(width), float(speed), float(phase),
                  modulation, interpolation)
+
+
+def oscillator_bank(frequencies, amplitudes, sample_rate, reduction='sum', dtype=torch.float64):
+    """``(…, time, N)`` instantaneous frequencies (Hz) and amplitudes → ``(…, time)`` (``reduction`` ``'sum'`` / ``'mean'`` over the
+    ``N`` oscillators) or ``(…, time, N)`` (``'none'``): torchaudio's ``prototype.functional.oscillator_bank``.  With ``inc = (2 pi f
+    / sample_rate) mod 2 pi`` and ``phi[t] = sum_{u <= t} inc[u]``: ``y[t, n] = a'[t, n] sin phi[t, n]``, ``a' = 0`` where ``|f| >=
+    sample_rate / 2`` (such a cell still advances the phase).  Shapes that differ and unknown reductions are a ``ValueError``.
+
+    float32 on a HIP device (any positive strides: ``N``-contiguous, or time-contiguous as the transpose of an ``(…, N, time)``
+    tensor, slices, unaligned starts; up to 1024 oscillators) runs the gfx950 kernels of csrc/ddsp.hip, forward and backward, in
+    one launch (two where few long rows are cut into spans of 2048 steps; the gradient takes one more).  Deviations from
+    torchaudio on that route: the phase is a 64-bit integer accumulator of ``frac(f / sample_rate)`` turns formed in float64, sine
+    and cosine are float64 and the result is rounded once — ``dtype`` is validated and otherwise ignored (torchaudio forms the
+    increments in the input's dtype and takes the sine of the phase rounded to it); and no warning is given for frequencies at or
+    beyond Nyquist (that would read the device; CPU tensors warn as torchaudio does).  Other dtypes, expanded views, more
+    oscillators, CPU tensors and double backward take ``_composite.oscillator_bank``, announced with ``CompositeRouteWarning`` on
+    a device."""
+    f, a = _tensor(frequencies, 'frequencies'), _tensor(amplitudes, 'amplitudes')
+    _ddsp.check_oscillator_bank(f, a, sample_rate, reduction, dtype)
+    return _call('oscillator_bank', f, a, float(sample_rate), reduction, dtype)
+
+
+def filter_waveform(waveform, kernels, delay_compensation=-1):
+    """``(…, T) → (…, T)``: torchaudio's ``prototype.functional.filter_waveform``, a time-varying FIR filter given as one impulse
+    response per chunk of time.  ``kernels`` is ``(F, K)`` (shared by every row) or ``(…, F, K)`` whose leading dims equal the
+    waveform's or are 1.  With ``C = ceil(T / F)``, ``x`` zero-extended to ``C F`` samples and ``s = delay_compensation`` (``K // 2``
+    where negative): ``full[n] = sum_k h_{(n - k) // C}[k] x[n - k]`` and ``y[t] = full[t + s]``.  ``delay_compensation > K - 1`` is a
+    ``ValueError`` (torchaudio accepts ``K - 1`` and ``K`` there with an empty or wrong slice).
+
+    float32 on a HIP device with ``K <= 768`` runs the gfx950 kernels of csrc/ddsp.hip: the direct form over LDS tiles of 1024
+    outputs, one launch forward, one for each gradient (the kernels' gradient is per-row partial sums and one ``torch.sum``).
+    Shared and size-1 kernel dims are read through zero strides.  Other dtypes, expanded views, longer filters, CPU tensors and
+    double backward take ``_composite.filter_waveform`` (FFT per chunk and ``fold``), announced with ``CompositeRouteWarning`` on
+    a device."""
+    x = _waveform(waveform, 'filter_waveform')
+    h = _tensor(kernels, 'kernels')
+    _ddsp.check_filter_waveform(x, h, int(delay_compensation))
+    return _call('filter_waveform', x, h, int(delay_compensation))
 
 
 def biquad(waveforms, b0, b1, b2, a0, a1, a2):

@@ -527,6 +527,38 @@ class Flanger(nn.Module):
         return self.__class__.__name__ + '(sample_rate={}, delay={}, depth={}, regen={}, width={}, speed={}, phase={}, modulation={!r}, interpolation={!r})'.format(*self.args)
 
 
+class OscillatorBank(nn.Module):
+    """``functional.oscillator_bank`` as a layer: ``(…, time, N)`` frequencies and amplitudes → ``(…, time)`` (``(…, time, N)`` for
+    ``reduction='none'``).  No buffers."""
+
+    def __init__(self, sample_rate, reduction='sum'):
+        super(OscillatorBank, self).__init__()
+        if reduction not in F._ddsp.REDUCTIONS:
+            raise ValueError('OscillatorBank: reduction must be one of %r, got %r' % (F._ddsp.REDUCTIONS, reduction))
+        self.sample_rate, self.reduction = float(sample_rate), reduction
+
+    def forward(self, frequencies, amplitudes):
+        return F.oscillator_bank(frequencies, amplitudes, self.sample_rate, self.reduction)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(sample_rate={}, reduction={!r})'.format(self.sample_rate, self.reduction)
+
+
+class FilterWaveform(nn.Module):
+    """``functional.filter_waveform`` as a layer: a waveform ``(…, T)`` and kernels ``(F, K)`` or ``(…, F, K)`` → ``(…, T)``.  No
+    buffers."""
+
+    def __init__(self, delay_compensation=-1):
+        super(FilterWaveform, self).__init__()
+        self.delay_compensation = int(delay_compensation)
+
+    def forward(self, waveform, kernels):
+        return F.filter_waveform(waveform, kernels, self.delay_compensation)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(delay_compensation={})'.format(self.delay_compensation)
+
+
 class Preemphasis(_ModuleNoStateBuffers):
     """``functional.preemphasis`` as a layer: ``y[n] = x[n] - coeff x[n-1]``.  No buffers: ``coeff`` is a Python float, and the
     two float64 host tensors the op takes are plain attributes (they stay float64 on the host whatever ``.to()`` is given)."""
