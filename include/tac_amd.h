@@ -1104,6 +1104,39 @@ int tac_filter_waveform_f32(const float* x, int64_t rows, int64_t length, int64_
 int tac_filter_waveform_grad_kernels_f32(const float* x, int64_t stride_r, const float* g, int64_t g_stride_r, int64_t rows,
                                          int64_t length, int64_t n_filters, int64_t taps, int64_t shift, float* part, void* stream);
 
+/* (36) functional.ctc_beam_search / CTCBeamDecoder: CTC prefix beam search without a language model (csrc/ctc_decode.hip), ONE
+ *      entry of TWO launches.  log_probs: float32 [batch][frames][classes] with positive element strides (read where they lie,
+ *      64-bit offsets); lengths: DEVICE int32 [batch] or NULL (frames in every entry).  1 <= nbest <= beam <=
+ *      tac_ctc_beam_max_beam() (32), classes >= 2, blank in [0, classes).  tokens: int32 [batch][nbest][frames], token_lengths:
+ *      int32 [batch][nbest], scores: float32 [batch][nbest], all DEVICE, dense, written in full.
+ *
+ *      Per entry over frames t < length, with K = beam: frame t is skipped when exp(lp[t][blank]) > blank_skip_threshold (in
+ *      float64; 1.0 keeps every frame).  S_t = the min(K + 1, classes - 1) non-blank classes with the largest lp[t][c], ties to
+ *      the lower class, in that order.  The beam holds at most K distinct prefixes with (pb, pnb), tot = logaddexp(pb, pnb),
+ *      float64 throughout, and starts as the empty prefix (0, -inf).  A step: every prefix p with last token l stays — pb' (+)=
+ *      tot + lp[blank], and pnb' (+)= pnb + lp[l] when p is not empty — and extends — for c in S_t and for c with p + c in the
+ *      beam, pnb'(p + c) (+)= (c == l ? pb : tot) + lp[c]; (+) is logaddexp and contributions to one prefix merge.  The K
+ *      prefixes with the largest tot' remain (tot' = -inf is dropped); among equal tot' the lower parent slot wins, in a slot
+ *      staying before extending, then the lower rank in S_t (slots are in descending tot').  After the last frame hypothesis
+ *      h < nbest is slot h: tokens[h][0 .. len) the prefix and -1 behind, token_lengths[h] = len, scores[h] = (float)tot; slots
+ *      that do not exist get length 0 and -inf.  Length 0 or all frames skipped: the empty prefix, score 0.
+ *
+ *      An entry with a length outside [0, frames] or a NaN in a frame t < length gets NaN scores, lengths 0 and tokens -1; the
+ *      other entries are unaffected, and every entry has the same bits from run to run and whatever else is in the batch.
+ *      Frames t >= length are not read.  workspace: DEVICE, tac_ctc_beam_workspace(batch, frames, beam) bytes, 8-byte aligned,
+ *      not initialised, not an output: per frame beam + 2 pairs (lp[blank], flag; S_t's (lp, class)) from the first launch and
+ *      beam (parent node, token) pairs of the second's prefix trie.  tac_ctc_beam_workspace returns -1 for sizes the entry
+ *      refuses (TAC_E_UNSUPPORTED: beam above 32, batch x frames or frames x beam of 2^31 - 1 or more, an axis of 2^30 or more).
+ *      tac_ctc_beam_wide_classes(): the longest row (6144) the first launch keeps in registers; longer rows are read again in
+ *      every one of its rounds. */
+int32_t tac_ctc_beam_max_beam(void);
+int32_t tac_ctc_beam_wide_classes(void);
+int64_t tac_ctc_beam_workspace(int64_t batch, int64_t frames, int64_t beam);
+int tac_ctc_beam_search_f32(const float* log_probs, int64_t batch, int64_t frames, int64_t classes, int64_t stride_b,
+                            int64_t stride_t, int64_t stride_c, const int32_t* lengths, int32_t beam, int32_t nbest, int32_t blank,
+                            double blank_skip_threshold, void* workspace, int32_t* tokens, int32_t* token_lengths, float* scores,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1104,6 +1104,81 @@ def forced_align(log_probs, targets, input_lengths, target_lengths, blank):
     return paths, scores
 
 
+# ----------------------------------------------------------------------------- ctc_beam_search
+def ctc_class_lists(x, n, blank):
+    """``(values (B, T, n), classes (B, T, n))``: per frame the ``n`` non-blank classes with the largest value, ties to the lower
+    class, in that order.  ``torch.topk`` finds the n-th value; the set is then every class above it and the lowest classes equal
+    to it, which ``topk`` alone does not promise.  A NaN counts as ``-inf`` here (its entry is refused elsewhere)."""
+    B, T, C = x.shape
+    v = torch.cat([x[..., :blank], x[..., blank + 1:]], dim=-1)
+    v = torch.where(torch.isnan(v), torch.full((), float('-inf'), dtype=v.dtype, device=v.device), v)
+    kth = torch.topk(v, n, dim=-1).values[..., -1:]
+    above, equal = v > kth, v == kth
+    chosen = above | (equal & (torch.cumsum(equal, dim=-1) <= n - above.sum(dim=-1, keepdim=True)))
+    cls = chosen.nonzero()[:, 2].reshape(B, T, n)                           # ascending in every frame
+    vals, order = torch.sort(v.gather(2, cls), dim=-1, descending=True, stable=True)
+    cls = cls.gather(2, order)
+    return vals, cls + (cls >= blank).to(cls.dtype)
+
+
+def _logaddexp(a, b):
+    m, n = (a, b) if a >= b else (b, a)
+    return m if m == float('-inf') else m + math.log1p(math.exp(n - m))
+
+
+def ctc_beam_search(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold):
+    """The definition of ``functional.ctc_beam_search``: the class lists by ``ctc_class_lists`` on the tensor's device, then one
+    read and the beam in Python floats (float64) on the host, a step of a loop per kept frame and entry.  The beam is a list in
+    descending total; among equal totals the lower parent slot comes first, in a slot staying before extending, then the lower
+    rank in the class list.  An entry with a length outside ``[0, T]`` or a NaN in a used frame gets NaN scores and length 0."""
+    B, T, C = log_probs.shape
+    dev = log_probs.device
+    K, ninf = beam_size, float('-inf')
+    n = min(K + 1, C - 1)
+    x = log_probs.detach()
+    vals, cls = ctc_class_lists(x, n, blank)
+    nan_frames = torch.isnan(x).any(dim=-1).cpu().tolist()
+    vals, cls = vals.double().cpu().tolist(), cls.cpu().tolist()
+    host = x.cpu().to(torch.float64 if x.dtype == torch.float64 else torch.float32).numpy()
+    lens = [T] * B if lengths is None else [int(v) for v in lengths.cpu().tolist()]
+    tokens = torch.full((B, nbest, T), -1, dtype=torch.int32)
+    token_lengths = torch.zeros((B, nbest), dtype=torch.int32)
+    scores = torch.full((B, nbest), ninf, dtype=torch.float64)
+    for b in range(B):
+        if not 0 <= lens[b] <= T or any(nan_frames[b][:lens[b]]):
+            scores[b] = float('nan')
+            continue
+        beam = [((), 0.0, ninf)]
+        for t in range(lens[b]):
+            frame = host[b, t]
+            lpb = float(frame[blank])
+            if math.exp(lpb) > blank_skip_threshold:
+                continue
+            slot = {p: i for i, (p, _, _) in enumerate(beam)}
+            cand = []
+            for i, (p, pb, pnb) in enumerate(beam):
+                tot = _logaddexp(pb, pnb)
+                last = p[-1] if p else None
+                el = float(frame[last]) if p else ninf
+                spb, spnb = tot + lpb, (pnb + el if p else ninf)
+                if p and p[:-1] in slot:
+                    q, qpb, qpnb = beam[slot[p[:-1]]]
+                    spnb = _logaddexp(spnb, (qpb if q and q[-1] == last else _logaddexp(qpb, qpnb)) + el)
+                cand.append((_logaddexp(spb, spnb), (i, -1), p, spb, spnb))
+                for r in range(n):
+                    c = cls[b][t][r]
+                    if p + (c,) not in slot:
+                        v = (pb if c == last else tot) + vals[b][t][r]
+                        cand.append((v, (i, r), p + (c,), ninf, v))
+            cand = sorted((c for c in cand if c[0] > ninf), key=lambda c: (-c[0], c[1]))
+            beam = [c[2:] for c in cand[:K]]
+        for h, (p, pb, pnb) in enumerate(beam[:nbest]):
+            tokens[b, h, :len(p)] = torch.tensor(p, dtype=torch.int32)
+            token_lengths[b, h] = len(p)
+            scores[b, h] = _logaddexp(pb, pnb)
+    return tokens.to(dev), token_lengths.to(dev), scores.float().to(dev)
+
+
 # ============================================================================= rir_ism, rir_ism_span
 def _rir_geometry(room, source, mic_array, max_order, sound_speed, sample_rate):
     """float64 ``(X (I, D) int64, dist (B, I, M), delay (B, I, M), di (B, I, M) float64)`` of the image sources: the definition's

@@ -1919,6 +1919,48 @@ def forced_align(log_probs, targets, input_lengths, target_lengths, blank):
     return paths, scores
 
 
+# ----------------------------------------------------------------------------- ctc_beam_search (csrc/ctc_decode.hip)
+def ctc_beam_max_beam():
+    """the largest beam the launch takes: a lane per slot, 32"""
+    return _native.lib().tac_ctc_beam_max_beam()
+
+
+def ctc_beam_wide_classes():
+    """the longest row the first launch keeps in registers; a longer one is read again in every round"""
+    return _native.lib().tac_ctc_beam_wide_classes()
+
+
+def ctc_beam_reason(log_probs, beam_size):
+    """why csrc/ctc_decode.hip does not take these float32 ``(B, T, C)`` log-probabilities as they lie, or None"""
+    if any(st <= 0 for st, n in zip(log_probs.stride(), log_probs.shape) if n > 1):
+        return 'expanded or non-positive strides'
+    if beam_size > ctc_beam_max_beam():
+        return 'a beam of %d (the kernel takes up to %d)' % (beam_size, ctc_beam_max_beam())
+    if max(log_probs.shape) >= 2 ** 30:
+        return 'an axis of 2^30 or more'
+    B, T, _ = log_probs.shape
+    if _native.lib().tac_ctc_beam_workspace(B, T, beam_size) < 0:
+        return 'batch x time or time x beam of 2^31 - 1 or more'
+    return None
+
+
+def ctc_beam_search(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold):
+    """``(tokens int32 (B, nbest, T), token_lengths int32 (B, nbest), scores float32 (B, nbest))`` of float32 log-probabilities
+    ``ctc_beam_reason`` passes: ONE entry, two launches (the frame tables, the beam).  ``lengths`` may be None."""
+    B, T, C = log_probs.shape
+    dev = log_probs.device
+    ln = None if lengths is None else _rnnt_ints(lengths, dev)
+    tokens = _empty((B, nbest, T), dtype=torch.int32, device=dev)
+    token_lengths = _empty((B, nbest), dtype=torch.int32, device=dev)
+    scores = _empty((B, nbest), device=dev)
+    need = _native.lib().tac_ctc_beam_workspace(B, T, beam_size)
+    work = torch.empty((need // 8,), dtype=torch.int64, device=dev)                        # (not an output: plain)
+    _launch('tac_ctc_beam_search_f32', dev, (tokens, token_lengths, scores), _native.ptr(log_probs), B, T, C, log_probs.stride(0),
+            log_probs.stride(1), log_probs.stride(2), None if ln is None else _native.ptr(ln), beam_size, nbest, blank,
+            float(blank_skip_threshold), _native.ptr(work), _native.ptr(tokens), _native.ptr(token_lengths), _native.ptr(scores))
+    return tokens, token_lengths, scores
+
+
 # ----------------------------------------------------------------------------- fftconvolve (csrc/fftconvolve.hip)
 #: the transform lengths of the partitioned route and the most partitions ``tac_spectral_mac_f32`` takes
 FFTCONV_SIZES = (2048, 4096, 8192)

@@ -224,6 +224,10 @@ PROTOTYPES = {
     'tac_filter_waveform_pieces': (_I64, [_I64, _I64]),
     'tac_filter_waveform_f32': (_INT, [_P, _I64, _I64, _I64, _P] + [_I64] * 8 + [_INT, _P, _P]),
     'tac_filter_waveform_grad_kernels_f32': (_INT, [_P, _I64, _P, _I64] + [_I64] * 5 + [_P, _P]),
+    'tac_ctc_beam_max_beam': (_I32, []),
+    'tac_ctc_beam_wide_classes': (_I32, []),
+    'tac_ctc_beam_workspace': (_I64, [_I64, _I64, _I64]),
+    'tac_ctc_beam_search_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

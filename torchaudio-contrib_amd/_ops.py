@@ -26,6 +26,7 @@ see them by name.
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
     tac_amd::forced_align       CTC Viterbi alignment of (B, T, C) log-probabilities: recursion, backtrack, paths and scores in one launch (csrc/align.hip)
+    tac_amd::ctc_beam_search    CTC prefix beam search of (B, T, C) log-probabilities: the k best classes of every frame, then the beams, in two launches (csrc/ctc_decode.hip)
     tac_amd::griffinlim         Griffin-Lim phase recovery of (…, F, T) magnitudes: prepare, then stft + inverse a step (csrc/griffinlim.hip)
     tac_amd::fftconvolve        full convolution along time by partitioned overlap-save (csrc/fftconvolve.hip)
     tac_amd::lfilter            recursive filter of order <= 2 along time: biquads, pre- / de-emphasis (csrc/lfilter.hip)
@@ -1988,6 +1989,77 @@ def _register_align_autograd():
 _register('forced_align', '(Tensor log_probs, Tensor targets, Tensor? input_lengths, Tensor? target_lengths, int blank) -> '
           '(Tensor, Tensor)', _align_cuda, _align_cpu, _align_fake, 2, differentiable=False)
 _register_align_autograd()
+
+
+# ============================================================================= ctc_beam_search
+def ctc_beam_check(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold):
+    """the argument checks of ``ctc_beam_search`` that need no device memory: dimensions, dtypes, ``C >= 2``, ``T >= 1``, ``blank`` in
+    ``[0, C)``, ``1 <= nbest <= beam_size``, a threshold that is a number, the lengths' shape and device.  ``ValueError`` on every
+    route."""
+    if not (isinstance(log_probs, torch.Tensor) and log_probs.is_floating_point()):
+        raise ValueError('ctc_beam_search: log_probs must be a floating-point tensor')
+    if log_probs.dim() != 3:
+        raise ValueError('ctc_beam_search: log_probs must be (batch, time, class), got %d dimension(s)' % log_probs.dim())
+    B, T, C = log_probs.shape
+    if T < 1 or C < 2:
+        raise ValueError('ctc_beam_search: log_probs of shape %r need a frame and two classes' % (tuple(log_probs.shape),))
+    if lengths is not None:
+        if not isinstance(lengths, torch.Tensor) or lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError('ctc_beam_search: lengths must be an int32 or int64 tensor or None')
+        if lengths.dim() != 1 or lengths.shape[0] != B:
+            raise ValueError('ctc_beam_search: lengths must have shape (%d,), got %r' % (B, tuple(lengths.shape)))
+        if lengths.device != log_probs.device:
+            raise ValueError('ctc_beam_search: lengths are on %s, log_probs on %s' % (lengths.device, log_probs.device))
+    if not 0 <= blank < C:
+        raise ValueError('ctc_beam_search: blank %d is outside the %d classes' % (blank, C))
+    if not 1 <= nbest <= beam_size:
+        raise ValueError('ctc_beam_search: need 1 <= nbest <= beam_size, got nbest %d and beam_size %d' % (nbest, beam_size))
+    if blank_skip_threshold != blank_skip_threshold:
+        raise ValueError('ctc_beam_search: blank_skip_threshold is not a number')
+
+
+def ctc_beam_reason(log_probs, beam_size):
+    """why the launches of csrc/ctc_decode.hip do not take these inputs, or None"""
+    if log_probs.dtype != torch.float32:
+        return 'dtype %s' % str(log_probs.dtype).replace('torch.', '')
+    return H.ctc_beam_reason(log_probs, beam_size)
+
+
+def _ctc_beam_empty(log_probs, nbest):
+    B, T, _ = log_probs.shape
+    dev = log_probs.device
+    return (torch.empty((B, nbest, T), dtype=torch.int32, device=dev), torch.empty((B, nbest), dtype=torch.int32, device=dev),
+            torch.empty((B, nbest), dtype=torch.float32, device=dev))
+
+
+def _ctc_beam_cuda(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold):
+    ctc_beam_check(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold)
+    if log_probs.shape[0] == 0:
+        return _ctc_beam_empty(log_probs, nbest)                    # an empty batch: nothing is launched
+    reason = ctc_beam_reason(log_probs, beam_size)
+    if reason is not None:
+        _composite_route('ctc_beam_search', reason)
+        return C.ctc_beam_search(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold)
+    return H.ctc_beam_search(log_probs.detach(), lengths, beam_size, nbest, blank, blank_skip_threshold)
+
+
+def _ctc_beam_cpu(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold):
+    ctc_beam_check(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold)
+    if log_probs.shape[0] == 0:
+        return _ctc_beam_empty(log_probs, nbest)
+    if lengths is not None:
+        for b, n in enumerate(lengths.tolist()):
+            if not 0 <= n <= log_probs.shape[1]:
+                raise ValueError('ctc_beam_search: entry %d: length %d is outside [0, %d]' % (b, n, log_probs.shape[1]))
+    return C.ctc_beam_search(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold)
+
+
+def _ctc_beam_fake(log_probs, lengths, beam_size, nbest, blank, blank_skip_threshold):
+    return _ctc_beam_empty(log_probs, nbest)
+
+
+_register('ctc_beam_search', '(Tensor log_probs, Tensor? lengths, int beam_size, int nbest, int blank, float blank_skip_threshold) -> '
+          '(Tensor, Tensor, Tensor)', _ctc_beam_cuda, _ctc_beam_cpu, _ctc_beam_fake, 3, differentiable=False)
 
 
 # ============================================================================= lfilter

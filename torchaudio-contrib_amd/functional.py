@@ -41,7 +41,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'sosfilt', 'tf2sos', 'filtfilt', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
-           'forced_align', 'merge_tokens', 'TokenSpan', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
+           'forced_align', 'merge_tokens', 'TokenSpan', 'ctc_beam_search', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
            'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform']
 
 _call = _ops.call
@@ -1196,6 +1196,32 @@ def merge_tokens(tokens, scores, blank=0):
                 spans.append(TokenSpan(token=toks[start], start=start, end=i, score=sum(vals[start:i]) / (i - start)))
             start = i
     return spans
+
+
+def ctc_beam_search(log_probs, lengths=None, beam_size=10, nbest=1, blank=0, blank_skip_threshold=0.95):
+    """CTC prefix beam search without a language model, the search of torchaudio's ``cuda_ctc_decoder``: ``(tokens, token_lengths,
+    scores)`` of ``log_probs`` ``(batch, time, class)`` (log-softmax output).  ``tokens`` int32 ``(batch, nbest, time)`` holds each
+    hypothesis in ``tokens[b, h, :token_lengths[b, h]]`` and ``-1`` behind it, best first; ``scores`` float32 ``(batch, nbest)`` is its
+    log-probability.  ``lengths`` is a ``(batch,)`` int32 / int64 tensor of used frames, or None for all of them.
+
+    Per entry over frames ``t < length``, with ``K = beam_size``: a frame is skipped when ``exp(lp[t, blank]) >
+    blank_skip_threshold`` (torchaudio's rule; 1.0 keeps every frame).  ``S_t`` is the ``min(K + 1, class - 1)`` non-blank classes
+    with the largest ``lp[t, c]``, ties to the lower class.  The beam holds at most ``K`` distinct prefixes with ``(pb, pnb)``, the
+    log-mass of alignments ending in blank and in non-blank, ``tot = logaddexp(pb, pnb)``, in float64, and starts as the empty prefix
+    ``(0, -inf)``.  Every prefix ``p`` with last token ``l`` stays (``pb' += tot + lp[blank]``, and ``pnb' += pnb + lp[l]`` unless
+    ``p`` is empty) and extends: for ``c`` in ``S_t`` and for ``c`` with ``p + c`` already in the beam, ``pnb'(p + c) += (pb if c == l
+    else tot) + lp[c]`` (``+=`` is ``logaddexp``; contributions to one prefix merge).  The ``K`` prefixes with the largest ``tot'``
+    remain, ``-inf`` is dropped; among equal totals the lower parent slot wins, in a slot staying before extending, then the lower
+    rank in ``S_t``.  Hypotheses that do not exist get length 0 and ``-inf``; a length of 0 or all frames skipped gives the empty
+    prefix with score 0.
+
+    float32 on a HIP device with positive strides and ``beam_size <= 32`` runs csrc/ctc_decode.hip: one launch for the class lists
+    of all frames, one for the beams, a wave per entry; the same bits from run to run and whatever else is in the batch.  An entry
+    with a length outside ``[0, time]`` or a NaN in a used frame gets NaN scores and length 0 there; CPU tensors raise
+    ``ValueError`` for such a length.  Other inputs (CPU, float64, half precision, expanded views, larger beams) take
+    ``_composite.ctc_beam_search``, the beam on the host, announced on a HIP device.  The outputs carry no gradient."""
+    _ops.ctc_beam_check(log_probs, lengths, int(beam_size), int(nbest), int(blank), float(blank_skip_threshold))
+    return _call('ctc_beam_search', log_probs, lengths, int(beam_size), int(nbest), int(blank), float(blank_skip_threshold))
 
 
 def preemphasis(waveforms, coeff=0.97):
