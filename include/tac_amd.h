@@ -1137,6 +1137,27 @@ int tac_ctc_beam_search_f32(const float* log_probs, int64_t batch, int64_t frame
                             double blank_skip_threshold, void* workspace, int32_t* tokens, int32_t* token_lengths, float* scores,
                             void* stream);
 
+/* (37) functional.cqt / CQT: the time-domain constant-Q (variable-Q) transform as a band-sparse fp32 MFMA GEMM (csrc/cqt.hip), ONE
+ *      launch.  x: float32 (rows, length), unit stride along time, read where it lies (64-bit offsets); no padded copy is made.
+ *      The wavelets lie on one tap axis e, every one centred at e = floor(N_0 / 2).  bank: DEVICE float32, blocks of 64 lanes x 4
+ *      floats = tac_cqt_step() (16) taps of tac_cqt_group_bins() (8) consecutive bins: lane (kk, i) of block s of a group holds
+ *      column i (bin i / 2 of the group, re / im of conj(g)) at taps E + 16 s + 4 kk + {0, 1, 2, 3}; zeros outside a bin's support.
+ *      groups: DEVICE int32 [n_groups][4] = (E, steps, first block, bins), longest first, E a multiple of 16, the spans nested;
+ *      span: the end of group 0's span.  out[row][bin][t] = sum_e x'[t hop + origin + e] bank[bin][e] as (re, im) pairs (power 0),
+ *      the modulus (1) or its square (2), dense (rows, n_bins, n_frames[, 2]); x' is x mirrored once at both ends (reflect != 0)
+ *      and zero beyond.  A unit is a row's tile of tac_cqt_frames_per_tile() (32) frames, the grid persistent with
+ *      tac_cqt_blocks_per_cu() workgroups per CU.  hop: a multiple of 4, at most tac_cqt_max_hop() (TAC_E_UNSUPPORTED otherwise).
+ *      Bit-identical from run to run and whatever else the batch holds.  A non-finite sample reaches all bins of every group
+ *      whose span covers it in a frame, not only the bins whose own wavelet does. */
+int32_t tac_cqt_frames_per_tile(void);
+int32_t tac_cqt_group_bins(void);
+int32_t tac_cqt_step(void);
+int32_t tac_cqt_max_hop(void);
+int32_t tac_cqt_blocks_per_cu(void);
+int tac_cqt_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, const float* bank, const int32_t* groups,
+                int32_t n_groups, int32_t n_bins, int32_t span, int32_t hop, int64_t n_frames, int64_t origin, int reflect, int power,
+                float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1365,3 +1365,32 @@ def filter_waveform(waveform, kernels, delay_compensation):
     seg = seg.expand(lead + (F, n)).reshape(rows, F, n).transpose(1, 2)
     full = TF.fold(seg, output_size=(1, C * F + K - 1), kernel_size=(1, n), stride=(1, C)).reshape(lead + (C * F + K - 1,))
     return full[..., s:s + T].contiguous()
+
+
+def cqt(waveform, kernels, n_max, hop, center, reflect, power):
+    """The time-domain constant-Q transform in torch operators, as the padded ``conv1d``: ``waveform`` ``(…, time)``, ``kernels``
+    the ``(2 K, N_max)`` matrix of ``_cqt.CqtPlan.dense()`` in the waveform's dtype (every ``conj(g_k)`` centred in ``N_max`` taps:
+    about five zeros per tap that matters) → ``(…, K, T, 2)`` pairs, or ``(…, K, T)`` moduli (``power`` 1) or their squares (2).
+    ``center``: the row is read from ``floor(N_max / 2)`` samples before its start, mirrored once at both ends (``reflect``) and
+    zero beyond.  The CPU path of ``tac_amd::cqt``, its float64 route and its announced route on a device; differentiable."""
+    if waveform.dtype in (torch.float16, torch.bfloat16):
+        waveform = waveform.float()
+    lead, length = tuple(waveform.shape[:-1]), waveform.shape[-1]
+    K = kernels.shape[0] // 2
+    x = waveform.reshape(-1, 1, length)
+    if center:
+        frames = 1 + length // hop
+        i = torch.arange(-(n_max // 2), (frames - 1) * hop - n_max // 2 + n_max, device=x.device)
+        if reflect:
+            i = torch.where(i < 0, -i, torch.where(i >= length, 2 * (length - 1) - i, i))
+        inside = (i >= 0) & (i < length)
+        x = x[..., i.clamp(0, length - 1)] * inside.to(x.dtype)
+    y = TF.conv1d(x, kernels.to(x.dtype).unsqueeze(1), stride=hop)
+    re, im = y[:, :K], y[:, K:]
+    if power == 0:
+        out = torch.stack((re, im), dim=-1)
+    else:
+        out = re * re + im * im
+        if power == 1:
+            out = out.sqrt()
+    return out.reshape(lead + tuple(out.shape[1:])).contiguous()

@@ -14,6 +14,7 @@ import weakref
 
 import torch
 
+from . import _cqt
 from . import _kaldi
 from . import _native
 from . import _resample
@@ -1349,6 +1350,52 @@ def filter_waveform_grad_kernels_rows(x, g, n_filters, taps, shift):
             xr.shape[0], x.shape[-1], n_filters, taps, int(shift), _native.ptr(part))
     part = part[:, :, 0] if pieces == 1 else part.sum(2)
     return part.reshape(tuple(x.shape[:-1]) + (n_filters, taps))
+
+
+# ----------------------------------------------------------------------------- cqt (csrc/cqt.hip)
+#: frames per unit of ``tac_cqt_f32``, bins per group and taps per block of its bank, the largest hop whose window fits the LDS
+#: and its workgroups per CU; checked against the library's own values at the first launch
+CQT_FRAMES_PER_TILE = 32
+CQT_GROUP_BINS = 8
+CQT_STEP = 16
+CQT_MAX_HOP = 1300
+CQT_BLOCKS_PER_CU = 2
+
+_cqt_checked = False
+
+
+def _cqt_check():
+    global _cqt_checked
+    if not _cqt_checked:
+        h = _native.lib()
+        found = (h.tac_cqt_frames_per_tile(), h.tac_cqt_group_bins(), h.tac_cqt_step(), h.tac_cqt_max_hop(), h.tac_cqt_blocks_per_cu())
+        said = (CQT_FRAMES_PER_TILE, CQT_GROUP_BINS, CQT_STEP, CQT_MAX_HOP, CQT_BLOCKS_PER_CU)
+        if found != said or (CQT_GROUP_BINS, CQT_STEP) != (_cqt.GROUP_BINS, _cqt.STEP):
+            raise RuntimeError('libtac_amd.so reports %r for the CQT kernel\'s tile, bank and limits, _hip says %r' % (found, said))
+        _cqt_checked = True
+
+
+def cqt_dense(plan, dtype, device):
+    """the composite's ``(2 K, N_max)`` kernels in ``dtype`` on ``device``, converted once and kept on the plan's host matrix"""
+    host = plan.dense()
+    return cached_on(host, '_tac_coef', ('cqt', dtype, str(device)), lambda: host.to(device=device, dtype=dtype), limit=2)
+
+
+def cqt_rows(x, plan, hop, n_frames, center, reflect, power):
+    """``(…, L) -> (…, K, T, 2)`` pairs (``power`` 0), ``(…, K, T)`` moduli (1) or their squares (2) through ``tac_cqt_f32``: one
+    launch.  ``plan``: a ``_cqt.CqtPlan``, its bank and group table uploaded once per device and kept on the host tensors."""
+    K = len(plan.lengths)
+    out = _empty(tuple(x.shape[:-1]) + ((K, n_frames, 2) if power == 0 else (K, n_frames)), device=x.device)
+    if out.numel():
+        _cqt_check()
+        rows = _sox_rows(x)
+        bank = cached_on(plan.bank, '_tac_coef', ('cqt', str(x.device)), lambda: plan.bank.to(x.device))
+        groups = cached_on(plan.groups, '_tac_coef', ('cqt', str(x.device)), lambda: plan.groups.to(x.device))
+        origin = (0 if center else plan.n_max // 2) - plan.c0
+        _launch('tac_cqt_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], x.shape[-1], rows.stride(0), _native.ptr(bank),
+                _native.ptr(groups), int(groups.shape[0]), K, int(plan.span), int(hop), int(n_frames), int(origin),
+                int(bool(reflect and center)), int(power), _native.ptr(out))
+    return out
 
 
 # ----------------------------------------------------------------------------- loudness (csrc/loudness.hip)

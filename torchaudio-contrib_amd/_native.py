@@ -228,6 +228,12 @@ PROTOTYPES = {
     'tac_ctc_beam_wide_classes': (_I32, []),
     'tac_ctc_beam_workspace': (_I64, [_I64, _I64, _I64]),
     'tac_ctc_beam_search_f32': (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I32, _I32, _I32, _D, _P, _P, _P, _P, _P]),
+    'tac_cqt_frames_per_tile': (_I32, []),
+    'tac_cqt_group_bins': (_I32, []),
+    'tac_cqt_step': (_I32, []),
+    'tac_cqt_max_hop': (_I32, []),
+    'tac_cqt_blocks_per_cu': (_I32, []),
+    'tac_cqt_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _INT, _INT, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

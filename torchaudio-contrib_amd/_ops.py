@@ -33,6 +33,7 @@ see them by name.
     tac_amd::sosfilt            cascade of up to 8 second-order sections along time in one launch, float64 between them (csrc/sosfilt.hip)
     tac_amd::lfilter_reverse, sosfilt_reverse   the two above run from the end of each row: filtfilt's second half (private)
     tac_amd::overdrive, phaser, flanger         the SoX effects defined by a loop over time, one launch each (csrc/sox_effects.hip)
+    tac_amd::cqt                the time-domain constant-Q transform of (…, L): a band-sparse fp32 MFMA GEMM in one launch (csrc/cqt.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -66,6 +67,7 @@ from . import _beamform as BF
 from . import _resample as RS
 from . import _sox as SX
 from . import _ddsp as DD
+from . import _cqt as CQ
 
 NS = 'tac_amd'
 _lib = Library(NS, 'DEF')
@@ -2280,6 +2282,54 @@ _register('oscillator_bank', '(Tensor frequencies, Tensor amplitudes, float samp
           _oscillator_bank_cuda, _oscillator_bank_cpu, _oscillator_bank_fake, 2)
 _register('filter_waveform', '(Tensor waveform, Tensor kernels, int delay_compensation) -> Tensor', _filter_waveform_cuda,
           _filter_waveform_cpu, _sox_fake, 2)
+
+
+# ============================================================================= cqt
+_CQT_ARGS = ('float sample_rate, int hop_length, float fmin, int n_bins, int bins_per_octave, float filter_scale, float gamma, '
+             'int norm, bool center, str pad_mode, bool scale, int power')
+
+
+def _cqt_plan(wave, sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, gamma, norm, center, pad_mode, scale, power):
+    """``(plan, frames)``; ``norm`` 0 is ``None``, ``power`` 0 the complex pairs.  The argument and length errors of ``cqt``."""
+    CQ.check(sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, gamma, norm or None, pad_mode, float(power) if power else None)
+    plan = CQ.plan(sample_rate, fmin, n_bins, bins_per_octave, filter_scale, gamma, norm or None, scale)
+    return plan, CQ.n_frames(wave.shape[-1], plan.n_max, hop, center, pad_mode)
+
+
+def _cqt_composite(wave, plan, hop, center, pad_mode, power):
+    return C.cqt(wave, H.cqt_dense(plan, _out_dtype(wave), wave.device), plan.n_max, hop, center, pad_mode == 'reflect', power)
+
+
+def _cqt_cpu(wave, *args):
+    plan, _ = _cqt_plan(wave, *args)
+    hop, center, pad_mode, power = args[1], args[8], args[9], args[11]
+    return _cqt_composite(wave, plan, hop, center, pad_mode, power)
+
+
+def _cqt_cuda(wave, *args):
+    plan, frames = _cqt_plan(wave, *args)
+    hop, center, pad_mode, power = args[1], args[8], args[9], args[11]
+    reason = _hip_dtype(wave)
+    if reason is None and hop % 4 != 0:
+        reason = 'hop_length %d is not a multiple of 4' % hop
+    if reason is None and hop > H.CQT_MAX_HOP:
+        reason = 'hop_length %d (the kernel\'s window holds %d)' % (hop, H.CQT_MAX_HOP)
+    if reason is None and any(st <= 0 for st, n in zip(wave.stride(), wave.shape) if n > 1):
+        reason = 'an expanded view or non-positive strides'
+    if reason is not None:
+        _composite_route('cqt', reason)
+        return _cqt_composite(wave, plan, hop, center, pad_mode, power)
+    return H.cqt_rows(_f32(wave), plan, hop, frames, center, pad_mode == 'reflect', power)
+
+
+def _cqt_fake(wave, *args):
+    plan, frames = _cqt_plan(wave, *args)
+    tail = (len(plan.lengths), frames) + ((2,) if args[11] == 0 else ())
+    return torch.empty(tuple(wave.shape[:-1]) + tail, dtype=_out_dtype(wave), device=wave.device)
+
+
+# (no gradient kernel: the backward pass re-evaluates the composite, announced)
+_register('cqt', '(Tensor waveform, ' + _CQT_ARGS + ') -> Tensor', _cqt_cuda, _cqt_cpu, _cqt_fake, 1)
 
 
 # ============================================================================= complex pairs

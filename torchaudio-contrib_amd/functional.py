@@ -33,6 +33,7 @@ from . import _specaug
 from . import _augment
 from . import _sox
 from . import _ddsp
+from . import _cqt
 from ._bounded import Bounded
 from ._lazy import realize as _realize
 
@@ -42,7 +43,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
            'forced_align', 'merge_tokens', 'TokenSpan', 'ctc_beam_search', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
-           'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform']
+           'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform', 'cqt']
 
 _call = _ops.call
 
@@ -760,6 +761,31 @@ def filter_waveform(waveform, kernels, delay_compensation=-1):
     h = _tensor(kernels, 'kernels')
     _ddsp.check_filter_waveform(x, h, int(delay_compensation))
     return _call('filter_waveform', x, h, int(delay_compensation))
+
+
+def cqt(waveforms, sample_rate, hop_length=512, fmin=32.70, n_bins=84, bins_per_octave=12, filter_scale=1.0, gamma=0.0, norm=1,
+        center=True, pad_mode='reflect', scale=True, power=None):
+    """``(…, time) → (…, n_bins, T, 2)``: the time-domain constant-Q transform (variable-Q for ``gamma > 0``) of nnAudio's
+    ``CQT1992v2`` and librosa's wavelet basis, as complex pairs; ``power=1.0`` / ``2.0`` give ``(…, n_bins, T)``, ``|C|`` / ``|C|^2``.
+    With ``B = bins_per_octave``, ``alpha = 2^(1/B) - 1``, ``Q = filter_scale / alpha``: ``f_k = fmin 2^(k/B)``, ``N_k = ceil(Q sr /
+    (f_k + gamma / alpha))``, ``g_k[j] = w_k[j] exp(2 pi i f_k n_j / sr)``, ``n_j = j - floor(N_k / 2)``, ``w_k`` the periodic Hann
+    window of ``N_k`` points; ``g_k`` is divided by its ``norm``-norm (1, 2; ``None``: not at all) and multiplied by ``sqrt(N_k)``
+    where ``scale``.  ``C[k, t] = sum_j x_pad[c_t + n_j] conj(g_k[j])``.  ``center=True``: the row is padded by ``P = floor(N_0 / 2)``
+    on both sides (``pad_mode`` ``'reflect'``, which needs a row longer than ``P``, or ``'constant'``), ``T = 1 + len // hop_length``,
+    ``c_t = P + t hop_length``; ``center=False``: ``T = 1 + (len - N_0) // hop_length``, ``c_t = floor(N_0 / 2) + t hop_length``.  The
+    one sample an odd ``N_0`` reaches beyond that padding is the mirror's next one where the row has it and zero where not.
+
+    float32 on a HIP device (float16 / bfloat16 widened) with ``hop_length % 4 == 0`` is ONE launch of ``tac_cqt_f32``
+    (csrc/cqt.hip): a band-sparse fp32 MFMA GEMM of the waveform's Toeplitz view, staged through LDS with the padding in the
+    load's index, against the bank built here in float64 and rounded once; ``gamma``, ``norm``, ``scale`` and ``filter_scale``
+    cost the kernel nothing.  Deviation: a non-finite sample reaches all 8 bins of a bank group whose span covers it in a frame
+    (DESIGN §7).  float64, other hops (and hops above 1300), expanded views, CPU tensors and the backward pass take
+    ``_composite.cqt`` (the padded ``conv1d``), announced with ``CompositeRouteWarning`` on a device.  ``TypeError`` for a
+    non-tensor, ``ValueError`` for the arguments, ``RuntimeError`` for a row too short."""
+    x = _waveform(waveforms, 'cqt')
+    _cqt.check(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, gamma, norm, pad_mode, power)
+    return _call('cqt', x, float(sample_rate), int(hop_length), float(fmin), int(n_bins), int(bins_per_octave), float(filter_scale),
+                 float(gamma), int(norm or 0), bool(center), pad_mode, bool(scale), int(power or 0))
 
 
 def biquad(waveforms, b0, b1, b2, a0, a1, a2):

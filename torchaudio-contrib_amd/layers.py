@@ -559,6 +559,24 @@ class FilterWaveform(nn.Module):
         return self.__class__.__name__ + '(delay_compensation={})'.format(self.delay_compensation)
 
 
+class CQT(nn.Module):
+    """``functional.cqt`` as a layer: ``(…, time) → (…, n_bins, T, 2)`` pairs, or ``(…, n_bins, T)`` for ``power`` 1.0 / 2.0.  No
+    buffers: the bank is built from the arguments in float64 and kept per argument set."""
+
+    def __init__(self, sample_rate, hop_length=512, fmin=32.70, n_bins=84, bins_per_octave=12, filter_scale=1.0, gamma=0.0, norm=1,
+                 center=True, pad_mode='reflect', scale=True, power=None):
+        super(CQT, self).__init__()
+        F._cqt.check(sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, gamma, norm, pad_mode, power)
+        self.args = (sample_rate, hop_length, fmin, n_bins, bins_per_octave, filter_scale, gamma, norm, center, pad_mode, scale, power)
+
+    def forward(self, waveforms):
+        return F.cqt(waveforms, *self.args)
+
+    def __repr__(self):
+        return self.__class__.__name__ + ('(sample_rate={}, hop_length={}, fmin={}, n_bins={}, bins_per_octave={}, filter_scale={}, '
+                                          'gamma={}, norm={}, center={}, pad_mode={!r}, scale={}, power={})').format(*self.args)
+
+
 class Preemphasis(_ModuleNoStateBuffers):
     """``functional.preemphasis`` as a layer: ``y[n] = x[n] - coeff x[n-1]``.  No buffers: ``coeff`` is a Python float, and the
     two float64 host tensors the op takes are plain attributes (they stay float64 on the host whatever ``.to()`` is given)."""
