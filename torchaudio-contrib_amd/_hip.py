@@ -1073,10 +1073,19 @@ def host_coeffs(t):
     return cached_on(t, '_tac_coef', (), build) if t.is_cuda else build()
 
 
+def _strided_rows(x):
+    """``x`` (…, L) as ``(rows, L)`` for the launches that take a row stride: read where it lies when its leading dims collapse into
+    one positive row stride over unit-stride rows, copied otherwise"""
+    length = int(x.shape[-1])
+    rows = x.reshape(-1, length)
+    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
+        rows = rows.contiguous()
+    return rows
+
+
 def lfilter_rows(x, b, a, clamp, reverse=False):
     """``(…, L) -> (…, L)`` through ``tac_lfilter_f32``: one launch.  ``b`` / ``a`` are tuples of Python floats; ``reverse`` runs the
-    filter from the end of each row (the adjoint).  ``x`` is read where it lies when its leading dims collapse into one positive
-    row stride over unit-stride rows; it is copied otherwise."""
+    filter from the end of each row (the adjoint).  ``x`` is read in place or copied by ``_strided_rows``' rule."""
     global _lfilter_chunk_checked
     length = x.shape[-1]
     out = _empty(tuple(x.shape), device=x.device)
@@ -1087,9 +1096,7 @@ def lfilter_rows(x, b, a, clamp, reverse=False):
                 raise RuntimeError('libtac_amd.so filters %d samples per lane, _hip.LFILTER_C says %d'
                                    % (h.tac_lfilter_chunk(), LFILTER_C))
             _lfilter_chunk_checked = True
-        rows = x.reshape(-1, length)
-        if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
-            rows = rows.contiguous()
+        rows = _strided_rows(x)
         cb, ca = _lfilter_arrays(b, a)
         _launch('tac_lfilter_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0), cb, ca, len(a),
                 int(bool(clamp)), int(bool(reverse)), _native.ptr(out))
@@ -1133,8 +1140,8 @@ def sosfilt_covers(sos):
 
 def sosfilt_rows(x, sos, clamp, reverse=False):
     """``(…, L) -> (…, L)`` through ``tac_sosfilt_f32``: the whole cascade in one launch.  ``sos`` as for ``sosfilt_covers``;
-    ``reverse`` runs the adjoint (the sections in reverse order, each from the end of the row).  ``x`` is read where it lies when
-    its leading dims collapse into one positive row stride over unit-stride rows; it is copied otherwise."""
+    ``reverse`` runs the adjoint (the sections in reverse order, each from the end of the row).  ``x`` is read in place or copied
+    by ``_strided_rows``' rule."""
     global _sosfilt_checked
     length = x.shape[-1]
     out = _empty(tuple(x.shape), device=x.device)
@@ -1146,9 +1153,7 @@ def sosfilt_rows(x, sos, clamp, reverse=False):
                 raise RuntimeError('libtac_amd.so reports (sections, tile, blocks per CU) = %r for sosfilt, _hip says %r'
                                    % (found, (SOSFILT_MAX_SECTIONS, SOSFILT_TILE, SOSFILT_BLOCKS_PER_CU)))
             _sosfilt_checked = True
-        rows = x.reshape(-1, length)
-        if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
-            rows = rows.contiguous()
+        rows = _strided_rows(x)
         _launch('tac_sosfilt_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0), _sosfilt_array(sos),
                 len(sos), int(bool(clamp)), int(bool(reverse)), _native.ptr(out))
     return out
@@ -1188,16 +1193,6 @@ def _sox_check():
         _sox_checked = True
 
 
-def _sox_rows(x):
-    """``x`` as ``(rows, length)`` read where it lies when its leading dims collapse into one positive row stride over unit-stride
-    rows; copied otherwise (``lfilter_rows``' rule)"""
-    length = x.shape[-1]
-    rows = x.reshape(-1, length)
-    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
-        rows = rows.contiguous()
-    return rows
-
-
 def sox_table(host, device):
     """The device copy of a host LFO table (``_sox.phaser_plan`` / ``flanger_plan``), uploaded once per device and kept on the host
     tensor object"""
@@ -1213,7 +1208,7 @@ def overdrive_rows(x, g, c):
     out = _empty(tuple(x.shape), device=x.device)
     if out.numel():
         _sox_check()
-        rows = _sox_rows(x)
+        rows = _strided_rows(x)
         _launch('tac_overdrive_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], x.shape[-1], rows.stride(0), float(g), float(c),
                 _native.ptr(out))
     return out
@@ -1229,7 +1224,7 @@ def phaser_rows(x, table, L, gain_in, gain_out, decay, sequential=False):
     out = _empty(tuple(x.shape), device=x.device)
     if out.numel():
         _sox_check()
-        rows = _sox_rows(x)
+        rows = _strided_rows(x)
         mod = sox_table(table, x.device)
         _launch('tac_phaser_seq_f32' if sequential else 'tac_phaser_f32', x.device, (out,), _native.ptr(rows), rows.shape[0],
                 x.shape[-1], rows.stride(0), _native.ptr(mod), int(table.numel()), int(L), float(gain_in), float(decay),
@@ -1248,7 +1243,7 @@ def flanger_rows(x, plan):
     if out.numel():
         _sox_check()
         channels = x.shape[-2]
-        rows = _sox_rows(x)
+        rows = _strided_rows(x)
         lfo = sox_table(plan.lfo, x.device)
         phases = (ctypes.c_int32 * channels)(*plan.phases[:channels])
         _launch('tac_flanger_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], channels, x.shape[-1], rows.stride(0),
@@ -1331,7 +1326,7 @@ def filter_waveform_rows(x, kernels, plan, shift, adjoint=False):
     out = _empty(tuple(x.shape), device=x.device)
     if out.numel():
         _ddsp_check()
-        rows = _sox_rows(x)
+        rows = _strided_rows(x)
         F, K = kernels.shape[-2:]
         _launch('tac_filter_waveform_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], x.shape[-1], rows.stride(0),
                 _native.ptr(kernels), plan[0], plan[1], plan[2], kernels.stride(-2), kernels.stride(-1), F, K, int(shift),
@@ -1343,7 +1338,7 @@ def filter_waveform_grad_kernels_rows(x, g, n_filters, taps, shift):
     """``(…, F, K)``: every row's own gradient w.r.t. its filters through ``tac_filter_waveform_grad_kernels_f32`` (one launch of
     per-piece partial sums) and one ``torch.sum`` over the pieces of long chunks; the caller adds the rows that share filters."""
     _ddsp_check()
-    xr, gr = _sox_rows(x), _sox_rows(g)
+    xr, gr = _strided_rows(x), _strided_rows(g)
     pieces = int(_native.lib().tac_filter_waveform_pieces(x.shape[-1], n_filters))
     part = _empty((xr.shape[0], n_filters, pieces, taps), device=x.device)
     _launch('tac_filter_waveform_grad_kernels_f32', x.device, (part,), _native.ptr(xr), xr.stride(0), _native.ptr(gr), gr.stride(0),
@@ -1388,7 +1383,7 @@ def cqt_rows(x, plan, hop, n_frames, center, reflect, power):
     out = _empty(tuple(x.shape[:-1]) + ((K, n_frames, 2) if power == 0 else (K, n_frames)), device=x.device)
     if out.numel():
         _cqt_check()
-        rows = _sox_rows(x)
+        rows = _strided_rows(x)
         bank = cached_on(plan.bank, '_tac_coef', ('cqt', str(x.device)), lambda: plan.bank.to(x.device))
         groups = cached_on(plan.groups, '_tac_coef', ('cqt', str(x.device)), lambda: plan.groups.to(x.device))
         origin = (0 if center else plan.n_max // 2) - plan.c0
@@ -2158,16 +2153,6 @@ def _kaldi_device_tables(p, w, n, device):
     return hit
 
 
-def _kaldi_rows(x):
-    """``x`` (…, L) as (rows, L) for the kaldi launches: read where it lies when its leading dims collapse into one positive row
-    stride over unit-stride rows, copied otherwise"""
-    length = int(x.shape[-1])
-    rows = x.reshape(-1, length)
-    if (length > 1 and rows.stride(1) != 1) or (rows.shape[0] > 1 and rows.stride(0) <= 0):
-        rows = rows.contiguous()
-    return rows
-
-
 def _kaldi_flags(p):
     return sum(bit for name, bit in _KALDI_FLAGS.items() if getattr(p, name, False))
 
@@ -2202,7 +2187,7 @@ def kaldi_mfcc(x, p, w, s, n, m):
     out = _empty(tuple(x.shape[:-1]) + (m, p.num_ceps), device=x.device)
     if not out.numel():
         return out
-    rows = _kaldi_rows(x)
+    rows = _strided_rows(x)
     _launch('tac_kaldi_mfcc_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0),
             _native.ptr(window), _native.ptr(weights), _native.ptr(table), _native.ptr(dct), n, w, s, p.num_mel_bins, w_total,
             p.num_ceps, _kaldi_flags(p), p.preemphasis_coefficient, p.energy_floor, _native.ptr(out))
@@ -2216,7 +2201,7 @@ def kaldi_spectrogram(x, p, w, s, n, m):
     out = _empty(tuple(x.shape[:-1]) + (m, n // 2 + 1), device=x.device)
     if not out.numel():
         return out
-    rows = _kaldi_rows(x)
+    rows = _strided_rows(x)
     _launch('tac_kaldi_spectrogram_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], int(x.shape[-1]), rows.stride(0),
             _native.ptr(window), n, w, s, _kaldi_flags(p), p.preemphasis_coefficient, p.energy_floor, _native.ptr(out))
     return out
@@ -2232,7 +2217,7 @@ def kaldi_fbank(x, p, w, s, n, m):
     out = _empty(tuple(x.shape[:-1]) + (m, cols), device=x.device)
     if not out.numel():
         return out
-    rows = _kaldi_rows(x)
+    rows = _strided_rows(x)
     _launch('tac_kaldi_fbank_f32', x.device, (out,), _native.ptr(rows), rows.shape[0], length, rows.stride(0), _native.ptr(window),
             _native.ptr(weights), _native.ptr(table), n, w, s, p.num_mel_bins, w_total, _kaldi_flags(p), p.preemphasis_coefficient,
             p.energy_floor, _native.ptr(out))

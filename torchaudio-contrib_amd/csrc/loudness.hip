@@ -9,9 +9,10 @@
 //
 // loudness_energy_kernel   A row (one channel of one entry) is walked from its start by ONE workgroup in tiles of LO_TILE = 1024 *
 //                          LO_C consecutive samples, lane l owning samples [l C, l C + C) of the tile.  Per tile and per stage the
-//                          recursion runs as in lfilter.hip: the chunk from zero state, a Kogge-Stone scan of the end states over the
-//                          host-computed powers M^(C 2^i) — six steps in a wave, four across the sixteen waves through the LDS — the
-//                          previous tile's carry entering by linearity, then the chunk again from its true incoming state.  State,
+//                          recursion runs through biquad_scan.hpp (bq_incoming_published): the chunk from zero state, a Kogge-Stone
+//                          scan of the end states over the host-computed powers M^(C 2^i) — six steps in a wave, four across the
+//                          sixteen waves through the LDS — the previous tile's carry entering by linearity, then the chunk again
+//                          from its true incoming state.  The tile geometry, xs and the tile load are that header's too.  State,
 //                          scan and the stage outputs are float64: the shelf's output is clipped IN float64, stays in registers (the
 //                          neighbour's last two values come by a cross-lane move, a wave's by the LDS) and feeds the high-pass, whose
 //                          clipped float64 output is squared and summed.  Nothing between the float32 load and the sums is rounded
@@ -31,109 +32,32 @@
 //
 // Nothing is shared between rows or entries and a lane's incoming state depends on earlier samples only: a non-finite sample
 // reaches its own entry and nothing else.
-#include <math.h>
-
-#include "host_common.hpp"
+#include "biquad_scan.hpp"
 
 namespace tac {
 
-typedef float lo_f4 __attribute__((ext_vector_type(4)));
-
+// The tile in the words tests/loudness_rules.py quotes, held to the shared header's
 constexpr int LO_C_LOG = 4;
 constexpr int LO_C = 1 << LO_C_LOG;             // samples per lane
 constexpr int LO_THREADS = 1024;
-constexpr int LO_WAVES = LO_THREADS / 64;
 constexpr int LO_TILE = LO_THREADS * LO_C;      // samples per tile
-constexpr int LO_XS = LO_TILE + LO_TILE / LO_C + 1;
-constexpr int LO_STEPS = 10;                    // log2(LO_THREADS): M^(C 2^i), i < 10
+static_assert(LO_C_LOG == BQ_C_LOG && LO_THREADS == BQ_THREADS && LO_TILE == BQ_TILE, "loudness walks biquad_scan.hpp's tile");
 constexpr int LO_MAX_CHANNELS = 5;
-static_assert(LO_WAVES == 16 && (1 << LO_STEPS) == LO_THREADS, "the scans are six steps in a wave and four across sixteen waves");
 
-struct LoMat { double a, b, c, d; };            // [[a, b], [c, d]]
-struct LoStage {
-    double b0, b1, b2, a1, a2;
-    LoMat p[LO_STEPS];                          // p[i] = M^(C 2^i)
-};
-struct LoParams { LoStage s[2]; };              // the shelf, the high-pass
+struct LoParams { BqSection s[2]; };            // the shelf, the high-pass
 
 // LDS of the energy kernel, in doubles from its base; the float part (carry_x, xs) lies behind
 constexpr int LO_D_WAVE_STATE = 0;                              // [2][16][2]: the waves' own end states, and scanned
-constexpr int LO_D_CARRY = LO_D_WAVE_STATE + 4 * LO_WAVES;      // [2][2]: the filter state at the end of the tile, per stage
+constexpr int LO_D_CARRY = LO_D_WAVE_STATE + 4 * BQ_WAVES;      // [2][2]: the filter state at the end of the tile, per stage
 constexpr int LO_D_CARRY_Y = LO_D_CARRY + 4;                    // [2]: the last two clipped shelf outputs of the tile
 constexpr int LO_D_TAIL = LO_D_CARRY_Y + 2;                     // [16][2]: the last two clipped shelf outputs of each wave
-constexpr int LO_D_OPEN = LO_D_TAIL + 2 * LO_WAVES;             // [16]: the sum of the bin open at the end of each wave
-constexpr int LO_D_CARRY_BIN = LO_D_OPEN + LO_WAVES;            // [2]: ... and at the end of the tile, by tile parity
+constexpr int LO_D_OPEN = LO_D_TAIL + 2 * BQ_WAVES;             // [16]: the sum of the bin open at the end of each wave
+constexpr int LO_D_CARRY_BIN = LO_D_OPEN + BQ_WAVES;            // [2]: ... and at the end of the tile, by tile parity
 constexpr int LO_D_CLOSED = LO_D_CARRY_BIN + 2;                 // [16] ints in 8 doubles: whether a bin ends in the wave
-constexpr int LO_D_END = LO_D_CLOSED + LO_WAVES / 2;
-constexpr size_t LO_LDS_BYTES = LO_D_END * sizeof(double) + (4 + LO_XS) * sizeof(float);
-
-__device__ __forceinline__ int lo_at(int i) { return i + (i >> LO_C_LOG); }
-
-__device__ __forceinline__ void lo_apply(const LoMat& m, double u0, double u1, double& s0, double& s1) {
-    s0 += m.a * u0 + m.b * u1;
-    s1 += m.c * u0 + m.d * u1;
-}
+constexpr int LO_D_END = LO_D_CLOSED + BQ_WAVES / 2;
+constexpr size_t LO_LDS_BYTES = LO_D_END * sizeof(double) + (4 + BQ_XS) * sizeof(float);
 
 __device__ __forceinline__ double lo_clip(double y) { return y < -1.0 ? -1.0 : (y > 1.0 ? 1.0 : y); }      // (a NaN stays a NaN)
-
-// The state (y[c0 - 1], y[c0 - 2]) the lane's chunk starts from, given the chunk's feed-forward part v and the state (in0, in1) the
-// TILE starts from (used by thread 0 alone): lfilter.hip's pass 1 and scan.  Two barriers.
-__device__ __forceinline__ void lo_incoming(const LoStage& P, const double (&v)[LO_C], double (*wave_state)[LO_WAVES][2], int tid,
-                                            double& in0, double& in1) {
-    const int lane = tid & 63, wave = tid >> 6;
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int k = 0; k < LO_C; ++k) {
-        const double y = fma(-P.a1, s0, fma(-P.a2, s1, v[k]));
-        s1 = s0;
-        s0 = y;
-    }
-    if (tid == 0) lo_apply(P.p[0], in0, in1, s0, s1);           // the previous tile's carry, by linearity (zero in tile 0)
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const double u0 = __shfl_up(s0, 1 << i), u1 = __shfl_up(s1, 1 << i);
-        if (lane >= (1 << i)) lo_apply(P.p[i], u0, u1, s0, s1);
-    }
-    double e0 = __shfl_up(s0, 1), e1 = __shfl_up(s1, 1);         // the wave-local state before the lane's chunk
-    if (lane == 0) e0 = e1 = 0.0;
-    if (lane == 63) {
-        wave_state[0][wave][0] = s0;
-        wave_state[0][wave][1] = s1;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        double w0 = lane < LO_WAVES ? wave_state[0][lane][0] : 0.0;
-        double w1 = lane < LO_WAVES ? wave_state[0][lane][1] : 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const double u0 = __shfl_up(w0, 1 << i), u1 = __shfl_up(w1, 1 << i);
-            if (lane >= (1 << i)) lo_apply(P.p[6 + i], u0, u1, w0, w1);
-        }
-        if (lane < LO_WAVES) {
-            wave_state[1][lane][0] = w0;
-            wave_state[1][lane][1] = w1;
-        }
-    }
-    __syncthreads();
-    if (tid > 0) {
-        in0 = e0;
-        in1 = e1;
-    }
-    if (wave > 0) {             // the state at the end of the previous wave, carried over the lane's `lane` chunks
-        double u0 = wave_state[1][wave - 1][0], u1 = wave_state[1][wave - 1][1];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            if ((lane >> i) & 1) {
-                double m0 = 0.0, m1 = 0.0;
-                lo_apply(P.p[i], u0, u1, m0, m1);
-                u0 = m0;
-                u1 = m1;
-            }
-        }
-        in0 += u0;
-        in1 += u1;
-    }
-}
 
 // Row r is channel r % channels of entry r / channels: it starts at (r / channels) stride_b + (r % channels) stride_c, unit time
 // stride.  used = nbins * step samples of it are read; bins: float64 [rows][nbins].
@@ -142,7 +66,7 @@ __global__ void __launch_bounds__(LO_THREADS)
 loudness_energy_kernel(const float* __restrict__ x, long long rows, int channels, long long stride_b, long long stride_c,
                        long long used, long long step, long long nbins, LoParams P, double* __restrict__ bins) {
     extern __shared__ __attribute__((aligned(16))) double lo_lds[];
-    double (*wave_state)[LO_WAVES][2] = reinterpret_cast<double (*)[LO_WAVES][2]>(lo_lds + LO_D_WAVE_STATE);
+    double (*wave_state)[BQ_WAVES][2] = reinterpret_cast<double (*)[BQ_WAVES][2]>(lo_lds + LO_D_WAVE_STATE);
     double (*carry_state)[2] = reinterpret_cast<double (*)[2]>(lo_lds + LO_D_CARRY);
     double* carry_y = lo_lds + LO_D_CARRY_Y;
     double (*wave_tail)[2] = reinterpret_cast<double (*)[2]>(lo_lds + LO_D_TAIL);
@@ -168,29 +92,8 @@ loudness_energy_kernel(const float* __restrict__ x, long long rows, int channels
                 ym1 = carry_y[0];
                 ym2 = carry_y[1];
             }
-            // ---- global -> xs
-            if constexpr (VEC) {
-                for (int q = tid; q < ((nt + 3) >> 2); q += LO_THREADS) {       // (n0 is a multiple of the tile: chunks stay aligned)
-                    const long long g = n0 + 4 * q;
-                    lo_f4 v;
-                    if (g + 3 < used) {
-                        v = *reinterpret_cast<const lo_f4*>(src + g);
-                    } else {
-                        v.x = g < used ? src[g] : 0.0f;
-                        v.y = g + 1 < used ? src[g + 1] : 0.0f;
-                        v.z = g + 2 < used ? src[g + 2] : 0.0f;
-                        v.w = 0.0f;
-                    }
-                    const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int j = 4 * q + k;
-                        if (j < nt) xs[lo_at(j)] = e[k];
-                    }
-                }
-            } else {
-                for (int j = tid; j < nt; j += LO_THREADS) xs[lo_at(j)] = src[n0 + j];
-            }
+            // ---- global -> xs (n0 is a multiple of the tile: the 16-byte loads have no lead)
+            bq_load<VEC, LO_THREADS>(src, used, n0, nt, tid, [=](int j, float e) { xs[bq_at(j)] = e; });
             __syncthreads();
 
             // ---- the shelf: the lane's chunk and the two samples before it (zero before the row and behind the samples read)
@@ -199,25 +102,25 @@ loudness_energy_kernel(const float* __restrict__ x, long long rows, int channels
             {
                 float xr[LO_C];
 #pragma unroll
-                for (int k = 0; k < LO_C; ++k) xr[k] = c0 + k < nt ? xs[lo_at(c0 + k)] : 0.0f;
+                for (int k = 0; k < LO_C; ++k) xr[k] = c0 + k < nt ? xs[bq_at(c0 + k)] : 0.0f;
                 float xm1 = 0.0f, xm2 = 0.0f;
                 if (tid > 0) {
-                    if (c0 - 1 < nt) xm1 = xs[lo_at(c0 - 1)];
-                    if (c0 - 2 < nt) xm2 = xs[lo_at(c0 - 2)];
+                    if (c0 - 1 < nt) xm1 = xs[bq_at(c0 - 1)];
+                    if (c0 - 2 < nt) xm2 = xs[bq_at(c0 - 2)];
                 } else if (t > 0) {
                     xm1 = carry_x[0];
                     xm2 = carry_x[1];
                     in0 = carry_state[0][0];
                     in1 = carry_state[0][1];
                 }
-                const LoStage& S = P.s[0];
+                const BqSection& S = P.s[0];
 #pragma unroll
                 for (int k = 0; k < LO_C; ++k) {
                     const float p1 = k >= 1 ? xr[k - 1] : xm1;
                     const float p2 = k >= 2 ? xr[k - 2] : (k == 1 ? xm1 : xm2);
                     v[k] = fma(S.b2, (double)p2, fma(S.b1, (double)p1, S.b0 * (double)xr[k]));
                 }
-                lo_incoming(S, v, wave_state, tid, in0, in1);
+                bq_incoming_published(S, v, wave_state, tid, in0, in1);
 #pragma unroll
                 for (int k = 0; k < LO_C; ++k) {
                     const double y = fma(-S.a1, in0, fma(-S.a2, in1, v[k]));
@@ -250,7 +153,7 @@ loudness_energy_kernel(const float* __restrict__ x, long long rows, int channels
                     ym1 = wave_tail[wave - 1][0];
                     ym2 = wave_tail[wave - 1][1];
                 }
-                const LoStage& S = P.s[1];
+                const BqSection& S = P.s[1];
                 in0 = in1 = 0.0;
                 if (tid == 0 && t > 0) {
                     in0 = carry_state[1][0];
@@ -262,7 +165,7 @@ loudness_energy_kernel(const float* __restrict__ x, long long rows, int channels
                     const double p2 = k >= 2 ? v[k - 2] : (k == 1 ? ym1 : ym2);
                     v[k] = fma(S.b2, p2, fma(S.b1, p1, S.b0 * v[k]));
                 }
-                lo_incoming(S, v, wave_state, tid, in0, in1);
+                bq_incoming_published(S, v, wave_state, tid, in0, in1);
 #pragma unroll
                 for (int k = 0; k < LO_C; ++k) {
                     const double y = fma(-S.a1, in0, fma(-S.a2, in1, v[k]));
@@ -384,32 +287,6 @@ loudness_gate_kernel(const double* __restrict__ bins, long long entries, int cha
     }
 }
 
-inline LoMat lo_mul(const LoMat& x, const LoMat& y) {
-    return LoMat{x.a * y.a + x.b * y.c, x.a * y.b + x.b * y.d, x.c * y.a + x.d * y.c, x.c * y.b + x.d * y.d};
-}
-
-// b[3], a[3] normalised by a[0] and the ten powers; TAC_E_INVALID for a zero a[0] or a non-finite coefficient, TAC_E_UNSUPPORTED
-// where one of the powers is not finite
-inline int lo_stage(const double* b, const double* a, LoStage* S) {
-    if (!(a[0] != 0.0) || !isfinite(a[0])) return TAC_E_INVALID;
-    double bn[3], an[3];
-    for (int k = 0; k < 3; ++k) {
-        bn[k] = b[k] / a[0];
-        an[k] = a[k] / a[0];
-        if (!isfinite(bn[k]) || !isfinite(an[k])) return TAC_E_INVALID;
-    }
-    S->b0 = bn[0], S->b1 = bn[1], S->b2 = bn[2], S->a1 = an[1], S->a2 = an[2];
-    const LoMat m{-an[1], -an[2], 1.0, 0.0};
-    LoMat q = m;
-    for (int k = 1; k < LO_C; ++k) q = lo_mul(q, m);
-    for (int i = 0; i < LO_STEPS; ++i) {
-        if (!isfinite(q.a) || !isfinite(q.b) || !isfinite(q.c) || !isfinite(q.d)) return TAC_E_UNSUPPORTED;
-        S->p[i] = q;
-        q = lo_mul(q, q);
-    }
-    return TAC_OK;
-}
-
 // blocks of `gate` samples every `step` in `length`, or 0
 inline long long lo_blocks(long long length, long long gate, long long step) {
     return (gate <= 0 || step <= 0 || length < gate) ? 0 : (length - gate) / step + 1;
@@ -440,7 +317,7 @@ int tac_loudness_f32(const float* waveform, int64_t entries, int32_t channels, i
     if ((entries > 1 && stride_b <= 0) || (channels > 1 && stride_c <= 0)) return TAC_E_INVALID;
     LoParams P;
     for (int i = 0; i < 2; ++i) {
-        const int rc = lo_stage(coeffs + 6 * i, coeffs + 6 * i + 3, &P.s[i]);
+        const int rc = bq_section(coeffs + 6 * i, coeffs + 6 * i + 3, 3, &P.s[i]);
         if (rc != TAC_OK) return rc;
     }
     const long long nb = lo_blocks(length, gate, step), nbins = nb + 3;

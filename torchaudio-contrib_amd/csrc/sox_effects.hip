@@ -2,12 +2,12 @@
 // ONE launch.  float32 is read once and written once; everything between is float64 on chip and rounded once.
 //
 //   overdrive   t = shape(g x + c);  v[n] = t[n] - t[n-1] + 0.995 v[n-1];  out = clamp(0.5 x + 0.75 v)
-//               lfilter.hip's tile walk: a row belongs to ONE workgroup, which walks it in tiles of OD_TILE = 1024 * OD_C samples;
-//               lane l owns samples [l C, l C + C).  The shaping runs on load, pass 1 gives the chunk's zero-state end value, a
-//               Kogge-Stone scan over the SCALAR powers a^(C 2^i) (six steps in the wave by cross-lane moves, then the sixteen
-//               wave values through the LDS, scanned by every wave for itself) gives the state the chunk starts from, pass 2
-//               runs the chunk from it, and 0.5 x + 0.75 v and the clamp run on store.  The last v and the last t of a tile are
-//               carried to lane 0 of the next one (two copies by the tile's parity).
+//               biquad_scan.hpp's tile geometry and load: a row belongs to ONE workgroup, which walks it in tiles of BQ_TILE =
+//               1024 * BQ_C samples; lane l owns samples [l C, l C + C).  The shaping runs on load, pass 1 gives the chunk's
+//               zero-state end value, a Kogge-Stone scan of this file's own over the SCALAR powers a^(C 2^i) (six steps in the
+//               wave by cross-lane moves, then the sixteen wave values through the LDS, scanned by every wave for itself) gives
+//               the state the chunk starts from, pass 2 runs the chunk from it, and 0.5 x + 0.75 v and the clamp run on store.
+//               The last v and the last t of a tile are carried to lane 0 of the next one (two copies by the tile's parity).
 //
 //   phaser      y[n] = gain_in x[n] + decay y[n - d(n)],  d(n) = L - m[n mod P] + 1 in [1, L];  out = clamp(gain_out y)
 //               every sample has ONE parent.  A workgroup walks a row in tiles of PH_TILE samples held in the LDS as
@@ -32,45 +32,10 @@
 //
 // Nothing is shared between rows and values move to later samples only: a non-finite sample reaches nothing in another row and
 // nothing before it in its own.  No atomics, no workspace, one writer per element: bit-identical from run to run.
-// (The tile geometry and the 16-byte loads restate lfilter.hip's under names of their own: that file's text is pinned by
-// tests/grid_rules.py and stays as it is.)
-#include <math.h>
-
-#include "host_common.hpp"
+// All three effects stage their samples with biquad_scan.hpp's bq_load.
+#include "biquad_scan.hpp"
 
 namespace tac {
-
-typedef float sx_f4 __attribute__((ext_vector_type(4)));
-
-// global -> LDS for `count` samples that start at row offset p0 (p0 >= 0, p0 + count <= length): 16 bytes per lane where the row
-// is aligned (VEC), a float per lane otherwise.  put(j, value) stores sample p0 + j.
-template <bool VEC, int THREADS, class Put>
-__device__ __forceinline__ void sx_load(const float* __restrict__ src, long long length, long long p0, int count, int tid, Put put) {
-    if constexpr (VEC) {
-        const long long a0f = p0 & ~3LL;
-        const int lead = (int)(p0 - a0f);
-        for (int q = tid; q < ((lead + count + 3) >> 2); q += THREADS) {
-            const long long g = a0f + 4 * q;
-            sx_f4 v;
-            if (g + 3 < length) {
-                v = *reinterpret_cast<const sx_f4*>(src + g);
-            } else {
-                v.x = g < length ? src[g] : 0.0f;
-                v.y = g + 1 < length ? src[g + 1] : 0.0f;
-                v.z = g + 2 < length ? src[g + 2] : 0.0f;
-                v.w = 0.0f;
-            }
-            const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int j = 4 * q + k - lead;
-                if (j >= 0 && j < count) put(j, e[k]);
-            }
-        }
-    } else {
-        for (int j = tid; j < count; j += THREADS) put(j, src[p0 + j]);
-    }
-}
 
 __device__ __forceinline__ float sx_clamp(double v) {
     const float f = (float)v;
@@ -78,23 +43,13 @@ __device__ __forceinline__ float sx_clamp(double v) {
 }
 
 // ============================================================================= overdrive
-constexpr int OD_C_LOG = 4;
-constexpr int OD_C = 1 << OD_C_LOG;             // samples per lane
-constexpr int OD_THREADS = 1024;
-constexpr int OD_WAVES = OD_THREADS / 64;
-constexpr int OD_TILE = OD_THREADS * OD_C;
-constexpr int OD_XS = OD_TILE + OD_TILE / OD_C + 1;
-constexpr int OD_STEPS = 10;                    // a^(C 2^i), i < 10
 constexpr int OD_BLOCKS_PER_CU = 2;
 constexpr double OD_A = 0.995;
-static_assert(OD_WAVES == 16 && (1 << OD_STEPS) == OD_THREADS, "the scan is six steps in a wave and four across sixteen waves");
 
 struct OdParams {
     double g, c;
-    double p[OD_STEPS];                         // 0.995^(C 2^i)
+    double p[BQ_STEPS];                         // 0.995^(C 2^i)
 };
-
-__device__ __forceinline__ int od_at(int i) { return i + (i >> OD_C_LOG); }     // xs is skewed by one float per chunk
 
 __device__ __forceinline__ double od_shape(float x, double g, double c) {
     const double t = g * (double)x + c;
@@ -103,50 +58,50 @@ __device__ __forceinline__ double od_shape(float x, double g, double c) {
     return t - t * t * t / 3.0;                 // (a NaN takes this branch and stays one)
 }
 
-constexpr int OD_HEAD = OD_WAVES + 4;           // doubles in front of xs: wave_state[16] | hist[2][2] (last v, last t)
+constexpr int OD_HEAD = BQ_WAVES + 4;           // doubles in front of xs: wave_state[16] | hist[2][2] (last v, last t)
 
 template <bool VEC>
-__global__ void __launch_bounds__(OD_THREADS)
+__global__ void __launch_bounds__(BQ_THREADS)
 overdrive_kernel(const float* __restrict__ x, long long rows, long long length, long long stride_r, OdParams P,
                  float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) double od_lds[];
     double* wave_state = od_lds;
-    double (*hist)[2] = reinterpret_cast<double (*)[2]>(od_lds + OD_WAVES);
+    double (*hist)[2] = reinterpret_cast<double (*)[2]>(od_lds + BQ_WAVES);
     float* xs = reinterpret_cast<float*>(od_lds + OD_HEAD);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
-    const int c0 = tid * OD_C;
-    const long long tiles = (length + OD_TILE - 1) / OD_TILE;
+    const int c0 = tid * BQ_C;
+    const long long tiles = (length + BQ_TILE - 1) / BQ_TILE;
 
     for (long long row = blockIdx.x; row < rows; row += gridDim.x) {
         const float* src = x + row * stride_r;
         float* dst = out + row * length;
         for (long long t = 0; t < tiles; ++t) {
-            const long long n0 = t * OD_TILE;
-            const int nt = (int)(length - n0 < OD_TILE ? length - n0 : OD_TILE);
+            const long long n0 = t * BQ_TILE;
+            const int nt = (int)(length - n0 < BQ_TILE ? length - n0 : BQ_TILE);
             const int cur = (int)(t & 1);
-            sx_load<VEC, OD_THREADS>(src, length, n0, nt, tid, [&](int j, float v) { xs[od_at(j)] = v; });
+            bq_load<VEC, BQ_THREADS>(src, length, n0, nt, tid, [&](int j, float v) { xs[bq_at(j)] = v; });
             __syncthreads();
 
             // ---- the shaping on load: the lane's chunk of t, and t just before it (zero before the row)
-            double v[OD_C];
+            double v[BQ_C];
 #pragma unroll
-            for (int k = 0; k < OD_C; ++k) v[k] = c0 + k < nt ? od_shape(xs[od_at(c0 + k)], P.g, P.c) : 0.0;
+            for (int k = 0; k < BQ_C; ++k) v[k] = c0 + k < nt ? od_shape(xs[bq_at(c0 + k)], P.g, P.c) : 0.0;
             double tprev = 0.0, in = 0.0;
             if (tid > 0) {
-                if (c0 - 1 < nt) tprev = od_shape(xs[od_at(c0 - 1)], P.g, P.c);
+                if (c0 - 1 < nt) tprev = od_shape(xs[bq_at(c0 - 1)], P.g, P.c);
             } else if (t > 0) {
                 in = hist[cur ^ 1][0];
                 tprev = hist[cur ^ 1][1];
             }
-            if (tid == OD_THREADS - 1) hist[cur][1] = v[OD_C - 1];
+            if (tid == BQ_THREADS - 1) hist[cur][1] = v[BQ_C - 1];
             // ---- u[k] = t[k] - t[k - 1], in place from the last sample down
 #pragma unroll
-            for (int k = OD_C - 1; k >= 0; --k) v[k] -= k >= 1 ? v[k - 1] : tprev;
+            for (int k = BQ_C - 1; k >= 0; --k) v[k] -= k >= 1 ? v[k - 1] : tprev;
             // ---- pass 1: the chunk's end value from zero state
             double s = 0.0;
 #pragma unroll
-            for (int k = 0; k < OD_C; ++k) s = fma(OD_A, s, v[k]);
+            for (int k = 0; k < BQ_C; ++k) s = fma(OD_A, s, v[k]);
             if (tid == 0) s = fma(P.p[0], in, s);           // the previous tile's carry, by linearity (zero in tile 0)
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -157,7 +112,7 @@ overdrive_kernel(const float* __restrict__ x, long long rows, long long length, 
             if (lane == 0) e = 0.0;
             if (lane == 63) wave_state[wave] = s;
             __syncthreads();
-            double w = lane < OD_WAVES ? wave_state[lane] : 0.0;
+            double w = lane < BQ_WAVES ? wave_state[lane] : 0.0;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const double u = __shfl_up(w, 1 << i);
@@ -173,16 +128,16 @@ overdrive_kernel(const float* __restrict__ x, long long rows, long long length, 
             }
             // ---- pass 2 from the true incoming state; 0.5 x + 0.75 v and the clamp on store
 #pragma unroll
-            for (int k = 0; k < OD_C; ++k) {
+            for (int k = 0; k < BQ_C; ++k) {
                 in = fma(OD_A, in, v[k]);
                 v[k] = in;
             }
-            if (tid == OD_THREADS - 1) hist[cur][0] = v[OD_C - 1];
+            if (tid == BQ_THREADS - 1) hist[cur][0] = v[BQ_C - 1];
 #pragma unroll
-            for (int k = 0; k < OD_C; ++k)
-                if (c0 + k < nt) xs[od_at(c0 + k)] = sx_clamp(0.5 * (double)xs[od_at(c0 + k)] + 0.75 * v[k]);
+            for (int k = 0; k < BQ_C; ++k)
+                if (c0 + k < nt) xs[bq_at(c0 + k)] = sx_clamp(0.5 * (double)xs[bq_at(c0 + k)] + 0.75 * v[k]);
             __syncthreads();
-            for (int j = tid; j < nt; j += OD_THREADS) dst[n0 + j] = xs[od_at(j)];
+            for (int j = tid; j < nt; j += BQ_THREADS) dst[n0 + j] = xs[bq_at(j)];
             __syncthreads();
         }
     }
@@ -193,8 +148,8 @@ inline int od_params(double g, double c, OdParams* P) {
     P->g = g;
     P->c = c;
     double q = 1.0;
-    for (int k = 0; k < OD_C; ++k) q *= OD_A;
-    for (int i = 0; i < OD_STEPS; ++i) {
+    for (int k = 0; k < BQ_C; ++k) q *= OD_A;
+    for (int i = 0; i < BQ_STEPS; ++i) {
         P->p[i] = q;
         q *= q;
     }
@@ -229,7 +184,7 @@ phaser_kernel(const float* __restrict__ x, long long rows, long long length, lon
             const long long n0 = t * PH_TILE;
             const int nt = (int)(length - n0 < PH_TILE ? length - n0 : PH_TILE);
             const unsigned m0 = (unsigned)(n0 % P);
-            sx_load<VEC, PH_THREADS>(src, length, n0, nt, tid, [&](int j, float v) { val[j] = gain_in * (double)v; });
+            bq_load<VEC, PH_THREADS>(src, length, n0, nt, tid, [&](int j, float v) { val[j] = gain_in * (double)v; });
 #pragma unroll
             for (int q = 0; q < PH_K; ++q) {
                 const int j = tid + PH_THREADS * q;
@@ -371,7 +326,7 @@ flanger_fir_kernel(const float* __restrict__ x, long long rows, long long length
         const long long n0 = t * FL_TILE;
         const int nt = (int)(length - n0 < FL_TILE ? length - n0 : FL_TILE);
         const int back = (int)(n0 < halo ? n0 : halo);      // samples before the tile that exist
-        sx_load<VEC, FL_THREADS>(src, length, n0 - back, back + nt, tid, [&](int j, float v) { fl_xs[halo - back + j] = v; });
+        bq_load<VEC, FL_THREADS>(src, length, n0 - back, back + nt, tid, [&](int j, float v) { fl_xs[halo - back + j] = v; });
         __syncthreads();
         const unsigned m0 = (unsigned)((n0 + Q.phase[row % Q.channels]) % Q.P);
         for (int j = tid; j < nt; j += FL_THREADS) {
@@ -440,7 +395,7 @@ inline bool fl_supported(int Lb, int P, int W, int channels) {
 
 extern "C" {
 
-int32_t tac_overdrive_tile(void) { return tac::OD_TILE; }
+int32_t tac_overdrive_tile(void) { return tac::BQ_TILE; }
 int32_t tac_overdrive_blocks_per_cu(void) { return tac::OD_BLOCKS_PER_CU; }
 
 int tac_overdrive_supported(double g, double c) {
@@ -457,10 +412,10 @@ int tac_overdrive_f32(const float* x, int64_t rows, int64_t length, int64_t stri
     const int rc = od_params(g, c, &P);
     if (rc != TAC_OK) return rc;
     const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (stride_r & 3) == 0;
-    const size_t bytes = OD_HEAD * sizeof(double) + OD_XS * sizeof(float);
+    const size_t bytes = OD_HEAD * sizeof(double) + BQ_XS * sizeof(float);
     const long long blocks = persistent_blocks(rows, 1, (long long)device_cu_count() * OD_BLOCKS_PER_CU);
     auto kern = vec ? overdrive_kernel<true> : overdrive_kernel<false>;
-    return launch_kernel(kern, blocks, OD_THREADS, bytes, (hipStream_t)stream, x, (long long)rows, (long long)length,
+    return launch_kernel(kern, blocks, BQ_THREADS, bytes, (hipStream_t)stream, x, (long long)rows, (long long)length,
                          (long long)stride_r, P, out);
 }
 
