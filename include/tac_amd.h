@@ -1158,6 +1158,54 @@ int tac_cqt_f32(const float* x, int64_t rows, int64_t length, int64_t stride_r, 
                 int32_t n_groups, int32_t n_bins, int32_t span, int32_t hop, int64_t n_frames, int64_t origin, int reflect, int power,
                 float* out, void* stream);
 
+/* (38) functional.ctc_loss and the CTCLoss layer: the CTC loss with torch.nn.functional.ctc_loss's semantics, and its gradient
+ *      (csrc/ctc_loss.hip).  log_probs: float32 [frames][batch][classes], TIME-MAJOR, read where it lies through its positive
+ *      element strides stride_t / stride_n / stride_c (a transposed (batch, frames, classes) output or a slice of a padded one is
+ *      not copied); element offsets are 64-bit.  targets: DEVICE, int64 where index64 != 0, else int32, targets_total elements:
+ *      either [batch][max_targets] contiguous (target_offsets NULL, targets_total = batch * max_targets), or the entries'
+ *      targets one after the other with target_offsets: DEVICE int64 [batch], where each entry's targets start.  input_lengths
+ *      (Tb), target_lengths (Lb): DEVICE int32 [batch].  blank in [0, classes).  max_targets = S is the width of the lattice:
+ *      alphas, betas: float32 [batch][frames][2 S + 1]; costs, grad_costs: float32 [batch].  S + 1 above
+ *      tac_ctc_loss_max_targets() (1024) or classes above tac_ctc_loss_max_classes() (32768: the gradient launch keeps a 16-bit
+ *      class table of 2 * classes bytes in the LDS): TAC_E_UNSUPPORTED.  Each entry below is ONE launch.  Every sum has one
+ *      fixed order and nothing is atomic: the same bits from run to run, for the 16-byte and the dword form of the class rows
+ *      (the form follows from the alignment of bases and strides, stride_c == 1 and classes % 4), and for an entry whatever
+ *      else is in the batch.
+ *
+ *      Per entry: states s = 0 .. 2 Lb, even ones the blank, s = 2k + 1 targets[k]; alpha[0][0] = lp[0][blank], alpha[0][1] =
+ *      lp[0][targets[0]], -inf elsewhere; alpha[t][s] = logsumexp(alpha[t-1][s], alpha[t-1][s-1], alpha[t-1][s-2] (only for odd
+ *      s >= 3 with targets[s/2] != targets[s/2 - 1])) + lp[t][label(s)]; beta likewise from (Tb - 1, 2 Lb) downwards with
+ *      beta[Tb-1][2 Lb] = lp[Tb-1][blank], beta[Tb-1][2 Lb - 1] = lp[Tb-1][targets[Lb-1]]; logsumexp of nothing but -inf is -inf.
+ *
+ *      tac_ctc_loss_f32: costs[b] = -logaddexp(alpha[Tb-1][2 Lb], alpha[Tb-1][2 Lb - 1]), Tb dependent steps per entry; +inf for an
+ *      entry no path fits (Tb < Lb + repeats).  alphas and betas both NULL: only the costs, by the alpha workgroups alone.
+ *      Otherwise every element of alphas and betas is written: ZERO outside an entry's (Tb, 2 Lb + 1) lattice.
+ *      tac_ctc_loss_group_steps() (8) steps have their emissions loaded together, tac_ctc_loss_ring_steps() (32) steps ahead.
+ *
+ *      tac_ctc_loss_grad_f32: grad[t][b][c] = (exp(lp[t][b][c]) - exp(ab[t][c] + costs[b] - lp[t][b][c])) grad_costs[b] with
+ *      ab[t][c] = logsumexp over the states s with label(s) = c of alphas[b][t][s] + betas[b][t][s] (the second term is absent
+ *      for a class without a state), written through grad_stride_t / grad_stride_n / grad_stride_c; zero for t >= Tb without a
+ *      read.  An entry whose cost is infinite: zero everywhere where zero_infinity != 0, else NaN for t < Tb and zero behind.
+ *      Every element of grad is written.
+ *
+ *      An entry with Tb outside [1, frames], Lb outside [0, S], targets that leave the targets tensor, or a used target equal
+ *      to blank or outside [0, classes) gets cost NaN, alphas and betas NaN and a NaN gradient over its whole block; none of
+ *      these values forms an address, and the other entries are unaffected.  (With target_offsets an entry with S < Lb that
+ *      stays inside the tensor is infeasible, not invalid: cost +inf.) */
+int32_t tac_ctc_loss_max_targets(void);
+int32_t tac_ctc_loss_max_classes(void);
+int32_t tac_ctc_loss_group_steps(void);
+int32_t tac_ctc_loss_ring_steps(void);
+int tac_ctc_loss_f32(const float* log_probs, int64_t frames, int64_t batch, int64_t classes, int64_t stride_t, int64_t stride_n,
+                     int64_t stride_c, const void* targets, int64_t max_targets, int64_t targets_total, int32_t index64,
+                     const int64_t* target_offsets, const int32_t* input_lengths, const int32_t* target_lengths, int32_t blank,
+                     float* alphas, float* betas, float* costs, void* stream);
+int tac_ctc_loss_grad_f32(const float* log_probs, int64_t frames, int64_t batch, int64_t classes, int64_t stride_t, int64_t stride_n,
+                          int64_t stride_c, const void* targets, int64_t max_targets, int64_t targets_total, int32_t index64,
+                          const int64_t* target_offsets, const int32_t* input_lengths, const int32_t* target_lengths, int32_t blank,
+                          int32_t zero_infinity, const float* alphas, const float* betas, const float* costs, const float* grad_costs,
+                          float* grad, int64_t grad_stride_t, int64_t grad_stride_n, int64_t grad_stride_c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,7 @@ from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filte
                          preemphasis, deemphasis, fftconvolve, convolve, kaldi_fbank, sliding_window_cmn,
                          compute_deltas, kaldi_mfcc, kaldi_spectrogram, mask_along_axis, mask_along_axis_iid,
                          add_noise, speed, pitch_shift, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
-                         apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, forced_align, ctc_beam_search,
+                         apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, ctc_loss, forced_align, ctc_beam_search,
                          merge_tokens, TokenSpan, vad, vad_start, simulate_rir_ism, simulate_rir_ism_batch,
                          overdrive, phaser, flanger, oscillator_bank, filter_waveform, cqt)
 from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
@@ -28,7 +28,7 @@ from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filt
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,
                      KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment,
                      AddNoise, Speed, SpeedPerturbation, PitchShift, Loudness, PitchFrequency, PSD, SoudenMVDR, MVDR,
-                     RTFMVDR, RNNTLoss, Vad, SimulateRirIsm)
+                     RTFMVDR, RNNTLoss, CTCLoss, Vad, SimulateRirIsm)
 from . import decoder
 from .decoder import CTCHypothesis, CTCBeamDecoder, ctc_decoder
 from . import distributed

@@ -1033,6 +1033,11 @@ def rnnt_loss_grad(logits, targets, logit_lengths, target_lengths, alphas, betas
     return grad.to(logits.dtype)
 
 
+# ----------------------------------------------------------------------------- ctc_loss
+#: the definition of ``functional.ctc_loss`` is torch's own operator
+ctc_loss = torch.nn.functional.ctc_loss
+
+
 # ----------------------------------------------------------------------------- forced_align
 def align_valid(log_probs, targets, input_lengths, target_lengths, blank):
     """``(ok, Tb, Lb, lab)``: which entries have ``1 <= Tb <= T``, ``0 <= Lb <= L``, every used target inside ``[0, C)`` and not the

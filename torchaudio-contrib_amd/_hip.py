@@ -1924,6 +1924,80 @@ def rnnt_grad(logits, targets, logit_lengths, target_lengths, alphas, betas, den
     return out
 
 
+# ----------------------------------------------------------------------------- ctc_loss (csrc/ctc_loss.hip)
+def ctc_loss_max_targets():
+    """the most ``S + 1`` the lattice launch takes: the pairs of states of one workgroup"""
+    return _native.lib().tac_ctc_loss_max_targets()
+
+
+def ctc_loss_max_classes():
+    """the most classes the gradient launch takes: its 16-bit class table lies in the LDS"""
+    return _native.lib().tac_ctc_loss_max_classes()
+
+
+def ctc_loss_reason(log_probs, max_targets):
+    """why the launches of csrc/ctc_loss.hip do not take these ``(T, N, C)`` log-probabilities as they lie with a target axis of
+    ``max_targets``, or None"""
+    if log_probs.dtype != torch.float32:
+        return 'dtype %s' % str(log_probs.dtype).replace('torch.', '')
+    if any(st <= 0 for st, n in zip(log_probs.stride(), log_probs.shape) if n > 1):
+        return 'expanded or non-positive strides'
+    if max_targets + 1 > ctc_loss_max_targets():
+        return 'a target axis of %d + 1 (the kernel takes up to %d)' % (max_targets, ctc_loss_max_targets())
+    if log_probs.shape[2] > ctc_loss_max_classes():
+        return '%d classes (the kernel takes up to %d)' % (log_probs.shape[2], ctc_loss_max_classes())
+    if max(log_probs.shape) >= 2 ** 30:
+        return 'an axis of 2^30 or more'
+    return None
+
+
+def _ctc_arguments(log_probs, targets, input_lengths, target_lengths, blank, max_targets):
+    """the leading arguments both entry points share, and the tensors that have to outlive the launch.  Concatenated targets get
+    their per-entry offsets from a ``cumsum`` on the device: nothing waits for the host."""
+    T, N, C = log_probs.shape
+    dev = log_probs.device
+    targets = targets if (targets.is_contiguous() and targets.device == dev) else targets.to(dev).contiguous()
+    il, tl = _rnnt_ints(input_lengths, dev), _rnnt_ints(target_lengths, dev)
+    offsets = None
+    if targets.dim() == 1:
+        wide = tl.to(torch.int64)
+        offsets = torch.cumsum(wide, 0) - wide
+    args = (_native.ptr(log_probs), T, N, C, log_probs.stride(0), log_probs.stride(1), log_probs.stride(2),
+            _native.ptr(targets) if targets.numel() else None, max_targets, targets.numel(),
+            1 if targets.dtype == torch.int64 else 0, None if offsets is None else _native.ptr(offsets), _native.ptr(il),
+            _native.ptr(tl), blank)
+    return args, (targets, il, tl, offsets)
+
+
+def ctc_loss_forward(log_probs, targets, input_lengths, target_lengths, blank, max_targets, lattice):
+    """``(costs (N,), alphas, betas (N, T, 2 S + 1))`` of float32 log-probabilities ``ctc_loss_reason`` passes: ONE launch.  Without
+    ``lattice`` only the alpha workgroups run and alphas / betas come back empty: nothing but the costs is allocated."""
+    T, N, C = log_probs.shape
+    dev = log_probs.device
+    args, keep = _ctc_arguments(log_probs, targets, input_lengths, target_lengths, blank, max_targets)
+    costs = _empty((N,), device=dev)
+    if lattice:
+        alphas, betas = (_empty((N, T, 2 * max_targets + 1), device=dev) for _ in range(2))
+        _launch('tac_ctc_loss_f32', dev, (costs, alphas, betas), *args, _native.ptr(alphas), _native.ptr(betas), _native.ptr(costs))
+    else:
+        alphas, betas = (torch.empty((0,), dtype=torch.float32, device=dev) for _ in range(2))
+        _launch('tac_ctc_loss_f32', dev, (costs,), *args, None, None, _native.ptr(costs))
+    return costs, alphas, betas
+
+
+def ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, alphas, betas, costs, grad_costs, blank, max_targets,
+                  zero_infinity):
+    """the gradient with respect to ``log_probs`` in its own layout where that is dense in some order, else contiguous: ONE launch,
+    one read of the valid frames, one write of every element"""
+    dev = log_probs.device
+    args, keep = _ctc_arguments(log_probs, targets, input_lengths, target_lengths, blank, max_targets)
+    alphas, betas, costs, grad_costs = (t.contiguous() for t in (alphas, betas, costs, grad_costs))
+    out = _empty_like(log_probs)                # (preserve_format: the strides of a dense tensor, a contiguous one otherwise)
+    _launch('tac_ctc_loss_grad_f32', dev, (out,), *args, 1 if zero_infinity else 0, _native.ptr(alphas), _native.ptr(betas),
+            _native.ptr(costs), _native.ptr(grad_costs), _native.ptr(out), out.stride(0), out.stride(1), out.stride(2))
+    return out
+
+
 # ----------------------------------------------------------------------------- forced_align (csrc/align.hip)
 def align_max_targets():
     """the most ``L + 1`` the launch takes: the pairs of states of one workgroup"""

@@ -234,6 +234,13 @@ PROTOTYPES = {
     'tac_cqt_max_hop': (_I32, []),
     'tac_cqt_blocks_per_cu': (_I32, []),
     'tac_cqt_f32': (_INT, [_P, _I64, _I64, _I64, _P, _P, _I32, _I32, _I32, _I32, _I64, _I64, _INT, _INT, _P, _P]),
+    'tac_ctc_loss_max_targets': (_I32, []),
+    'tac_ctc_loss_max_classes': (_I32, []),
+    'tac_ctc_loss_group_steps': (_I32, []),
+    'tac_ctc_loss_ring_steps': (_I32, []),
+    'tac_ctc_loss_f32': (_INT, [_P] + [_I64] * 6 + [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    'tac_ctc_loss_grad_f32': (_INT, [_P] + [_I64] * 6 + [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I64, _I64,
+                                     _I64, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -25,6 +25,7 @@ see them by name.
     tac_amd::psd, mvdr_weights_souden, apply_beamforming, mvdr_souden   mask-based MVDR beamforming over (…, C, F, T) (csrc/beamform.hip)
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
+    tac_amd::ctc_loss, ctc_loss_grad     CTC loss over time-major (T, N, C) log-probabilities: costs with alpha / beta in one launch, the gradient in one (csrc/ctc_loss.hip)
     tac_amd::forced_align       CTC Viterbi alignment of (B, T, C) log-probabilities: recursion, backtrack, paths and scores in one launch (csrc/align.hip)
     tac_amd::ctc_beam_search    CTC prefix beam search of (B, T, C) log-probabilities: the k best classes of every frame, then the beams, in two launches (csrc/ctc_decode.hip)
     tac_amd::griffinlim         Griffin-Lim phase recovery of (…, F, T) magnitudes: prepare, then stft + inverse a step (csrc/griffinlim.hip)
@@ -1865,6 +1866,168 @@ _register_rnnt_autograd()
 _register('rnnt_loss_grad', '(Tensor logits, Tensor targets, Tensor logit_lengths, Tensor target_lengths, Tensor alphas, Tensor betas, '
           'Tensor denominators, Tensor costs, Tensor grad_costs, int blank, float clamp, bool fused_log_softmax) -> Tensor',
           _rnnt_grad_cuda, C.rnnt_loss_grad, _rnnt_grad_fake, 1, differentiable=False)
+
+
+# ============================================================================= ctc_loss, ctc_loss_grad
+def ctc_check(log_probs, targets, input_lengths, target_lengths, blank):
+    """The argument checks of ``ctc_loss`` that need no device memory, and its arguments in the form the op takes:
+    ``(log_probs (T, N, C), targets, input_lengths (N,), target_lengths (N,), max_targets, batched)``.  Lengths given as tuples or
+    lists become int64 host tensors.  ``max_targets`` (``S``, the width of the lattice arrays) is the target axis of padded
+    targets; for concatenated ones the longest target length where the lengths are on the host, else ``min(len(targets), T)`` —
+    an entry with more targets than frames is infeasible whatever they are.  ``ValueError`` on every route that gets here."""
+    if not (isinstance(log_probs, torch.Tensor) and log_probs.is_floating_point()):
+        raise ValueError('ctc_loss: log_probs must be a floating-point tensor')
+    if log_probs.dim() not in (2, 3):
+        raise ValueError('ctc_loss: log_probs must be (T, N, C) or (T, C), got %d dimension(s)' % log_probs.dim())
+    if not isinstance(targets, torch.Tensor) or targets.dtype not in (torch.int32, torch.int64):
+        raise ValueError('ctc_loss: targets must be an int32 or int64 tensor')
+    batched = log_probs.dim() == 3
+    host = {}
+    lengths = []
+    for name, t in (('input_lengths', input_lengths), ('target_lengths', target_lengths)):
+        if isinstance(t, (tuple, list)):
+            host[name] = [int(v) for v in t]
+            t = torch.tensor(host[name], dtype=torch.int64)
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError('ctc_loss: %s must be an integer tensor, a tuple or a list' % name)
+        lengths.append(t)
+    il, tl = lengths
+    if not batched:
+        if targets.dim() != 1 or il.numel() != 1 or tl.numel() != 1:
+            raise ValueError('ctc_loss: (T, C) log_probs take 1-D targets and one length each')
+        log_probs, targets, il, tl = log_probs.unsqueeze(1), targets.reshape(1, -1), il.reshape(1), tl.reshape(1)
+    T, N, C = log_probs.shape
+    if T < 1 or C < 1:
+        raise ValueError('ctc_loss: log_probs of shape %r have an empty time or class axis' % (tuple(log_probs.shape),))
+    if targets.dim() not in (1, 2) or (targets.dim() == 2 and targets.shape[0] != N):
+        raise ValueError('ctc_loss: targets must be (N, S) or concatenated 1-D, got shape %r for a batch of %d'
+                         % (tuple(targets.shape), N))
+    if il.dim() != 1 or tl.dim() != 1 or il.shape[0] != N or tl.shape[0] != N:
+        raise ValueError('ctc_loss: %d input lengths and %d target lengths for a batch of %d' % (il.numel(), tl.numel(), N))
+    if not 0 <= blank < C:
+        raise ValueError('ctc_loss: blank %d is outside the %d classes' % (blank, C))
+    if targets.dim() == 2:
+        max_targets = targets.shape[1]
+    else:
+        total = targets.shape[0]
+        if 'target_lengths' in host:
+            longest = max(host['target_lengths'] + [0])
+        elif tl.device.type == 'cpu' and N and not torch.compiler.is_compiling():
+            longest = int(tl.max())
+        else:
+            longest = min(total, T)
+        max_targets = max(0, min(longest, total))
+    return log_probs, targets, il, tl, max_targets, batched
+
+
+def ctc_reason(log_probs, max_targets):
+    """why the launches of csrc/ctc_loss.hip do not take these log-probabilities, or None"""
+    return H.ctc_loss_reason(log_probs, max_targets)
+
+
+def _ctc_outputs(log_probs, max_targets, lattice):
+    T, N, C = log_probs.shape
+    kept = lattice and N > 0 and ctc_reason(log_probs, max_targets) is None
+    shape = (N, T, 2 * max_targets + 1) if kept else (0,)
+    return (log_probs.new_empty((N,)),) + tuple(log_probs.new_empty(shape, dtype=torch.float32) for _ in range(2))
+
+
+def _ctc_torch_costs(log_probs, targets, input_lengths, target_lengths, blank, max_targets):
+    """the costs by torch's own operator (half precision widened), and no lattice arrays: its backward evaluates it again"""
+    costs = C.ctc_loss(_f32(log_probs).detach(), targets, input_lengths, target_lengths, blank, 'none', False)
+    return (costs.to(log_probs.dtype),) + _ctc_outputs(log_probs, max_targets, False)[1:]
+
+
+def _ctc_loss_cuda(log_probs, targets, input_lengths, target_lengths, blank, zero_infinity, max_targets, lattice):
+    if log_probs.shape[1] == 0:
+        return _ctc_outputs(log_probs, max_targets, lattice)       # an empty batch: nothing is launched
+    reason = ctc_reason(log_probs, max_targets)
+    if reason is not None:
+        _composite_route('ctc_loss', reason)
+        return _ctc_torch_costs(log_probs, targets, input_lengths, target_lengths, blank, max_targets)
+    return H.ctc_loss_forward(log_probs, targets, input_lengths, target_lengths, blank, max_targets, lattice)
+
+
+def _ctc_loss_cpu(log_probs, targets, input_lengths, target_lengths, blank, zero_infinity, max_targets, lattice):
+    if log_probs.shape[1] == 0:
+        return _ctc_outputs(log_probs, max_targets, False)
+    return _ctc_torch_costs(log_probs, targets, input_lengths, target_lengths, blank, max_targets)
+
+
+def _ctc_loss_fake(log_probs, targets, input_lengths, target_lengths, blank, zero_infinity, max_targets, lattice):
+    return _ctc_outputs(log_probs, max_targets, lattice and log_probs.device.type != 'cpu')
+
+
+def _ctc_grad_torch(log_probs, targets, input_lengths, target_lengths, alphas, betas, costs, grad_costs, blank, zero_infinity,
+                    max_targets):
+    """the gradient by differentiating torch's own operator once more: what every route outside the kernels does"""
+    with torch.enable_grad():
+        x = _f32(log_probs).detach().requires_grad_(True)
+        again = C.ctc_loss(x, targets, input_lengths, target_lengths, blank, 'none', zero_infinity)
+        (grad,) = torch.autograd.grad(again, x, grad_costs.to(again.dtype))
+    return grad.to(log_probs.dtype)
+
+
+def _ctc_grad_cuda(log_probs, targets, input_lengths, target_lengths, alphas, betas, costs, grad_costs, blank, zero_infinity,
+                   max_targets):
+    if log_probs.numel() == 0:
+        return torch.empty_like(log_probs)
+    reason = ctc_reason(log_probs, max_targets)
+    if reason is None and alphas.numel() == 0:
+        reason = 'no lattice arrays were kept'
+    if reason is None and not _plain_hip_f32(alphas, betas, costs, grad_costs):
+        reason = 'tensor subclass or dtype of the saved arrays'
+    if reason is not None:
+        _composite_route('ctc_loss', 'backward: ' + reason)
+        return _ctc_grad_torch(log_probs, targets, input_lengths, target_lengths, alphas, betas, costs, grad_costs, blank,
+                               zero_infinity, max_targets)
+    return H.ctc_loss_grad(log_probs, targets, input_lengths, target_lengths, alphas, betas, costs, grad_costs, blank, max_targets,
+                           zero_infinity)
+
+
+def _ctc_grad_fake(log_probs, targets, input_lengths, target_lengths, alphas, betas, costs, grad_costs, blank, zero_infinity,
+                   max_targets):
+    return torch.empty_like(log_probs)
+
+
+def _register_ctc_autograd():
+    """Backward of ``tac_amd::ctc_loss``: the costs are the one differentiable output and ``log_probs`` the one input with a
+    gradient.  What the forward pass saved — alphas, betas, costs — goes to ``tac_amd::ctc_loss_grad``, which routes like every op.
+    A double backward differentiates torch's own operator on the saved ``log_probs``, announced on a HIP device."""
+
+    def setup_context(ctx, inputs, output):
+        log_probs, targets, input_lengths, target_lengths, blank, zero_infinity, max_targets, lattice = inputs
+        costs, alphas, betas = output
+        ctx.mark_non_differentiable(alphas, betas)
+        ctx.save_for_backward(log_probs, targets, input_lengths, target_lengths, alphas, betas, costs)
+        ctx.rest = (blank, zero_infinity, max_targets)
+
+    def backward(ctx, g, *unused):
+        log_probs, targets, input_lengths, target_lengths, alphas, betas, costs = ctx.saved_tensors
+        blank, zero_infinity, max_targets = ctx.rest
+        if g is None or not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        if torch.is_grad_enabled():                                 # keep the graph: the saved log_probs are the caller's own
+            if log_probs.is_cuda:
+                _composite_route('ctc_loss', 'backward: double backward (create_graph=True)')
+            with torch.enable_grad():
+                again = C.ctc_loss(_f32(log_probs), targets, input_lengths, target_lengths, blank, 'none', zero_infinity)
+                (grad,) = torch.autograd.grad(again, log_probs, g.to(again.dtype), create_graph=True)
+        else:
+            grad = call('ctc_loss_grad', log_probs, targets, input_lengths, target_lengths, alphas, betas, costs, g, blank,
+                        zero_infinity, max_targets)
+        return (grad,) + (None,) * 7
+
+    torch.library.register_autograd('%s::ctc_loss' % NS, backward, setup_context=setup_context, lib=_lib)
+
+
+_register('ctc_loss', '(Tensor log_probs, Tensor targets, Tensor input_lengths, Tensor target_lengths, int blank, bool zero_infinity, '
+          'int max_targets, bool lattice) -> (Tensor, Tensor, Tensor)', _ctc_loss_cuda, _ctc_loss_cpu, _ctc_loss_fake, 1,
+          differentiable=False)
+_register_ctc_autograd()
+_register('ctc_loss_grad', '(Tensor log_probs, Tensor targets, Tensor input_lengths, Tensor target_lengths, Tensor alphas, '
+          'Tensor betas, Tensor costs, Tensor grad_costs, int blank, bool zero_infinity, int max_targets) -> Tensor',
+          _ctc_grad_cuda, _ctc_grad_torch, _ctc_grad_fake, 1, differentiable=False)
 
 
 # ============================================================================= forced_align

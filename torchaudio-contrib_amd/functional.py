@@ -41,7 +41,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'phase_vocoder', 'amplitude_to_db', 'db_to_amplitude', 'mu_law_encoding', 'mu_law_decoding', 'hpss',
            'create_dct', 'dct', 'resample', 'kaldi_fbank', 'kaldi_mfcc', 'kaldi_spectrogram', 'sliding_window_cmn', 'compute_deltas', 'mask_along_axis', 'mask_along_axis_iid', 'add_noise', 'speed', 'pitch_shift', 'fftconvolve', 'convolve', 'lfilter', 'sosfilt', 'tf2sos', 'filtfilt', 'biquad', 'lowpass_biquad', 'highpass_biquad', 'bandpass_biquad',
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
-           'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss',
+           'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss', 'ctc_loss',
            'forced_align', 'merge_tokens', 'TokenSpan', 'ctc_beam_search', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
            'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform', 'cqt']
 
@@ -1157,6 +1157,46 @@ def rnnt_loss(logits, targets, logit_lengths, target_lengths, blank=-1, clamp=-1
     if reduction == 'sum':
         return costs.sum()
     return costs
+
+
+def ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reduction='mean', zero_infinity=False):
+    """The CTC loss with the signature, defaults and semantics of ``torch.nn.functional.ctc_loss``.
+
+    ``log_probs`` is ``(T, N, C)`` or ``(T, C)``, time-major; ``targets`` ``(N, S)`` padded or 1-D concatenated, int32 or int64,
+    without blanks; ``input_lengths`` (``Tb``) and ``target_lengths`` (``Lb``) tensors, tuples or lists.  ``reduction``: ``'none'``
+    gives the ``(N,)`` costs, ``'sum'`` their sum, ``'mean'`` the batch mean of ``cost / max(Lb, 1)``.  An entry no path fits
+    (``Tb < Lb +`` the number of targets equal to the one before) costs ``+inf``; with ``zero_infinity`` its cost and its whole
+    gradient are 0, without its gradient is NaN for ``t < Tb`` and 0 behind.  The gradient is torch's:
+    ``(exp(lp[t,b,c]) - exp(ab[t,c] + cost_b - lp[t,b,c])) grad_out_b`` with ``ab[t,c]`` the log of the sum of ``alpha_t(s) beta_t(s)``
+    over the states of class ``c`` — the gradient by the logits under ``log_probs = log_softmax(logits)`` — and zero for ``t >= Tb``.
+
+    float32 on a HIP device with positive strides (``(N, T, C)`` model output passed as ``.transpose(0, 1)``, or a slice of a padded
+    output, is read where it lies), ``S + 1 <= 1024`` and ``C <= 32768`` runs csrc/ctc_loss.hip: forward ONE launch (alpha and beta
+    side by side; the alpha workgroups alone, and nothing but the costs allocated, when ``log_probs`` needs no gradient), backward
+    ONE (one read of the valid frames, one write of the gradient, in the layout of ``log_probs`` where that is dense).  Kept for
+    the backward pass: two ``(N, T, 2 S + 1)`` arrays and the costs.  Bit-identical from run to run and, for an entry, whatever
+    else is in the batch.  Other device inputs (float64, half precision, expanded views, larger ``S`` or ``C``, a double backward)
+    take torch's own operator, announced; CPU tensors take it silently.  For 1-D targets with device-resident lengths ``S`` is
+    taken as ``min(len(targets), T)``, since nothing waits for the host; pass the lengths as a list or a host tensor to have the
+    longest one used.
+
+    The one deviation from torch on a HIP device: nothing is read back, so an entry with ``Tb`` outside ``[1, T]``, ``Lb`` outside
+    ``[0, S]`` or a used target that is the blank or outside ``[0, C)`` gets a NaN cost and a NaN gradient over its own block; the
+    other entries are unaffected and no address outside the tensors is formed."""
+    if reduction not in ('none', 'mean', 'sum'):
+        raise ValueError("ctc_loss: reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+    if not (isinstance(log_probs, torch.Tensor) and log_probs.is_cuda):
+        return _composite.ctc_loss(log_probs, targets, input_lengths, target_lengths, blank, reduction, zero_infinity)
+    lp, tg, il, tl, max_targets, batched = _ops.ctc_check(log_probs, targets, input_lengths, target_lengths, int(blank))
+    lattice = torch.is_grad_enabled() and log_probs.requires_grad
+    costs = _call('ctc_loss', lp, tg, il, tl, int(blank), bool(zero_infinity), max_targets, lattice)[0]
+    if zero_infinity:
+        costs = torch.where(costs == float('inf'), torch.zeros((), dtype=costs.dtype, device=costs.device), costs)
+    if reduction == 'mean':
+        return (costs / tl.to(device=costs.device, dtype=costs.dtype).clamp_min(1)).mean()
+    if reduction == 'sum':
+        return costs.sum()
+    return costs if batched else costs[0]
 
 
 def forced_align(log_probs, targets, input_lengths=None, target_lengths=None, blank=0):

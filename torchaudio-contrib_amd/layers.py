@@ -915,6 +915,22 @@ class RNNTLoss(_ModuleNoStateBuffers):
                            self.fused_log_softmax)
 
 
+class CTCLoss(_ModuleNoStateBuffers):
+    """``torch.nn.CTCLoss``: ``forward(log_probs, targets, input_lengths, target_lengths)`` is ``functional.ctc_loss`` with the
+    ``blank``, ``reduction`` and ``zero_infinity`` of the constructor.  No buffers, no parameters."""
+
+    def __init__(self, blank=0, reduction='mean', zero_infinity=False):
+        super(CTCLoss, self).__init__()
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError("CTCLoss: reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+        self.blank = blank
+        self.reduction = reduction
+        self.zero_infinity = zero_infinity
+
+    def forward(self, log_probs, targets, input_lengths, target_lengths):
+        return F.ctc_loss(log_probs, targets, input_lengths, target_lengths, self.blank, self.reduction, self.zero_infinity)
+
+
 class MVDR(_ModuleNoStateBuffers):
     """torchaudio's mask-based ``transforms.MVDR`` at ``solution='ref_channel'``: ``forward(specgram, mask_s, mask_n=None)`` maps a
     ``(…, channel, freq, time)`` spectrogram and real ``(…, freq, time)`` masks (``(…, channel, freq, time)`` with ``multi_mask``,
