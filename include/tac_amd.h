@@ -1206,6 +1206,39 @@ int tac_ctc_loss_grad_f32(const float* log_probs, int64_t frames, int64_t batch,
                           int32_t zero_infinity, const float* alphas, const float* betas, const float* costs, const float* grad_costs,
                           float* grad, int64_t grad_stride_t, int64_t grad_stride_n, int64_t grad_stride_c, void* stream);
 
+/* (39) functional.pcen and the PCEN layer: per-channel energy normalisation and its gradient (csrc/pcen.hip).  specgram: float32,
+ *      rows x n_bands x n_frames, read where it lies through the non-negative element strides stride_r / stride_f / stride_t of a
+ *      row, a band and a frame (a stride is never used for an axis of length one): frame-major storage (stride_f == 1) is loaded
+ *      straight into the lanes, time-contiguous storage (stride_t == 1) is turned through LDS; element offsets are 64-bit.
+ *      table: float32 [4][n_bands]: gain, bias (> 0), power (> 0) and the smoothing coefficient s (0 < s <= 1) of every band.
+ *
+ *        M[0] = E[0], M[t] = (1 - s) M[t-1] + s E[t] in float64, rounded once to float32;
+ *        out = bias^power expm1(power log1p(E exp(-gain log(eps + M)) / bias)) in float32
+ *
+ *      tac_pcen_f32: ONE launch.  out and smoother (NULL: not kept) are dense frame-major [rows][n_frames][n_bands]; every element
+ *      is written.  A unit of work is a row with tac_pcen_block_bands() (64) bands; its frames are walked in tiles of
+ *      tac_pcen_tile_frames() (64), a wave per chunk of tac_pcen_chunk_frames() (16), on a grid of at most
+ *      tac_pcen_blocks_per_cu() workgroups per CU.  n_bands or n_frames above tac_pcen_max_axis() (2^30): TAC_E_UNSUPPORTED.
+ *
+ *      tac_pcen_backward_f32: grad_out like specgram through its own strides; smoother as tac_pcen_f32 wrote it.  ONE launch (on a
+ *      grid of at most two workgroups per CU: what its registers and LDS leave resident) writes
+ *      grad_specgram (dense frame-major; NULL: not formed) and, where want != 0, the float64 sums per (row, band) of the parameters
+ *      whose bit is set in want (1 gain, 2 bias, 4 power, 8 s) into workspace: 4 x rows x n_bands doubles; a SECOND small launch
+ *      adds them over rows in row order into grad_table, float32 [4][n_bands], zero for a parameter that was not wanted.  Nothing
+ *      is atomic: the same bits from run to run and, for grad_specgram, whatever else is in the batch.  A non-finite E[t] reaches
+ *      the outputs of frames t … of its own (row, band) only. */
+int32_t tac_pcen_chunk_frames(void);
+int32_t tac_pcen_tile_frames(void);
+int32_t tac_pcen_block_bands(void);
+int32_t tac_pcen_blocks_per_cu(void);
+int64_t tac_pcen_max_axis(void);
+int tac_pcen_f32(const float* specgram, int64_t rows, int64_t n_bands, int64_t n_frames, int64_t stride_r, int64_t stride_f,
+                 int64_t stride_t, const float* table, float eps, float* out, float* smoother, void* stream);
+int tac_pcen_backward_f32(const float* grad_out, int64_t grad_stride_r, int64_t grad_stride_f, int64_t grad_stride_t,
+                          const float* specgram, int64_t rows, int64_t n_bands, int64_t n_frames, int64_t stride_r, int64_t stride_f,
+                          int64_t stride_t, const float* smoother, const float* table, float eps, int32_t want, float* grad_specgram,
+                          double* workspace, float* grad_table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

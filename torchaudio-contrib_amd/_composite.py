@@ -1399,3 +1399,82 @@ def cqt(waveform, kernels, n_max, hop, center, reflect, power):
         if power == 1:
             out = out.sqrt()
     return out.reshape(lead + tuple(out.shape[1:])).contiguous()
+
+
+# ----------------------------------------------------------------------------- pcen
+def _pcen_smoother(specgram, s):
+    """``(E, M)`` as ``(…, T, F)``: the frames and their first-order smoother, ``M[0] = E[0]``, ``M[t] = (1 - s) M[t-1] + s E[t]``"""
+    frames = specgram.transpose(-1, -2).unbind(-2)
+    a = 1.0 - s
+    m = frames[0]
+    smooth = [m]
+    for e in frames[1:]:
+        m = a * m + s * e
+        smooth.append(m)
+    return torch.stack(frames, dim=-2), torch.stack(smooth, dim=-2)
+
+
+def pcen_grad(grad_out, specgram, table, eps, form):
+    """``(grad_specgram, grad_table)`` of ``pcen`` in closed form, in torch operators: the recursion of csrc/pcen.hip's backward
+    launch.  With ``u = eps + M``, ``w = E u^-gain`` and ``D = d out / d w`` (``power z^(power-1)``, ``z = w + bias``; ``1 / (1 + w)``
+    for ``form`` 1; ``power w^(power-1)`` for ``form`` 2): ``lam[t] = q[t] + (1 - s) lam[t+1]`` with ``q = g D (-gain w / u)``,
+    ``grad_E[t] = g D u^-gain + s lam[t]`` (``lam[0]`` unscaled at ``t = 0``), and the per-band sums ``d_gain = sum -g D w log u``,
+    ``d_bias = sum g power (z^(power-1) - bias^(power-1))``, ``d_power = sum g (z^power log z - bias^power log bias)`` (``sum g w^power
+    log w`` for ``form`` 2), ``d_b = sum_{t >= 1} lam[t] (E[t] - M[t-1])``, the bias and power ones in difference-free form.  The CPU
+    path of ``tac_amd::pcen_grad``."""
+    if specgram.dtype in (torch.float16, torch.bfloat16):
+        specgram = specgram.float()
+    gain, bias, power, s = table.to(specgram.dtype).unbind(0)
+    E, M = _pcen_smoother(specgram, s)
+    g = grad_out.to(specgram.dtype).transpose(-1, -2)
+    u = eps + M
+    lu = torch.log(u)
+    ug = torch.exp(-gain * lu)
+    w = E * ug
+    zero = torch.zeros_like(w)
+    if form == 1:
+        D, d_bias, d_power = 1.0 / (1.0 + w), zero, zero
+    elif form == 2:
+        lw = torch.log(w)
+        D, d_bias, d_power = power * torch.exp((power - 1.0) * lw), zero, g * w ** power * lw
+    else:
+        lb, l1 = torch.log(bias), torch.log1p(w / bias)
+        em = torch.expm1(power * l1)
+        D = power * torch.exp((power - 1.0) * (lb + l1))
+        d_bias = g * power * torch.exp((power - 1.0) * lb) * torch.expm1((power - 1.0) * l1)
+        d_power = g * torch.exp(power * lb) * (em * lb + (1.0 + em) * l1)
+    G = g * D
+    q = (G * (-gain * w / u)).unbind(-2)
+    lam = [q[-1]]
+    for qt in reversed(q[:-1]):
+        lam.append(qt + (1.0 - s) * lam[-1])
+    lam = torch.stack(lam[::-1], dim=-2)
+    first = torch.zeros(E.shape[-2], 1, dtype=E.dtype, device=E.device)
+    first[0] = 1.0
+    grad_spec = G * ug + (first + (1.0 - first) * s) * lam
+    d_b = torch.zeros_like(w)
+    d_b[..., 1:, :] = lam[..., 1:, :] * (E[..., 1:, :] - M[..., :-1, :])
+    over = tuple(range(E.dim() - 1))
+    grad_table = torch.stack([(-G * w * lu).sum(over), d_bias.sum(over), d_power.sum(over), d_b.sum(over)])
+    return grad_spec.transpose(-1, -2), grad_table
+
+
+def pcen(specgram, table, eps, form):
+    """Per-channel energy normalisation in torch operators: ``specgram`` ``(…, F, T)``, ``table`` ``(4, F)`` holding ``gain``,
+    ``bias``, ``power`` and the smoothing coefficient ``s`` of every band → ``(…, F, T)`` as a view of frame-major ``(…, T, F)``
+    storage.  ``M[0] = E[0]``, ``M[t] = (1 - s) M[t-1] + s E[t]`` is a loop over frames in vector operators that reads nothing back;
+    the output is librosa's difference-free ``bias^power expm1(power log1p(E exp(-gain log(eps + M)) / bias))``, ``form`` 1 its
+    ``power == 0`` limit ``log1p(E (eps + M)^-gain)`` and ``form`` 2 its ``bias == 0`` one, ``exp(power (log E - gain log(eps + M)))``.
+    The CPU path of ``tac_amd::pcen``, its float64 route and its announced route on a device; differentiable, the table included."""
+    if specgram.dtype in (torch.float16, torch.bfloat16):
+        specgram = specgram.float()
+    gain, bias, power, s = table.to(specgram.dtype).unbind(0)
+    E, M = _pcen_smoother(specgram, s)
+    log_smooth = -gain * torch.log(eps + M)
+    if form == 1:
+        out = torch.log1p(E * torch.exp(log_smooth))
+    elif form == 2:
+        out = torch.exp(power * (torch.log(E) + log_smooth))
+    else:
+        out = torch.exp(power * torch.log(bias)) * torch.expm1(power * torch.log1p(E * torch.exp(log_smooth) / bias))
+    return out.transpose(-1, -2)

@@ -1393,6 +1393,64 @@ def cqt_rows(x, plan, hop, n_frames, center, reflect, power):
     return out
 
 
+# ----------------------------------------------------------------------------- pcen (csrc/pcen.hip)
+def pcen_max_axis():
+    """the most bands, and the most frames, ``tac_pcen_f32`` takes"""
+    return _native.lib().tac_pcen_max_axis()
+
+
+def pcen_reason(spec):
+    """why the launches of csrc/pcen.hip do not read this ``(…, F, T)`` tensor where it lies, or None (the dtype is the caller's)"""
+    if spec.dim() < 2:
+        return 'fewer than two dimensions'
+    if any(st <= 0 for st, n in zip(spec.stride(), spec.shape) if n > 1):
+        return 'an expanded view or non-positive strides'
+    if max(spec.shape[-2:]) > pcen_max_axis():
+        return 'an axis above %d' % pcen_max_axis()
+    return None
+
+
+def _pcen_strides(rows):
+    """row, band and frame stride of a ``(rows, F, T)`` view"""
+    return rows.stride(0), rows.stride(1), rows.stride(2)
+
+
+def pcen_forward(spec, table, eps, keep):
+    """``(out, M)`` of a float32 ``(…, F, T)`` tensor ``pcen_reason`` passes and a float32 ``(4, F)`` table on its device: ONE launch
+    of ``tac_pcen_f32`` on ``spec`` where it lies.  Both are ``(…, F, T)`` views of frame-major ``(…, T, F)`` storage; ``M``, the
+    smoother rounded once, is empty unless ``keep``."""
+    lead, (F, T) = tuple(spec.shape[:-2]), spec.shape[-2:]
+    out = _empty(lead + (T, F), device=spec.device)
+    smoother = _empty(lead + (T, F), device=spec.device) if keep else torch.empty((0,), dtype=torch.float32, device=spec.device)
+    if out.numel():
+        rows = _rows3(spec)
+        table = table.contiguous()
+        _launch('tac_pcen_f32', spec.device, (out, smoother) if keep else (out,), _native.ptr(rows), rows.shape[0], F, T,
+                *_pcen_strides(rows), _native.ptr(table), float(eps), _native.ptr(out), _native.ptr(smoother) if keep else None)
+    return out.transpose(-1, -2), (smoother.transpose(-1, -2) if keep else smoother)
+
+
+def pcen_backward(grad_out, spec, smoother, table, eps, need_input, want):
+    """``(grad_specgram, grad_table)`` through ``tac_pcen_backward_f32``: one launch, plus the small reduction over rows where ``want``
+    (bit ``j``: the gradient of table row ``j``) is not zero.  ``smoother``: the ``M`` view ``pcen_forward`` kept.  The parts not asked
+    for come back as None."""
+    lead, (F, T) = tuple(spec.shape[:-2]), spec.shape[-2:]
+    dev = spec.device
+    grad_spec = _empty(lead + (T, F), device=dev) if need_input else None
+    grad_table = _empty((4, F), device=dev) if want else None
+    if spec.numel() == 0:
+        return (None if grad_spec is None else grad_spec.transpose(-1, -2)), (None if grad_table is None else grad_table.zero_())
+    rows, g = _rows3(spec), _rows3(grad_out)
+    table = table.contiguous()
+    m = smoother.transpose(-1, -2).contiguous()                 # (the frame-major storage itself: no copy)
+    work = torch.empty((4, rows.shape[0], F), dtype=torch.float64, device=dev) if want else None
+    _launch('tac_pcen_backward_f32', dev, tuple(t for t in (grad_spec, grad_table) if t is not None), _native.ptr(g), *_pcen_strides(g),
+            _native.ptr(rows), rows.shape[0], F, T, *_pcen_strides(rows), _native.ptr(m), _native.ptr(table), float(eps), int(want),
+            None if grad_spec is None else _native.ptr(grad_spec), None if work is None else _native.ptr(work),
+            None if grad_table is None else _native.ptr(grad_table))
+    return (None if grad_spec is None else grad_spec.transpose(-1, -2)), grad_table
+
+
 # ----------------------------------------------------------------------------- loudness (csrc/loudness.hip)
 #: samples of one row per tile of ``tac_loudness_f32`` (csrc/loudness.hip: LO_TILE), checked against the library's own value at the
 #: first launch, and the shortest hop its bins take (LO_C: at most one bin edge in a lane's chunk)

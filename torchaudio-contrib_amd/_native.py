@@ -241,6 +241,13 @@ PROTOTYPES = {
     'tac_ctc_loss_f32': (_INT, [_P] + [_I64] * 6 + [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _P, _P, _P, _P]),
     'tac_ctc_loss_grad_f32': (_INT, [_P] + [_I64] * 6 + [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _I64, _I64,
                                      _I64, _P]),
+    'tac_pcen_chunk_frames': (_I32, []),
+    'tac_pcen_tile_frames': (_I32, []),
+    'tac_pcen_block_bands': (_I32, []),
+    'tac_pcen_blocks_per_cu': (_I32, []),
+    'tac_pcen_max_axis': (_I64, []),
+    'tac_pcen_f32': (_INT, [_P] + [_I64] * 6 + [_P, _F, _P, _P, _P]),
+    'tac_pcen_backward_f32': (_INT, [_P] + [_I64] * 3 + [_P] + [_I64] * 6 + [_P, _P, _F, _I32, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -35,6 +35,7 @@ see them by name.
     tac_amd::lfilter_reverse, sosfilt_reverse   the two above run from the end of each row: filtfilt's second half (private)
     tac_amd::overdrive, phaser, flanger         the SoX effects defined by a loop over time, one launch each (csrc/sox_effects.hip)
     tac_amd::cqt                the time-domain constant-Q transform of (…, L): a band-sparse fp32 MFMA GEMM in one launch (csrc/cqt.hip)
+    tac_amd::pcen, pcen_grad    per-channel energy normalisation of (…, F, T): smoother and compression in one launch, the gradient with its reversed scan in one (csrc/pcen.hip)
     tac_amd::apply_filterbank, complex_norm, angle, magphase, phase_vocoder, amplitude_to_db, db_to_amplitude,
     tac_amd::mu_law_encoding, mu_law_decoding                           likewise
 
@@ -69,6 +70,7 @@ from . import _resample as RS
 from . import _sox as SX
 from . import _ddsp as DD
 from . import _cqt as CQ
+from ._bounded import Bounded
 
 NS = 'tac_amd'
 _lib = Library(NS, 'DEF')
@@ -2493,6 +2495,170 @@ def _cqt_fake(wave, *args):
 
 # (no gradient kernel: the backward pass re-evaluates the composite, announced)
 _register('cqt', '(Tensor waveform, ' + _CQT_ARGS + ') -> Tensor', _cqt_cuda, _cqt_cpu, _cqt_fake, 1)
+
+
+# ============================================================================= pcen, pcen_grad
+_PCEN_NAMES = ('gain', 'bias', 'power', 'b')
+_pcen_tables = Bounded(16)
+
+
+def pcen_smoothing(sample_rate, hop_length, time_constant):
+    """librosa's ``b`` of a ``time_constant`` in seconds: ``(sqrt(1 + 4 Tc^2) - 1) / (2 Tc^2)``, ``Tc`` the constant in frames"""
+    if not time_constant > 0:
+        raise ValueError('pcen: time_constant=%r must be strictly positive' % (time_constant,))
+    if not (sample_rate > 0 and hop_length > 0):
+        raise ValueError('pcen: sample_rate and hop_length must be positive, got %r and %r' % (sample_rate, hop_length))
+    t_frames = time_constant * sample_rate / float(hop_length)
+    return (math.sqrt(1 + 4 * t_frames ** 2) - 1) / (2 * t_frames ** 2)
+
+
+def pcen_check(specgram, sample_rate, hop_length, gain, bias, power, time_constant, eps, b):
+    """The argument errors of ``pcen`` (librosa's, on Python numbers only: a tensor value is never read) and its arguments in the
+    form the op takes: ``(table, form, want)``.  ``table`` is ``(4, F)`` — gain, bias, power, ``b`` — on the spectrogram's device,
+    float64 for a float64 spectrogram and float32 otherwise, built by differentiable operators from the tensor-valued parameters
+    (the all-numbers table, filled on the device like the rest, is kept per argument set outside a graph capture); ``form`` 1 for ``power == 0``, 2 for ``bias == 0``, else 0; bit ``j`` of ``want``
+    is set where parameter ``j`` is a tensor that requires grad."""
+    if not specgram.is_floating_point():
+        raise ValueError('pcen: specgram must be a floating-point tensor, got %s' % specgram.dtype)
+    if specgram.dim() < 2 or specgram.shape[-1] < 1 or specgram.shape[-2] < 1:
+        raise ValueError('pcen: specgram must be (…, bands, frames) with at least one of each, got shape %r' % (tuple(specgram.shape),))
+    if not eps > 0:
+        raise ValueError('pcen: eps=%r must be strictly positive' % (eps,))
+    if b is None:
+        b = pcen_smoothing(sample_rate, hop_length, time_constant)
+    values = (gain, bias, power, b)
+    F = specgram.shape[-2]
+    for name, v in zip(_PCEN_NAMES, values):
+        if isinstance(v, torch.Tensor):
+            if v.dim() != 1 or v.shape[0] != F or not v.is_floating_point() or v.device != specgram.device:
+                raise ValueError('pcen: a tensor %s must hold one floating-point value per band (%d) on %s, got shape %r on %s'
+                                 % (name, F, specgram.device, tuple(v.shape), v.device))
+        elif name == 'b':
+            if not 0 < v <= 1:
+                raise ValueError('pcen: b=%r must be strictly positive and at most 1' % (v,))
+        elif not v >= 0:
+            raise ValueError('pcen: %s=%r must be non-negative' % (name, v))
+    dtype = torch.float64 if specgram.dtype == torch.float64 else torch.float32
+    form = 1 if (not isinstance(power, torch.Tensor) and power == 0) else \
+        2 if (not isinstance(bias, torch.Tensor) and bias == 0) else 0
+    want = sum(1 << j for j, v in enumerate(values) if isinstance(v, torch.Tensor) and v.requires_grad)
+    dev = specgram.device
+    build = lambda: torch.stack([v.to(dtype) if isinstance(v, torch.Tensor) else torch.full((F,), float(v), dtype=dtype, device=dev)
+                                 for v in values])                    # (fills on the device: nothing is copied from the host)
+    if (any(isinstance(v, torch.Tensor) for v in values) or type(specgram) is not torch.Tensor or torch.compiler.is_compiling()
+            or (specgram.is_cuda and torch.cuda.is_current_stream_capturing())):
+        return build(), form, want
+    key = tuple(float(v) for v in values) + (F, dtype, str(dev))
+    table = _pcen_tables.get(key)               # (all numbers: the five small launches of the build are paid once per argument set)
+    if table is None:
+        with torch.inference_mode(False):
+            table = _pcen_tables[key] = build()
+    return table, form, want
+
+
+def _pcen_route(spec, table, form):
+    """why the launches of csrc/pcen.hip do not take this call, or None"""
+    reason = _hip_dtype(spec, table)
+    if reason is None and form:
+        reason = 'power == 0 (the logarithmic form)' if form == 1 else 'bias == 0'
+    return reason or H.pcen_reason(spec)
+
+
+def _pcen_outputs(spec, kept):
+    lead, (F, T) = spec.shape[:-2], spec.shape[-2:]
+    out = _swapped(lead, (T, F), _out_dtype(spec), spec.device, -1, -2)
+    return out, (_swapped(lead, (T, F), torch.float32, spec.device, -1, -2) if kept else
+                 torch.empty((0,), dtype=out.dtype, device=spec.device))
+
+
+def _pcen_composite(spec, table, eps, form):
+    return C.pcen(spec, table, eps, form), torch.empty((0,), dtype=_out_dtype(spec), device=spec.device)
+
+
+def _pcen_cuda(spec, table, eps, form, keep, want):
+    _same_device('pcen', spec, table)
+    reason = _pcen_route(spec, table, form)
+    if reason is not None:
+        _composite_route('pcen', reason)
+        return _pcen_composite(spec, table, eps, form)
+    return H.pcen_forward(_f32(spec), _f32(table), eps, keep)
+
+
+def _pcen_cpu(spec, table, eps, form, keep, want):
+    return _pcen_composite(spec, table, eps, form)
+
+
+def _pcen_fake(spec, table, eps, form, keep, want):
+    return _pcen_outputs(spec, keep and spec.device.type != 'cpu' and _pcen_route(spec, table, form) is None)
+
+
+def _frame_major(t):
+    return t.transpose(-1, -2).contiguous().transpose(-1, -2)
+
+
+def _pcen_grad_torch(g, spec, smoother, table, eps, form, need_input, want):
+    """both gradients by the composite's closed form: what every route outside the kernels does"""
+    gs, gt = C.pcen_grad(g, spec.detach(), table.detach(), eps, form)
+    return (_frame_major(gs.to(spec.dtype)) if need_input else spec.new_empty((0,)),
+            gt.to(table.dtype) if want else table.new_empty((0,)))
+
+
+def _pcen_grad_cuda(g, spec, smoother, table, eps, form, need_input, want):
+    _same_device('pcen', g, spec, table)
+    reason = _pcen_route(spec, table, form)
+    if reason is None and smoother.shape != spec.shape:
+        reason = 'the smoother was not kept'
+    if reason is None and not _plain_hip_f32(g, smoother):
+        reason = 'tensor subclass or dtype of the gradient'
+    if reason is not None:
+        _composite_route('pcen', 'backward: ' + reason)
+        return _pcen_grad_torch(g, spec, smoother, table, eps, form, need_input, want)
+    gs, gt = H.pcen_backward(g, _f32(spec), smoother, _f32(table), eps, need_input, want)
+    return (spec.new_empty((0,)) if gs is None else gs.to(spec.dtype)), (table.new_empty((0,)) if gt is None else gt.to(table.dtype))
+
+
+def _pcen_grad_fake(g, spec, smoother, table, eps, form, need_input, want):
+    gs = _swapped(spec.shape[:-2], (spec.shape[-1], spec.shape[-2]), spec.dtype, spec.device, -1, -2) if need_input else spec.new_empty((0,))
+    return gs, (table.new_empty(tuple(table.shape)) if want else table.new_empty((0,)))
+
+
+def _register_pcen_autograd():
+    """Backward of ``tac_amd::pcen``: the output is differentiable, the kept smoother is not; ``specgram``, the saved smoother and
+    the table go to ``tac_amd::pcen_grad``, which routes like every op, and autograd hands the table's gradient on to the
+    tensor-valued parameters it was stacked from.  A double backward differentiates the composite on the saved tensors, announced
+    on a HIP device."""
+
+    def setup_context(ctx, inputs, output):
+        spec, table, eps, form, keep, want = inputs
+        ctx.mark_non_differentiable(output[1])
+        ctx.save_for_backward(spec, table, output[1])
+        ctx.rest = (eps, form, want)
+
+    def backward(ctx, g, *unused):
+        spec, table, smoother = ctx.saved_tensors
+        eps, form, want = ctx.rest
+        need_spec, need_table = ctx.needs_input_grad[:2]
+        if g is None or not (need_spec or need_table):
+            return (None,) * 6
+        if torch.is_grad_enabled():                                 # keep the graph: the saved tensors are the caller's own
+            if spec.is_cuda:
+                _composite_route('pcen', 'backward: double backward (create_graph=True)')
+            with torch.enable_grad():
+                again = C.pcen(spec, table, eps, form)
+                wanted = [t for t, need in ((spec, need_spec), (table, need_table)) if need and t.requires_grad]
+                got = dict(zip(map(id, wanted), torch.autograd.grad(again, wanted, g.to(again.dtype), create_graph=True)))
+            return (got.get(id(spec)), got.get(id(table))) + (None,) * 4
+        gs, gt = call('pcen_grad', g, spec, smoother, table, eps, form, bool(need_spec), (want or 15) if need_table else 0)
+        return (gs if need_spec else None, gt if need_table else None) + (None,) * 4
+
+    torch.library.register_autograd('%s::pcen' % NS, backward, setup_context=setup_context, lib=_lib)
+
+
+_register('pcen', '(Tensor specgram, Tensor table, float eps, int form, bool keep, int want) -> (Tensor, Tensor)', _pcen_cuda, _pcen_cpu,
+          _pcen_fake, 2, differentiable=False)
+_register_pcen_autograd()
+_register('pcen_grad', '(Tensor grad_out, Tensor specgram, Tensor smoother, Tensor table, float eps, int form, bool need_input, '
+          'int want) -> (Tensor, Tensor)', _pcen_grad_cuda, _pcen_grad_torch, _pcen_grad_fake, 4, differentiable=False)
 
 
 # ============================================================================= complex pairs

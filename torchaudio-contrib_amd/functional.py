@@ -43,7 +43,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss', 'ctc_loss',
            'forced_align', 'merge_tokens', 'TokenSpan', 'ctc_beam_search', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
-           'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform', 'cqt']
+           'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform', 'cqt', 'pcen']
 
 _call = _ops.call
 
@@ -1197,6 +1197,36 @@ def ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reducti
     if reduction == 'sum':
         return costs.sum()
     return costs if batched else costs[0]
+
+
+def pcen(specgram, sample_rate=22050, hop_length=512, gain=0.98, bias=2.0, power=0.5, time_constant=0.4, eps=1e-6, b=None):
+    """Per-channel energy normalisation (Wang et al. 2017) of a non-negative spectrogram ``(…, F, T)`` with ``librosa.pcen``'s
+    arguments at ``max_size=1``: per band, with ``s = b`` and ``a = 1 - s``,
+
+        ``M[0] = E[0]``, ``M[t] = a M[t-1] + s E[t]``;  ``out = (E / (eps + M)**gain + bias)**power - bias**power``
+
+    evaluated in librosa's difference-free form ``bias**power * expm1(power * log1p(E * exp(-gain * log(eps + M)) / bias))``.
+    ``b=None`` takes ``(sqrt(1 + 4 Tc**2) - 1) / (2 Tc**2)`` with ``Tc = time_constant * sample_rate / hop_length``.  Each of ``gain``,
+    ``bias``, ``power`` and ``b`` is a Python number or a 1-D tensor of ``F`` values, one per band, which may require grad.  The
+    result is a ``(…, F, T)`` view of frame-major storage like every spectral output here; float16 / bfloat16 give float32.
+
+    ``ValueError`` as in librosa for a number outside ``gain >= 0``, ``bias >= 0``, ``power >= 0``, ``eps > 0``, ``0 < b <= 1``,
+    ``time_constant > 0``.  A tensor-valued parameter is never read back: a band whose value lies outside these ranges gets what
+    the formula gives — NaN for a ``bias`` that is negative or 0, zeros for ``power == 0`` (not the logarithmic form), a smoother
+    that alternates or grows for ``b`` outside ``(0, 1]`` — in that band alone.
+
+    float32 on a HIP device (half precision widened) with numbers ``bias > 0`` and ``power > 0`` or tensors runs csrc/pcen.hip:
+    forward ONE launch (a lane per band, time down the lane's registers, float64 recursion state rounded once), reading frame-major
+    views, channel slices, padded rows and dense time-contiguous tensors where they lie; backward ONE launch for the gradient of
+    ``specgram`` — the reversed scan — plus a small reduction over rows where a parameter wants its gradient.  Kept for the backward
+    pass: the float32 smoother.  Nothing is atomic: the same bits from run to run, for a row whatever else is in the batch.
+    float64, ``power == 0`` (the logarithmic form ``log1p(E (eps + M)**-gain)``), ``bias == 0``, expanded views and a double
+    backward take ``_composite.pcen``, announced with ``CompositeRouteWarning`` on a device; CPU tensors take it silently.
+    A NaN in ``E[t]`` reaches frames ``t…`` of its own band and row only (and, in the gradient, every frame of that band and row)."""
+    x = _tensor(specgram, 'specgram')
+    table, form, want = _ops.pcen_check(x, sample_rate, hop_length, gain, bias, power, time_constant, eps, b)
+    keep = torch.is_grad_enabled() and (x.requires_grad or table.requires_grad)
+    return _call('pcen', x, table, float(eps), form, keep, want)[0]
 
 
 def forced_align(log_probs, targets, input_lengths=None, target_lengths=None, blank=0):

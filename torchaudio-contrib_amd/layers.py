@@ -577,6 +577,34 @@ class CQT(nn.Module):
                                           'gamma={}, norm={}, center={}, pad_mode={!r}, scale={}, power={})').format(*self.args)
 
 
+class PCEN(nn.Module):
+    """``functional.pcen`` as a layer: ``(…, n_bands, T) → (…, n_bands, T)``.  With ``trainable=True`` (which needs ``n_bands``)
+    ``gain``, ``bias``, ``power`` and ``b`` are ``nn.Parameter`` s of shape ``(n_bands,)`` started at the given numbers — ``b`` at
+    librosa's value for ``time_constant`` where it is None —; otherwise the layer holds numbers only: no buffers, no parameters."""
+
+    def __init__(self, n_bands=None, trainable=False, sample_rate=22050, hop_length=512, gain=0.98, bias=2.0, power=0.5,
+                 time_constant=0.4, eps=1e-6, b=None):
+        super(PCEN, self).__init__()
+        if b is None:
+            b = F._ops.pcen_smoothing(sample_rate, hop_length, time_constant)
+        if not any(torch.is_tensor(v) for v in (gain, bias, power, b)):         # (tensors are checked against the input's bands)
+            F._ops.pcen_check(torch.empty(1, 1), sample_rate, hop_length, gain, bias, power, time_constant, eps, b)
+        self.n_bands, self.trainable, self.eps = n_bands, bool(trainable), float(eps)
+        if self.trainable:
+            if n_bands is None or int(n_bands) < 1:
+                raise ValueError('PCEN: trainable=True needs n_bands, the length of the parameters')
+            for name, v in zip(('gain', 'bias', 'power', 'b'), (gain, bias, power, b)):
+                setattr(self, name, nn.Parameter(torch.full((int(n_bands),), float(v))))
+        else:
+            self.gain, self.bias, self.power, self.b = gain, bias, power, b
+
+    def forward(self, specgram):
+        return F.pcen(specgram, gain=self.gain, bias=self.bias, power=self.power, eps=self.eps, b=self.b)
+
+    def __repr__(self):
+        return self.__class__.__name__ + '(n_bands={}, trainable={}, eps={})'.format(self.n_bands, self.trainable, self.eps)
+
+
 class Preemphasis(_ModuleNoStateBuffers):
     """``functional.preemphasis`` as a layer: ``y[n] = x[n] - coeff x[n-1]``.  No buffers: ``coeff`` is a Python float, and the
     two float64 host tensors the op takes are plain attributes (they stay float64 on the host whatever ``.to()`` is given)."""
