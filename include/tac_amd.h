@@ -1239,6 +1239,50 @@ int tac_pcen_backward_f32(const float* grad_out, int64_t grad_stride_r, int64_t 
                           int64_t stride_t, const float* smoother, const float* table, float eps, int32_t want, float* grad_specgram,
                           double* workspace, float* grad_table, void* stream);
 
+/* (40) functional.soft_dtw and the SoftDTW layer: soft-DTW (Cuturi & Blondel 2017) with the squared Euclidean cost, its gradient by
+ *      both sequences and the expected alignment (csrc/soft_dtw.hip).  x: float32 [batch][n][d], y: float32 [batch][m][d], each read
+ *      where it lies through its positive element strides (a transposed or sliced view is not copied); element offsets are
+ *      64-bit.  x_lengths (Nb), y_lengths (Mb): DEVICE int32 [batch].  gamma > 0 and finite.  n or m above tac_soft_dtw_max_len()
+ *      (4096) or d above tac_soft_dtw_max_dim() (256): TAC_E_UNSUPPORTED.
+ *
+ *      Per entry: delta[i][j] = sum_d (x[i][d] - y[j][d])^2;  R[i][j] = delta[i][j] + softmin(R[i-1][j], R[i][j-1], R[i-1][j-1]) with
+ *      softmin(a, b, c) = -gamma log(e^(-a/gamma) + e^(-b/gamma) + e^(-c/gamma)), R[-1][-1] = 0 and +inf on the rest of the border;
+ *      value = R[Nb-1][Mb-1];  Q the same recursion from (Nb-1, Mb-1) downwards;  E[i][j] = exp(-(R + Q - delta - value) / gamma).
+ *
+ *      cost, r, q: float32 [batch][n + m - 1][n], SKEWED: element (i, j) lies in row i + j at position i.  Every element is
+ *      written: ZERO wherever the position is no row of the entry or row - position no column of it.
+ *
+ *      tac_soft_dtw_f32: two kernels, the costs and then the lattice: a workgroup per (entry, direction) of up to
+ *      tac_soft_dtw_lanes() (1024) lanes, each on tac_soft_dtw_rows_per_lane(n) (1, 2 or 4) consecutive rows, n + m - 1 dependent
+ *      steps.  r and q both NULL: only the R workgroups run and only cost and value [batch] are written.
+ *
+ *      tac_soft_dtw_grad_f32: ONE launch.  grad_x[i] = 2 grad_value[b] (x[i] sum_j E[i][j] - sum_j E[i][j] y[j]) and grad_y[j]
+ *      likewise over i, written through their own strides; rows i >= Nb and j >= Mb get zeros.  Either of grad_x and grad_y may be
+ *      NULL.  A workgroup owns tac_soft_dtw_tile() (32) rows of one side; E goes through float32 matrix instructions and never to
+ *      memory.  tac_soft_dtw_alignment_f32: E as float32 [batch][n][m], zero outside an entry's (Nb, Mb); ONE launch.
+ *
+ *      Nothing is atomic and every sum has one fixed order: the same bits from run to run, for the 16-byte and the dword form
+ *      of the x and y loads, and for an entry whatever else is in the batch.  An entry with Nb outside [1, n] or Mb outside
+ *      [1, m] gets value NaN, r, q and its alignment NaN and NaN gradients over its whole blocks; no address is formed from such
+ *      a length, and the other entries are unaffected. */
+int32_t tac_soft_dtw_max_len(void);
+int32_t tac_soft_dtw_max_dim(void);
+int32_t tac_soft_dtw_lanes(void);
+int32_t tac_soft_dtw_tile(void);
+int32_t tac_soft_dtw_rows_per_lane(int64_t rows);
+int tac_soft_dtw_f32(const float* x, const float* y, int64_t batch, int64_t n, int64_t m, int64_t d, int64_t x_stride_b,
+                     int64_t x_stride_n, int64_t x_stride_d, int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d,
+                     const int32_t* x_lengths, const int32_t* y_lengths, float gamma, float* cost, float* r, float* q, float* value,
+                     void* stream);
+int tac_soft_dtw_grad_f32(const float* x, const float* y, int64_t batch, int64_t n, int64_t m, int64_t d, int64_t x_stride_b,
+                          int64_t x_stride_n, int64_t x_stride_d, int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d,
+                          const int32_t* x_lengths, const int32_t* y_lengths, float gamma, const float* cost, const float* r,
+                          const float* q, const float* value, const float* grad_value, float* grad_x, int64_t gx_stride_b,
+                          int64_t gx_stride_n, int64_t gx_stride_d, float* grad_y, int64_t gy_stride_b, int64_t gy_stride_m,
+                          int64_t gy_stride_d, void* stream);
+int tac_soft_dtw_alignment_f32(int64_t batch, int64_t n, int64_t m, const int32_t* x_lengths, const int32_t* y_lengths, float gamma,
+                               const float* cost, const float* r, const float* q, const float* value, float* alignment, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

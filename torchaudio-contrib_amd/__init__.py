@@ -21,14 +21,14 @@ from .functional import (stft, istft, griffinlim, complex_norm, create_mel_filte
                          add_noise, speed, pitch_shift, loudness, detect_pitch_frequency, psd, mvdr_weights_souden,
                          apply_beamforming, rtf_evd, rtf_power, mvdr_weights_rtf, rnnt_loss, ctc_loss, forced_align, ctc_beam_search,
                          merge_tokens, TokenSpan, vad, vad_start, simulate_rir_ism, simulate_rir_ism_batch,
-                         overdrive, phaser, flanger, oscillator_bank, filter_waveform, cqt, pcen)
+                         overdrive, phaser, flanger, oscillator_bank, filter_waveform, cqt, pcen, soft_dtw)
 from .layers import (STFT, ISTFT, GriffinLim, ComplexNorm, ApplyFilterbank, Filterbank, MelFilterbank, TimeStretch,
                      Spectrogram, Melspectrogram, AmplitudeToDb, DbToAmplitude, MuLawEncoding,
                      MuLawDecoding, HPSS, DCT, MFCC, Resample, LFilter, SosFilt, Overdrive, Phaser, Flanger, OscillatorBank, FilterWaveform, CQT, Preemphasis, Deemphasis,
                      FFTConvolve, Convolve, KaldiFbank, SlidingWindowCmn, ComputeDeltas,
                      KaldiMfcc, KaldiSpectrogram, TimeMasking, FrequencyMasking, SpecAugment,
                      AddNoise, Speed, SpeedPerturbation, PitchShift, Loudness, PitchFrequency, PSD, SoudenMVDR, MVDR,
-                     RTFMVDR, RNNTLoss, CTCLoss, Vad, SimulateRirIsm, PCEN)
+                     RTFMVDR, RNNTLoss, CTCLoss, Vad, SimulateRirIsm, PCEN, SoftDTW)
 from . import decoder
 from .decoder import CTCHypothesis, CTCBeamDecoder, ctc_decoder
 from . import distributed

@@ -1478,3 +1478,89 @@ def pcen(specgram, table, eps, form):
     else:
         out = torch.exp(power * torch.log(bias)) * torch.expm1(power * torch.log1p(E * torch.exp(log_smooth) / bias))
     return out.transpose(-1, -2)
+
+
+# ----------------------------------------------------------------------------- soft_dtw
+def _sdtw_lengths(lengths, limit):
+    """``(ok, clamped)``: which entries have a length inside ``[1, limit]``, and the lengths forced into it"""
+    lengths = lengths.to(torch.int64)
+    return (lengths >= 1) & (lengths <= limit), lengths.clamp(1, limit)
+
+
+def _sdtw_mirror(t, xl, yl):
+    """every entry of ``(B, N, M)`` mirrored in both axes inside its own ``(Nb, Mb)`` (an involution); the rest stays where it is"""
+    B, N, M = t.shape
+    rows, cols = torch.arange(N, device=t.device).view(1, N), torch.arange(M, device=t.device).view(1, M)
+    i = torch.where(rows < xl.view(B, 1), xl.view(B, 1) - 1 - rows, rows)
+    j = torch.where(cols < yl.view(B, 1), yl.view(B, 1) - 1 - cols, cols)
+    return t[torch.arange(B, device=t.device).view(B, 1, 1), i.view(B, N, 1), j.view(B, 1, M)]
+
+
+def _sdtw_recursion(delta, xl, yl, gamma):
+    """``R`` of ``(B, N, M)`` costs, an anti-diagonal at a time: ``+inf`` outside an entry's ``(Nb, Mb)``"""
+    B, N, M = delta.shape
+    inf = float('inf')
+    R = delta.new_full((B, N + 1, M + 1), inf)
+    R[:, 0, 0] = 0
+    for k in range(N + M - 1):
+        i = torch.arange(max(0, k - M + 1), min(N - 1, k) + 1, device=delta.device)
+        j = k - i
+        up, left, diag = R[:, i, j + 1], R[:, i + 1, j], R[:, i, j]
+        m = torch.minimum(torch.minimum(up, left), diag)
+        mm = torch.where(m == inf, torch.zeros_like(m), m)
+        s = torch.exp((mm - up) / gamma) + torch.exp((mm - left) / gamma) + torch.exp((mm - diag) / gamma)
+        live = (i.view(1, -1) < xl.view(B, 1)) & (j.view(1, -1) < yl.view(B, 1))
+        R[:, i + 1, j + 1] = torch.where(live, delta[:, i, j] + (m - gamma * torch.log(s)), torch.full_like(m, inf))
+    return R[:, 1:, 1:]
+
+
+def soft_dtw_lattice(x, y, x_lengths, y_lengths, gamma, both=True):
+    """``(value (B,), delta, R, Q (B, N, M))`` of soft-DTW with the squared Euclidean cost between ``x`` ``(B, N, D)`` and ``y``
+    ``(B, M, D)`` in torch operators, without a tape: ``Q`` is the recursion of ``R`` on every entry mirrored in both axes (None
+    without ``both``).  The three arrays are zero outside an entry's ``(Nb, Mb)``; an entry with a length outside its axis has the
+    value NaN."""
+    x, y = x.detach(), y.detach()
+    B, N, _ = x.shape
+    M = y.shape[1]
+    okx, xl = _sdtw_lengths(x_lengths.to(x.device), N)
+    oky, yl = _sdtw_lengths(y_lengths.to(x.device), M)
+    inside = (torch.arange(N, device=x.device).view(1, N, 1) < xl.view(B, 1, 1)) & \
+             (torch.arange(M, device=x.device).view(1, 1, M) < yl.view(B, 1, 1))
+    delta = ((x.unsqueeze(2) - y.unsqueeze(1)) ** 2).sum(-1)
+    delta = torch.where(inside, delta, torch.zeros_like(delta))
+    R = _sdtw_recursion(delta, xl, yl, gamma)
+    value = R[torch.arange(B, device=x.device), xl - 1, yl - 1]
+    value = torch.where(okx & oky, value, torch.full_like(value, float('nan')))
+    if not both:
+        return value, delta, None, None
+    Q = _sdtw_mirror(_sdtw_recursion(_sdtw_mirror(delta, xl, yl), xl, yl, gamma), xl, yl)
+    zero = torch.zeros_like(delta)
+    return value, delta, torch.where(inside, R, zero), torch.where(inside, Q, zero)
+
+
+def soft_dtw_alignment(x_lengths, y_lengths, delta, R, Q, value, gamma):
+    """``E = exp(-(R + Q - delta - value) / gamma)`` ``(B, N, M)``: zero outside an entry's ``(Nb, Mb)``, NaN for an invalid entry"""
+    B, N, M = delta.shape
+    _, xl = _sdtw_lengths(x_lengths.to(delta.device), N)
+    _, yl = _sdtw_lengths(y_lengths.to(delta.device), M)
+    inside = (torch.arange(N, device=delta.device).view(1, N, 1) < xl.view(B, 1, 1)) & \
+             (torch.arange(M, device=delta.device).view(1, 1, M) < yl.view(B, 1, 1))
+    excess = ((R + Q) - delta) - value.view(B, 1, 1)
+    E = torch.where(inside, torch.exp(-excess.clamp_min(0) / gamma), torch.zeros_like(delta))
+    return torch.where(torch.isnan(value).view(B, 1, 1), torch.full_like(E, float('nan')), E)
+
+
+def soft_dtw_grad(x, y, x_lengths, y_lengths, delta, R, Q, value, grad_value, gamma):
+    """``(grad_x, grad_y)`` in closed form from ``R`` and ``Q``: ``2 g (x[i] sum_j E[i][j] - sum_j E[i][j] y[j])`` and the same over
+    ``i`` for ``y``; zero rows behind an entry's lengths, NaN over an invalid entry"""
+    E = soft_dtw_alignment(x_lengths, y_lengths, delta, R, Q, value, gamma)
+    x, y = x.detach().to(E.dtype), y.detach().to(E.dtype)
+    g2 = 2 * grad_value.to(E.dtype).view(-1, 1, 1)
+    bad = torch.isnan(value).view(-1, 1, 1)
+    out = []
+    for own, other, e, lengths in ((x, y, E, x_lengths), (y, x, E.transpose(1, 2), y_lengths)):
+        grad = g2 * (own * e.sum(2, keepdim=True) - e @ other)
+        live = torch.arange(own.shape[1], device=own.device).view(1, -1, 1) < lengths.to(own.device).view(-1, 1, 1)
+        grad = torch.where(live, grad, torch.zeros_like(grad))
+        out.append(torch.where(bad, torch.full_like(grad, float('nan')), grad))
+    return out[0], out[1]

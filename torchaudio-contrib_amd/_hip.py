@@ -3319,3 +3319,75 @@ def melspectrogram_coded(samples, window, fb, n_fft, hop, win_length, center, pa
                  _native.ptr(desc), ctypes.cast(info, ctypes.c_void_p), fb.shape[1], 1 if db else 0, float(ref), float(amin),
                  _native.ptr(out), accept=_DECLINED)
     return None if rc == _native.TAC_E_UNSUPPORTED else out.transpose(-2, -1)
+
+
+# ----------------------------------------------------------------------------- soft_dtw (csrc/soft_dtw.hip)
+def soft_dtw_max_len():
+    """the most rows of ``x`` or ``y`` the launches take: the rows of one lattice workgroup"""
+    return _native.lib().tac_soft_dtw_max_len()
+
+
+def soft_dtw_max_dim():
+    """the most features the launches take: the column blocks of a gradient workgroup"""
+    return _native.lib().tac_soft_dtw_max_dim()
+
+
+def soft_dtw_reason(x, y):
+    """why the launches of csrc/soft_dtw.hip do not take ``x`` ``(B, N, D)`` and ``y`` ``(B, M, D)`` as they lie, or None"""
+    for t in (x, y):
+        if t.dtype != torch.float32:
+            return 'dtype %s' % str(t.dtype).replace('torch.', '')
+        if any(st <= 0 for st, n in zip(t.stride(), t.shape) if n > 1):
+            return 'expanded or non-positive strides'
+    if max(x.shape[1], y.shape[1]) > soft_dtw_max_len():
+        return 'sequences of %d and %d rows (the kernel takes up to %d)' % (x.shape[1], y.shape[1], soft_dtw_max_len())
+    if x.shape[2] > soft_dtw_max_dim():
+        return '%d features (the kernel takes up to %d)' % (x.shape[2], soft_dtw_max_dim())
+    return None
+
+
+def _soft_dtw_geometry(x, y):
+    return (_native.ptr(x), _native.ptr(y), x.shape[0], x.shape[1], y.shape[1], x.shape[2]) + tuple(x.stride()) + tuple(y.stride())
+
+
+def soft_dtw_forward(x, y, x_lengths, y_lengths, gamma, lattice):
+    """``(value (B,), delta, R, Q)`` of float32 inputs ``soft_dtw_reason`` passes: ONE entry point, the costs and the lattice.  The
+    three arrays are ``(B, N + M - 1, N)``, skewed: element ``(i, j)`` in row ``i + j`` at position ``i``.  Without ``lattice`` only
+    the R workgroups run and R / Q come back empty."""
+    B, N, _ = x.shape
+    M = y.shape[1]
+    dev = x.device
+    xl, yl = _rnnt_ints(x_lengths, dev), _rnnt_ints(y_lengths, dev)
+    value = _empty((B,), device=dev)
+    delta = _empty((B, N + M - 1, N), device=dev)
+    if lattice:
+        R, Q = (_empty((B, N + M - 1, N), device=dev) for _ in range(2))
+        filled, ptrs = (value, delta, R, Q), (_native.ptr(R), _native.ptr(Q))
+    else:
+        R, Q = (torch.empty((0,), dtype=torch.float32, device=dev) for _ in range(2))
+        filled, ptrs = (value, delta), (None, None)
+    _launch('tac_soft_dtw_f32', dev, filled, *_soft_dtw_geometry(x, y), _native.ptr(xl), _native.ptr(yl), float(gamma),
+            _native.ptr(delta), *ptrs, _native.ptr(value))
+    return value, delta, R, Q
+
+
+def soft_dtw_grad(x, y, x_lengths, y_lengths, delta, R, Q, value, grad_value, gamma):
+    """``(grad_x, grad_y)`` in the layouts of ``x`` and ``y`` where those are dense, else contiguous: ONE launch"""
+    dev = x.device
+    xl, yl = _rnnt_ints(x_lengths, dev), _rnnt_ints(y_lengths, dev)
+    delta, R, Q, value, grad_value = (t.contiguous() for t in (delta, R, Q, value, grad_value))
+    gx, gy = _empty_like(x), _empty_like(y)
+    _launch('tac_soft_dtw_grad_f32', dev, (gx, gy), *_soft_dtw_geometry(x, y), _native.ptr(xl), _native.ptr(yl), float(gamma),
+            _native.ptr(delta), _native.ptr(R), _native.ptr(Q), _native.ptr(value), _native.ptr(grad_value), _native.ptr(gx),
+            *gx.stride(), _native.ptr(gy), *gy.stride())
+    return gx, gy
+
+
+def soft_dtw_alignment(n, m, x_lengths, y_lengths, delta, R, Q, value, gamma):
+    """the expected alignment ``E`` ``(B, N, M)`` from the skewed arrays of ``soft_dtw_forward``: ONE launch"""
+    dev = delta.device
+    xl, yl = _rnnt_ints(x_lengths, dev), _rnnt_ints(y_lengths, dev)
+    E = _empty((delta.shape[0], n, m), device=dev)
+    _launch('tac_soft_dtw_alignment_f32', dev, (E,), delta.shape[0], n, m, _native.ptr(xl), _native.ptr(yl), float(gamma),
+            _native.ptr(delta), _native.ptr(R), _native.ptr(Q), _native.ptr(value), _native.ptr(E))
+    return E

@@ -248,6 +248,15 @@ PROTOTYPES = {
     'tac_pcen_max_axis': (_I64, []),
     'tac_pcen_f32': (_INT, [_P] + [_I64] * 6 + [_P, _F, _P, _P, _P]),
     'tac_pcen_backward_f32': (_INT, [_P] + [_I64] * 3 + [_P] + [_I64] * 6 + [_P, _P, _F, _I32, _P, _P, _P, _P]),
+    'tac_soft_dtw_max_len': (_I32, []),
+    'tac_soft_dtw_max_dim': (_I32, []),
+    'tac_soft_dtw_lanes': (_I32, []),
+    'tac_soft_dtw_tile': (_I32, []),
+    'tac_soft_dtw_rows_per_lane': (_I32, [_I64]),
+    'tac_soft_dtw_f32': (_INT, [_P, _P] + [_I64] * 10 + [_P, _P, _F, _P, _P, _P, _P, _P]),
+    'tac_soft_dtw_grad_f32': (_INT, [_P, _P] + [_I64] * 10 + [_P, _P, _F, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _I64,
+                                     _I64, _P]),
+    'tac_soft_dtw_alignment_f32': (_INT, [_I64, _I64, _I64, _P, _P, _F, _P, _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

@@ -26,6 +26,7 @@ see them by name.
     tac_amd::rtf_evd, rtf_power, mvdr_weights_rtf, rtf_mvdr   steering vectors from the PSDs and the MVDR solved for one (csrc/beamform.hip)
     tac_amd::rnnt_loss, rnnt_loss_grad   transducer loss over (B, T, U + 1, V) logits: costs with alpha / beta, and the gradient (csrc/rnnt.hip)
     tac_amd::ctc_loss, ctc_loss_grad     CTC loss over time-major (T, N, C) log-probabilities: costs with alpha / beta in one launch, the gradient in one (csrc/ctc_loss.hip)
+    tac_amd::soft_dtw, soft_dtw_grad     soft-DTW between (B, N, D) and (B, M, D): costs, R and Q behind one entry point, both gradients in one launch (csrc/soft_dtw.hip)
     tac_amd::forced_align       CTC Viterbi alignment of (B, T, C) log-probabilities: recursion, backtrack, paths and scores in one launch (csrc/align.hip)
     tac_amd::ctc_beam_search    CTC prefix beam search of (B, T, C) log-probabilities: the k best classes of every frame, then the beams, in two launches (csrc/ctc_decode.hip)
     tac_amd::griffinlim         Griffin-Lim phase recovery of (…, F, T) magnitudes: prepare, then stft + inverse a step (csrc/griffinlim.hip)
@@ -2659,6 +2660,151 @@ _register('pcen', '(Tensor specgram, Tensor table, float eps, int form, bool kee
 _register_pcen_autograd()
 _register('pcen_grad', '(Tensor grad_out, Tensor specgram, Tensor smoother, Tensor table, float eps, int form, bool need_input, '
           'int want) -> (Tensor, Tensor)', _pcen_grad_cuda, _pcen_grad_torch, _pcen_grad_fake, 4, differentiable=False)
+
+
+# ============================================================================= soft_dtw, soft_dtw_grad
+def soft_dtw_check(x, y, gamma, x_lengths, y_lengths):
+    """The argument checks of ``soft_dtw`` that need no device memory, and its arguments in the form the op takes:
+    ``(x (B, N, D), y (B, M, D), x_lengths (B,), y_lengths (B,), gamma, batched)``.  Absent lengths are the whole axes; tuples and
+    lists become tensors.  ``ValueError`` on every route."""
+    for name, t in (('x', x), ('y', y)):
+        if not (isinstance(t, torch.Tensor) and t.is_floating_point()):
+            raise ValueError('soft_dtw: %s must be a floating-point tensor' % name)
+    if x.dim() not in (2, 3) or y.dim() != x.dim():
+        raise ValueError('soft_dtw: x and y must both be (B, len, D) or both (len, D), got %d and %d dimension(s)' % (x.dim(), y.dim()))
+    gamma = float(gamma)
+    if not (math.isfinite(gamma) and gamma > 0):
+        raise ValueError('soft_dtw: gamma must be finite and positive, got %r' % (gamma,))
+    batched = x.dim() == 3
+    if not batched:
+        x, y = x.unsqueeze(0), y.unsqueeze(0)
+    if x.shape[0] != y.shape[0]:
+        raise ValueError('soft_dtw: x has a batch of %d and y of %d' % (x.shape[0], y.shape[0]))
+    if x.shape[2] != y.shape[2]:
+        raise ValueError('soft_dtw: x has %d features and y %d' % (x.shape[2], y.shape[2]))
+    if min(x.shape[1], y.shape[1], x.shape[2]) < 1:
+        raise ValueError('soft_dtw: x of shape %r and y of shape %r have an empty axis' % (tuple(x.shape), tuple(y.shape)))
+    if x.dtype != y.dtype or x.device != y.device:
+        raise ValueError('soft_dtw: x and y must share dtype and device')
+    lengths = []
+    for name, t, whole in (('x_lengths', x_lengths, x.shape[1]), ('y_lengths', y_lengths, y.shape[1])):
+        if t is None:
+            t = torch.full((x.shape[0],), whole, dtype=torch.int32, device=x.device)
+        elif isinstance(t, (tuple, list)):
+            t = torch.tensor([int(v) for v in t], dtype=torch.int32)
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError('soft_dtw: %s must be an integer tensor, a tuple or a list' % name)
+        if t.reshape(-1).shape[0] != x.shape[0]:
+            raise ValueError('soft_dtw: %d %s for a batch of %d' % (t.numel(), name, x.shape[0]))
+        lengths.append(t.reshape(-1).to(x.device))
+    return x, y, lengths[0], lengths[1], gamma, batched
+
+
+def _sdtw_kernel_route(x, y):
+    return x.is_cuda and x.shape[0] > 0 and H.soft_dtw_reason(x, y) is None
+
+
+def _sdtw_outputs(x, y, lattice):
+    """empty outputs with the shapes and dtypes of the route these inputs take: skewed float32 arrays from the kernels, natural ones
+    in the (widened) dtype of the inputs from the composite"""
+    B, N, _ = x.shape
+    M = y.shape[1]
+    kernel = x.device.type != 'cpu' and H.soft_dtw_reason(x, y) is None
+    shape = (B, N + M - 1, N) if kernel else (B, N, M)
+    dtype = _out_dtype(x)
+    return (x.new_empty((B,)), x.new_empty(shape, dtype=dtype)) + tuple(x.new_empty(shape if lattice else (0,), dtype=dtype)
+                                                                        for _ in range(2))
+
+
+def _sdtw_composite(x, y, x_lengths, y_lengths, gamma, lattice):
+    value, delta, R, Q = C.soft_dtw_lattice(_f32(x), _f32(y), x_lengths, y_lengths, gamma, both=lattice)
+    if not lattice:
+        R, Q = (delta.new_empty((0,)) for _ in range(2))
+    return value.to(x.dtype), delta, R, Q
+
+
+def _sdtw_cuda(x, y, x_lengths, y_lengths, gamma, lattice):
+    _same_device('soft_dtw', x, y)
+    if x.shape[0] == 0:
+        return _sdtw_outputs(x, y, lattice)                        # an empty batch: nothing is launched
+    reason = H.soft_dtw_reason(x, y)
+    if reason is not None:
+        _composite_route('soft_dtw', reason)
+        return _sdtw_composite(x, y, x_lengths, y_lengths, gamma, lattice)
+    return H.soft_dtw_forward(x, y, x_lengths, y_lengths, gamma, lattice)
+
+
+def _sdtw_fake(x, y, x_lengths, y_lengths, gamma, lattice):
+    return _sdtw_outputs(x, y, lattice)
+
+
+def _sdtw_grad_torch(x, y, x_lengths, y_lengths, delta, R, Q, value, grad_value, gamma):
+    """the closed-form gradient in torch operators from the natural-layout arrays; without them the lattice is evaluated again"""
+    xf, yf = _f32(x), _f32(y)
+    natural = (x.shape[0], x.shape[1], y.shape[1])
+    if tuple(R.shape) != natural or tuple(delta.shape) != natural or _sdtw_kernel_route(x, y):
+        value, delta, R, Q = C.soft_dtw_lattice(xf, yf, x_lengths, y_lengths, gamma)
+    gx, gy = C.soft_dtw_grad(xf, yf, x_lengths, y_lengths, delta, R, Q, value.to(delta.dtype), grad_value, gamma)
+    return gx.to(x.dtype), gy.to(y.dtype)
+
+
+def _sdtw_grad_cuda(x, y, x_lengths, y_lengths, delta, R, Q, value, grad_value, gamma):
+    if x.numel() == 0:
+        return torch.empty_like(x), torch.empty_like(y)
+    reason = H.soft_dtw_reason(x, y)
+    if reason is None and R.numel() == 0:
+        reason = 'no lattice arrays were kept'
+    if reason is None and not _plain_hip_f32(delta, R, Q, value, grad_value):
+        reason = 'tensor subclass or dtype of the saved arrays'
+    if reason is not None:
+        _composite_route('soft_dtw', 'backward: ' + reason)
+        return _sdtw_grad_torch(x, y, x_lengths, y_lengths, delta, R, Q, value, grad_value, gamma)
+    return H.soft_dtw_grad(x, y, x_lengths, y_lengths, delta, R, Q, value, grad_value, gamma)
+
+
+def _sdtw_grad_fake(x, y, x_lengths, y_lengths, delta, R, Q, value, grad_value, gamma):
+    return torch.empty_like(x), torch.empty_like(y)
+
+
+def soft_dtw_alignment(x, y, x_lengths, y_lengths, delta, R, Q, value, gamma):
+    """the expected alignment ``E`` ``(B, N, M)`` float32 from what ``tac_amd::soft_dtw`` kept, on the route that op took"""
+    if _sdtw_kernel_route(x, y) and _plain_hip_f32(delta, R, Q, value):
+        return H.soft_dtw_alignment(x.shape[1], y.shape[1], x_lengths, y_lengths, delta, R, Q, value.contiguous(), gamma)
+    return C.soft_dtw_alignment(x_lengths, y_lengths, delta, R, Q, value.to(delta.dtype), gamma).float()
+
+
+def _register_sdtw_autograd():
+    """Backward of ``tac_amd::soft_dtw``: the value is the one differentiable output, ``x`` and ``y`` the inputs with a gradient.
+    What the forward pass kept — the costs, R, Q, the value — goes to ``tac_amd::soft_dtw_grad``, which routes like every op.  The
+    gradient is a closed form without a graph on every route: a double backward is refused."""
+
+    def setup_context(ctx, inputs, output):
+        x, y, x_lengths, y_lengths, gamma, lattice = inputs
+        value, delta, R, Q = output
+        ctx.mark_non_differentiable(delta, R, Q)
+        ctx.save_for_backward(x, y, x_lengths, y_lengths, delta, R, Q, value)
+        ctx.gamma = gamma
+
+    def backward(ctx, g, *unused):
+        x, y, x_lengths, y_lengths, delta, R, Q, value = ctx.saved_tensors
+        need_x, need_y = ctx.needs_input_grad[:2]
+        if g is None or not (need_x or need_y):
+            return (None,) * 6
+        if torch.is_grad_enabled():
+            raise RuntimeError('tac_amd::soft_dtw: double backward (create_graph=True) is not supported: the gradient is a closed '
+                               'form of the saved lattice, on the gfx950 kernels and in torch operators alike')
+        gx, gy = call('soft_dtw_grad', x, y, x_lengths, y_lengths, delta, R, Q, value, g, ctx.gamma)
+        return (gx if need_x else None, gy if need_y else None) + (None,) * 4
+
+    torch.library.register_autograd('%s::soft_dtw' % NS, backward, setup_context=setup_context, lib=_lib)
+
+
+_register('soft_dtw', '(Tensor x, Tensor y, Tensor x_lengths, Tensor y_lengths, float gamma, bool lattice) -> '
+          '(Tensor, Tensor, Tensor, Tensor)', _sdtw_cuda, _sdtw_composite, _sdtw_fake, 2, differentiable=False)
+_register_sdtw_autograd()
+_register('soft_dtw_grad', '(Tensor x, Tensor y, Tensor x_lengths, Tensor y_lengths, Tensor delta, Tensor r, Tensor q, Tensor value, '
+          'Tensor grad_value, float gamma) -> (Tensor, Tensor)', _sdtw_grad_cuda, _sdtw_grad_torch, _sdtw_grad_fake, 2,
+          differentiable=False)
 
 
 # ============================================================================= complex pairs

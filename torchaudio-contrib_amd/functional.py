@@ -43,7 +43,7 @@ __all__ = ['stft', 'istft', 'griffinlim', 'complex_norm', 'create_mel_filter', '
            'bandreject_biquad', 'allpass_biquad', 'equalizer_biquad', 'preemphasis', 'deemphasis', 'loudness', 'detect_pitch_frequency',
            'psd', 'mvdr_weights_souden', 'apply_beamforming', 'rtf_evd', 'rtf_power', 'mvdr_weights_rtf', 'rnnt_loss', 'ctc_loss',
            'forced_align', 'merge_tokens', 'TokenSpan', 'ctc_beam_search', 'vad', 'vad_start', 'simulate_rir_ism', 'simulate_rir_ism_batch',
-           'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform', 'cqt', 'pcen']
+           'overdrive', 'phaser', 'flanger', 'oscillator_bank', 'filter_waveform', 'cqt', 'pcen', 'soft_dtw']
 
 _call = _ops.call
 
@@ -1197,6 +1197,50 @@ def ctc_loss(log_probs, targets, input_lengths, target_lengths, blank=0, reducti
     if reduction == 'sum':
         return costs.sum()
     return costs if batched else costs[0]
+
+
+def soft_dtw(x, y, gamma=1.0, x_lengths=None, y_lengths=None, normalize=False, reduction='none', return_alignment=False):
+    """Soft-DTW (Cuturi & Blondel 2017) between feature sequences ``x`` ``(B, N, D)`` and ``y`` ``(B, M, D)`` (or ``(N, D)`` and
+    ``(M, D)``) with the squared Euclidean cost ``delta[i][j] = sum_d (x[i][d] - y[j][d])^2``:
+    ``R[i][j] = delta[i][j] + softmin_gamma(R[i-1][j], R[i][j-1], R[i-1][j-1])`` with
+    ``softmin_gamma(a, b, c) = -gamma log(e^(-a/gamma) + e^(-b/gamma) + e^(-c/gamma))``, and the value of entry ``b`` is ``R[Nb][Mb]``.
+    ``x_lengths`` (``Nb``) and ``y_lengths`` (``Mb``) are tensors, tuples or lists; absent, the whole axes.  ``reduction``: ``'none'``
+    gives the ``(B,)`` values, ``'mean'`` and ``'sum'`` reduce them over the batch.  ``normalize=True`` returns the soft-DTW divergence
+    ``sdtw(x, y) - (sdtw(x, x) + sdtw(y, y)) / 2``, three evaluations.  ``return_alignment=True`` returns ``(value, E)`` with the
+    expected alignment ``E`` ``(B, N, M)`` float32 of ``x`` against ``y``, detached, zero outside an entry's ``(Nb, Mb)``.  The
+    gradient is the closed form ``2 g (x[i] sum_j E[i][j] - sum_j E[i][j] y[j])`` and its counterpart for ``y``, zero on rows behind an
+    entry's lengths.  ``ValueError``: a ``gamma`` that is not finite and positive, mismatched batches or feature axes, an unknown
+    ``reduction``.
+
+    float32 on a HIP device with positive strides (a transposed or sliced view is read where it lies), ``N, M <= 4096`` and
+    ``D <= 256`` runs csrc/soft_dtw.hip: forward ONE entry point (the costs, then R and Q side by side in ``N + M - 1`` dependent
+    steps; the R workgroups alone when nothing needs a gradient or the alignment), backward ONE launch, the alignment ONE.  Kept for
+    the backward pass: three ``(B, N + M - 1, N)`` float32 arrays (costs, R, Q; 12 (N + M - 1) N bytes an entry) and the values.
+    Bit-identical from run to run and, for an entry, whatever else is in the batch.  An entry with ``Nb`` outside ``[1, N]`` or
+    ``Mb`` outside ``[1, M]`` gets a NaN value and NaN gradients over its own blocks; the other entries are unaffected.  Other
+    device inputs (float64, half precision, expanded views, longer sequences, more features) take ``_composite.soft_dtw_lattice``
+    — an anti-diagonal of torch operators at a time, the same closed-form gradient — announced with ``CompositeRouteWarning``;
+    CPU tensors take it silently.  A double backward is not supported on any route: ``RuntimeError``."""
+    if reduction not in ('none', 'mean', 'sum'):
+        raise ValueError("soft_dtw: reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+    x3, y3, xl, yl, gamma, batched = _ops.soft_dtw_check(x, y, gamma, x_lengths, y_lengths)
+    grad = torch.is_grad_enabled() and (x3.requires_grad or y3.requires_grad)
+    value, delta, R, Q = _call('soft_dtw', x3, y3, xl, yl, gamma, bool(grad or return_alignment))
+    if return_alignment:
+        alignment = _ops.soft_dtw_alignment(x3, y3, xl, yl, delta.detach(), R.detach(), Q.detach(), value.detach(), gamma)
+    if normalize:
+        own = [_call('soft_dtw', t, t, tl, tl, gamma, bool(torch.is_grad_enabled() and t.requires_grad))[0]
+               for t, tl in ((x3, xl), (y3, yl))]
+        value = value - 0.5 * (own[0] + own[1])
+    if reduction == 'mean':
+        value = value.mean()
+    elif reduction == 'sum':
+        value = value.sum()
+    elif not batched:
+        value = value[0]
+    if return_alignment:
+        return value, (alignment if batched else alignment[0])
+    return value
 
 
 def pcen(specgram, sample_rate=22050, hop_length=512, gain=0.98, bias=2.0, power=0.5, time_constant=0.4, eps=1e-6, b=None):

@@ -959,6 +959,24 @@ class CTCLoss(_ModuleNoStateBuffers):
         return F.ctc_loss(log_probs, targets, input_lengths, target_lengths, self.blank, self.reduction, self.zero_infinity)
 
 
+class SoftDTW(_ModuleNoStateBuffers):
+    """``functional.soft_dtw`` as a loss layer: ``forward(x, y, x_lengths=None, y_lengths=None)`` with the ``gamma``, ``normalize`` and
+    ``reduction`` of the constructor.  No buffers, no parameters."""
+
+    def __init__(self, gamma=1.0, normalize=False, reduction='mean'):
+        super(SoftDTW, self).__init__()
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError("SoftDTW: reduction must be 'none', 'mean' or 'sum', got %r" % (reduction,))
+        if not (math.isfinite(float(gamma)) and float(gamma) > 0):
+            raise ValueError('SoftDTW: gamma must be finite and positive, got %r' % (gamma,))
+        self.gamma = float(gamma)
+        self.normalize = normalize
+        self.reduction = reduction
+
+    def forward(self, x, y, x_lengths=None, y_lengths=None):
+        return F.soft_dtw(x, y, self.gamma, x_lengths, y_lengths, self.normalize, self.reduction)
+
+
 class MVDR(_ModuleNoStateBuffers):
     """torchaudio's mask-based ``transforms.MVDR`` at ``solution='ref_channel'``: ``forward(specgram, mask_s, mask_n=None)`` maps a
     ``(…, channel, freq, time)`` spectrogram and real ``(…, freq, time)`` masks (``(…, channel, freq, time)`` with ``multi_mask``,
